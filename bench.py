@@ -11,12 +11,16 @@ N = 1 keeps four frames in flight (four library contexts on four HIP streams = t
 --frames-in-flight);
 the strictly serial figures are reported next to the headline under "serial".
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  Extra keys: "roofline" (render kernel: algorithmic HBM bytes per launch
-over its HIP-event duration, next to the VALU-op rate that actually bounds it) and "cpu_baseline"
-(the oracle's SIMD port of the reference's mode 8, timed on this host on a bounded sample).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and reports the headline
+(value, ms_per_step).  --full adds what is measured or checked after the timed region: the serial, moving-camera,
+frames-in-flight and exact-settings loops, the per-rank phases and the frame-parallel control (N > 1), the frame
+check against a single-GPU render, "roofline" (render kernel: algorithmic HBM bytes per launch over its HIP-event
+duration, next to the VALU-op rate that actually bounds it), "parity" (the oracle on seeded pixels) and
+"cpu_baseline" (the oracle's SIMD port of the reference's mode 8, timed on this host on a bounded sample).
+--dump-outputs DIR writes the frame of the last timed step (see dump_image).
 """
 import argparse
 import importlib.util
@@ -200,6 +204,28 @@ def parity_check(scene_mod, g, w, h, tiles_n, rad, npix, seed, cull_eps, cull_pr
             "settings": "the timed loop's (cull_eps, ray-level prune, table kernel as configured)"}
 
 
+DUMP_PIXELS = 1 << 21   # 24 B a pixel (four float32 channels + a float64 index): 48 MiB at most
+
+
+def dump_image(out_dir, image, w, h):
+    """The frame a caller of the timed path receives (u32 pixels A<<24 | R<<16 | G<<8 | B, raster order) as
+    out_dir/image_rgba.npy: float32 [P, 4], the R, G, B, A channels (0..255) of P pixels, and out_dir/pixel_index.npy:
+    float64 [P], their raster indices y * w + x.  Every pixel while there are at most DUMP_PIXELS; a larger frame is
+    sampled, by a fixed seed: the same pixels in every run with the same --width."""
+    import numpy as np
+    px = np.ascontiguousarray(image).reshape(-1).view(np.uint32)
+    assert px.size == w * h
+    if px.size <= DUMP_PIXELS:
+        idx = np.arange(px.size)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(px.size, DUMP_PIXELS, replace=False))
+    sel = px[idx]
+    rgba = np.stack([(sel >> s) & 255 for s in (16, 8, 0, 24)], axis=1).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "image_rgba.npy"), rgba)
+    np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+
+
 def gather_batch_frames(gather_frames, steps):
     """Frames per RCCL gather for a run of `steps` timed steps: --gather-frames, but never more than a quarter of the run."""
     return max(1, min(int(gather_frames), max(int(steps), 1) // 4 if steps >= 4 else 1))
@@ -252,7 +278,7 @@ def main():
     ap.add_argument("--tiles", type=int, default=16)
     ap.add_argument("--cull-eps", type=float, default=1e-9)
     ap.add_argument("--table-step", type=float, default=0.05, help="node spacing of the table kernel (library default 0.05; 0 = exact kernels only)")
-    ap.add_argument("--parity-pixels", type=int, default=256, help="lit pixels the oracle checks after the timed region (N = 1; with --no-cpu-baseline: none)")
+    ap.add_argument("--parity-pixels", type=int, default=256, help="--full: lit pixels the oracle checks after the timed region (N = 1; with --no-cpu-baseline: none)")
     ap.add_argument("--cull-prune", type=float, default=6.0, help="budget factor of the block kernel's ray-level prune (library default 6; 0 = off)")
     ap.add_argument("--gather-frames", type=int, default=32, help="N > 1: frames per RCCL gather (one collective per batch)")
     ap.add_argument("--exchange", choices=["all_gather", "gather"], default="all_gather",
@@ -265,13 +291,18 @@ def main():
                     help="N = 1: library contexts (each on its own HIP stream) the timed frames alternate between; 1 = strictly serial "
                          "frames; default 2 = double buffering, whatever --steps is (round 4: every context costs a timed region ~30 us "
                          "of start-up and drain -- 20 steps read 24.5 us per step with two contexts, 26.5 with four -- and the steady "
-                         "state loses 2 %: 21.2 against 20.7 us; 1..4 are measured after the timed region: in_flight_sweep)")
+                         "state loses 2 %%: 21.2 against 20.7 us; with --full, 1..4 are measured after the timed region: in_flight_sweep)")
     ap.add_argument("--parallel", choices=["tiles", "frames"], default="tiles",
                     help="N > 1: 'tiles' = one frame's tiles sharded over the ranks + gather (the headline, SURVEY 8e); 'frames' = "
                          "every rank renders whole frames of its own, no collective (the replicas-only alternative: weak scaling)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--plane-arrays", action="store_true", help="feed reference-style plane arrays (12 B/ray reads)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame of the last timed step as DIR/*.npy (dump_image)")
+    ap.add_argument("--full", action="store_true", help="also run everything after the timed region: serial / moving-camera / "
+                    "exact-settings loops, frame check, roofline, parity and CPU baseline (N = 1), per-rank phases and control (N > 1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -322,9 +353,9 @@ def main():
     if args.frames_in_flight <= 0:
         args.frames_in_flight = 2
     nfl = max(1, args.frames_in_flight) if solo else 1          # frames in flight of the timed region
-    # contexts: N = 1 also measures 1..4 frames in flight after the timed region (--frames-in-flight 1 = a strictly serial process:
-    # one context, nothing ever overlaps -- what the serial rocprofv3 summaries under profiles/ are taken with)
-    nctx = (max(nfl, 4) if (world == 1 and nfl > 1) else nfl) if solo else 1
+    # contexts: N = 1 with --full also measures 1..4 frames in flight after the timed region (--frames-in-flight 1 = a strictly
+    # serial process: one context, nothing ever overlaps -- what the serial rocprofv3 summaries under profiles/ are taken with)
+    nctx = (max(nfl, 4) if (args.full and world == 1 and nfl > 1) else nfl) if solo else 1
 
     def make_renderer():
         r_ = pkg.Renderer(local_rank)
@@ -483,13 +514,20 @@ def main():
     # HIP events around the dominant kernel, on the stream it runs on, live in the timed region -- on every 8th frame:
     # an event costs the stream 2-3 us and a frame is ~55 us, so bracketing every launch would take a tenth of the
     # throughput being measured.  The per-kernel breakdown of the launch sequence (four events per frame, every frame)
-    # is measured in a second loop after the timed region.
-    r.enable_kernel_timing(3)
+    # is measured in a second loop after the timed region.  Both only with --full: the roofline is their one reader.
+    if args.full:
+        r.enable_kernel_timing(3)
     t0 = time.perf_counter()
     run(args.steps)
     t_enqueued = time.perf_counter() - t0      # the host's share: all K steps are enqueued (the GPU may be far behind, or waiting)
     barrier()
     elapsed = time.perf_counter() - t0
+    # the frame of the last timed step, copied before anything after the timed region reuses the frame buffers: step k went to
+    # buffer k % nfl (N = 1), to buffer k % F of its gather batch (N > 1, batched assembly) or to the one frame buffer
+    last_image = None
+    if args.dump_outputs and rank == 0:
+        last_buf = (args.steps - 1) % (nfl if solo else (1 if args.no_batch else F))
+        last_image = images[last_buf].cpu().numpy()
     if os.environ.get("VRT_BENCH_DEBUG") and not solo:
         for b in range(fg.NB):
             print(f"[debug rank {rank}] shard buffer {b} headers:", fg.shard[b].view(fg.F, fg.words)[:, :4].cpu().tolist(), "prefix", fg.prefix[b], file=sys.stderr)
@@ -497,21 +535,22 @@ def main():
                 print(f"[debug rank {rank}] recv {b} headers:", fg.recv[b][:, :, :4].cpu().tolist(), file=sys.stderr)
         if rank == 0:
             print("[debug] lit pixels per image:", [int((im != 0).sum()) for im in images], file=sys.stderr)
-    kt = r.kernel_timing()
-    r.enable_kernel_timing(False)
-    # after the timed region: strictly serial frames on one context (no events), then the per-kernel breakdown
-    n_serial = max(200, min(args.steps, 400))   # its own sample size: a 20-step timed region says little about one frame's latency
-    barrier()
-    t1 = time.perf_counter()
-    run(n_serial, 1, serial=True)
-    barrier()
-    serial_ms = (time.perf_counter() - t1) / max(n_serial, 1) * 1e3
+    if args.full:
+        kt = r.kernel_timing()
+        r.enable_kernel_timing(False)
+        # after the timed region: strictly serial frames on one context (no events), then the per-kernel breakdown
+        n_serial = max(200, min(args.steps, 400))   # its own sample size: a 20-step timed region says little about one frame's latency
+        barrier()
+        t1 = time.perf_counter()
+        run(n_serial, 1, serial=True)
+        barrier()
+        serial_ms = (time.perf_counter() - t1) / max(n_serial, 1) * 1e3
     # What a frame loop with a MOVING camera costs (N = 1): the same workload, the view turned by 1e-4 degrees per step, so
     # nothing a static view lets the library keep (per-origin tables, tile cones, the dense-launch report) applies: every
     # frame sets its rays, rebuilds the cone table and runs all launches.  Same frames in flight, then serial.
     moving = None
     sweep = None
-    if solo and world == 1 and not args.plane_arrays:
+    if args.full and solo and world == 1 and not args.plane_arrays:
         poses = [scene.cli_camera(w, h, initial_rot=1e-4 * k)[0] for k in range(64)]
         mcalls = [[r_.frame_view_call(tw, th, p_.view, p_.position, pack) for p_ in poses] for r_ in ctxs]
 
@@ -585,7 +624,7 @@ def main():
     # What the speed costs in accuracy (round-3 verdict): the same loop at EXACT settings -- no budgeted prune, table kernel off
     # (cull_eps stays: its thresholds' share is <= 2.5e-6) -- in flight and serial, after the timed region.
     exact = None
-    if solo and world == 1 and not args.plane_arrays:
+    if args.full and solo and world == 1 and not args.plane_arrays:
         for r_ in ctxs:
             r_.set_cull_prune(0.0)
             r_.set_table_step(0.0)
@@ -611,7 +650,7 @@ def main():
     # N > 1: where a rank's time goes -- the timed loop once more with the gatherer's phase timers on (sharding.py: "render" on the
     # batch's render stream, "gather" from enqueue until the frame stream may use it, "assemble" on rank 0), all ranks to rank 0
     per_rank = None
-    if not solo:
+    if args.full and not solo:
         fg.timing = True
         fg.phase_ms()
         run(args.steps)
@@ -631,7 +670,7 @@ def main():
     # times, N x one GPU by construction.  Beside `value` it separates what the tile-sharded path loses to its collective from what a rank
     # loses to anything else (a busy host, a slow device).  The collective part is unconditional: a rank whose control fails reports NaN.
     control = None
-    if not solo:
+    if args.full and not solo:
         c_ms = float("nan")
         try:
             c_ctx = []
@@ -674,120 +713,39 @@ def main():
         if c_fr is not None:
             for rc in c_ctx:
                 rc.close()
-    r.enable_kernel_timing(1)
-    run(max(50, min(args.steps, 100)), 1, serial=True)
-    barrier()
-    seq = r.kernel_timing()
-    r.enable_kernel_timing(False)
-    kt["lists_ms"], kt["dense_ms"], kt["render_serial_ms"] = seq["lists_ms"], seq["dense_ms"], seq["render_ms"]
-    if not kt["launches"] or not kt["render_ms"] > 0:   # frame batches carry no per-launch events: the serial launch's duration
-        kt["render_ms"] = seq["render_ms"]
+    if args.full:
+        r.enable_kernel_timing(1)
+        run(max(50, min(args.steps, 100)), 1, serial=True)
+        barrier()
+        seq = r.kernel_timing()
+        r.enable_kernel_timing(False)
+        kt["lists_ms"], kt["dense_ms"], kt["render_serial_ms"] = seq["lists_ms"], seq["dense_ms"], seq["render_ms"]
+        if not kt["launches"] or not kt["render_ms"] > 0:   # frame batches carry no per-launch events: the serial launch's duration
+            kt["render_ms"] = seq["render_ms"]
 
     red_dev = "cuda" if backend == "nccl" else "cpu"
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
-    kern_ms = torch.tensor([kt["render_ms"]], dtype=torch.float64, device=red_dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        dist.all_reduce(kern_ms, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
-    kernel_ms = float(kern_ms.item())
+    if args.full:
+        kern_ms = torch.tensor([kt["render_ms"]], dtype=torch.float64, device=red_dev)
+        if world > 1:
+            dist.all_reduce(kern_ms, op=dist.ReduceOp.MAX)
+        kernel_ms = float(kern_ms.item())
 
     if rank == 0:
         rays = w * h * args.steps * (world if (solo and world > 1) else 1)   # frames mode: every rank renders K whole frames
         ms_per_step = elapsed / args.steps * 1e3
-        # ---- statistics pass (outside the timed region): list lengths, shaded blocks ----
-        counts = r.tile_counts()
-        n_entries = int(counts.sum())
-        r.enable_stats(True)
-        r.set_shard(0, 1)
-        _img, _rad = r.render(origin, pack)
-        # the gathered + assembled frame of the timed loop must be the single-GPU frame, bit for bit
-        bad = [(i_, int((im.cpu().numpy().view(np.uint32) != _img.reshape(-1)).sum())) for i_, im in enumerate(images)]
-        bad = [b_ for b_ in bad if b_[1]]
-        frame_ok = not bad
-        if bad:
-            print(f"bench.py: frame buffers that differ from the single-GPU frame (buffer, pixels): {bad}", file=sys.stderr)
-        st = r.stats()
-        r.enable_stats(False)
-        r.set_shard(*((0, 1) if solo else (rank, world)))
-        sb = max(st["shaded_blocks"], 1)
-        # ---- roofline.  Algorithmic HBM bytes: 4 B per ray written (+12 B per ray
-        # read with --plane-arrays), the Gaussian rows once (64 B each), the candidate lists once (4 B per entry).
-        # Dominant kernel = render_kernel: it writes the rays it shades and reads their cells' lists; the other rays
-        # of the frame are cleared by the list kernel, so the FRAME figure is given next to it.
-        per_ray = 4 + (12 if args.plane_arrays else 0)
-        share = 1 if solo else world   # tile sharding: a rank's kernels see 1/world of the frame
-        render_bytes = (sb * 64 * per_ray + 4 * st["tile_entries"] + 64 * len(g)) / share
-        frame_bytes = (w * h * per_ray + 64 * len(g) + 4 * n_entries) / share
-        # the dominant kernel's duration is that of the SERIAL launch (frames in flight stretch a launch: it shares the GPU with
-        # the other contexts' kernels, and is then no component of the step); the overlapped figure is kept beside it
-        kernel_ms_overlapped = kernel_ms
-        kernel_ms = kt["render_serial_ms"] if (solo and kt["render_serial_ms"] > 0) else kernel_ms
-        render_gbs = render_bytes / (kernel_ms * 1e-3) / 1e9
-        # the whole frame: wall time per step of the timed region (one rank: nothing but the launch sequence is in it)
-        frame_ms = ms_per_step if solo else kt["lists_ms"] + kt["render_ms"] + kt["dense_ms"]
-        frame_gbs = frame_bytes / (frame_ms * 1e-3) / 1e9
-        # ---- VALU (what actually bounds the path).  ALGORITHMIC lane-ops: per (ray, candidate of its block)
-        # one cull / precompute = 14 lane-ops, per surviving (emitter i, sample k, absorber j) of a ray 16 lane-ops
-        # (1 fma + A&S erf with 1 rcp + 1 fma); both counted by the statistics pass above, nothing skipped is credited.
-        # 64 lane-ops = one wave-instruction equivalent.
-        culls = 64 * st["list_entries"]
-        terms = 5 * st["lane_pairs"]
-        alg_wave_instr = (14 * culls + 16 * terms) / 64.0
-        valu = {"algorithmic": {"ray_candidate_culls": culls, "surviving_ikj_terms": terms,
-                                "lane_ops": 14 * culls + 16 * terms, "wave_instruction_equivalents": alg_wave_instr,
-                                "achieved_per_s": alg_wave_instr / (kernel_ms * 1e-3),
-                                "frac": alg_wave_instr / (kernel_ms * 1e-3) / VALU_PEAK_WAVE_INSTR,
-                                "frac_serial_launch": alg_wave_instr / (kt["render_serial_ms"] * 1e-3) / VALU_PEAK_WAVE_INSTR,
-                                # per FRAME TIME of the timed region: what the GPU as a whole sustains with frames in flight
-                                # (a launch that shares the GPU with other frames' kernels lasts longer than its share of it)
-                                "frac_of_frame_time": (alg_wave_instr / (ms_per_step * 1e-3) / VALU_PEAK_WAVE_INSTR) if solo else None},
-                "peak_per_s": VALU_PEAK_WAVE_INSTR,
-                "peak_note": "spec: 1024 SIMDs x 2.4 GHz / 2 cycles per wave64 VALU instruction (MI355X_MICROARCH.md)"}
-        try:
-            valu["measured_fma_issue"] = json.load(open(VALU_MEASURED_FILE))
-        except (OSError, ValueError):
-            pass
-        # ---- constants from separate PMC passes (rocprofv3 --pmc cannot run inside this process): HBM traffic and
-        # EXECUTED instruction counts per launch.  Used only when they were taken with these very kernel sources.
-        traffic, traffic_frame = None, None
-        pmc_path, pmc = latest_pmc_summary()
-        sha = kernel_source_sha()
-        if pmc is not None and world == 1 and args.grid == 64 and w == 2048 and not args.plane_arrays:
-            if pmc.get("kernel_source_sha") == sha:
-                try:
-                    traffic = pmc["render_kernel_traffic_bytes_per_launch"]["lower"]
-                    traffic_frame = pmc["frame_hbm_bytes"]["write"] + pmc["frame_hbm_bytes"]["fetch_raw"]
-                    sq = pmc.get("sq_counters_bench_scene_per_launch", {})
-                    nv = sq.get("render_kernel", {}).get("SQ_INSTS_VALU")
-                    nl = sq.get("build_tile_lists_kernel", {}).get("SQ_INSTS_VALU", 0.0)
-                    if nv:
-                        rate = nv / (kernel_ms * 1e-3)
-                        valu["executed"] = {"wave_instructions_per_launch": nv, "achieved_per_s": rate,
-                                            "frac": rate / VALU_PEAK_WAVE_INSTR,
-                                            "frac_serial_launch": nv / (kt["render_serial_ms"] * 1e-3) / VALU_PEAK_WAVE_INSTR,
-                                            "algorithmic_share": alg_wave_instr / nv,
-                                            "frame_wave_instructions": nv + nl,
-                                            "frame_frac_of_frame_time": ((nv + nl) / (ms_per_step * 1e-3) / VALU_PEAK_WAVE_INSTR) if solo else None}
-                    valu["from"] = {"file": pmc_path, "kernel_source_sha": sha, "kind": "constants of separate --pmc passes"}
-                except KeyError:
-                    traffic, traffic_frame = None, None
-            else:
-                valu["from"] = {"file": pmc_path, "dropped": "taken with other kernel sources "
-                                f"({pmc.get('kernel_source_sha')} != {sha}): traffic and executed counts omitted"}
         result = {
             "metric": "Mrays/sec (whole node), 2048^2 image, 64x64 Gaussian grid", "value": rays / elapsed / 1e6,
             "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            # ms/frame of the metric = what ONE caller of the vrt:: API waits for a frame (strictly serial frames on one
-            # context, measured after the timed region); ms_per_step is the timed loop's wall time per step, which with
-            # several frames in flight is a throughput figure
-            "ms_per_frame": serial_ms if solo else ms_per_step,
             # how long the host took to ENQUEUE the K timed steps (rank 0): where this approaches ms_per_step the loop is host-bound
             "host_enqueue_ms_per_step": t_enqueued / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak" if (solo and world > 1) else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"-g {args.grid} -w {w} (tiles {args.tiles}, mode-8 packing, cull_eps {args.cull_eps:g}, ray-level prune {args.cull_prune:g}, "
                                    f"{'plane arrays' if args.plane_arrays else 'in-kernel rays'})",
-                       "gaussians": int(len(g)), "rays_per_frame": w * h, "tile_list_entries": n_entries,
+                       "gaussians": int(len(g)), "rays_per_frame": w * h,
                        "parallelism": (f"whole frames on each of {world} ranks, no collective" if (solo and world > 1) else
                                        f"tile-shard x{world}" + (f" + RCCL {args.exchange} of sparse shards every {F} frames, assembled on rank 0" if world > 1 else "")
                                        + (f", {F} frames per kernel launch" if (world > 1 and not args.no_batch) else "")),
@@ -797,48 +755,137 @@ def main():
                        "frames_per_gather": (None if solo else F),
                        "gather_batches_in_timed_region": (None if solo else (args.steps + F - 1) // F),
                        "frames_in_flight": nfl,
-                       "stream_probe_us_per_frame": stream_probe,
-                       "frame_equals_single_gpu_frame": frame_ok},
-            "roofline": {"bound": "hbm", "achieved": render_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": render_gbs / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_from": (valu.get("from") if traffic is not None else None),
-                         "kernel": "render_kernel<VCL,AS,4>", "kernel_ms": kernel_ms, "kernel_ms_with_frames_in_flight": kernel_ms_overlapped,
-                         "algorithmic_bytes": render_bytes,
-                         # (an event pair with nothing between reads ~5 us on this stack -- measured in round 1 on an empty
-                         # launch slot; rocprofv3's kernel durations under profiles/ are the event figures minus that)
-                         # strictly serial frames, after the timed region: four events per frame
-                         "launch_sequence_ms": {"lists": kt["lists_ms"], "render_kernel": kt["render_serial_ms"],
-                                                "render_dense_kernel": kt["dense_ms"]},
-                         "frame": {"algorithmic_bytes": frame_bytes, "ms": frame_ms, "achieved": frame_gbs,
-                                   "frac": frame_gbs / HBM_PEAK_GBS, "traffic": traffic_frame},
-                         "note": "the path is VALU/transcendental-bound, not HBM-bound (SURVEY 7 hard part 4): see valu; "
-                                 "traffic = WRITE_SIZE + raw FETCH_SIZE of separate PMC passes (profiles/); with several frames "
-                                 "in flight a launch shares the GPU with the other contexts' kernels and lasts longer "
-                                 "(kernel_ms_with_frames_in_flight); kernel_ms is the serial launch, a component of ms_per_frame"},
-            # the same loop with one context: frame k+1 starts when frame k is done
-            # the same loop at exact settings, and what the timed settings deviate by (checked by the oracle below: "parity")
-            "exact_settings": exact,
-            "collective": ({"backend": dist.get_backend(), "world_size": dist.get_world_size(), "frame_parallel_control": control, "per_rank": per_rank,
-                            "per_rank_note": "a repeat of the timed loop with phase timers on (after the timed region); gather = from enqueue "
-                                             "until the frame stream may use the result (upper bound of the collective; its own duration "
-                                             "where TORCH_NCCL_ENABLE_TIMING=1 makes the backend keep it)"} if world > 1 else None),
-            "serial": {"frames_in_flight": 1, "ms_per_step": serial_ms, "value": w * h / (serial_ms * 1e-3) / 1e6, "steps": n_serial},
-            "moving_camera": moving,
-            "in_flight_sweep_ms_per_step": sweep,   # frames in flight -> ms per step; + the retained-buffer variant of the loop
-            "valu": {**valu, "blocks": st["blocks"], "shaded_blocks": st["shaded_blocks"], "dense_blocks": st["dense_blocks"],
-                     "mean_cell_list": st["tile_entries"] / sb, "mean_block_list": st["list_entries"] / sb,
-                     "mean_ray_list": st["lane_entries"] / (sb * 64), "mean_block_longest_ray_list": st["lane_max_entries"] / sb,
-                     "dense_overflow_blocks": st["overflow_blocks"]},
+                       "stream_probe_us_per_frame": stream_probe},
         }
-        if not args.no_cpu_baseline and world == 1:
-            # the oracle as the CHECKER of the frame the timed loop renders (after the timed region), then as the CPU baseline
-            if args.parity_pixels > 0 and not args.plane_arrays:
-                result["parity"] = parity_check(scene, g, w, h, args.tiles, _rad, args.parity_pixels, 2048 + args.grid, args.cull_eps,
-                                                args.cull_prune, 2.5e-5, st["dense_blocks"] > 0)
-                if exact is not None:
-                    result["parity"]["timed_vs_exact_settings_max_abs"] = float(np.abs(_rad - ex_rad).max())
-            result["cpu_baseline"] = cpu_baseline(scene, g, w, h, args.tiles, args.grid, "")
-            result["speedup_vs_cpu_baseline"] = result["value"] / result["cpu_baseline"]["value"]
+        if args.full:
+            # ---- statistics pass (outside the timed region): list lengths, shaded blocks ----
+            counts = r.tile_counts()
+            n_entries = int(counts.sum())
+            r.enable_stats(True)
+            r.set_shard(0, 1)
+            _img, _rad = r.render(origin, pack)
+            # the gathered + assembled frame of the timed loop must be the single-GPU frame, bit for bit
+            bad = [(i_, int((im.cpu().numpy().view(np.uint32) != _img.reshape(-1)).sum())) for i_, im in enumerate(images)]
+            bad = [b_ for b_ in bad if b_[1]]
+            frame_ok = not bad
+            if bad:
+                print(f"bench.py: frame buffers that differ from the single-GPU frame (buffer, pixels): {bad}", file=sys.stderr)
+            st = r.stats()
+            r.enable_stats(False)
+            r.set_shard(*((0, 1) if solo else (rank, world)))
+            sb = max(st["shaded_blocks"], 1)
+            # ---- roofline.  Algorithmic HBM bytes: 4 B per ray written (+12 B per ray
+            # read with --plane-arrays), the Gaussian rows once (64 B each), the candidate lists once (4 B per entry).
+            # Dominant kernel = render_kernel: it writes the rays it shades and reads their cells' lists; the other rays
+            # of the frame are cleared by the list kernel, so the FRAME figure is given next to it.
+            per_ray = 4 + (12 if args.plane_arrays else 0)
+            share = 1 if solo else world   # tile sharding: a rank's kernels see 1/world of the frame
+            render_bytes = (sb * 64 * per_ray + 4 * st["tile_entries"] + 64 * len(g)) / share
+            frame_bytes = (w * h * per_ray + 64 * len(g) + 4 * n_entries) / share
+            # the dominant kernel's duration is that of the SERIAL launch (frames in flight stretch a launch: it shares the GPU with
+            # the other contexts' kernels, and is then no component of the step); the overlapped figure is kept beside it
+            kernel_ms_overlapped = kernel_ms
+            kernel_ms = kt["render_serial_ms"] if (solo and kt["render_serial_ms"] > 0) else kernel_ms
+            render_gbs = render_bytes / (kernel_ms * 1e-3) / 1e9
+            # the whole frame: wall time per step of the timed region (one rank: nothing but the launch sequence is in it)
+            frame_ms = ms_per_step if solo else kt["lists_ms"] + kt["render_ms"] + kt["dense_ms"]
+            frame_gbs = frame_bytes / (frame_ms * 1e-3) / 1e9
+            # ---- VALU (what actually bounds the path).  ALGORITHMIC lane-ops: per (ray, candidate of its block)
+            # one cull / precompute = 14 lane-ops, per surviving (emitter i, sample k, absorber j) of a ray 16 lane-ops
+            # (1 fma + A&S erf with 1 rcp + 1 fma); both counted by the statistics pass above, nothing skipped is credited.
+            # 64 lane-ops = one wave-instruction equivalent.
+            culls = 64 * st["list_entries"]
+            terms = 5 * st["lane_pairs"]
+            alg_wave_instr = (14 * culls + 16 * terms) / 64.0
+            valu = {"algorithmic": {"ray_candidate_culls": culls, "surviving_ikj_terms": terms,
+                                    "lane_ops": 14 * culls + 16 * terms, "wave_instruction_equivalents": alg_wave_instr,
+                                    "achieved_per_s": alg_wave_instr / (kernel_ms * 1e-3),
+                                    "frac": alg_wave_instr / (kernel_ms * 1e-3) / VALU_PEAK_WAVE_INSTR,
+                                    "frac_serial_launch": alg_wave_instr / (kt["render_serial_ms"] * 1e-3) / VALU_PEAK_WAVE_INSTR,
+                                    # per FRAME TIME of the timed region: what the GPU as a whole sustains with frames in flight
+                                    # (a launch that shares the GPU with other frames' kernels lasts longer than its share of it)
+                                    "frac_of_frame_time": (alg_wave_instr / (ms_per_step * 1e-3) / VALU_PEAK_WAVE_INSTR) if solo else None},
+                    "peak_per_s": VALU_PEAK_WAVE_INSTR,
+                    "peak_note": "spec: 1024 SIMDs x 2.4 GHz / 2 cycles per wave64 VALU instruction (MI355X_MICROARCH.md)"}
+            try:
+                valu["measured_fma_issue"] = json.load(open(VALU_MEASURED_FILE))
+            except (OSError, ValueError):
+                pass
+            # ---- constants from separate PMC passes (rocprofv3 --pmc cannot run inside this process): HBM traffic and
+            # EXECUTED instruction counts per launch.  Used only when they were taken with these very kernel sources.
+            traffic, traffic_frame = None, None
+            pmc_path, pmc = latest_pmc_summary()
+            sha = kernel_source_sha()
+            if pmc is not None and world == 1 and args.grid == 64 and w == 2048 and not args.plane_arrays:
+                if pmc.get("kernel_source_sha") == sha:
+                    try:
+                        traffic = pmc["render_kernel_traffic_bytes_per_launch"]["lower"]
+                        traffic_frame = pmc["frame_hbm_bytes"]["write"] + pmc["frame_hbm_bytes"]["fetch_raw"]
+                        sq = pmc.get("sq_counters_bench_scene_per_launch", {})
+                        nv = sq.get("render_kernel", {}).get("SQ_INSTS_VALU")
+                        nl = sq.get("build_tile_lists_kernel", {}).get("SQ_INSTS_VALU", 0.0)
+                        if nv:
+                            rate = nv / (kernel_ms * 1e-3)
+                            valu["executed"] = {"wave_instructions_per_launch": nv, "achieved_per_s": rate,
+                                                "frac": rate / VALU_PEAK_WAVE_INSTR,
+                                                "frac_serial_launch": nv / (kt["render_serial_ms"] * 1e-3) / VALU_PEAK_WAVE_INSTR,
+                                                "algorithmic_share": alg_wave_instr / nv,
+                                                "frame_wave_instructions": nv + nl,
+                                                "frame_frac_of_frame_time": ((nv + nl) / (ms_per_step * 1e-3) / VALU_PEAK_WAVE_INSTR) if solo else None}
+                        valu["from"] = {"file": pmc_path, "kernel_source_sha": sha, "kind": "constants of separate --pmc passes"}
+                    except KeyError:
+                        traffic, traffic_frame = None, None
+                else:
+                    valu["from"] = {"file": pmc_path, "dropped": "taken with other kernel sources "
+                                    f"({pmc.get('kernel_source_sha')} != {sha}): traffic and executed counts omitted"}
+            # ms/frame of the metric = what ONE caller of the vrt:: API waits for a frame (strictly serial frames on one
+            # context, measured after the timed region); ms_per_step is the timed loop's wall time per step, which with
+            # several frames in flight is a throughput figure
+            result["ms_per_frame"] = serial_ms if solo else ms_per_step
+            result["config"].update({"tile_list_entries": n_entries, "frame_equals_single_gpu_frame": frame_ok})
+            result.update({
+                "roofline": {"bound": "hbm", "achieved": render_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": render_gbs / HBM_PEAK_GBS, "traffic": traffic,
+                             "traffic_from": (valu.get("from") if traffic is not None else None),
+                             "kernel": "render_kernel<VCL,AS,4>", "kernel_ms": kernel_ms, "kernel_ms_with_frames_in_flight": kernel_ms_overlapped,
+                             "algorithmic_bytes": render_bytes,
+                             # (an event pair with nothing between reads ~5 us on this stack -- measured in round 1 on an empty
+                             # launch slot; rocprofv3's kernel durations under profiles/ are the event figures minus that)
+                             # strictly serial frames, after the timed region: four events per frame
+                             "launch_sequence_ms": {"lists": kt["lists_ms"], "render_kernel": kt["render_serial_ms"],
+                                                    "render_dense_kernel": kt["dense_ms"]},
+                             "frame": {"algorithmic_bytes": frame_bytes, "ms": frame_ms, "achieved": frame_gbs,
+                                       "frac": frame_gbs / HBM_PEAK_GBS, "traffic": traffic_frame},
+                             "note": "the path is VALU/transcendental-bound, not HBM-bound (SURVEY 7 hard part 4): see valu; "
+                                     "traffic = WRITE_SIZE + raw FETCH_SIZE of separate PMC passes (profiles/); with several frames "
+                                     "in flight a launch shares the GPU with the other contexts' kernels and lasts longer "
+                                     "(kernel_ms_with_frames_in_flight); kernel_ms is the serial launch, a component of ms_per_frame"},
+                # the same loop with one context: frame k+1 starts when frame k is done
+                # the same loop at exact settings, and what the timed settings deviate by (checked by the oracle below: "parity")
+                "exact_settings": exact,
+                "collective": ({"backend": dist.get_backend(), "world_size": dist.get_world_size(), "frame_parallel_control": control, "per_rank": per_rank,
+                                "per_rank_note": "a repeat of the timed loop with phase timers on (after the timed region); gather = from enqueue "
+                                                 "until the frame stream may use the result (upper bound of the collective; its own duration "
+                                                 "where TORCH_NCCL_ENABLE_TIMING=1 makes the backend keep it)"} if world > 1 else None),
+                "serial": {"frames_in_flight": 1, "ms_per_step": serial_ms, "value": w * h / (serial_ms * 1e-3) / 1e6, "steps": n_serial},
+                "moving_camera": moving,
+                "in_flight_sweep_ms_per_step": sweep,   # frames in flight -> ms per step; + the retained-buffer variant of the loop
+                "valu": {**valu, "blocks": st["blocks"], "shaded_blocks": st["shaded_blocks"], "dense_blocks": st["dense_blocks"],
+                         "mean_cell_list": st["tile_entries"] / sb, "mean_block_list": st["list_entries"] / sb,
+                         "mean_ray_list": st["lane_entries"] / (sb * 64), "mean_block_longest_ray_list": st["lane_max_entries"] / sb,
+                         "dense_overflow_blocks": st["overflow_blocks"]},
+            })
+            if not args.no_cpu_baseline and world == 1:
+                # the oracle as the CHECKER of the frame the timed loop renders (after the timed region), then as the CPU baseline
+                if args.parity_pixels > 0 and not args.plane_arrays:
+                    result["parity"] = parity_check(scene, g, w, h, args.tiles, _rad, args.parity_pixels, 2048 + args.grid, args.cull_eps,
+                                                    args.cull_prune, 2.5e-5, st["dense_blocks"] > 0)
+                    if exact is not None:
+                        result["parity"]["timed_vs_exact_settings_max_abs"] = float(np.abs(_rad - ex_rad).max())
+                result["cpu_baseline"] = cpu_baseline(scene, g, w, h, args.tiles, args.grid, "")
+                result["speedup_vs_cpu_baseline"] = result["value"] / result["cpu_baseline"]["value"]
+        if last_image is not None:
+            dump_image(args.dump_outputs, last_image, w, h)
         print(json.dumps(result))
     barrier()
     for r_ in ctxs:

@@ -4,7 +4,8 @@
   - without a GPU the library refuses to create a context (no CPU fallback), with an error string;
   - the product's host producers (scene.py: grid scene, OBJ loader, camera, view matrix) agree with
     the oracle's restatement of the reference;
-  - the host mirror of the shard map (sharding.py) covers every tile exactly once.
+  - the host mirror of the shard map (sharding.py) covers every tile exactly once;
+  - bench.py's host helpers: gather batch sizes, the --dump-outputs format.
 """
 import ctypes as C
 import os
@@ -164,15 +165,45 @@ def test_shard_table_partitions_the_frame(pkg):
         assert load.max() == load.min()
 
 
-def test_bench_gather_batches_of_a_short_run():
-    """bench.py, N > 1: the driver times 20 steps; a gather batch must then be a fraction of the run (round-2 verdict: one
-    batch of 20 was a single un-overlapped render -> gather -> assemble chain)."""
+def load_bench():
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_gather_batches_of_a_short_run():
+    """bench.py, N > 1: the driver times 20 steps; a gather batch must then be a fraction of the run (round-2 verdict: one
+    batch of 20 was a single un-overlapped render -> gather -> assemble chain)."""
+    bench = load_bench()
     for steps in (4, 12, 20, 40, 100, 127):
         F = bench.gather_batch_frames(32, steps)
         assert 1 <= F <= 32 and (steps + F - 1) // F >= 4, (steps, F)
     assert bench.gather_batch_frames(32, 400) == 32 and bench.gather_batch_frames(32, 20) == 5
     assert bench.gather_batch_frames(32, 1) == 1 and bench.gather_batch_frames(4, 400) == 4
+
+
+def test_bench_dump_image(tmp_path):
+    """bench.py --dump-outputs: R, G, B, A of the packed pixels (A<<24 | R<<16 | G<<8 | B) as float32 beside their raster
+    indices; a small frame whole, a 2048^2 frame as a fixed seeded sample within the 64 MB the dump may hold."""
+    bench = load_bench()
+    rng = np.random.default_rng(5)
+    small = rng.integers(0, 1 << 32, 64 * 48, dtype=np.uint64).astype(np.uint32).view(np.int32)
+    bench.dump_image(str(tmp_path / "s"), small, 64, 48)
+    rgba, idx = np.load(tmp_path / "s" / "image_rgba.npy"), np.load(tmp_path / "s" / "pixel_index.npy")
+    assert rgba.dtype == np.float32 and idx.dtype == np.float64 and rgba.shape == (64 * 48, 4)
+    np.testing.assert_array_equal(idx, np.arange(64 * 48))
+    u = small.view(np.uint32)
+    np.testing.assert_array_equal(rgba, np.stack([(u >> 16) & 255, (u >> 8) & 255, u & 255, u >> 24], axis=1))
+    big = np.arange(2048 * 2048, dtype=np.uint32)
+    for d in ("a", "b"):
+        bench.dump_image(str(tmp_path / d), big, 2048, 2048)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64e6
+    ia, ib = np.load(tmp_path / "a" / "pixel_index.npy"), np.load(tmp_path / "b" / "pixel_index.npy")
+    np.testing.assert_array_equal(ia, ib)
+    assert ia.size == bench.DUMP_PIXELS and (np.diff(ia) > 0).all() and ia[-1] < 2048 * 2048
+    rgba = np.load(tmp_path / "a" / "image_rgba.npy")
+    ii = ia.astype(np.int64)
+    np.testing.assert_array_equal(rgba[:, 0], (ii >> 16) & 255)
+    np.testing.assert_array_equal(rgba[:, 2], ii & 255)

@@ -1,5 +1,6 @@
 """bench.py's contract on one GPU: ONE JSON line with the driver's keys, `value` = rays of exactly K timed steps over their
-wall time, the roofline and CPU-baseline objects, every frame buffer of the timed loop equal to a reference render."""
+wall time; with --full also the roofline and CPU-baseline objects and every frame buffer of the timed loop equal to a reference
+render; with --dump-outputs the frame of the last timed step, equal to a reference render."""
 import json
 import os
 import subprocess
@@ -14,7 +15,8 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("steps,in_flight", [(20, 2), (40, 2)])
 def test_bench_line(tmp_path, steps, in_flight):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "3", "--setup-ms", "5"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "3", "--setup-ms", "5",
+                        "--full"],
                        cwd=tmp_path, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -64,3 +66,35 @@ def test_bench_line(tmp_path, steps, in_flight):
     assert 0 < par["max_abs"] <= par["bound"] <= 5e-5, par
     assert par["timed_vs_exact_settings_max_abs"] <= par["bound"]
     assert d["collective"] is None                                # N = 1: no collective
+
+
+def test_bench_plain_line_and_dump(tmp_path, pkg, renderer):
+    """A plain run is the headline alone; --dump-outputs writes the frame of the last timed step: the fixed seeded pixel sample
+    of the 2048^2 frame, each pixel equal to a fresh render with the benchmark's settings."""
+    import numpy as np
+    from sgrt_amd import scene
+    out = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "21", "--warmup", "3", "--setup-ms", "5",
+                        "--dump-outputs", str(out)], cwd=tmp_path, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{")
+    d = json.loads(lines[0])
+    assert d["steps"] == 21 and d["unit"] == "Mrays/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2048 * 2048 / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-6 * d["value"] and 10e-3 < d["ms_per_step"] < 80e-3
+    for k in ("roofline", "cpu_baseline", "parity", "serial", "moving_camera", "exact_settings", "ms_per_frame"):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["image_rgba.npy", "pixel_index.npy"]
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64e6
+    rgba, idx = np.load(out / "image_rgba.npy"), np.load(out / "pixel_index.npy")
+    assert rgba.dtype == np.float32 and idx.dtype == np.float64 and rgba.shape == (idx.size, 4) and idx.size == 1 << 21
+    w = 2048
+    cam = scene.cli_camera(w, w)[0]
+    renderer.set_gaussians(scene.grid_scene(64))
+    renderer.set_options(pkg.EXP_VCL, pkg.ERF_AS, 1e-9)
+    renderer.set_camera_view(w, w, cam.view)
+    renderer.tile_gaussians(2.0 / 16, 2.0 / 16, cam.view)
+    want = renderer.render(cam.position, pkg.PACK_ROUND | pkg.ALPHA_COMPUTED, want_radiance=False)[0].reshape(-1)[idx.astype(np.int64)]
+    want = np.stack([(want >> s) & 255 for s in (16, 8, 0, 24)], axis=1)
+    assert (want[:, 3] > 0).any()
+    np.testing.assert_array_equal(rgba, want.astype(np.float32))

@@ -316,7 +316,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
     env = dict(os.environ, VRT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",   # what the driver times
-           "--width", "1024", "--no-cpu-baseline"]
+           "--width", "1024", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]

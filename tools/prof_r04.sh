@@ -16,14 +16,14 @@ echo "pmc done"
 cd $R && python3 tools/pmc_traffic.py $OUT > $OUT/pmc_traffic.json && cp $OUT/pmc_traffic.json profiles/r04_pmc_traffic.json
 # --- bench under rocprofv3 --stats, then plain ---
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $R/bench.py --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_serial -o bench -- python3 $R/bench.py --frames-in-flight 1 --no-cpu-baseline > $OUT/bench_serial_under_rocprof.json 2>> $OUT/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_serial -o bench -- python3 $R/bench.py --full --frames-in-flight 1 --no-cpu-baseline > $OUT/bench_serial_under_rocprof.json 2>> $OUT/stats.log
 cd $R
 find $OUT/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/bench_kernel_stats.csv
 find $OUT/stats_serial -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/bench_serial_kernel_stats.csv
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.log
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_20steps.json 2>> $OUT/bench.log
-python3 bench.py --frames-in-flight 1 --no-cpu-baseline > $OUT/bench_serial.json 2>> $OUT/bench.log
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.log
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_20steps.json 2>> $OUT/bench.log
+python3 bench.py --full --frames-in-flight 1 --no-cpu-baseline > $OUT/bench_serial.json 2>> $OUT/bench.log
 python3 tools/timeline.py 64 2048 2> $OUT/timeline.txt > /dev/null
 echo "bench done"
 python3 -c "
