@@ -1,0 +1,246 @@
+// vrt_hip_ctx.hpp -- internal to libvrt_hip.so: the context behind the C ABI (include/vrt_hip.h), the owning buffer types and
+// what the host runtime's translation units share (vrt_hip_api.cpp: context, setters, frame pipeline, shard map;
+// vrt_hip_assembly.cpp: shard assembly; vrt_hip_query.cpp: point queries; vrt_hip_diag.cpp: stats, kernel timing, timelines).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/vrt_hip.h"
+#include "vrt_kernels.h"
+
+#pragma GCC visibility push(hidden) // nothing declared here is part of the library's ABI
+
+// Device memory owned by its holder: freed when the holder goes (hipFree waits for the device first).  reserve() grows
+// without keeping the contents; release() frees now.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { release(); std::swap(p, o.p); std::swap(cap, o.cap); }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    hipError_t reserve(size_t n)
+    {
+        if (n <= cap) return hipSuccess;
+        release();
+        hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
+        if (e == hipSuccess) cap = n ? n : 1;
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// Pinned host memory owned by its holder.
+template <typename T>
+struct PinnedBuf {
+    T *p = nullptr;
+    PinnedBuf &operator=(PinnedBuf &&o) noexcept { std::swap(p, o.p); return *this; }
+    ~PinnedBuf() { if (p) (void)hipHostFree((void *)p); }
+    hipError_t alloc(size_t n, unsigned flags) { *this = PinnedBuf{}; return hipHostMalloc((void **)&p, n * sizeof(T), flags); }
+};
+
+// Every VRT_HIP_* setting of the host runtime, read from the environment once, by vrt_hip_create (read_tuning).  The
+// initialisers are the defaults.
+struct Tuning {
+    int render_waves_per_cu = 13; // VRT_HIP_RENDER_WAVES (1..16): persistent one-wave workgroups per CU: what LDS allows (VGPRs: three
+                                  // per SIMD run at a time; the 13th starts when the first retires)
+    uint32_t render_grid_override = 0; // VRT_HIP_RENDER_GRID (tests): exactly this many block-kernel workgroups, e.g. ONE wave that drains all work queues
+    float cull_ref_n = 4096.f / 3.f; // TileLists::cull_ref_n; VRT_HIP_CULL_REF_N=0: one threshold at every level (round 1)
+    int use_chunks = 1;          // VRT_HIP_CHUNKS: 0 every tile tests every Gaussian (rounds 1-2); 1 (default) chunks first for scenes beyond 8192 Gaussians; 2 always
+    float cull_prune = 6.f;      // VRT_HIP_CULL_PRUNE: the context's first vrt_hip_ctx::cull_prune
+    float table_step = 0.05f;    // VRT_HIP_TABLE_STEP (0..1): the context's first vrt_hip_ctx::table_hx
+    float table_budget = 2.5e-5f; // VRT_HIP_TABLE_BUDGET (> 0): the context's first vrt_hip_ctx::table_budget
+    float table_room = 0.9f;      // VRT_HIP_TABLE_ROOM (0..10]: share of the budget the kernel's ESTIMATE of its bound may fill when it coarsens the spacing
+    float table_adapt = 3.f;      // VRT_HIP_TABLE_ADAPT (1..3): the table kernel may coarsen the requested spacing by up to this factor where its
+                                  // estimate of the bound leaves room (1 = never)
+    int claim_early = 8;         // CellGrid::claim_early (measured: 2 leaves `-g 16 -w 2048` at 67 us, 8 takes it to 43, "always" costs a 12-waves-per-CU grid 8 % in flight); VRT_HIP_CLAIM_EARLY=0: the block kernel's waves ask for their next block only when they are done with the current one
+    bool skip_idle_dense = true; // VRT_HIP_DENSE_SKIP=0: the dense kernel is launched behind every block kernel
+    int dense_waves = 16;        // waves per block in the dense kernel (tuning knob: VRT_HIP_DENSE_WAVES = 4 | 8 | 16; 17 = 16 waves without saturation skipping, A/B)
+    bool timeline = false;       // VRT_HIP_TIMELINE set: vrt_hip_render prints where the kernels' time goes (print_timeline) ...
+    std::string timeline_csv;    // ... and, when its value names a .csv file, writes the raw stamps there
+    bool table_diag = false;     // VRT_HIP_TABLE_DIAG set: vrt_hip_render with stats on prints the table phase split
+    bool retain_frame = true;    // VRT_HIP_RETAIN_FRAME=0: every vrt_hip_frame clears its whole image (no retained history)
+};
+
+enum TileMode { TILES_NONE = 0, TILES_HOST = 1, TILES_DEVICE = 2 };
+
+struct vrt_hip_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    // the caller's stream the last *_device call enqueued on (may differ from `stream`): state-changing calls wait for
+    // it before they touch buffers its kernels may still be reading (quiesce)
+    hipStream_t last_stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::string err;
+    Tuning tune;
+
+    // counts every change of scene, options or table settings (vrt_hip_state_generation): a holder of mirrored contexts
+    // (vrt_hip_group's batch lanes) sees when they are out of date
+    uint64_t state_gen = 1;
+    // scene (static SoA copy kept so options can be re-applied)
+    uint32_t n = 0;
+    DevBuf<float> soa[9]; // mu_x mu_y mu_z ar ag ab aa sigma mag
+    bool has_alpha = false;
+    DevBuf<float4> mu_sig, gA, gB, gC, gD;
+    DevBuf<float4> gChunk;       // bounding spheres of every 64 consecutive Gaussians (launch_build_chunks): the tile level tests these first
+    DevBuf<uint32_t> iota;
+    bool tables_dirty = true;
+    bool gA_valid = false;
+    float gA_origin[3] = { 0, 0, 0 };
+
+    // tiles.  "ref" lists carry the reference semantics (tiles_t): uploaded by the caller (TILES_HOST), one
+    // tile holding everything (TILES_NONE), or produced on demand for queries (TILES_DEVICE).  "work" lists
+    // are what the render kernel scans: ref lists intersected with the tile-level cull.
+    TileMode tile_mode = TILES_NONE;
+    float tw = 2.f, th = 2.f;
+    uint32_t tiles_w = 1, tiles_h = 1;
+    float view[16] = { 0 };
+    DevBuf<uint32_t> ref_start, ref_count, ref_indices;
+    bool ref_valid = false;
+    DevBuf<uint32_t> w_start, w_count, w_indices;
+    // frame batches (vrt_hip_frame_batch_device): while `defer` is set the three per-frame launches are recorded, not made
+    vrtk::FrameArgs *defer = nullptr;
+    struct Deferred {
+        bool lists = false, from_list = false, render = false, order = false;
+        uint32_t list_grid = 0, render_grid = 0, dense_grid = 0;
+    } deferred;
+    // the context a batch is issued through keeps the argument rows: a ring of pinned host slots and device slots
+    static constexpr int BATCH_SLOTS = 4;
+    PinnedBuf<vrtk::FrameArgs> batch_host;
+    DevBuf<vrtk::FrameArgs> batch_dev;
+    size_t batch_cap = 0; // frames per slot
+    hipEvent_t batch_copied[BATCH_SLOTS] = {};
+    uint32_t batch_seq = 0;
+    // retained assembly (vrt_hip_scatter_sparse_retained_device): which cells the buffer's last assembly stored
+    struct Retained {
+        uint32_t *image = nullptr;
+        uint64_t sig = 0;
+        uint32_t bg = 0, seq = 0;
+        DevBuf<uint32_t> stamp;
+    };
+    std::vector<Retained> retained; // one history per frame buffer (at most MAX_ASSEMBLY_FRAMES, oldest dropped)
+    // tile cones of the list kernel: a function of the rays and the tile geometry only, kept across frames (cone_key =
+    // what they were made for)
+    DevBuf<float4> tile_cones;
+    uint32_t cone_gen = 0;     // tag of the rows made for cone_key's camera (BinArgs::cone_gen)
+    std::string cone_key;
+    uint32_t plane_gen = 0;
+    // cells with at most this many candidates are shaded last (CellGrid::light_threshold; 32 and more file too many cells as light, profiles/r02_experiments.md);
+    // lists_light: what the lists now in the buffers were built with (0 for sparse shards and the two-kernel list path)
+    static constexpr uint32_t light_cells = 24;
+    uint32_t lists_light = 0;
+    float albedo_scale = 1.f;    // max(1, largest |albedo| of the scene): divides the prune budget
+    float cull_prune;            // vrt_hip_set_cull_prune(): a block-kernel ray may drop the smallest entries of its list while their sum stays below
+                                 // cull_prune * cull_ref_n * cull_eps (prune_list; 0 = off).  6: 3 * 6 * 1365 * 1e-9 = 2.46e-5 -- DESIGN.md section 4
+    // second level: 32x32-pixel cells of the local tiles + the active / dense queues of the render kernels
+    DevBuf<uint32_t> c_count, c_indices, c_active, c_dense, c_dense_sorted, c_scratch, c_overflow, c_counters, c_rq, c_slot;
+    uint32_t rq_gen = 0;      // render launches: selects the work-queue counter set (CellGrid::rq)
+    uint32_t cells_x = 1, cells_y = 1, cstride = 1, n_cells = 0;
+    int lists_for_shard = -1; // sharding mode the cell lists were built for
+    bool prep_pending = false; // the per-origin table (gA) of gA_origin is still to be written: by the next list kernel, or by flush_prep()
+    bool lists_fresh = false; // the queue counters were zeroed by the list build of this very call
+    uint32_t list_gen = 0;    // list generation: selects the counter set (see cell_grid)
+    // dense-launch feedback (CellGrid::feedback): host-mapped, read frames later
+    PinnedBuf<volatile uint32_t> h_fb;
+    uint32_t *d_fb = nullptr;
+    // dense-launch sizing: frame_seq counts render launches; a report in h_fb[3] (the sequence number of the frame
+    // that wrote it) newer than reset_seq comes from the current scene / camera / options
+    // A camera that moved keeps the reports (an orbit changes the picture gradually) but widens the idle launch until a
+    // report from the new pose has arrived (cam_seq): a jump to a pose with dense cells costs one frame at a quarter of
+    // the GPU, not one frame on one workgroup.
+    uint32_t frame_seq = 0, reset_seq = 0, cam_seq = 0;
+    int num_cus = 256;
+    float table_hx;               // vrt_hip_set_table_step(): requested node spacing of the table kernel; 0 = the exact kernels only
+    float table_budget;           // vrt_hip_set_table_budget(): worst-case change of a ray's radiance the table kernel may cause
+    static constexpr int dense_idle_grid = 1; // workgroups of the dense launch when nothing is expected for it: one
+                             // 1024-thread workgroup finds a CU with 61 KB of LDS free sooner than eight do (-2 % with frames in flight)
+    bool work_is_ref = false; // render straight from the ref lists (no tile-level cull possible)
+    bool lists_dirty = true;
+    DevBuf<float> xc, yc;
+    float grid_tw = 0.f, grid_th = 0.f;
+    uint32_t grid_n = 0xFFFFFFFFu;
+
+    // rays
+    uint32_t w = 0, h = 0;
+    bool plane_mode = false;
+    bool view_mode = false;   // rays from inverse(view) (vrt_hip_set_camera_view)
+    float inv_view[16] = { 0 };
+    bool plane_affine = false; // plane arrays are a pinhole pattern: corner rays bound a tile's cone
+    DevBuf<float> xs, ys, zs;
+    float cam_pos[3] = { 0, 0, 0 }, cam_right[3] = { 1, 0, 0 }, cam_up[3] = { 0, 1, 0 }, cam_front[3] = { 0, 0, -1 };
+    float focal = 1.f;
+    bool rays_set = false;
+
+    // options
+    int exp_kind = VRT_EXP_VCL, erf_kind = VRT_ERF_AS;
+    float cull_eps = 1e-9f;
+
+    // sharding
+    int rank = 0, world = 1;
+    DevBuf<uint32_t> tile_map, slot_tiles;
+    uint32_t n_local = 0, n_slots = 0;
+    bool shard_dirty = true;
+
+    // scratch + statistics
+    // d_image: the library's own frame buffer (vrt_hip_frame, vrt_hip_render).  Retained between vrt_hip_frame calls: own_stamp[cell]
+    // = own_seq of the last frame that lit the cell, valid while own_sig (image size, tile grid, background) stays and nothing else
+    // wrote the buffer (own_seq = 0: the next frame clears everything and starts a new history)
+    DevBuf<uint32_t> own_stamp;
+    uint32_t own_seq = 0;
+    struct OwnGeometry { // what a retained history is valid for: compared field by field (a hash of overlapping fields let two tile grids collide)
+        uint32_t w = 0, h = 0, tiles_w = 0, tiles_h = 0, tile_w = 0, tile_h = 0, background = 0;
+        const uint32_t *image = nullptr;
+        bool operator==(const OwnGeometry &o) const
+        {
+            return w == o.w && h == o.h && tiles_w == o.tiles_w && tiles_h == o.tiles_h && tile_w == o.tile_w && tile_h == o.tile_h &&
+                   background == o.background && image == o.image;
+        }
+    } own_sig;
+    bool retain_next = false; // set by vrt_hip_frame around its render_common call
+    DevBuf<uint32_t> d_image;
+    DevBuf<float4> d_rad;
+    DevBuf<unsigned long long> d_stats, d_timeline; // d_timeline: VRT_HIP_TIMELINE diagnostics
+    size_t timeline_items = 0, timeline_tiles = 0;
+    DevBuf<unsigned long long> d_timeline_lists;
+    bool stats_on = false;
+    vrt_hip_stats last{};
+    // kernel timing ring (vrt_hip_enable_kernel_timing)
+    static constexpr int TIMING_RING = 512;
+    bool timing_on = false;
+    std::vector<hipEvent_t> tev; // 4 per slot: before lists, before render, after render, after dense
+    bool timing_full = true;
+    uint32_t timing_period = 1, timing_frame = 0;
+    uint64_t timing_count = 0;
+};
+
+int fail(vrt_hip_ctx *c, int code, const std::string &msg); // records msg (c's, or vrt_hip_create's) and returns code
+
+#define HIPCHK(c, call)                                                                            \
+    do {                                                                                           \
+        hipError_t _e = (call);                                                                    \
+        if (_e != hipSuccess)                                                                      \
+            return fail((c), VRT_HIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+// vrt_hip_api.cpp
+int quiesce(vrt_hip_ctx *c);
+int check_ready(vrt_hip_ctx *c);
+int rebuild_tables(vrt_hip_ctx *c);
+int rebuild_shard(vrt_hip_ctx *c);
+vrtk::SceneTables tables(const vrt_hip_ctx *c);
+vrtk::TileLists tile_geometry(const vrt_hip_ctx *c);
+uint32_t sparse_capacity(vrt_hip_ctx *c); // cells a sparse shard of this context can hold (the same on every rank)
+// vrt_hip_diag.cpp
+int ensure_timing_ring(vrt_hip_ctx *c);
+int read_stats(vrt_hip_ctx *c);
+void print_timeline(vrt_hip_ctx *c);
+
+#pragma GCC visibility pop

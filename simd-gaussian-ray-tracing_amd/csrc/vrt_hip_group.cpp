@@ -9,14 +9,12 @@
 // shard's used prefix otherwise.  No collective library is involved: one process owns all devices, so the "gather" is
 // peer loads of the assembling kernel -- the same wires RCCL's own send/recv kernels use (bench.py, one process per
 // GPU, goes through RCCL instead).
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "../../include/vrt_hip.h"
+#include "vrt_hip_ctx.hpp" // DevBuf
 
 struct vrt_hip_group {
     struct Member {
@@ -24,22 +22,20 @@ struct vrt_hip_group {
         vrt_hip_ctx *ctx = nullptr;
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr;       // this member's shard of the current frame is complete
-        uint32_t *shard = nullptr;       // sparse shard buffer on the member's device
-        size_t shard_words = 0;
-        uint32_t *staged = nullptr;      // copy on member 0's device when member 0 cannot read `shard` directly
+        DevBuf<uint32_t> shard;          // sparse shard buffer on the member's device
+        DevBuf<uint32_t> staged;         // copy on member 0's device when member 0 cannot read `shard` directly
         bool peer_ok = true;
         // frame batches: lanes[f] renders frame f of a batch (lanes[0] = ctx; the others mirror its scene and options)
         std::vector<vrt_hip_ctx *> lanes;
         uint64_t mirrored_gen = 0;       // vrt_hip_state_generation(ctx) the mirrors were copied at
-        uint32_t *bshard = nullptr;      // the batch's sparse shards, frame f at bshard + f * bwords
+        DevBuf<uint32_t> bshard;         // the batch's sparse shards, frame f at bshard + f * bwords
         size_t bwords = 0;               // words per frame
         int bframes = 0;                 // frames the buffer holds
-        uint32_t *bstaged = nullptr;
+        DevBuf<uint32_t> bstaged;
     };
     std::vector<Member> m;
-    uint32_t *image = nullptr;           // assembled frame, member 0's device
-    size_t image_px = 0;
-    std::vector<uint32_t *> bimages;     // assembled frames of the last batch, member 0's device
+    DevBuf<uint32_t> image;              // assembled frame, member 0's device
+    std::vector<DevBuf<uint32_t>> bimages; // assembled frames of the last batch, member 0's device
     size_t bimage_px = 0;
     hipEvent_t assembled = nullptr;      // the previous frame has been assembled: shard buffers may be overwritten
     bool have_assembled = false;
@@ -116,18 +112,16 @@ void vrt_hip_group_destroy(vrt_hip_group *g)
         (void)hipSetDevice(mb.device);
         if (mb.stream) (void)hipStreamSynchronize(mb.stream);
     }
-    if (!g->m.empty()) {
+    if (!g->m.empty()) { // the buffers are freed with their own device current
         (void)hipSetDevice(g->m[0].device);
-        if (g->image) (void)hipFree(g->image);
-        for (auto &mb : g->m) if (mb.staged) (void)hipFree(mb.staged);
-        for (auto &mb : g->m) if (mb.bstaged) (void)hipFree(mb.bstaged);
-        for (auto p : g->bimages) if (p) (void)hipFree(p);
+        g->image.release();
+        for (auto &mb : g->m) { mb.staged.release(); mb.bstaged.release(); }
+        g->bimages.clear();
         if (g->assembled) (void)hipEventDestroy(g->assembled);
     }
     for (auto &mb : g->m) {
         (void)hipSetDevice(mb.device);
-        if (mb.shard) (void)hipFree(mb.shard);
-        if (mb.bshard) (void)hipFree(mb.bshard);
+        mb.shard.release(); mb.bshard.release();
         for (size_t k = 1; k < mb.lanes.size(); ++k) if (mb.lanes[k]) vrt_hip_destroy(mb.lanes[k]);
         if (mb.done) (void)hipEventDestroy(mb.done);
         if (mb.stream) (void)hipStreamDestroy(mb.stream);
@@ -142,7 +136,7 @@ vrt_hip_ctx *vrt_hip_group_ctx(vrt_hip_group *g, int member)
     return (g && member >= 0 && member < (int)g->m.size()) ? g->m[member].ctx : nullptr;
 }
 const char *vrt_hip_group_last_error(const vrt_hip_group *g) { return g ? g->err.c_str() : g_group_create_error.c_str(); }
-const uint32_t *vrt_hip_group_image_device(const vrt_hip_group *g) { return g ? g->image : nullptr; }
+const uint32_t *vrt_hip_group_image_device(const vrt_hip_group *g) { return g ? g->image.p : nullptr; }
 
 int vrt_hip_group_frame(vrt_hip_group *g, float tw, float th, const float view[16], const float origin[3], int pack_flags,
                         uint32_t *image_out, int wait)
@@ -158,20 +152,17 @@ int vrt_hip_group_frame(vrt_hip_group *g, float tw, float th, const float view[1
         if (rc0 != VRT_HIP_OK) return gfail(g, rc0, std::string("group_frame: member ") + std::to_string(i) + ": " + vrt_hip_last_error(mb.ctx));
         const size_t words = vrt_hip_sparse_shard_words(mb.ctx);
         if (!words) return gfail(g, VRT_HIP_ERR_INVALID, "group_frame: set the rays of every member first (vrt_hip_set_camera_view / set_plane)");
-        if (words > mb.shard_words) {
+        if (words > mb.shard.cap) {
             GCHK(g, hipStreamSynchronize(mb.stream));
             // the previous frame's assembly on member 0's stream may still be reading this shard (peer access) or its
             // staged copy: wait for it on the host before either is freed (round-2 advisor finding)
             if (g->have_assembled) GCHK(g, hipEventSynchronize(g->assembled));
-            if (mb.shard) (void)hipFree(mb.shard);
-            mb.shard = nullptr; mb.shard_words = 0;
-            GCHK(g, hipMalloc((void **)&mb.shard, words * sizeof(uint32_t)));
-            mb.shard_words = words;
-            if (mb.staged) { (void)hipSetDevice(g->m[0].device); (void)hipFree(mb.staged); mb.staged = nullptr; (void)hipSetDevice(mb.device); }
+            GCHK(g, mb.shard.reserve(words));
+            if (mb.staged.p) { (void)hipSetDevice(g->m[0].device); mb.staged.release(); (void)hipSetDevice(mb.device); }
         }
         // the previous frame's assembly (on member 0) still reads this buffer
         if (g->have_assembled) GCHK(g, hipStreamWaitEvent(mb.stream, g->assembled, 0));
-        const int rc = vrt_hip_frame_sparse_device(mb.ctx, tw, th, view, origin, pack_flags, mb.shard, mb.stream);
+        const int rc = vrt_hip_frame_sparse_device(mb.ctx, tw, th, view, origin, pack_flags, mb.shard.p, mb.stream);
         if (rc != VRT_HIP_OK) return gfail(g, rc, std::string("group_frame: member ") + std::to_string(i) + ": " + vrt_hip_last_error(mb.ctx));
         GCHK(g, hipEventRecord(mb.done, mb.stream));
     }
@@ -183,37 +174,34 @@ int vrt_hip_group_frame(vrt_hip_group *g, float tw, float th, const float view[1
         auto &mb = g->m[i];
         if (i) GCHK(g, hipStreamWaitEvent(root.stream, mb.done, 0));
         if (mb.device == root.device || mb.peer_ok) {
-            ptrs[i] = mb.shard;
+            ptrs[i] = mb.shard.p;
         } else {
             // no peer access: the used prefix of the shard is copied across.  Its length is data (header word 0), so
             // this path reads the header on the host first -- one round trip per member and frame, only without xGMI
             uint32_t hdr[4] = { 0, 0, 0, 0 };
             GCHK(g, hipSetDevice(mb.device));
             GCHK(g, hipEventSynchronize(mb.done));
-            GCHK(g, hipMemcpy(hdr, mb.shard, sizeof hdr, hipMemcpyDeviceToHost));
+            GCHK(g, hipMemcpy(hdr, mb.shard.p, sizeof hdr, hipMemcpyDeviceToHost));
             GCHK(g, hipSetDevice(root.device));
-            if (!mb.staged) GCHK(g, hipMalloc((void **)&mb.staged, mb.shard_words * sizeof(uint32_t)));
+            GCHK(g, mb.staged.reserve(mb.shard.cap));
             const size_t pix_off = (4 + (size_t)hdr[1] + 3) / 4 * 4;
-            const size_t used = std::min(mb.shard_words, pix_off + (size_t)hdr[0] * 1024);
-            GCHK(g, hipMemcpyPeerAsync(mb.staged, root.device, mb.shard, mb.device, used * sizeof(uint32_t), root.stream));
-            ptrs[i] = mb.staged;
+            const size_t used = std::min(mb.shard.cap, pix_off + (size_t)hdr[0] * 1024);
+            GCHK(g, hipMemcpyPeerAsync(mb.staged.p, root.device, mb.shard.p, mb.device, used * sizeof(uint32_t), root.stream));
+            ptrs[i] = mb.staged.p;
         }
     }
     const size_t npix = vrt_hip_image_pixels(root.ctx); // w * h of member 0's rays
     if (!npix) return gfail(g, VRT_HIP_ERR_INVALID, "group_frame: member 0 has no image size");
-    if (npix > g->image_px) {
+    if (npix > g->image.cap) {
         GCHK(g, hipStreamSynchronize(root.stream));
-        if (g->image) (void)hipFree(g->image);
-        g->image = nullptr; g->image_px = 0;
-        GCHK(g, hipMalloc((void **)&g->image, npix * sizeof(uint32_t)));
-        g->image_px = npix;
+        GCHK(g, g->image.reserve(npix));
     }
     // g->image is the group's own buffer and only this call writes it: the retained variant resets just the cells that went dark
-    const int rc = vrt_hip_scatter_sparse_retained_device(root.ctx, ptrs.data(), n, pack_flags, g->image, root.stream);
+    const int rc = vrt_hip_scatter_sparse_retained_device(root.ctx, ptrs.data(), n, pack_flags, g->image.p, root.stream);
     if (rc != VRT_HIP_OK) return gfail(g, rc, std::string("group_frame: assemble: ") + vrt_hip_last_error(root.ctx));
     GCHK(g, hipEventRecord(g->assembled, root.stream));
     g->have_assembled = true;
-    if (image_out) GCHK(g, hipMemcpyAsync(image_out, g->image, npix * sizeof(uint32_t), hipMemcpyDeviceToHost, root.stream));
+    if (image_out) GCHK(g, hipMemcpyAsync(image_out, g->image.p, npix * sizeof(uint32_t), hipMemcpyDeviceToHost, root.stream));
     if (image_out || wait) GCHK(g, hipStreamSynchronize(root.stream));
     return VRT_HIP_OK;
 }
@@ -258,15 +246,14 @@ int vrt_hip_group_frame_batch(vrt_hip_group *g, int nf, float tw, float th, cons
         if (words != mb.bwords || nf > mb.bframes) {
             GCHK(g, hipStreamSynchronize(mb.stream));
             if (g->have_assembled) GCHK(g, hipEventSynchronize(g->assembled)); // member 0 may still be reading the old buffer
-            if (mb.bshard) (void)hipFree(mb.bshard);
-            mb.bshard = nullptr; mb.bwords = 0; mb.bframes = 0;
-            GCHK(g, hipMalloc((void **)&mb.bshard, words * (size_t)nf * sizeof(uint32_t)));
+            mb.bwords = 0; mb.bframes = 0;
+            GCHK(g, mb.bshard.reserve(words * (size_t)nf));
             mb.bwords = words; mb.bframes = nf;
-            if (mb.bstaged) { (void)hipSetDevice(g->m[0].device); (void)hipFree(mb.bstaged); mb.bstaged = nullptr; (void)hipSetDevice(mb.device); }
+            if (mb.bstaged.p) { (void)hipSetDevice(g->m[0].device); mb.bstaged.release(); (void)hipSetDevice(mb.device); }
         }
         if (g->have_assembled) GCHK(g, hipStreamWaitEvent(mb.stream, g->assembled, 0)); // the previous assembly still reads the shards
         std::vector<uint32_t *> outs(nf);
-        for (int f = 0; f < nf; ++f) outs[f] = mb.bshard + (size_t)f * mb.bwords;
+        for (int f = 0; f < nf; ++f) outs[f] = mb.bshard.p + (size_t)f * mb.bwords;
         const int rc = vrt_hip_frame_batch_device(mb.lanes.data(), nf, tw, th, views, origins, pack_flags, outs.data(), 2 /* sparse shards */, mb.stream);
         if (rc != VRT_HIP_OK) return gfail(g, rc, std::string("group_frame_batch: member ") + std::to_string(i) + ": " + vrt_hip_last_error(mb.lanes[0]));
         GCHK(g, hipEventRecord(mb.done, mb.stream));
@@ -279,40 +266,42 @@ int vrt_hip_group_frame_batch(vrt_hip_group *g, int nf, float tw, float th, cons
         auto &mb = g->m[i];
         if (i) GCHK(g, hipStreamWaitEvent(root.stream, mb.done, 0));
         if (mb.device == root.device || mb.peer_ok) {
-            ptrs[i] = mb.bshard;
+            ptrs[i] = mb.bshard.p;
         } else { // no peer access: the whole batch buffer is copied across
-            if (!mb.bstaged) GCHK(g, hipMalloc((void **)&mb.bstaged, mb.bwords * (size_t)mb.bframes * sizeof(uint32_t)));
-            GCHK(g, hipMemcpyPeerAsync(mb.bstaged, root.device, mb.bshard, mb.device, mb.bwords * (size_t)nf * sizeof(uint32_t), root.stream));
-            ptrs[i] = mb.bstaged;
+            GCHK(g, mb.bstaged.reserve(mb.bwords * (size_t)mb.bframes));
+            GCHK(g, hipMemcpyPeerAsync(mb.bstaged.p, root.device, mb.bshard.p, mb.device, mb.bwords * (size_t)nf * sizeof(uint32_t), root.stream));
+            ptrs[i] = mb.bstaged.p;
         }
     }
     const size_t npix = (size_t)w * h;
     if (npix != g->bimage_px || (int)g->bimages.size() < nf) {
         GCHK(g, hipStreamSynchronize(root.stream));
-        if (npix != g->bimage_px) { for (auto p : g->bimages) if (p) (void)hipFree(p); g->bimages.clear(); }
+        if (npix != g->bimage_px) g->bimages.clear();
         while ((int)g->bimages.size() < nf) {
-            uint32_t *p = nullptr;
-            GCHK(g, hipMalloc((void **)&p, npix * sizeof(uint32_t)));
-            g->bimages.push_back(p);
+            DevBuf<uint32_t> b;
+            GCHK(g, b.reserve(npix));
+            g->bimages.push_back(std::move(b));
         }
         g->bimage_px = npix;
     }
+    std::vector<uint32_t *> images(nf);
+    for (int f = 0; f < nf; ++f) images[f] = g->bimages[f].p;
     // the group's own buffers, written by nothing but this call: retained assembly (only cells that went dark are reset)
-    const int rc = vrt_hip_scatter_sparse_batch_device(root.ctx, ptrs.data(), n, g->m[0].bwords, nf, pack_flags, g->bimages.data(), 1, root.stream);
+    const int rc = vrt_hip_scatter_sparse_batch_device(root.ctx, ptrs.data(), n, g->m[0].bwords, nf, pack_flags, images.data(), 1, root.stream);
     if (rc != VRT_HIP_OK) return gfail(g, rc, std::string("group_frame_batch: assemble: ") + vrt_hip_last_error(root.ctx));
     GCHK(g, hipEventRecord(g->assembled, root.stream));
     g->have_assembled = true;
     bool any = false;
     if (images_out)
         for (int f = 0; f < nf; ++f)
-            if (images_out[f]) { GCHK(g, hipMemcpyAsync(images_out[f], g->bimages[f], npix * sizeof(uint32_t), hipMemcpyDeviceToHost, root.stream)); any = true; }
+            if (images_out[f]) { GCHK(g, hipMemcpyAsync(images_out[f], g->bimages[f].p, npix * sizeof(uint32_t), hipMemcpyDeviceToHost, root.stream)); any = true; }
     if (any || wait) GCHK(g, hipStreamSynchronize(root.stream));
     return VRT_HIP_OK;
 }
 
 const uint32_t *vrt_hip_group_batch_image_device(const vrt_hip_group *g, int f)
 {
-    return (g && f >= 0 && f < (int)g->bimages.size()) ? g->bimages[f] : nullptr;
+    return (g && f >= 0 && f < (int)g->bimages.size()) ? g->bimages[f].p : nullptr;
 }
 
 int vrt_hip_group_sync(vrt_hip_group *g)
