@@ -186,6 +186,30 @@ int vrt_hip_frame(vrt_hip_ctx *ctx, float tw, float th, const float view[16], co
                   uint32_t *image_out, int wait);
 int vrt_hip_sync(vrt_hip_ctx *ctx);
 
+/* -------- host frames: the frame loop's `image` in host memory (main.cpp:245, rt.h:344-346, 388-399) ---------------------
+ * The reference renders every frame into a u32 *image that its caller allocated once in host memory (64-byte aligned,
+ * main.cpp:245) and that the renderer overwrites frame after frame (rt.h:344-346, copy loop rt.h:388-399).  Register such
+ * a buffer once; then each vrt_hip_frame_host enqueues the frame and its delivery into the buffer on the context's stream
+ * and returns, and vrt_hip_sync waits.  A delivery writes only the 32x32-pixel cells that changed in that buffer since its
+ * last delivery (cells lit now, and cells lit then that are dark now); the first delivery, another image size, tile grid or
+ * background, and frames whose per-cell stamps were not kept (VRT_HIP_RETAIN_FRAME=0) copy the whole frame.  Up to 16
+ * buffers per context (a ring of frames in flight), each with its own history. */
+/* Page-locks and maps a caller-owned host buffer of `pixels` u32s for this context (hipHostRegister, mapped).  `image` must
+ * be 64-byte aligned (what simd::aligned_malloc gives, main.cpp:245).  Refused (VRT_HIP_ERR_INVALID): NULL or misaligned
+ * pointer, 0 pixels, a buffer already registered, with this or any context.  The buffer's history starts empty: its
+ * next delivery is a full one. */
+int vrt_hip_host_register(vrt_hip_ctx *ctx, uint32_t *image, size_t pixels);
+/* Waits for every frame of this context still in flight, then unregisters the buffer.  vrt_hip_destroy does the same for
+ * every buffer still registered. */
+int vrt_hip_host_unregister(vrt_hip_ctx *ctx, uint32_t *image);
+/* The frame of vrt_hip_frame (tile_gaussians + render into the context's own buffer, the same bits), then delivered into the
+ * registered buffer `image` on the context's stream; returns once both are enqueued.  `image` holds the frame (its first
+ * w*h pixels, what vrt_hip_frame(.., image_out, 1) returns) when vrt_hip_sync(ctx) returns.  The caller promises that
+ * nothing but this context's deliveries wrote `image` since it was registered.  VRT_HIP_ERR_INVALID, with nothing
+ * enqueued, when `image` is not registered with this context or holds fewer than w*h pixels. */
+int vrt_hip_frame_host(vrt_hip_ctx *ctx, float tw, float th, const float view[16], const float origin[3], int pack_flags,
+                       uint32_t *image);
+
 /* Multi-GPU tile sharding: the context renders only tiles t with shard_of(t) == rank.
  * Owned tiles are written tile-major into a compact buffer of
  * vrt_hip_shard_pixels() u32s: [local tile][tile_h][tile_w].  assemble() scatters the

@@ -10,6 +10,7 @@ The directory name contains '-', so import it through `load()` in tests/conftest
 __graft_entry__.py (importlib by path) under the module name `sgrt_amd`.
 """
 import ctypes as C
+import mmap
 import os
 import subprocess
 
@@ -79,6 +80,9 @@ SYMBOLS = {
     "vrt_hip_set_camera_view": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _f32p]),
     "vrt_hip_frame": (C.c_int, [_vp, C.c_float, C.c_float, _f32p, _f32p, C.c_int, _vp, C.c_int]),
     "vrt_hip_sync": (C.c_int, [_vp]),
+    "vrt_hip_host_register": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "vrt_hip_host_unregister": (C.c_int, [_vp, _vp]),
+    "vrt_hip_frame_host": (C.c_int, [_vp, C.c_float, C.c_float, _f32p, _f32p, C.c_int, _vp]),
     "vrt_hip_assemble_shards_device": (C.c_int, [_vp, _vp, _vp, _vp]),
     "vrt_hip_assemble_shards_strided_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
     "vrt_hip_image_pixels": (C.c_size_t, [_vp]),
@@ -147,6 +151,13 @@ def _fp(a):
     return a.ctypes.data_as(_f32p)
 
 
+def host_frame(w, h):
+    """A host frame buffer for Renderer.register_host: uint32 [h, w] in anonymous memory of its own whole pages (page
+    aligned, so two registrations never share a page).  The array keeps its memory alive."""
+    mm = mmap.mmap(-1, max(1, int(w) * int(h)) * 4)
+    return np.frombuffer(mm, np.uint32, count=int(w) * int(h)).reshape(int(h), int(w))
+
+
 def _f3(v):
     return np.ascontiguousarray(np.asarray(v, np.float32)[:3])
 
@@ -164,15 +175,19 @@ class Renderer:
                 raise VrtHipError(f"vrt_hip_create({device}) failed ({rc}): {self._L.vrt_hip_last_error(None).decode()}")
             _handle = h
         self._h = _handle
+        self._host = {}   # registered host buffers by address: kept alive while the GPU may write them
         self.n = 0
         self.w = self.h = 0
         self.table_step = float(os.environ.get("VRT_HIP_TABLE_STEP", TABLE_STEP_DEFAULT))
 
     def close(self):
         if getattr(self, "_h", None):
+            for addr in list(self._host):   # each waits for the frames in flight, then unregisters (destroy would too)
+                self._L.vrt_hip_host_unregister(self._h, addr)
             if self._owned:
                 self._L.vrt_hip_destroy(self._h)
             self._h = None
+            self._host.clear()              # no frame of this context can write the arrays any more
 
     def __del__(self):
         try:
@@ -322,6 +337,29 @@ class Renderer:
 
     def sync(self):
         self._chk(self._L.vrt_hip_sync(self._h), "sync")
+
+    # ---- host frames (a frame buffer in host memory, registered once) ----
+    def register_host(self, arr):
+        """vrt_hip_host_register: `arr` (uint32, C-contiguous; host_frame() makes one) becomes a delivery target of this
+        context.  The Renderer holds a reference to it until unregister_host / close."""
+        if not isinstance(arr, np.ndarray) or arr.dtype != np.uint32 or not arr.flags.c_contiguous:
+            raise VrtHipError("register_host: a C-contiguous uint32 array is required")
+        addr = arr.ctypes.data
+        self._chk(self._L.vrt_hip_host_register(self._h, addr, arr.size), "host_register")
+        self._host[addr] = arr
+
+    def unregister_host(self, arr):
+        """vrt_hip_host_unregister: returns once every frame in flight has landed."""
+        addr = arr.ctypes.data
+        self._chk(self._L.vrt_hip_host_unregister(self._h, addr), "host_unregister")
+        self._host.pop(addr, None)
+
+    def frame_host(self, tw, th, view, origin, pack, arr):
+        """vrt_hip_frame_host: the frame of frame() delivered into the registered array `arr`; enqueues only, sync() waits.
+        Afterwards arr.reshape(-1)[:w*h] holds the frame."""
+        v = np.ascontiguousarray(view, np.float32).ravel()
+        self._chk(self._L.vrt_hip_frame_host(self._h, float(tw), float(th), _fp(v), _fp(_f3(origin)), int(pack), arr.ctypes.data),
+                  "frame_host")
 
     def set_shard(self, rank, world):
         self._chk(self._L.vrt_hip_set_shard(self._h, rank, world), "set_shard")

@@ -726,6 +726,21 @@ Tuning read_tuning()
 
 } // namespace
 
+int frame_own_image(vrt_hip_ctx *c, float tw, float th, const float view[16], const float origin[3], int pack_flags)
+{
+    int rc = check_ready(c);
+    if (rc) return rc;
+    const size_t npix = (size_t)c->w * c->h;
+    if (c->d_image.cap < npix) { // first frame at this size: pixels no tile covers read 0
+        HIPCHK(c, c->d_image.reserve(npix));
+        HIPCHK(c, hipMemsetAsync(c->d_image.p, 0, npix * 4, c->stream));
+        c->own_seq = 0;
+    }
+    // Retained frame buffer: d_image is written by nothing but this function and vrt_hip_render (which ends the history), so
+    // an empty cell that was empty in the previous frame already holds the background.
+    return vrt_hip_frame_retained_device(c, tw, th, view, origin, pack_flags, c->d_image.p, c->stream);
+}
+
 extern "C" {
 
 const char *vrt_hip_version(void) { return "vrt_hip 0.2 (gfx950)"; }
@@ -768,6 +783,7 @@ void vrt_hip_destroy(vrt_hip_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)quiesce(c); // frames still in flight on the context's stream or on the caller's last stream read its buffers
+    c->host_regs.clear(); // the caller's host buffers: unregistered once nothing in flight can write them
     for (auto &e : c->batch_copied) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->tev) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1099,17 +1115,9 @@ int vrt_hip_frame(vrt_hip_ctx *c, float tw, float th, const float view[16], cons
                   uint32_t *image_out, int wait)
 {
     if (!c || !origin || !view) return VRT_HIP_ERR_INVALID;
-    int rc = check_ready(c);
+    int rc = frame_own_image(c, tw, th, view, origin, pack_flags);
     if (rc) return rc;
     const size_t npix = (size_t)c->w * c->h;
-    if (c->d_image.cap < npix) { // first frame at this size: pixels no tile covers read 0
-        HIPCHK(c, c->d_image.reserve(npix));
-        HIPCHK(c, hipMemsetAsync(c->d_image.p, 0, npix * 4, c->stream));
-        c->own_seq = 0;
-    }
-    // Retained frame buffer: d_image is written by nothing but this call and vrt_hip_render (which ends the history), so an
-    // empty cell that was empty in the previous frame already holds the background.
-    if ((rc = vrt_hip_frame_retained_device(c, tw, th, view, origin, pack_flags, c->d_image.p, c->stream))) return rc;
     if (image_out) HIPCHK(c, hipMemcpyAsync(image_out, c->d_image.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
     if (image_out || wait) HIPCHK(c, hipStreamSynchronize(c->stream));
     return VRT_HIP_OK;

@@ -205,6 +205,41 @@ struct vrt_hip_ctx {
         }
     } own_sig;
     bool retain_next = false; // set by vrt_hip_frame around its render_common call
+    // A caller's host frame buffer (vrt_hip_host_register): page-locked and mapped while its holder lives.  history[cell] = 1: the
+    // buffer holds that cell of a frame in which it was lit (anything else holds background); valid for `sig` (own_sig without the
+    // image pointer) once a delivery with stamps has recorded it.  slot: its word in h_cells (the cells its last finished delivery
+    // counted) and its two tally words.  The holder's owner waits for the frames in flight first (quiesce).
+    struct HostReg {
+        uint32_t *host = nullptr, *dev = nullptr;
+        size_t pixels = 0;
+        DevBuf<uint8_t> history;
+        OwnGeometry sig;
+        bool history_valid = false;
+        uint32_t slot = 0, launches = 0;
+        HostReg() = default;
+        HostReg(HostReg &&o) noexcept
+            : host(o.host), dev(o.dev), pixels(o.pixels), history(std::move(o.history)), sig(o.sig), history_valid(o.history_valid), slot(o.slot), launches(o.launches)
+        {
+            o.host = nullptr;
+        }
+        HostReg &operator=(HostReg &&o) noexcept
+        {
+            if (this != &o) {
+                release();
+                host = o.host; dev = o.dev; pixels = o.pixels; history = std::move(o.history); sig = o.sig; history_valid = o.history_valid;
+                slot = o.slot; launches = o.launches;
+                o.host = nullptr;
+            }
+            return *this;
+        }
+        ~HostReg() { release(); }
+        void release(); // hipHostUnregister (vrt_hip_host_frame.cpp)
+    };
+    static constexpr size_t MAX_HOST_BUFFERS = 16;
+    std::vector<HostReg> host_regs;
+    PinnedBuf<volatile uint32_t> h_cells; // [MAX_HOST_BUFFERS] host-mapped, written by the delivery kernel (HostFrameArgs::cells_out)
+    uint32_t *d_cells = nullptr;
+    DevBuf<uint32_t> host_tally;          // [2 * MAX_HOST_BUFFERS] HostFrameArgs::tally of each slot
     DevBuf<uint32_t> d_image;
     DevBuf<float4> d_rad;
     DevBuf<unsigned long long> d_stats, d_timeline; // d_timeline: VRT_HIP_TIMELINE diagnostics
@@ -238,6 +273,8 @@ int rebuild_shard(vrt_hip_ctx *c);
 vrtk::SceneTables tables(const vrt_hip_ctx *c);
 vrtk::TileLists tile_geometry(const vrt_hip_ctx *c);
 uint32_t sparse_capacity(vrt_hip_ctx *c); // cells a sparse shard of this context can hold (the same on every rank)
+// the frame of vrt_hip_frame into the context's own buffer d_image, on its stream (vrt_hip_frame, vrt_hip_frame_host)
+int frame_own_image(vrt_hip_ctx *c, float tw, float th, const float view[16], const float origin[3], int pack_flags);
 // vrt_hip_diag.cpp
 int ensure_timing_ring(vrt_hip_ctx *c);
 int read_stats(vrt_hip_ctx *c);

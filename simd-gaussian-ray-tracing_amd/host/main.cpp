@@ -27,7 +27,8 @@ static const char *const HELP_MSG =
     "image\n"
     "  -w, --width PX            image width  (256); also the height unless --height is given\n"
     "  -h, --height PX           image height (256); also the width unless --width is given\n"
-    "  -o, --output PATH         write the frame as PNG; with --frames N > 1: <stem>_<k>.<ext>, k = 1..N\n"
+    "  -o, --output PATH         write the frame as PNG; with --frames N > 1: <stem>_<k>.<ext>, k = 1..N.  With -o the\n"
+    "                            time includes the frame's delivery into host memory; without -o the frame stays on the device\n"
     "      --tiles N             N x N image tiles, each rendered with its own Gaussian subset (16)\n"
     "  -m, --mode 1..8           rendering mode of the reference: 1-4 untiled, 5-8 tiled; picks the pixel packing and\n"
     "                            the exp/erf pair of that mode (8 = tiled, SIMD-over-pixels semantics; the default)\n"
@@ -346,6 +347,15 @@ int main(int argc, char **argv)
 
     const u64 width = cmd.w, height = cmd.h;
     std::vector<u32> image(width * height);
+    // Tiled frames that are written out are delivered into a 64-byte aligned host buffer registered once with the (then only)
+    // context, like the reference's `image` (main.cpp:245): each frame sends only the cells that changed since the last one.
+    u32 *host_image = nullptr;
+    if (use_tiling && cmd.outfile != nullptr) {
+        host_image = (u32 *)aligned_alloc(64, (width * height * sizeof(u32) + 63) / 64 * 64);
+        if (!host_image) { fprintf(stderr, "[ ERROR ]\tout of host memory\n"); return EXIT_FAILURE; }
+        ctx = ctxs[0];
+        chk(vrt_hip_host_register(ctx, host_image, width * height), "host_register");
+    }
 
     // main.cpp:247-255
     vrt::camera_t cam({ 0.f, 0.f, cmd.camera_offset }, { 0.f, 1.f, 0.f }, { 0.f, 0.f, 1.f }, -90.f, 0.f,
@@ -412,9 +422,11 @@ int main(int argc, char **argv)
         const bool wait = need_image || cmd.nr_frames == 1 || (trace && !trace_async);
         double t0 = now_ms();
         if (frames == 1) t_first = t0;
-        if (use_tiling) {
-            chk(vrt_hip_frame(ctx, 2.f / cmd.tiles, 2.f / cmd.tiles, cam.view_matrix.data(), origin, pack,
-                              need_image ? image.data() : nullptr, wait ? 1 : 0), "frame");
+        if (use_tiling && need_image) {
+            chk(vrt_hip_frame_host(ctx, 2.f / cmd.tiles, 2.f / cmd.tiles, cam.view_matrix.data(), origin, pack, host_image), "frame_host");
+            chk(vrt_hip_sync(ctx), "sync");
+        } else if (use_tiling) {
+            chk(vrt_hip_frame(ctx, 2.f / cmd.tiles, 2.f / cmd.tiles, cam.view_matrix.data(), origin, pack, nullptr, wait ? 1 : 0), "frame");
         } else {
             chk(vrt_hip_clear_tiles(ctx), "clear_tiles");
             chk(vrt_hip_render(ctx, origin, pack, need_image ? image.data() : nullptr, nullptr), "render");
@@ -427,7 +439,7 @@ int main(int argc, char **argv)
             const size_t dot = of.find_last_of('.');
             const std::string stem = of.substr(0, dot), ext = dot == std::string::npos ? "png" : of.substr(dot + 1);
             const std::string path = cmd.nr_frames > 1 ? stem + "_" + std::to_string(frames) + "." + ext : stem + "." + ext;
-            if (!png::write_rgba(path.c_str(), (u32)width, (u32)height, image.data(), width * 4))
+            if (!png::write_rgba(path.c_str(), (u32)width, (u32)height, host_image ? host_image : image.data(), width * 4))
                 fprintf(stderr, "[ ERROR ]\tcould not write %s\n", path.c_str());
         }
         if (cmd.nr_frames == 1) printf("TIME: %g ms\n", frame_time);
@@ -446,6 +458,8 @@ int main(int argc, char **argv)
         angle -= angle_change;
         cam.turn(angle, 0.f);
     }
+    if (host_image) chk(vrt_hip_host_unregister(ctxs[0], host_image), "host_unregister");
     for (int i = 0; i < n_created; ++i) vrt_hip_destroy(ctxs[i]);
+    free(host_image);
     return EXIT_SUCCESS;
 }
