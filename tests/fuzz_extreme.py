@@ -1,6 +1,7 @@
-"""Extreme-value cross-check against the oracle, run by hand on an MI355X (python tests/fuzz_extreme.py [seed] [cases]):
-optically thick media (magnitude up to 50), sigma 1e-3 .. 3, Gaussians behind the camera and on the image plane, negative and
-zero magnitudes, albedo > 1.  Round 1: 80 cases, worst relative deviation 1.8e-6, packed pixels within one step."""
+"""Extreme-value cross-check against the oracle on an MI355X (python tests/fuzz_extreme.py [seed] [cases]; a short run is part
+of the GPU suite, tests/test_gpu_fuzz.py): optically thick media (magnitude up to 50), sigma 1e-3 .. 3, Gaussians behind the camera
+and on the image plane, negative and zero magnitudes, albedo > 1.  Round 1: 80 cases, worst relative deviation 1.8e-6, packed
+pixels within one step.  Exits non-zero when a case fails."""
 import sys, os
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE); sys.path.insert(0, os.path.join(HERE, "..", "oracle"))
@@ -12,6 +13,7 @@ O.build()
 r = pkg.Renderer(0)
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
 worst = 0
+failed = 0
 for case in range(int(sys.argv[2]) if len(sys.argv) > 2 else 40):
     n = int(rng.choice([2, 10, 60, 300]))
     w, h = int(rng.choice([48, 64, 96])), int(rng.choice([48, 64]))
@@ -50,5 +52,9 @@ for case in range(int(sys.argv[2]) if len(sys.argv) > 2 else 40):
     pxd = int(np.abs(((img.reshape(-1)[pix][:, None] >> np.array([16, 8, 0, 24])) & 255).astype(int) - ((oimg[pix][:, None] >> np.array([16, 8, 0, 24])) & 255).astype(int)).max())
     worst = max(worst, err)
     flag = "  <-- FAIL" if (err > 1e-4 or not both_nan.all() or pxd > 1) else ""
+    failed += bool(flag)
     print(f"case {case}: {kind:10s} n={n} {w}x{h} tiles={tiles_n} eps={eps:g} table={tstep:g} peak={np.nanmax(orad):.3g} nonfinite {int((~fin).sum())}: rel err {err:.2e} u8 diff {pxd}{flag}", flush=True)
 print("worst", worst)
+print("failed cases:", failed)
+r.close()
+sys.exit(1 if failed else 0)

@@ -386,9 +386,12 @@ def _blob_scene(oracle, n, seed, spread=0.15, sigma=(0.25, 0.45), mag=(0.01, 0.0
 
 @pytest.mark.parametrize("n,w,what", [(300, 16, "per-ray lists > 48: blocks handed to the 16-wave kernel"),
                                       (1100, 8, "block candidates > 1024: LDS overflow, streamed list"),
-                                      (4200, 4, "cell list > 4096: cell slot overflow, tile list used")])
+                                      (4200, 4, "tile list > 1024: no cell lists, every block reads the tile list")])
 def test_capacity_overflow_paths(pkg, oracle, renderer, n, w, what):
-    """Every fixed-capacity structure of the kernels has a correct (slower) way out; heterogeneous sigma/magnitude."""
+    """Every fixed-capacity structure of the kernels has a correct (slower) way out; heterogeneous sigma/magnitude.
+    (The third case is one tile of one cell, so it goes through the fused list kernel, where a tile list beyond TCAP = 1024 sends
+    every cell to the tile's list long before a cell slot of cstride = 4096 entries could overflow.  The slot's own limit is
+    reached through a tile of more than 64 cells: tests/test_gpu_boundaries.py, test_cell_slot_at_cstride.)"""
     g = _blob_scene(oracle, n, 5 + n)
     cam, plane, origin, tiles = setup_scene(pkg, oracle, renderer, g, w, w, tiles_n=1)
     renderer.set_options(pkg.EXP_VCL, pkg.ERF_AS, 1e-9)
