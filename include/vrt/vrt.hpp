@@ -419,6 +419,41 @@ simd_vec4f_t broadcast_radiance(const simd_vec4f_t o, const simd_vec4f_t n, cons
     return L;
 }
 
+// ======== EXTENSION -- not in the reference ===========================================================================
+// Ray bundles: broadcast_radiance for ANY number of rays in ONE call, culled per ray (vrt_hip_radiance_rays in
+// include/vrt_hip.h: a ray loses less than 3 * cull_eps * min(N, 4096) = 1.23e-5 of radiance at the defaults).  Ray r has
+// origin o[r] and unit direction n[r] (normalised by the caller); out[r] = its radiance (x, y, z = rgb, w = sum albedo.w *
+// inner); image (nullable): one packed pixel per ray.  A stereo pair, a fisheye, light probes or a second bounce are one
+// call each.  vrt::radiance / broadcast_radiance above stay the reference's full sum.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void radiance_rays(const vec4f_t *o, const vec4f_t *n, size_t nrays, const gaussians_t &gaussians, vec4f_t *out, u32 *image = nullptr,
+                   int pack_flags = VRT_PACK_ROUND | VRT_ALPHA_COMPUTED)
+{
+    static_assert(sizeof(vec4f_t) == 4 * sizeof(f32), "out is handed to the library as 4 floats per ray");
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    std::vector<f32> oo(3 * nrays), nn(3 * nrays);
+    for (size_t r = 0; r < nrays; ++r) {
+        oo[3 * r] = o[r].x; oo[3 * r + 1] = o[r].y; oo[3 * r + 2] = o[r].z;
+        nn[3 * r] = n[r].x; nn[3 * r + 1] = n[r].y; nn[3 * r + 2] = n[r].z;
+    }
+    d.check(vrt_hip_radiance_rays(d.ctx, nrays, oo.data(), 1, nn.data(), out ? &out[0].x : nullptr, image, pack_flags), "vrt_hip_radiance_rays");
+}
+// The same for rays and results that live on the device (3 floats per origin -- or 3 in all with origin_per_ray = false -- and
+// per direction, 4 floats of radiance and / or one u32 per ray): enqueued on hip_stream, nothing waits.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void radiance_rays_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const gaussians_t &gaussians,
+                          f32 *d_radiance, u32 *d_image, int pack_flags, void *hip_stream)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    d.check(vrt_hip_radiance_rays_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_radiance, d_image, pack_flags, hip_stream),
+            "vrt_hip_radiance_rays_device");
+}
+// ======== end of the extension ==========================================================================================
+
 // ---- rt.cpp:8-27 -----------------------------------------------------------------------------------------------------
 inline f32 transmittance_step(const vec4f_t o, const vec4f_t n, const f32 s, const f32 delta, const std::vector<gaussian_t> gaussians)
 {

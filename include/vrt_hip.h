@@ -313,6 +313,42 @@ int vrt_hip_transmittance_rays(vrt_hip_ctx *ctx, size_t nrays, const float *orig
 /* out[4*r..] = radiance / broadcast_radiance (rt.h:146-164, 205-223) for ray r with origin
  * origins[3*r..], unit direction dirs[3*r..], over all Gaussians of the scene (no tiling). */
 int vrt_hip_radiance(vrt_hip_ctx *ctx, size_t nrays, const float *origins, const float *dirs, float *out);
+/* -------- ray bundles: broadcast_radiance (rt.h:205-223) for ANY rays, as a fast path ------------------------------------
+ * Radiance (and optionally packed pixels) of nrays caller-given rays through the scene, culled per ray like the image
+ * kernels' last level.  origins: 3 floats per ray (origin_per_ray != 0) or 3 floats in all (== 0: one origin for the
+ * whole bundle).  dirs: 3 floats per ray, unit length (the caller normalises, like broadcast_radiance's callers).
+ * d_radiance: 4 floats per ray (nullable); d_image: one u32 per ray, packed with pack_flags (nullable).
+ * Uses the scene and vrt_hip_set_options (every Exp / Erf pair, cull_eps); ignores tiles, the rays of set_plane /
+ * set_camera*, shard, table settings and cull_prune: an untiled bundle sees every Gaussian, as in the gaussians_t overloads.
+ * Cull rule: a ray drops Gaussian j iff x > cull_x_j, x = (|oc|^2 - mubar^2) / (2 sigma_j^2), cull_x_j = ln(sigma_j mag_j /
+ * eps_eff), eps_eff = cull_eps * min(1, 4096 / N), clamped at the point where Exp gives exactly 0 (cull_eps = 0: a ray keeps
+ * everything Exp does not flush to exactly 0).  This is one level, entered by the whole scene, with the tile level's
+ * threshold: a ray then loses less than 3 * cull_eps * min(N, 4096) = 1.23e-5 of radiance at the defaults, for any N.
+ * Rays with at most 32 kept Gaussians are shaded lane = ray in the reference's summation order; longer lists by one wave per
+ * ray, which sums in another (fixed) order.  Which of the two shades a ray depends on that ray alone: a ray's result is a
+ * function of (ray, scene, options), whatever else is in the bundle.
+ * The _device form takes device pointers and follows the stream rules at the top of this header: everything is enqueued on
+ * hip_stream, without host synchronisation and without allocation once a bundle of at least this size has been seen; the
+ * call counts as a frame in flight.  nrays == 0 returns VRT_HIP_OK with nothing launched; NULL dirs or origins with
+ * nrays > 0, or both outputs NULL: VRT_HIP_ERR_INVALID, nothing enqueued.  vrt_hip_radiance below stays the full sum. */
+int vrt_hip_radiance_rays_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_origins, int origin_per_ray,
+                                 const float *d_dirs, float *d_radiance, uint32_t *d_image, int pack_flags,
+                                 void *hip_stream);
+int vrt_hip_radiance_rays(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                          float *radiance_out, uint32_t *image_out, int pack_flags);        /* host pointers, waits */
+typedef struct {
+    uint64_t rays;           /* rays of the bundle                                                                  */
+    uint64_t short_rays;     /* shaded lane = ray (list of at most 32)                                              */
+    uint64_t long_rays;      /* shaded one wave per ray                                                             */
+    uint64_t lane_entries;   /* sum over the short rays of the list length                                          */
+    uint64_t lane_pairs;     /* sum over the short rays of (list length)^2: their (emitter, absorber) pairs          */
+    uint64_t chunks_tested;  /* sum over rays of the chunk spheres (64 Gaussians each) tested                        */
+    uint64_t chunks_kept;    /* ... and of those the ray's line reaches                                             */
+    uint64_t members_tested; /* sum over rays of the Gaussians tested one by one (members of chunks its WAVE kept)    */
+    uint64_t scratch_rays;   /* long rays with more than 1024 kept Gaussians (list continued in device memory)      */
+} vrt_hip_ray_stats;
+int vrt_hip_get_ray_stats(vrt_hip_ctx *ctx, vrt_hip_ray_stats *out);   /* of the last bundle, when vrt_hip_enable_stats is on (waits for it) */
+
 /* Numeric cross-checks of rt.cpp:8-27 (transmittance_step uses fast_exp like the reference). */
 int vrt_hip_transmittance_step(vrt_hip_ctx *ctx, const float o[3], const float n[3], const float *s, size_t ns,
                                float delta, float *T_out);

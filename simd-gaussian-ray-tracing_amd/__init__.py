@@ -42,10 +42,15 @@ class Stats(C.Structure):
                 ("table_skips", C.c_uint64), ("table_declined", C.c_uint64), ("table_coarser", C.c_uint64), ("table_empty", C.c_uint64), ("table_phase_ticks", C.c_uint64 * 8), ("dense_launch_skips", C.c_uint64)]
 
 
+class RayStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("rays", "short_rays", "long_rays", "lane_entries", "lane_pairs", "chunks_tested",
+                                          "chunks_kept", "members_tested", "scratch_rays")]
+
+
 def build(verbose=False):
     """Compile csrc/ for gfx950 with hipcc (cross-compiles without a GPU)."""
     out = None if verbose else subprocess.DEVNULL
-    subprocess.check_call(["make", "-j4", "-C", os.path.join(_HERE, "csrc")], stdout=out)   # the three kernel translation units side by side
+    subprocess.check_call(["make", "-j4", "-C", os.path.join(_HERE, "csrc")], stdout=out)   # the kernel translation units side by side
     return LIB_PATH
 
 
@@ -108,6 +113,9 @@ SYMBOLS = {
     "vrt_hip_transmittance": (C.c_int, [_vp, _f32p, _f32p, _f32p, C.c_size_t, _f32p]),
     "vrt_hip_transmittance_rays": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p, _f32p, _f32p]),
     "vrt_hip_radiance": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p, _f32p]),
+    "vrt_hip_radiance_rays_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
+    "vrt_hip_radiance_rays": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _u32p, C.c_int]),
+    "vrt_hip_get_ray_stats": (C.c_int, [_vp, C.POINTER(RayStats)]),
     "vrt_hip_transmittance_step": (C.c_int, [_vp, _f32p, _f32p, _f32p, C.c_size_t, C.c_float, _f32p]),
     "vrt_hip_density": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p]),
     "vrt_hip_eval_erf": (C.c_int, [_vp, C.c_int, _f32p, C.c_size_t, _f32p]),
@@ -469,6 +477,35 @@ class Renderer:
         out = np.zeros((len(dirs), 4), np.float32)
         self._chk(self._L.vrt_hip_radiance(self._h, len(dirs), _fp(origins), _fp(dirs), _fp(out)), "radiance")
         return out
+
+    # ---- ray bundles (any rays, culled per ray) ----
+    def radiance_rays(self, origins, dirs, want_image=False, pack=PACK_ROUND | ALPHA_COMPUTED):
+        """vrt_hip_radiance_rays: origins [3] (one for the bundle) or [nrays, 3], dirs [nrays, 3] unit length.  Returns the
+        radiance f32 [nrays, 4], or (radiance, packed pixels u32 [nrays]) with want_image."""
+        origins = np.ascontiguousarray(origins, np.float32)
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        per_ray = origins.size != 3
+        if per_ray:
+            assert origins.size == dirs.size
+        rad = np.zeros((len(dirs), 4), np.float32)
+        img = np.zeros(len(dirs), np.uint32) if want_image else None
+        self._chk(self._L.vrt_hip_radiance_rays(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(rad),
+                                                img.ctypes.data_as(_u32p) if want_image else None, int(pack)), "radiance_rays")
+        return (rad, img) if want_image else rad
+
+    def radiance_rays_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_radiance=0, d_image=0, pack=PACK_ROUND | ALPHA_COMPUTED,
+                             stream=0):
+        """vrt_hip_radiance_rays_device: device pointers, everything enqueued on `stream`."""
+        rc = self._L.vrt_hip_radiance_rays_device(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None,
+                                                  d_radiance or None, d_image or None, int(pack), stream or None)
+        if rc != 0:
+            self._chk(rc, "radiance_rays_device")
+
+    def ray_stats(self):
+        """Counts of the last bundle (enable_stats first): see vrt_hip_ray_stats in include/vrt_hip.h."""
+        s = RayStats()
+        self._chk(self._L.vrt_hip_get_ray_stats(self._h, C.byref(s)), "get_ray_stats")
+        return {k: getattr(s, k) for k, _ in RayStats._fields_}
 
     def eval_erf(self, kind, x):
         x = np.ascontiguousarray(x, np.float32)

@@ -30,7 +30,7 @@ int fail(vrt_hip_ctx *c, int code, const std::string &msg)
 
 // Before work on `st` rewrites what the last frame's kernels on another stream may still be reading, wait for that stream.
 // An error from it (it may have been destroyed, which completes its work) is not this call's error.
-static void wait_for_last_stream(vrt_hip_ctx *c, hipStream_t st)
+void wait_for_last_stream(vrt_hip_ctx *c, hipStream_t st)
 {
     if (!c->last_stream || c->last_stream == st) return;
     if (hipStreamSynchronize(c->last_stream) != hipSuccess) (void)hipGetLastError();

@@ -1,6 +1,6 @@
 // vrt_hip_ctx.hpp -- internal to libvrt_hip.so: the context behind the C ABI (include/vrt_hip.h), the owning buffer types and
 // what the host runtime's translation units share (vrt_hip_api.cpp: context, setters, frame pipeline, shard map;
-// vrt_hip_assembly.cpp: shard assembly; vrt_hip_query.cpp: point queries; vrt_hip_diag.cpp: stats, kernel timing, timelines).
+// vrt_hip_assembly.cpp: shard assembly; vrt_hip_query.cpp: point queries; vrt_hip_rays.cpp: ray bundles; vrt_hip_diag.cpp: stats, kernel timing, timelines).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -242,6 +242,14 @@ struct vrt_hip_ctx {
     DevBuf<uint32_t> host_tally;          // [2 * MAX_HOST_BUFFERS] HostFrameArgs::tally of each slot
     DevBuf<uint32_t> d_image;
     DevBuf<float4> d_rad;
+    // ray bundles (vrt_hip_rays.cpp): the long-ray queue, its two counters, the long kernel's scratch slots and the
+    // statistics words grow only; rays_in / rays_rad / rays_img stage the host-pointer form
+    DevBuf<uint32_t> ray_queue, ray_counters, ray_scratch;
+    DevBuf<unsigned long long> ray_stats;
+    DevBuf<float> rays_in[2];
+    DevBuf<float4> rays_rad;
+    DevBuf<uint32_t> rays_img;
+    bool ray_stats_valid = false; // ray_stats holds the counts of the last bundle (stats were on for it)
     DevBuf<unsigned long long> d_stats, d_timeline; // d_timeline: VRT_HIP_TIMELINE diagnostics
     size_t timeline_items = 0, timeline_tiles = 0;
     DevBuf<unsigned long long> d_timeline_lists;
@@ -267,6 +275,7 @@ int fail(vrt_hip_ctx *c, int code, const std::string &msg); // records msg (c's,
 
 // vrt_hip_api.cpp
 int quiesce(vrt_hip_ctx *c);
+void wait_for_last_stream(vrt_hip_ctx *c, hipStream_t st); // before work on `st` rewrites what the last frame on another stream may still read
 int check_ready(vrt_hip_ctx *c);
 int rebuild_tables(vrt_hip_ctx *c);
 int rebuild_shard(vrt_hip_ctx *c);

@@ -270,6 +270,36 @@ void launch_clear_stale_cells(const uint32_t *stamp, uint32_t seq, uint32_t n_ce
 constexpr uint32_t SPARSE_HDR_WORDS = 4; // [0] cells stored, [1] capacity (cells), [2] cells per tile, [3] reserved
 __host__ __device__ inline size_t sparse_pixel_offset(uint32_t cap) { return (SPARSE_HDR_WORDS + (size_t)cap + 3) / 4 * 4; }
 
+// Ray bundles (vrt_ray_kernel.hip): caller-given rays, culled per ray, no camera and no tiles.
+#ifndef VRT_RAY_PL
+#define VRT_RAY_PL 32
+#endif
+#ifndef VRT_RAY_LCAP
+#define VRT_RAY_LCAP 1024
+#endif
+constexpr int RAY_PL = VRT_RAY_PL;     // per-ray list capacity of the lane = ray kernel (u32 scene indices in LDS, [k*64 + lane]: 8 KB); a ray with a longer
+                                       // list goes to the one-wave-per-ray kernel
+constexpr int RAY_LCAP = VRT_RAY_LCAP; // survivors the one-wave-per-ray kernel keeps in LDS; beyond that its list continues in its scratch slot
+struct RayArgs {
+    SceneTables S;
+    const float4 *chunks;        // bounding spheres of every 64 consecutive Gaussians (launch_build_chunks)
+    const float *origins;        // 3 floats per ray (origin_per_ray != 0) or 3 floats in all
+    const float *dirs;           // 3 floats per ray, unit length
+    int origin_per_ray;
+    uint64_t nrays;              // < 2^32: the queue holds ray ids as u32
+    float4 *radiance;            // nullable
+    uint32_t *image;             // nullable
+    int pack_flags;
+    uint32_t *queue;             // ids of the rays whose list outgrew RAY_PL
+    uint32_t queue_cap;
+    uint32_t *counters;          // [0] entries of the queue, [1] the long kernel's work counter; cleared on the stream per call
+    uint32_t *scratch;           // S.n words per workgroup of the long kernel
+    unsigned long long *stats;   // nullable: rays, short rays, long rays, sum of short list lengths, sum of their squares, chunk tests,
+                                 // chunks kept, member tests (per ray: the members its wave visited), long rays that used their scratch slot
+};
+constexpr int RAY_STATS_WORDS = 9;
+void launch_ray_bundle(const RayArgs &a, uint32_t long_grid /* one-wave workgroups of the long kernel */, int exp_kind, int erf_kind, hipStream_t st);
+
 // point queries
 void launch_transmittance(const SceneTables &s, const float o[3], const float n[3], const float *d_s, size_t ns,
                           float *d_T, int exp_kind, int erf_kind, hipStream_t st);

@@ -1,6 +1,7 @@
-// vrt_kernels_common.hpp -- device code shared by the three kernel translation units of libvrt_hip.so (csrc/Makefile):
+// vrt_kernels_common.hpp -- device code shared by the four kernel translation units of libvrt_hip.so (csrc/Makefile):
 //   vrt_block_kernel.hip   the one-wave "block kernel" (sparse scenes), scheduled for instruction-level parallelism
 //   vrt_table_kernel.hip   the table kernel (default path of dense blocks)
+//   vrt_ray_kernel.hip     ray bundles: caller-given rays, culled per ray (no camera, no tiles)
 //   vrt_kernels.hip        everything else: exact dense kernel, list kernels, scene tables, frame assembly, point queries
 // Hand-written for gfx950 (CDNA4, wave64).  No MFMA: the path is VALU + quarter-rate transcendental bound (one v_rcp_f32 per
 // Abramowitz-Stegun erf term); Gaussian parameters reach the inner loops through LDS rows or wave-uniform scalar loads.

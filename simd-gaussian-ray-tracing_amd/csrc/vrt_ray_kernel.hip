@@ -1,0 +1,334 @@
+// vrt_ray_kernel.hip -- ray bundles (vrt_hip_radiance_rays*): radiance of caller-given rays, each with its own origin and
+// direction, culled per ray like the image kernels' last level.  No camera, no tiles, no cones: the whole scene enters ONE
+// level with the tile level's threshold (gB.w), so a ray loses less than 3 * cull_eps * min(N, 4096).
+// Two kernels per call, both always enqueued:
+//   ray_short_kernel  lane = ray, one wave per 64 consecutive rays; per-ray lists of at most RAY_PL global indices in LDS
+//   ray_long_kernel   one wave per ray whose list is longer, lane = emitter; reads its work count on the device
+// Which kernel shades a ray depends on that ray's own list length alone, and a lane's list on its own tests alone: a ray's
+// bits are a function of (ray, scene, options), whatever its wave-mates are.
+// Compiled like the block kernel with -mllvm -amdgpu-sched-strategy=max-ilp (see the note at the top of vrt_block_kernel.hip):
+// the pair loops are the same independent erf terms.
+#include "vrt_kernels_common.hpp"
+
+namespace vrtk {
+
+// The chunk's sphere (centre, radius incl. its members' reach: build_chunks_kernel) against the LINE of one ray.  A member
+// is kept by the ray criterion only within its reach of the line, and the distance to a line is 1-Lipschitz in the point,
+// so a line farther than the radius from the centre keeps no member.  The d^2 - t^2 cancellation is guarded on the keeping
+// side, as in chunk_keeps.  Unfused: both kernels must decide alike.
+__device__ __forceinline__ bool ray_chunk_keeps(float4 ch, const LaneRay &ray)
+{
+    const float ax = sub_ref(ch.x, ray.ox), ay = sub_ref(ch.y, ray.oy), az = sub_ref(ch.z, ray.oz);
+    const float d2 = dot3_ref(ax, ay, az, ax, ay, az);
+    const float t = dot3_ref(ax, ay, az, ray.nx, ray.ny, ray.nz);
+    const float dperp = __builtin_sqrtf(fmaxf(0.f, sub_ref(sub_ref(d2, mul_ref(t, t)), mul_ref(8e-6f, d2))));
+    return !(mul_ref(dperp, 0.9999f) > ch.w);
+}
+// x = (|oc|^2 - mubar^2) / (2 sigma^2) of one ray and one Gaussian in the reference's order (ray_gaussian<false>); kept iff !(x > cull_x)
+__device__ __forceinline__ bool ray_member_keeps(float4 ms, float4 bq, const LaneRay &ray)
+{
+    const float cx = ms.x - ray.ox, cy = ms.y - ray.oy, cz = ms.z - ray.oz;
+    const float mubar = dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz);
+    const float x = mul_ref(sub_ref(dot3_ref(cx, cy, cz, cx, cy, cz), mul_ref(mubar, mubar)), bq.y);
+    return !(x > bq.w);
+}
+
+__device__ __forceinline__ LaneRay load_ray(const RayArgs &P, uint64_t r)
+{
+    const uint64_t ro = P.origin_per_ray ? r : 0ull;
+    LaneRay ray;
+    ray.ox = P.origins[3 * ro]; ray.oy = P.origins[3 * ro + 1]; ray.oz = P.origins[3 * ro + 2];
+    ray.nx = P.dirs[3 * r]; ray.ny = P.dirs[3 * r + 1]; ray.nz = P.dirs[3 * r + 2];
+    return ray;
+}
+__device__ __forceinline__ void store_ray(const RayArgs &P, uint64_t r, float Lr, float Lg, float Lb, float La)
+{
+    if (P.image) P.image[r] = pack_pixel(Lr, Lg, Lb, La, P.pack_flags);
+    if (P.radiance) P.radiance[r] = make_float4(Lr, Lg, Lb, La);
+}
+
+// One chunk of EC emitters (list positions i0 .. i0+EC-1 of every lane) against the lane's whole list: shade_chunk of the block
+// kernel with the parameter rows gathered per lane from the scene tables (L2-resident; a coherent bundle reads one address in
+// all lanes) and oc = mu - o formed per lane, as shade_list<.., false> does.  The next absorber's rows are fetched one iteration ahead.
+template <int EXP, int ERF, int EC>
+__device__ __forceinline__ void ray_shade_chunk(const SceneTables &S, const uint32_t *s_list /*[k*64 + lane]*/, uint32_t nl,
+                                                uint32_t nmax, uint32_t lane, const LaneRay &ray, uint32_t i0, float &Lr,
+                                                float &Lg, float &Lb, float &La)
+{
+    const ErfEval<ERF> erf;
+    float e_mubar[EC], e_sigma[EC];
+    uint32_t e_idx[EC];
+#pragma unroll
+    for (int e = 0; e < EC; ++e) {
+        e_idx[e] = (i0 + e < nl) ? s_list[(i0 + e) * 64 + lane] : 0u;
+        const float4 ms = S.mu_sig[e_idx[e]];
+        const float cx = ms.x - ray.ox, cy = ms.y - ray.oy, cz = ms.z - ray.oz;
+        e_mubar[e] = dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz);
+        e_sigma[e] = ms.w;
+    }
+    float acc[EC][5];
+#pragma unroll
+    for (int e = 0; e < EC; ++e)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) acc[e][k] = 0.f;
+
+    uint32_t lj = nl ? s_list[lane] : 0u;
+    float4 a = S.mu_sig[lj], b = S.gB[lj];
+    for (uint32_t j = 0; j < nmax; ++j) {
+        const float4 ca = a, cb = b;
+        const bool vj = j < nl;
+        if (j + 1 < nmax) {
+            lj = (j + 1 < nl) ? s_list[(j + 1) * 64 + lane] : 0u;
+            a = S.mu_sig[lj]; b = S.gB[lj];
+        }
+        const float cx = ca.x - ray.ox, cy = ca.y - ray.oy, cz = ca.z - ray.oz;
+        const float mubar = dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz);
+        const float d2 = sub_ref(dot3_ref(cx, cy, cz, cx, cy, cz), mul_ref(mubar, mubar));
+        const float A = vj ? cb.z * vexp<EXP>(-(d2 * cb.y)) : 0.f; // past the end of the lane's list: exact zeros
+        const float m = mubar * cb.x;
+        const float E = erf(-m);
+#pragma unroll
+        for (int e = 0; e < EC; ++e) {
+            const float base = __builtin_fmaf(e_mubar[e], cb.x, -m);
+            const float step = e_sigma[e] * cb.x;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const float x = __builtin_fmaf((float)(k - 4), step, base);
+                acc[e][k] = __builtin_fmaf(A, E - erf(x), acc[e][k]);
+            }
+        }
+    }
+
+    // emission from the sample point (see shade_list)
+#pragma unroll
+    for (int e = 0; e < EC; ++e) {
+        if (i0 + e < nl) {
+            const float4 ms = S.mu_sig[e_idx[e]];
+            const float inv2s2 = S.gB[e_idx[e]].y;
+            const float q = S.gD[e_idx[e]].y;
+            float inner = 0.f;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const float sk = madd_ref((float)(k - 4), ms.w, e_mubar[e]);
+                const float px = sub_ref(madd_ref(ray.nx, sk, ray.ox), ms.x);
+                const float py = sub_ref(madd_ref(ray.ny, sk, ray.oy), ms.y);
+                const float pz = sub_ref(madd_ref(ray.nz, sk, ray.oz), ms.z);
+                const float dd = dot3_ref(px, py, pz, px, py, pz);
+                inner += emission_term<EXP>(q, dd * inv2s2, acc[e][k]);
+            }
+            const float4 alb = S.gC[e_idx[e]];
+            Lr = __builtin_fmaf(alb.x, inner, Lr);
+            Lg = __builtin_fmaf(alb.y, inner, Lg);
+            Lb = __builtin_fmaf(alb.z, inner, Lb);
+            La = __builtin_fmaf(alb.w, inner, La);
+        }
+    }
+}
+
+template <int EXP, int ERF>
+__global__ __launch_bounds__(64) void ray_short_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
+{
+    const RayArgs &P = kernel_args<RayArgs>();
+    const SceneTables &S = P.S;
+    __shared__ uint32_t s_list[RAY_PL * 64]; // [k*64 + lane]: consecutive lanes on consecutive banks
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t r = (uint64_t)blockIdx.x * 64u + lane;
+    const bool valid = r < P.nrays; // the grid has no wave without a valid ray
+    const LaneRay ray = load_ray(P, valid ? r : P.nrays - 1);
+
+    // ---- cull: chunk spheres per lane, members of the chunks some lane keeps with a wave-uniform index ----
+    const uint32_t N = S.n, nch = (N + 63u) / 64u;
+    uint32_t nl = 0, chunks_kept = 0, members = 0;
+    for (uint32_t c = 0; c < nch; ++c) {
+        const bool kc = valid && ray_chunk_keeps(uload(P.chunks, c), ray);
+        if (__ballot(kc) == 0ull) continue;
+        chunks_kept += kc ? 1u : 0u;
+        const uint32_t first = c * 64u, last = min(first + 64u, N);
+        members += last - first;
+#pragma unroll 4
+        for (uint32_t idx = first; idx < last; ++idx) {
+            // a lane files only what its OWN chunk test admits: its list does not depend on its wave-mates
+            const bool km = ray_member_keeps(uload(S.mu_sig, idx), uload(S.gB, idx), ray);
+            if (kc && km) {
+                if (nl < (uint32_t)RAY_PL) s_list[nl * 64u + lane] = idx; // ascending; the count runs on
+                ++nl;
+            }
+        }
+    }
+    const bool is_long = nl > (uint32_t)RAY_PL;
+    if (is_long) { // to the one-wave-per-ray kernel behind this one
+        const uint32_t pos = atomicAdd(&P.counters[0], 1u);
+        if (pos < P.queue_cap) P.queue[pos] = (uint32_t)r;
+    }
+    if (P.stats && valid) {
+        atomicAdd(&P.stats[0], 1ull);
+        atomicAdd(&P.stats[is_long ? 2 : 1], 1ull);
+        if (!is_long) { atomicAdd(&P.stats[3], (unsigned long long)nl); atomicAdd(&P.stats[4], (unsigned long long)nl * nl); }
+        atomicAdd(&P.stats[5], (unsigned long long)nch);
+        atomicAdd(&P.stats[6], (unsigned long long)chunks_kept);
+        atomicAdd(&P.stats[7], (unsigned long long)members);
+    }
+
+    // ---- shade: every lane walks its own list; the loops run to the longest list of the wave's short rays ----
+    if (is_long) nl = 0;
+    const uint32_t nmax = wave_max_u32(nl);
+    float Lr = 0.f, Lg = 0.f, Lb = 0.f, La = 0.f;
+    constexpr int EC = 4;
+    for (uint32_t i0 = 0; i0 < nmax; i0 += EC) {
+        const uint32_t rem = nmax - i0;
+        if (rem >= (uint32_t)EC) ray_shade_chunk<EXP, ERF, EC>(S, s_list, nl, nmax, lane, ray, i0, Lr, Lg, Lb, La);
+        else if (rem == 3) ray_shade_chunk<EXP, ERF, 3>(S, s_list, nl, nmax, lane, ray, i0, Lr, Lg, Lb, La);
+        else if (rem == 2) ray_shade_chunk<EXP, ERF, 2>(S, s_list, nl, nmax, lane, ray, i0, Lr, Lg, Lb, La);
+        else ray_shade_chunk<EXP, ERF, 1>(S, s_list, nl, nmax, lane, ray, i0, Lr, Lg, Lb, La);
+    }
+    if (valid && !is_long) store_ray(P, r, Lr, Lg, Lb, La);
+}
+
+// sum over the 64 lanes of a full wave in a fixed order, on the DPP path (wave_inclusive_sum's steps on floats; zeros are shifted in)
+#define VRT_DPP_ZERO(v, ctrl, rows, bound) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, rows, 0xf, bound))
+__device__ __forceinline__ float wave_sum(float v)
+{
+    v = add_ref(v, VRT_DPP_ZERO(v, 0x111, 0xf, true));  // row_shr:1
+    v = add_ref(v, VRT_DPP_ZERO(v, 0x112, 0xf, true));  // row_shr:2
+    v = add_ref(v, VRT_DPP_ZERO(v, 0x114, 0xf, true));  // row_shr:4
+    v = add_ref(v, VRT_DPP_ZERO(v, 0x118, 0xf, true));  // row_shr:8
+    v = add_ref(v, VRT_DPP_ZERO(v, 0x142, 0xa, false)); // row_bcast:15 into rows 1 and 3
+    v = add_ref(v, VRT_DPP_ZERO(v, 0x143, 0xc, false)); // row_bcast:31 into rows 2 and 3
+    return lane_value(v, 63);
+}
+
+// One wave per long ray, lane = emitter.  The ray is wave-uniform: its survivors are compacted in index order (ballot / mbcnt, as the
+// block cull does) into s_list, and beyond RAY_LCAP into this workgroup's scratch slot of N words (entry k at slot[k]), so no
+// list length is refused.  Lane l then takes emitters l, l + 64, ... against all survivors as absorbers (wave-uniform: scalar
+// row loads); the four sums are reduced over the lanes in a fixed order -- another summation order than the reference's.
+template <int EXP, int ERF>
+__global__ __launch_bounds__(64) void ray_long_kernel(RayArgs)
+{
+    const RayArgs &P = kernel_args<RayArgs>();
+    const SceneTables &S = P.S;
+    __shared__ uint32_t s_list[RAY_LCAP];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n_long = min(P.counters[0], P.queue_cap); // final: the short kernel is done
+    uint32_t *slot = P.scratch + (size_t)blockIdx.x * S.n;
+    const uint32_t N = S.n, nch = (N + 63u) / 64u;
+    const ErfEval<ERF> erf;
+    constexpr int EC = 2;
+
+    while (true) {
+        // Every lane executes the atomic (lane 0 adds 1, the others 0: one wave-level atomic after the compiler's atomic optimizer).
+        // With `if (lane == 0) k = atomicAdd(..)` the compiler threaded lane 0's store at the end of the loop body into this claim and
+        // left the other 63 lanes in a loop of their own, reading k = 0 for ever: a claim must not sit behind a branch on the lane.
+        const uint32_t k = __builtin_amdgcn_readfirstlane(atomicAdd(&P.counters[1], lane == 0 ? 1u : 0u));
+        if (k >= n_long) break;
+        const uint64_t r = P.queue[k];
+        if (r >= P.nrays) continue;
+        const LaneRay ray = load_ray(P, r);
+
+        // ---- cull: 64 chunk spheres at a time (lane = chunk), then the members of the kept ones (lane = Gaussian) ----
+        __syncthreads(); // the previous ray's list reads are done
+        uint32_t n = 0;
+        for (uint32_t c0 = 0; c0 < nch; c0 += 64u) {
+            const uint32_t c = c0 + lane;
+            unsigned long long cmask = __ballot(c < nch && ray_chunk_keeps(P.chunks[min(c, nch - 1u)], ray));
+            while (cmask) {
+                const uint32_t idx = (c0 + (uint32_t)__builtin_ctzll(cmask)) * 64u + lane;
+                cmask &= cmask - 1ull;
+                const uint32_t ic = min(idx, N - 1u);
+                const bool keep = idx < N && ray_member_keeps(S.mu_sig[ic], S.gB[ic], ray);
+                const unsigned long long mask = __ballot(keep);
+                const uint32_t pos = n + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+                if (keep) {
+                    if (pos < (uint32_t)RAY_LCAP) s_list[pos] = idx;
+                    else if (pos < N) slot[pos] = idx;
+                }
+                n += (uint32_t)__popcll(mask);
+            }
+        }
+        n = min(n, N);
+        __syncthreads(); // list and scratch writes of this wave are visible to it
+        if (P.stats && lane == 0 && n > (uint32_t)RAY_LCAP) atomicAdd(&P.stats[8], 1ull);
+        auto entry = [&](uint32_t p) -> uint32_t { return p < (uint32_t)RAY_LCAP ? s_list[p] : slot[p]; };
+
+        // ---- shade ----
+        float Lr = 0.f, Lg = 0.f, Lb = 0.f, La = 0.f;
+        for (uint32_t e0 = 0; e0 < n; e0 += 64u * EC) {
+            float e_mubar[EC], e_sigma[EC];
+            uint32_t e_idx[EC];
+            bool e_on[EC];
+#pragma unroll
+            for (int e = 0; e < EC; ++e) {
+                const uint32_t p = e0 + (uint32_t)e * 64u + lane;
+                e_on[e] = p < n;
+                e_idx[e] = entry(e_on[e] ? p : 0u);
+                const float4 ms = S.mu_sig[e_idx[e]];
+                const float cx = ms.x - ray.ox, cy = ms.y - ray.oy, cz = ms.z - ray.oz;
+                e_mubar[e] = dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz);
+                e_sigma[e] = ms.w;
+            }
+            float acc[EC][5];
+#pragma unroll
+            for (int e = 0; e < EC; ++e)
+#pragma unroll
+                for (int kk = 0; kk < 5; ++kk) acc[e][kk] = 0.f;
+            for (uint32_t j = 0; j < n; ++j) {
+                const uint32_t idx = __builtin_amdgcn_readfirstlane(entry(j));
+                const float4 ms = uload(S.mu_sig, idx), b = uload(S.gB, idx);
+                const float cx = ms.x - ray.ox, cy = ms.y - ray.oy, cz = ms.z - ray.oz;
+                const float mubar = dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz);
+                const float d2 = sub_ref(dot3_ref(cx, cy, cz, cx, cy, cz), mul_ref(mubar, mubar));
+                const float A = b.z * vexp<EXP>(-(d2 * b.y));
+                const float m = mubar * b.x;
+                const float E = erf(-m);
+#pragma unroll
+                for (int e = 0; e < EC; ++e) {
+                    const float base = __builtin_fmaf(e_mubar[e], b.x, -m);
+                    const float step = e_sigma[e] * b.x;
+#pragma unroll
+                    for (int kk = 0; kk < 5; ++kk) {
+                        const float x = __builtin_fmaf((float)(kk - 4), step, base);
+                        acc[e][kk] = __builtin_fmaf(A, E - erf(x), acc[e][kk]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < EC; ++e) {
+                if (e_on[e]) {
+                    const float4 ms = S.mu_sig[e_idx[e]];
+                    const float inv2s2 = S.gB[e_idx[e]].y;
+                    const float q = S.gD[e_idx[e]].y;
+                    float inner = 0.f;
+#pragma unroll
+                    for (int kk = 0; kk < 5; ++kk) {
+                        const float sk = madd_ref((float)(kk - 4), ms.w, e_mubar[e]);
+                        const float px = sub_ref(madd_ref(ray.nx, sk, ray.ox), ms.x);
+                        const float py = sub_ref(madd_ref(ray.ny, sk, ray.oy), ms.y);
+                        const float pz = sub_ref(madd_ref(ray.nz, sk, ray.oz), ms.z);
+                        const float dd = dot3_ref(px, py, pz, px, py, pz);
+                        inner += emission_term<EXP>(q, dd * inv2s2, acc[e][kk]);
+                    }
+                    const float4 alb = S.gC[e_idx[e]];
+                    Lr = __builtin_fmaf(alb.x, inner, Lr);
+                    Lg = __builtin_fmaf(alb.y, inner, Lg);
+                    Lb = __builtin_fmaf(alb.z, inner, Lb);
+                    La = __builtin_fmaf(alb.w, inner, La);
+                }
+            }
+        }
+        Lr = wave_sum(Lr); Lg = wave_sum(Lg); Lb = wave_sum(Lb); La = wave_sum(La);
+        if (lane == 0) store_ray(P, r, Lr, Lg, Lb, La);
+    }
+}
+
+template <int EXP, int ERF>
+static void launch_ray_bundle_t(const RayArgs &a, uint32_t long_grid, hipStream_t st)
+{
+    hipLaunchKernelGGL((ray_short_kernel<EXP, ERF>), dim3((uint32_t)((a.nrays + 63u) / 64u)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((ray_long_kernel<EXP, ERF>), dim3(long_grid), dim3(64), 0, st, a);
+}
+void launch_ray_bundle(const RayArgs &a, uint32_t long_grid, int exp_kind, int erf_kind, hipStream_t st)
+{
+    if (!a.nrays || !long_grid) return;
+    VRT_DISPATCH_EXP_ERF(launch_ray_bundle_t, a, long_grid, st);
+}
+
+} // namespace vrtk

@@ -1,0 +1,217 @@
+"""Ray bundles (vrt_hip_radiance_rays*) measured against the two paths they sit between: the full sum of vrt_hip_radiance
+and the camera path of vrt_hip_frame_device.  Needs the GPU.
+
+    python tools/ray_bundles.py [--out-dir profiles]      writes ray_bundles.json and ray_bundles.md there, prints the JSON line
+
+  (a) 64 rays aimed at Gaussian centres of `-g 64` (N = 4096), host pointers in, host pointers out: vrt_hip_radiance (every ray
+      against all N^2 pairs) and vrt_hip_radiance_rays.  Host clock around the calls, which return after completion; the new
+      call warmed up first; medians and the spread over the repeats.  The new call has to be at least 100 times faster.
+  (b) the headline frame's own rays (`-g 64 -w 2048`, the CLI camera) as ONE device bundle -- one origin, 2048^2 directions
+      normalised once on the host in the reference's arithmetic -- against vrt_hip_frame_device of the same frame (16 x 16 tiles).
+  (c) the same number of rays with an origin per ray: two eyes 0.06 apart, interleaved, 2048 x 1024 pixels each.
+  (b), (c): stream events around `--calls` calls enqueued back to back, after warm-up; median and spread over `--repeats` such
+  windows; the two paths of (b) alternate.  ray_stats of one bundle says where the time goes: chunk spheres and Gaussians
+  tested per ray, list entries and pairs per ray, rays per kernel.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as ge  # noqa: E402
+
+pkg = ge._load_pkg()
+from sgrt_amd import scene  # noqa: E402
+
+PACK = pkg.PACK_ROUND | pkg.ALPHA_COMPUTED
+f32 = np.float32
+
+
+def spread(xs):
+    xs = np.asarray(xs, np.float64)
+    return {"median": round(float(np.median(xs)), 5), "min": round(float(xs.min()), 5), "max": round(float(xs.max()), 5), "n": int(xs.size)}
+
+
+def directions(plane, origin):
+    """normalize(plane - origin) in float32, every operation rounded on its own: rt.h:366-371, vec4f_t::normalize."""
+    d = [np.asarray(p, f32) - f32(o) for p, o in zip(plane, origin)]
+    norm = np.sqrt(((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]).astype(f32)).astype(f32)
+    return np.ascontiguousarray(np.stack([c / norm for c in d], 1).astype(f32))
+
+
+def centre_rays(g, count=64):
+    mu = g["mu"][:, :3].astype(np.float64)
+    near = np.sort(np.argsort(np.linalg.norm(mu - mu.mean(0), axis=1), kind="stable")[:count])
+    o = np.array([0.0, 0.0, -4.0], f32)
+    d = mu[near] - o
+    return o, np.ascontiguousarray((d / np.linalg.norm(d, axis=1, keepdims=True)).astype(f32))
+
+
+def part_a(g, repeats_full=3, repeats_rays=50):
+    r = pkg.Renderer(0)
+    r.set_gaussians(g)
+    o, d = centre_rays(g)
+    oo = np.ascontiguousarray(np.tile(o, (len(d), 1)))
+    full_ms, rays_ms = [], []
+    for _ in range(3):
+        rays = r.radiance_rays(o, d)
+    for k in range(repeats_rays):
+        t0 = time.perf_counter()
+        rays = r.radiance_rays(o, d)
+        rays_ms.append((time.perf_counter() - t0) * 1e3)
+        if k % (repeats_rays // repeats_full) == 0 and len(full_ms) < repeats_full:   # in the same run, in between
+            t0 = time.perf_counter()
+            full = r.radiance(oo, d)
+            full_ms.append((time.perf_counter() - t0) * 1e3)
+    r.enable_stats(True)
+    r.radiance_rays(o, d)
+    st = r.ray_stats()
+    r.close()
+    out = {"rays": len(d), "gaussians": len(g), "full_sum_ms": spread(full_ms), "ray_bundle_ms": spread(rays_ms),
+           "speedup": round(float(np.median(full_ms) / np.median(rays_ms)), 1),
+           "max_abs_difference": float(np.abs(rays.astype(np.float64) - full).max()), "peak_radiance": float(full.max()), "ray_stats": st}
+    return out
+
+
+def windows(fns, calls, repeats, warm=3):
+    """ms per call of each fn: `repeats` windows of `calls` back-to-back calls between two stream events, the fns alternating."""
+    import torch
+    ms = [[] for _ in fns]
+    for _ in range(warm):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(repeats):
+        for k, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(calls):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / calls)
+    return [spread(m) for m in ms]
+
+
+def per_ray(st):
+    n = max(st["rays"], 1)
+    return {"chunks_tested": round(st["chunks_tested"] / n, 2), "chunks_kept": round(st["chunks_kept"] / n, 2),
+            "members_tested": round(st["members_tested"] / n, 1), "list_entries": round(st["lane_entries"] / max(st["short_rays"], 1), 2),
+            "pairs": round(st["lane_pairs"] / max(st["short_rays"], 1), 2), "long_rays": st["long_rays"], "scratch_rays": st["scratch_rays"]}
+
+
+def parts_bc(g, w, tiles, calls, repeats):
+    import torch
+    cam, _ = scene.cli_camera(w, w)
+    st = torch.cuda.current_stream().cuda_stream
+    r = pkg.Renderer(0)
+    r.set_gaussians(g)
+    r.set_camera_view(w, w, cam.view)
+    frame = r.frame_call(2.0 / tiles, 2.0 / tiles, cam.view, cam.position, PACK)
+    img_frame = torch.zeros(w * w, dtype=torch.int32, device="cuda")
+    rb = pkg.Renderer(0)          # the bundles get a context of their own: the two paths alternate without disturbing each other's state
+    rb.set_gaussians(g)
+    origin = cam.position
+    d = directions(cam.plane(), origin)
+    t_o, t_d = torch.from_numpy(np.ascontiguousarray(origin, f32)).cuda(), torch.from_numpy(d).cuda()
+    img_b = torch.zeros(w * w, dtype=torch.int32, device="cuda")
+    rad_b = torch.zeros((w * w, 4), dtype=torch.float32, device="cuda")
+    # (c) two eyes, interleaved: ray 2 p + e is pixel p of the upper half of the frame, seen from eye e
+    half = w * (w // 2)
+    eyes = np.stack([origin, origin + f32(0.06) * cam.right]).astype(f32)
+    plane = [np.asarray(p, f32)[:half] for p in cam.plane()]
+    o2 = np.ascontiguousarray(np.tile(eyes, (half, 1)))
+    d2 = np.empty((2 * half, 3), f32)
+    for e in (0, 1):
+        d2[e::2] = directions(plane, eyes[e])
+    t_o2, t_d2 = torch.from_numpy(o2).cuda(), torch.from_numpy(d2).cuda()
+    img_c = torch.zeros(2 * half, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+
+    def run_frame():
+        frame(img_frame.data_ptr(), st)
+
+    def run_b():
+        rb.radiance_rays_device(w * w, t_o.data_ptr(), 0, t_d.data_ptr(), 0, img_b.data_ptr(), PACK, st)
+
+    def run_c():
+        rb.radiance_rays_device(2 * half, t_o2.data_ptr(), 1, t_d2.data_ptr(), 0, img_c.data_ptr(), PACK, st)
+
+    t_frame, t_b = windows([run_frame, run_b], calls, repeats)
+    (t_c,) = windows([run_c], calls, repeats)
+    torch.cuda.synchronize()
+    # the same frame?  (the camera path culls through three more levels and prunes: both sit inside the documented bounds)
+    a, b = img_frame.cpu().numpy().view(np.uint32), img_b.cpu().numpy().view(np.uint32)
+    ch = lambda x: ((x[:, None] >> np.array([0, 8, 16, 24], np.uint32)) & 255).astype(np.int32)  # noqa: E731
+    lsb = int(np.abs(ch(a) - ch(b)).max())
+    rb.enable_stats(True)
+    rb.radiance_rays_device(w * w, t_o.data_ptr(), 0, t_d.data_ptr(), rad_b.data_ptr(), 0, PACK, st)
+    st_b = rb.ray_stats()
+    rb.radiance_rays_device(2 * half, t_o2.data_ptr(), 1, t_d2.data_ptr(), 0, img_c.data_ptr(), PACK, st)
+    st_c = rb.ray_stats()
+    lit = int((rad_b.cpu().numpy()[:, :3].sum(1) > 0).sum())
+    r.close()
+    rb.close()
+    return {"rays": w * w, "frame_device_ms": t_frame, "bundle_one_origin_ms": t_b, "bundle_two_eyes_ms": t_c,
+            "bundle_over_frame": round(t_b["median"] / t_frame["median"], 2), "two_eyes_over_frame": round(t_c["median"] / t_frame["median"], 2),
+            "max_u8_difference_to_frame": lsb, "lit_rays": lit, "per_ray_one_origin": per_ray(st_b), "per_ray_two_eyes": per_ray(st_c),
+            "ray_stats_one_origin": st_b, "ray_stats_two_eyes": st_c}
+
+
+def markdown(res):
+    a, bc = res["a"], res["bc"]
+    pb, pc = bc["per_ray_one_origin"], bc["per_ray_two_eyes"]
+    return f"""# Ray bundles (tools/ray_bundles.py)
+
+(a) {a['rays']} rays at Gaussian centres of `-g 64` (N = {a['gaussians']}), host pointers, call returns after completion:
+
+| call | ms (median, min .. max) |
+|---|---|
+| `vrt_hip_radiance` (full sum) | {a['full_sum_ms']['median']} ({a['full_sum_ms']['min']} .. {a['full_sum_ms']['max']}, n = {a['full_sum_ms']['n']}) |
+| `vrt_hip_radiance_rays` | {a['ray_bundle_ms']['median']} ({a['ray_bundle_ms']['min']} .. {a['ray_bundle_ms']['max']}, n = {a['ray_bundle_ms']['n']}) |
+
+{a['speedup']}x; largest difference of a radiance component {a['max_abs_difference']:.2e} (peak {a['peak_radiance']:.3f}).
+
+(b), (c) {bc['rays']} rays of the `-g 64 -w 2048` frame, device pointers, stream events around back-to-back calls:
+
+| path | ms per call (median, min .. max) | over the camera path |
+|---|---|---|
+| `vrt_hip_frame_device` (16 x 16 tiles) | {bc['frame_device_ms']['median']} ({bc['frame_device_ms']['min']} .. {bc['frame_device_ms']['max']}) | 1 |
+| bundle, one origin | {bc['bundle_one_origin_ms']['median']} ({bc['bundle_one_origin_ms']['min']} .. {bc['bundle_one_origin_ms']['max']}) | {bc['bundle_over_frame']} |
+| bundle, two eyes interleaved | {bc['bundle_two_eyes_ms']['median']} ({bc['bundle_two_eyes_ms']['min']} .. {bc['bundle_two_eyes_ms']['max']}) | {bc['two_eyes_over_frame']} |
+
+The bundle's pixels differ from the frame's by at most {bc['max_u8_difference_to_frame']} LSB; {bc['lit_rays']} of its rays are lit.
+Per ray, one origin: {pb['chunks_tested']} chunk spheres tested, {pb['chunks_kept']} kept, {pb['members_tested']} Gaussians tested one by one,
+{pb['list_entries']} list entries and {pb['pairs']} pairs per lane = ray ray, {pb['long_rays']} rays to the one-wave-per-ray kernel.
+Two eyes: {pc['chunks_tested']} / {pc['chunks_kept']} / {pc['members_tested']} / {pc['list_entries']} / {pc['pairs']} / {pc['long_rays']}.
+"""
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--grid", type=int, default=64)
+    ap.add_argument("--width", type=int, default=2048)
+    ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=7)
+    a = ap.parse_args()
+    g = scene.grid_scene(a.grid)
+    res = {"what": "ray bundles against the full sum and against the camera path; see tools/ray_bundles.py",
+           "a": part_a(g), "bc": parts_bc(g, a.width, 16, a.calls, a.repeats)}
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(a.out_dir, exist_ok=True)
+    with open(os.path.join(a.out_dir, "ray_bundles.json"), "w") as f:
+        f.write(line + "\n")
+    with open(os.path.join(a.out_dir, "ray_bundles.md"), "w") as f:
+        f.write(markdown(res))
+    assert res["a"]["speedup"] >= 100.0, "the ray bundle call has to be at least 100 times faster than the full sum on the same rays"
+
+
+if __name__ == "__main__":
+    main()
