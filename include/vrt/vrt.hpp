@@ -452,6 +452,13 @@ void radiance_rays_device(const f32 *d_origins, bool origin_per_ray, const f32 *
     d.check(vrt_hip_radiance_rays_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_radiance, d_image, pack_flags, hip_stream),
             "vrt_hip_radiance_rays_device");
 }
+// Ray bundles cull through the Morton index of the scene from the next call on (vrt_hip_set_ray_index in include/vrt_hip.h: off by
+// default, the same radiance and the same pixels bit for bit either way; the index is made once per scene).
+inline void set_ray_index(bool on)
+{
+    auto &d = detail::device_t::get();
+    d.check(vrt_hip_set_ray_index(d.ctx, on ? 1 : 0), "vrt_hip_set_ray_index");
+}
 // ======== end of the extension ==========================================================================================
 
 // ---- rt.cpp:8-27 -----------------------------------------------------------------------------------------------------

@@ -348,6 +348,32 @@ typedef struct {
     uint64_t scratch_rays;   /* long rays with more than 1024 kept Gaussians (list continued in device memory)      */
 } vrt_hip_ray_stats;
 int vrt_hip_get_ray_stats(vrt_hip_ctx *ctx, vrt_hip_ray_stats *out);   /* of the last bundle, when vrt_hip_enable_stats is on (waits for it) */
+/* Spatial index of the ray bundles (replaces nothing in the reference, which has no such path; off by default, first value from
+ * VRT_HIP_RAY_INDEX=0|1 at vrt_hip_create).  Without it a bundle's only bounding volumes are spheres over runs of 64 CONSECUTIVE
+ * Gaussians, which in a scene that is not laid out along a space-filling curve are as large as the scene: nearly every one is kept and
+ * every Gaussian is tested against every wave of rays.  With on != 0 the bundles cull through a two-level index instead: the Gaussians
+ * in the Morton order of their centres (10 bits per axis over the centres' bounding box, ties by scene index), leaf spheres over 64
+ * consecutive positions of that order, group spheres over 64 consecutive leaves, both with the radius that includes the members' cull
+ * reach.  Results do not change: the spheres drop only what the per-Gaussian rule above drops, and a ray's list is put back into
+ * ascending scene order before it is shaded, so radiance and packed pixels are the same bit for bit, the same rays go to the same
+ * kernel, and rays / short_rays / long_rays / lane_entries / lane_pairs / scratch_rays of vrt_hip_ray_stats are the same numbers
+ * (its chunk fields are 0 for an indexed bundle: vrt_hip_ray_index_stats below has their counterparts).
+ * The index depends on the scene and cull_eps alone: it is made with the scene tables (or by the first bundle after it was switched
+ * on), on the host from the centres read back, and never per bundle.  Costs 36 B per Gaussian of device memory plus one bit per
+ * Gaussian and workgroup of the one-wave-per-ray kernel.  The call waits for bundles in flight, counts as a state change
+ * (vrt_hip_state_generation) and is carried over by vrt_hip_copy_state, whose mirror builds the same index. */
+int vrt_hip_set_ray_index(vrt_hip_ctx *ctx, int on);
+typedef struct {
+    uint64_t indexed;        /* 1: the last bundle culled through the index (all other fields are 0 when it did not)   */
+    uint64_t groups;         /* group spheres of the scene: ceil(leaves / 64)                                          */
+    uint64_t leaves;         /* leaf spheres of the scene: ceil(N / 64)                                                */
+    uint64_t groups_tested;  /* sum over rays of the group spheres tested (all of them)                                */
+    uint64_t groups_kept;    /* ... and of those the ray's OWN test keeps                                              */
+    uint64_t leaves_tested;  /* sum over rays of the leaf spheres tested (the leaves of groups its WAVE kept)            */
+    uint64_t leaves_kept;    /* sum over rays of the leaves its OWN group and leaf tests keep                           */
+    uint64_t members_tested; /* sum over rays of the Gaussians tested one by one (members of leaves its WAVE kept)       */
+} vrt_hip_ray_index_stats;
+int vrt_hip_get_ray_index_stats(vrt_hip_ctx *ctx, vrt_hip_ray_index_stats *out); /* of the last bundle, when vrt_hip_enable_stats is on (waits for it) */
 
 /* Numeric cross-checks of rt.cpp:8-27 (transmittance_step uses fast_exp like the reference). */
 int vrt_hip_transmittance_step(vrt_hip_ctx *ctx, const float o[3], const float n[3], const float *s, size_t ns,

@@ -47,6 +47,11 @@ class RayStats(C.Structure):
                                           "chunks_kept", "members_tested", "scratch_rays")]
 
 
+class RayIndexStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("indexed", "groups", "leaves", "groups_tested", "groups_kept", "leaves_tested", "leaves_kept",
+                                          "members_tested")]
+
+
 def build(verbose=False):
     """Compile csrc/ for gfx950 with hipcc (cross-compiles without a GPU)."""
     out = None if verbose else subprocess.DEVNULL
@@ -116,6 +121,8 @@ SYMBOLS = {
     "vrt_hip_radiance_rays_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     "vrt_hip_radiance_rays": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _u32p, C.c_int]),
     "vrt_hip_get_ray_stats": (C.c_int, [_vp, C.POINTER(RayStats)]),
+    "vrt_hip_set_ray_index": (C.c_int, [_vp, C.c_int]),
+    "vrt_hip_get_ray_index_stats": (C.c_int, [_vp, C.POINTER(RayIndexStats)]),
     "vrt_hip_transmittance_step": (C.c_int, [_vp, _f32p, _f32p, _f32p, C.c_size_t, C.c_float, _f32p]),
     "vrt_hip_density": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p]),
     "vrt_hip_eval_erf": (C.c_int, [_vp, C.c_int, _f32p, C.c_size_t, _f32p]),
@@ -506,6 +513,17 @@ class Renderer:
         s = RayStats()
         self._chk(self._L.vrt_hip_get_ray_stats(self._h, C.byref(s)), "get_ray_stats")
         return {k: getattr(s, k) for k, _ in RayStats._fields_}
+
+    def set_ray_index(self, on):
+        """Ray bundles cull through the Morton index of the scene (off by default; the same bits either way): see
+        vrt_hip_set_ray_index in include/vrt_hip.h."""
+        self._chk(self._L.vrt_hip_set_ray_index(self._h, int(bool(on))), "set_ray_index")
+
+    def ray_index_stats(self):
+        """The index's counts of the last bundle (enable_stats first): see vrt_hip_ray_index_stats in include/vrt_hip.h."""
+        s = RayIndexStats()
+        self._chk(self._L.vrt_hip_get_ray_index_stats(self._h, C.byref(s)), "get_ray_index_stats")
+        return {k: getattr(s, k) for k, _ in RayIndexStats._fields_}
 
     def eval_erf(self, kind, x):
         x = np.ascontiguousarray(x, np.float32)

@@ -91,6 +91,8 @@ int rebuild_tables(vrt_hip_ctx *c)
     launch_iota(c->iota.p, c->n, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream)); // later launches may use a caller's stream
+    c->ray_index_dirty = true;
+    if (c->ray_index) { int rc = build_ray_index(c); if (rc) return rc; }
     c->tables_dirty = false;
     c->gA_valid = false;
     c->lists_dirty = true;
@@ -721,6 +723,7 @@ Tuning read_tuning()
     if (const char *e = getenv("VRT_HIP_TIMELINE")) { t.timeline = true; if (strstr(e, ".csv")) t.timeline_csv = e; }
     t.table_diag = getenv("VRT_HIP_TABLE_DIAG") != nullptr;
     if (const char *e = getenv("VRT_HIP_RETAIN_FRAME")) t.retain_frame = atoi(e) != 0;
+    if (const char *e = getenv("VRT_HIP_RAY_INDEX")) t.ray_index = atoi(e) != 0;
     return t;
 }
 
@@ -768,6 +771,7 @@ int vrt_hip_create(int device, vrt_hip_ctx **out)
     }
     c->tune = read_tuning();
     c->cull_prune = c->tune.cull_prune; c->table_hx = c->tune.table_step; c->table_budget = c->tune.table_budget;
+    c->ray_index = c->tune.ray_index;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         c->d_stats.reserve(32) != hipSuccess) {
@@ -873,6 +877,7 @@ int vrt_hip_copy_state(vrt_hip_ctx *dst, const vrt_hip_ctx *src)
     dst->exp_kind = src->exp_kind; dst->erf_kind = src->erf_kind; dst->cull_eps = src->cull_eps; dst->cull_prune = src->cull_prune;
     dst->table_hx = src->table_hx; dst->table_budget = src->table_budget; dst->tune.table_adapt = src->tune.table_adapt; dst->tune.table_room = src->tune.table_room;
     dst->rank = src->rank; dst->world = src->world;
+    dst->ray_index = src->ray_index; // the mirror builds the same index with its tables: the order is a function of the scene alone
     dst->tables_dirty = true; dst->lists_dirty = true; dst->shard_dirty = true; dst->ref_valid = false;
     dst->reset_seq = dst->frame_seq;
     if (dst->tile_mode == TILES_HOST) { dst->tile_mode = TILES_NONE; dst->tw = dst->th = 2.f; dst->tiles_w = dst->tiles_h = 1; }
@@ -921,6 +926,16 @@ int vrt_hip_set_cull_prune(vrt_hip_ctx *c, float kappa)
     if (!(kappa >= 0.f)) return fail(c, VRT_HIP_ERR_INVALID, "set_cull_prune: the factor must be >= 0 (0 = off)");
     if (kappa != c->cull_prune) c->reset_seq = c->frame_seq;
     c->cull_prune = kappa;
+    ++c->state_gen;
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_set_ray_index(vrt_hip_ctx *c, int on)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // bundles in flight keep the cull they were enqueued with
+    c->ray_index = on != 0; // the index itself is made with the tables, or by the next bundle if they are already there
     ++c->state_gen;
     return VRT_HIP_OK;
 }

@@ -68,6 +68,7 @@ struct Tuning {
     std::string timeline_csv;    // ... and, when its value names a .csv file, writes the raw stamps there
     bool table_diag = false;     // VRT_HIP_TABLE_DIAG set: vrt_hip_render with stats on prints the table phase split
     bool retain_frame = true;    // VRT_HIP_RETAIN_FRAME=0: every vrt_hip_frame clears its whole image (no retained history)
+    bool ray_index = false;      // VRT_HIP_RAY_INDEX=1: the context's first vrt_hip_ctx::ray_index
 };
 
 enum TileMode { TILES_NONE = 0, TILES_HOST = 1, TILES_DEVICE = 2 };
@@ -250,6 +251,15 @@ struct vrt_hip_ctx {
     DevBuf<float4> rays_rad;
     DevBuf<uint32_t> rays_img;
     bool ray_stats_valid = false; // ray_stats holds the counts of the last bundle (stats were on for it)
+    // Morton index of the ray bundles (vrt_hip_set_ray_index; build_ray_index in vrt_hip_rays.cpp): made with the static tables
+    // while it is switched on, or by the first bundle after it was switched on; never per bundle
+    bool ray_index = false;       // bundles cull through the index
+    bool ray_index_dirty = true;  // the buffers below do not belong to the tables as they are
+    DevBuf<uint32_t> ri_perm;     // Morton position -> scene index
+    DevBuf<float4> ri_mu_sig, ri_gB, ri_leaves, ri_groups; // permuted rows, spheres over 64 positions, spheres over 64 leaves
+    DevBuf<uint32_t> ri_bitmap;   // the long kernel's bitmaps, ceil(n / 32) words per workgroup: zeroed when it grows, left all zero by every bundle
+    bool ray_indexed_last = false; // the last bundle went through the index
+    uint32_t ri_last_leaves = 0, ri_last_groups = 0; // ... over this many leaves and groups
     DevBuf<unsigned long long> d_stats, d_timeline; // d_timeline: VRT_HIP_TIMELINE diagnostics
     size_t timeline_items = 0, timeline_tiles = 0;
     DevBuf<unsigned long long> d_timeline_lists;
@@ -278,6 +288,7 @@ int quiesce(vrt_hip_ctx *c);
 void wait_for_last_stream(vrt_hip_ctx *c, hipStream_t st); // before work on `st` rewrites what the last frame on another stream may still read
 int check_ready(vrt_hip_ctx *c);
 int rebuild_tables(vrt_hip_ctx *c);
+int build_ray_index(vrt_hip_ctx *c); // vrt_hip_rays.cpp: the tables are built and nothing is in flight
 int rebuild_shard(vrt_hip_ctx *c);
 vrtk::SceneTables tables(const vrt_hip_ctx *c);
 vrtk::TileLists tile_geometry(const vrt_hip_ctx *c);

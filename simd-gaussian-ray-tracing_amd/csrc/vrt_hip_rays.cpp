@@ -2,6 +2,9 @@
 // (vrt_ray_kernel.hip).  The scene tables and the chunk spheres are the frame pipeline's; the long-ray queue, its counters and the
 // long kernel's scratch slots belong to the context and only grow.
 #include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <numeric>
 
 #include "vrt_hip_ctx.hpp"
 
@@ -17,7 +20,90 @@ uint32_t long_grid(const vrt_hip_ctx *c)
     return (uint32_t)std::max<uint64_t>(16, std::min<uint64_t>((uint64_t)c->num_cus * 4, by_memory));
 }
 
+// 10 bits spread to every third bit
+uint32_t spread3(uint32_t v)
+{
+    v &= 0x3FFu;
+    v = (v | (v << 16)) & 0x030000FFu;
+    v = (v | (v << 8)) & 0x0300F00Fu;
+    v = (v | (v << 4)) & 0x030C30C3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+
+bool finite_centre(const float4 &p) { return std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z); }
+
+// perm[Morton position] = scene index (build_ray_index says how the key is made)
+std::vector<uint32_t> morton_order(const std::vector<float4> &ms)
+{
+    const uint32_t n = (uint32_t)ms.size();
+    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (const float4 &p : ms) {
+        if (!finite_centre(p)) continue;
+        const float v[3] = { p.x, p.y, p.z };
+        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], v[a]); hi[a] = std::max(hi[a], v[a]); }
+    }
+    std::vector<uint32_t> key(n), perm(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!finite_centre(ms[i])) { key[i] = 0; continue; }
+        const float v[3] = { ms[i].x, ms[i].y, ms[i].z };
+        uint32_t k = 0;
+        for (int a = 0; a < 3; ++a) {
+            const double ext = (double)hi[a] - (double)lo[a];
+            const uint32_t q = ext > 0.0 ? (uint32_t)std::min(1023.0, std::floor(((double)v[a] - (double)lo[a]) / ext * 1024.0)) : 0u;
+            k |= spread3(q) << a;
+        }
+        key[i] = k;
+    }
+    std::iota(perm.begin(), perm.end(), 0u);
+    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+    return perm;
+}
+
 } // namespace
+
+// The Morton index of the ray bundles (include/vrt_hip.h, vrt_hip_set_ray_index).  Key of a Gaussian: its centre quantised to 10 bits
+// per axis over the bounding box of the finite centres (an axis of zero extent: 0), x in the lowest bit of every triple; a centre that is
+// not finite: key 0.  Order: by key, ties by scene index -- a function of the scene alone, so a mirror's index is the same index.
+// Sorted on the host from the rows read back: the caller has waited for everything in flight, as every table build does.
+int build_ray_index(vrt_hip_ctx *c)
+{
+    const uint32_t n = c->n, nleaves = (n + 63u) / 64u, ngroups = (nleaves + 63u) / 64u;
+    std::vector<float4> ms(n), gb(n), pms(n), pgb(n);
+    if (n) {
+        HIPCHK(c, hipMemcpy(ms.data(), c->mu_sig.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(gb.data(), c->gB.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
+    }
+    const std::vector<uint32_t> perm = morton_order(ms);
+    for (uint32_t p = 0; p < n; ++p) { pms[p] = ms[perm[p]]; pgb[p] = gb[perm[p]]; }
+    HIPCHK(c, c->ri_perm.reserve(n)); HIPCHK(c, c->ri_mu_sig.reserve(n)); HIPCHK(c, c->ri_gB.reserve(n));
+    HIPCHK(c, c->ri_leaves.reserve(nleaves)); HIPCHK(c, c->ri_groups.reserve(ngroups));
+    if (n) {
+        HIPCHK(c, hipMemcpy(c->ri_perm.p, perm.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->ri_mu_sig.p, pms.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->ri_gB.p, pgb.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    // leaf spheres: the chunk table's arithmetic, margins included, over the permuted rows
+    launch_build_chunks(n, c->ri_mu_sig.p, c->ri_gB.p, c->ri_leaves.p, c->stream);
+    HIPCHK(c, hipGetLastError());
+    // The chunk kernel's minima and maxima pass over a NaN: a member whose centre or reach is not finite would sit outside its leaf's
+    // sphere, yet the member test keeps it (a comparison with NaN is false).  Such a leaf gets a NaN radius, which keeps.
+    std::vector<uint32_t> open_leaves;
+    for (uint32_t p = 0; p < n; ++p) {
+        const bool ok = finite_centre(pms[p]) && !std::isnan(pgb[p].y) && !std::isnan(pgb[p].w) && pgb[p].w < INFINITY;
+        if (!ok && (open_leaves.empty() || open_leaves.back() != p / 64u)) open_leaves.push_back(p / 64u);
+    }
+    if (!open_leaves.empty()) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const float nan = std::nanf("");
+        for (uint32_t lf : open_leaves) HIPCHK(c, hipMemcpy(&c->ri_leaves.p[lf].w, &nan, sizeof(float), hipMemcpyHostToDevice));
+    }
+    launch_build_ray_groups(nleaves, c->ri_leaves.p, c->ri_groups.p, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // bundles may use a caller's stream
+    c->ray_index_dirty = false;
+    return VRT_HIP_OK;
+}
 
 extern "C" {
 
@@ -32,6 +118,11 @@ int vrt_hip_radiance_rays_device(vrt_hip_ctx *c, size_t nrays, const float *d_or
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
     { int rc = rebuild_tables(c); if (rc) return rc; }
+    const bool indexed = c->ray_index;
+    if (indexed && c->ray_index_dirty) { // switched on after the tables were made
+        { int rc = quiesce(c); if (rc) return rc; }
+        { int rc = build_ray_index(c); if (rc) return rc; }
+    }
     wait_for_last_stream(c, st); // a bundle in flight on another stream uses the queue and the scratch slots
     c->last_stream = st;
     const uint32_t grid = long_grid(c);
@@ -39,10 +130,17 @@ int vrt_hip_radiance_rays_device(vrt_hip_ctx *c, size_t nrays, const float *d_or
     HIPCHK(c, c->ray_queue.reserve(nrays));
     HIPCHK(c, c->ray_counters.reserve(2));
     HIPCHK(c, c->ray_scratch.reserve((size_t)grid * c->n));
-    HIPCHK(c, c->ray_stats.reserve(RAY_STATS_WORDS));
+    constexpr size_t stats_words = RAY_STATS_WORDS + RAY_INDEX_STATS_WORDS;
+    HIPCHK(c, c->ray_stats.reserve(stats_words));
+    const uint32_t bitmap_words = (c->n + 31u) / 32u;
+    if (indexed && c->ri_bitmap.cap < (size_t)grid * bitmap_words) { // new memory: all zero once, every ray leaves it so
+        HIPCHK(c, c->ri_bitmap.reserve((size_t)grid * bitmap_words));
+        HIPCHK(c, hipMemsetAsync(c->ri_bitmap.p, 0, c->ri_bitmap.cap * sizeof(uint32_t), st));
+    }
     HIPCHK(c, hipMemsetAsync(c->ray_counters.p, 0, 2 * sizeof(uint32_t), st));
-    if (c->stats_on) HIPCHK(c, hipMemsetAsync(c->ray_stats.p, 0, RAY_STATS_WORDS * sizeof(unsigned long long), st));
+    if (c->stats_on) HIPCHK(c, hipMemsetAsync(c->ray_stats.p, 0, stats_words * sizeof(unsigned long long), st));
     c->ray_stats_valid = c->stats_on;
+    c->ray_indexed_last = indexed; c->ri_last_leaves = (c->n + 63u) / 64u; c->ri_last_groups = (c->ri_last_leaves + 63u) / 64u;
     RayArgs a{};
     a.S = tables(c);
     a.chunks = c->gChunk.p;
@@ -53,7 +151,12 @@ int vrt_hip_radiance_rays_device(vrt_hip_ctx *c, size_t nrays, const float *d_or
     a.counters = c->ray_counters.p;
     a.scratch = c->ray_scratch.p;
     a.stats = c->stats_on ? c->ray_stats.p : nullptr;
-    launch_ray_bundle(a, grid, c->exp_kind, c->erf_kind, st);
+    if (indexed) {
+        a.perm = c->ri_perm.p; a.mu_sig_m = c->ri_mu_sig.p; a.gB_m = c->ri_gB.p; a.leaves = c->ri_leaves.p; a.groups = c->ri_groups.p;
+        a.bitmap = c->ri_bitmap.p;
+        a.index_stats = c->stats_on ? c->ray_stats.p + RAY_STATS_WORDS : nullptr;
+    }
+    launch_ray_bundle(a, grid, indexed, c->exp_kind, c->erf_kind, st);
     HIPCHK(c, hipGetLastError());
     return VRT_HIP_OK;
 }
@@ -94,6 +197,20 @@ int vrt_hip_get_ray_stats(vrt_hip_ctx *c, vrt_hip_ray_stats *out)
     HIPCHK(c, hipMemcpy(w, c->ray_stats.p, sizeof(w), hipMemcpyDeviceToHost));
     out->rays = w[0]; out->short_rays = w[1]; out->long_rays = w[2]; out->lane_entries = w[3]; out->lane_pairs = w[4];
     out->chunks_tested = w[5]; out->chunks_kept = w[6]; out->members_tested = w[7]; out->scratch_rays = w[8];
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_get_ray_index_stats(vrt_hip_ctx *c, vrt_hip_ray_index_stats *out)
+{
+    if (!c || !out) return VRT_HIP_ERR_INVALID;
+    *out = vrt_hip_ray_index_stats{};
+    if (!c->ray_stats_valid || !c->ray_indexed_last) return VRT_HIP_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // waits for the bundle
+    unsigned long long w[RAY_INDEX_STATS_WORDS];
+    HIPCHK(c, hipMemcpy(w, c->ray_stats.p + RAY_STATS_WORDS, sizeof(w), hipMemcpyDeviceToHost));
+    out->indexed = 1; out->groups = c->ri_last_groups; out->leaves = c->ri_last_leaves;
+    out->groups_tested = w[0]; out->groups_kept = w[1]; out->leaves_tested = w[2]; out->leaves_kept = w[3]; out->members_tested = w[4];
     return VRT_HIP_OK;
 }
 

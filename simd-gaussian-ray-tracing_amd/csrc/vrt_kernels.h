@@ -296,9 +296,21 @@ struct RayArgs {
     uint32_t *scratch;           // S.n words per workgroup of the long kernel
     unsigned long long *stats;   // nullable: rays, short rays, long rays, sum of short list lengths, sum of their squares, chunk tests,
                                  // chunks kept, member tests (per ray: the members its wave visited), long rays that used their scratch slot
+    // The Morton index (vrt_hip_set_ray_index; read by the INDEXED instantiations only, nullptr otherwise): the scene's rows in the
+    // order of their centres' Morton keys, spheres over every 64 consecutive positions (leaves) and over every 64 consecutive leaves (groups)
+    const uint32_t *perm;        // [n] Morton position -> scene index
+    const float4 *mu_sig_m, *gB_m; // [n] SceneTables::mu_sig / gB rows in Morton order: the member loops keep their consecutive rows
+    const float4 *leaves;        // [ceil(n / 64)] launch_build_chunks over the permuted rows
+    const float4 *groups;        // [ceil(leaves / 64)] launch_build_ray_groups
+    uint32_t *bitmap;            // ceil(n / 32) words per workgroup of the long kernel, all zero between rays: bit j = scene index j survives
+    unsigned long long *index_stats; // nullable: sums over rays of group tests, groups kept, leaf tests, leaves kept (both by the ray's own tests),
+                                 // member tests (the members of the leaves its wave visited)
 };
-constexpr int RAY_STATS_WORDS = 9;
-void launch_ray_bundle(const RayArgs &a, uint32_t long_grid /* one-wave workgroups of the long kernel */, int exp_kind, int erf_kind, hipStream_t st);
+constexpr int RAY_STATS_WORDS = 9, RAY_INDEX_STATS_WORDS = 5; // one device buffer: the index's words follow the nine
+void launch_ray_bundle(const RayArgs &a, uint32_t long_grid /* one-wave workgroups of the long kernel */, bool indexed, int exp_kind, int erf_kind,
+                       hipStream_t st);
+// group spheres of the Morton index: one per 64 consecutive leaf spheres, bounding them
+void launch_build_ray_groups(uint32_t nleaves, const float4 *leaves, float4 *groups, hipStream_t st);
 
 // point queries
 void launch_transmittance(const SceneTables &s, const float o[3], const float n[3], const float *d_s, size_t ns,

@@ -6,6 +6,9 @@
 //   ray_long_kernel   one wave per ray whose list is longer, lane = emitter; reads its work count on the device
 // Which kernel shades a ray depends on that ray's own list length alone, and a lane's list on its own tests alone: a ray's
 // bits are a function of (ray, scene, options), whatever its wave-mates are.
+// Both kernels come in a second, INDEXED form (vrt_hip_set_ray_index): the cull walks the scene in the Morton order of its centres --
+// group spheres (64 leaves), leaf spheres (64 consecutive Morton positions), members -- and hands the shading code the SAME list in
+// the same ascending scene order: the sphere tests only ever drop what the member test drops, so no bit of a result moves.
 // Compiled like the block kernel with -mllvm -amdgpu-sched-strategy=max-ilp (see the note at the top of vrt_block_kernel.hip):
 // the pair loops are the same independent erf terms.
 #include "vrt_kernels_common.hpp"
@@ -31,6 +34,38 @@ __device__ __forceinline__ bool ray_member_keeps(float4 ms, float4 bq, const Lan
     const float mubar = dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz);
     const float x = mul_ref(sub_ref(dot3_ref(cx, cy, cz, cx, cy, cz), mul_ref(mubar, mubar)), bq.y);
     return !(x > bq.w);
+}
+
+// Uniform (scalar) 4-byte load, as uload
+typedef const uint32_t __attribute__((address_space(4))) *cu32ptr;
+__device__ __forceinline__ uint32_t uload_u32(const uint32_t *base, uint32_t idx) { return ((cu32ptr)(const void *)base)[idx]; }
+
+// Group spheres of the Morton index: lane = leaf sphere of the group, one wave per group.  Centre = mid-point of the box of the leaf
+// centres, radius = the farthest leaf centre plus that leaf's radius, widened by build_chunks_kernel's margins: a line farther from the
+// centre than that is farther from every leaf centre than the leaf's radius (the distance to a line is 1-Lipschitz in the point).
+// A leaf sphere that is not finite (a NaN or infinite centre or reach among its members) makes the radius NaN, which ray_chunk_keeps keeps.
+__global__ __launch_bounds__(256) void build_ray_groups_kernel(uint32_t nleaves, const float4 *__restrict__ leaves, float4 *__restrict__ groups)
+{
+    const uint32_t lane = threadIdx.x & 63u, group = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (group * 64u >= nleaves) return;
+    const uint32_t i = group * 64u + lane;
+    const bool valid = i < nleaves;
+    const float4 p = valid ? leaves[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool finite = fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY && fabsf(p.w) < INFINITY;
+    const bool all_finite = __ballot(valid && !finite) == 0ull;
+    const float lo_x = wave_min(valid ? p.x : INFINITY), hi_x = wave_max(valid ? p.x : -INFINITY);
+    const float lo_y = wave_min(valid ? p.y : INFINITY), hi_y = wave_max(valid ? p.y : -INFINITY);
+    const float lo_z = wave_min(valid ? p.z : INFINITY), hi_z = wave_max(valid ? p.z : -INFINITY);
+    const float mx = 0.5f * (lo_x + hi_x), my = 0.5f * (lo_y + hi_y), mz = 0.5f * (lo_z + hi_z);
+    const float dx = p.x - mx, dy = p.y - my, dz = p.z - mz;
+    float rho = wave_max(valid ? sqrtf(dx * dx + dy * dy + dz * dz) + p.w : 0.f);
+    rho = rho * 1.0001f + 1e-6f * (1.f + fabsf(mx) + fabsf(my) + fabsf(mz));
+    if (lane == 0) groups[group] = make_float4(mx, my, mz, all_finite ? rho : __builtin_nanf(""));
+}
+void launch_build_ray_groups(uint32_t nleaves, const float4 *leaves, float4 *groups, hipStream_t st)
+{
+    const uint32_t ngr = (nleaves + 63u) / 64u;
+    if (ngr) hipLaunchKernelGGL(build_ray_groups_kernel, dim3((ngr + 3u) / 4u), dim3(256), 0, st, nleaves, leaves, groups);
 }
 
 __device__ __forceinline__ LaneRay load_ray(const RayArgs &P, uint64_t r)
@@ -125,7 +160,7 @@ __device__ __forceinline__ void ray_shade_chunk(const SceneTables &S, const uint
     }
 }
 
-template <int EXP, int ERF>
+template <int EXP, int ERF, bool INDEXED>
 __global__ __launch_bounds__(64) void ray_short_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -139,6 +174,47 @@ __global__ __launch_bounds__(64) void ray_short_kernel(RayArgs) // read through 
     // ---- cull: chunk spheres per lane, members of the chunks some lane keeps with a wave-uniform index ----
     const uint32_t N = S.n, nch = (N + 63u) / 64u;
     uint32_t nl = 0, chunks_kept = 0, members = 0;
+    [[maybe_unused]] uint32_t groups_kept = 0, leaf_tests = 0;
+    if constexpr (INDEXED) {
+        // ---- the same cull through the Morton index: group spheres, the leaf spheres of the groups some lane keeps, the members of the
+        // leaves some lane keeps -- all three with a wave-uniform index (scalar loads of consecutive permuted rows).  The leaf spheres
+        // take the place of the chunk spheres (nch of them, 64 consecutive Morton positions each).
+        const uint32_t ngr = (nch + 63u) / 64u;
+        for (uint32_t g = 0; g < ngr; ++g) {
+            const bool kg = valid && ray_chunk_keeps(uload(P.groups, g), ray);
+            if (__ballot(kg) == 0ull) continue;
+            groups_kept += kg ? 1u : 0u;
+            const uint32_t lf0 = g * 64u, lf1 = min(lf0 + 64u, nch);
+            leaf_tests += lf1 - lf0;
+            for (uint32_t lf = lf0; lf < lf1; ++lf) {
+                // a lane files only what its OWN group and leaf tests admit
+                const bool kc = kg && ray_chunk_keeps(uload(P.leaves, lf), ray);
+                if (__ballot(kc) == 0ull) continue;
+                chunks_kept += kc ? 1u : 0u;
+                const uint32_t first = lf * 64u, last = min(first + 64u, N);
+                members += last - first;
+#pragma unroll 2
+                for (uint32_t pos = first; pos < last; ++pos) {
+                    const bool km = ray_member_keeps(uload(P.mu_sig_m, pos), uload(P.gB_m, pos), ray);
+                    if (kc && km) {
+                        if (nl < (uint32_t)RAY_PL) {
+                            // entries arrive in Morton order: filed at their place in ascending SCENE order, the order the shading sums in
+                            const uint32_t idx = uload_u32(P.perm, pos);
+                            uint32_t k = nl;
+                            while (k > 0u) {
+                                const uint32_t prev = s_list[(k - 1u) * 64u + lane];
+                                if (prev < idx) break;
+                                s_list[k * 64u + lane] = prev;
+                                --k;
+                            }
+                            s_list[k * 64u + lane] = idx;
+                        }
+                        ++nl; // the count runs on: such a ray's list is not used
+                    }
+                }
+            }
+        }
+    } else
     for (uint32_t c = 0; c < nch; ++c) {
         const bool kc = valid && ray_chunk_keeps(uload(P.chunks, c), ray);
         if (__ballot(kc) == 0ull) continue;
@@ -164,9 +240,17 @@ __global__ __launch_bounds__(64) void ray_short_kernel(RayArgs) // read through 
         atomicAdd(&P.stats[0], 1ull);
         atomicAdd(&P.stats[is_long ? 2 : 1], 1ull);
         if (!is_long) { atomicAdd(&P.stats[3], (unsigned long long)nl); atomicAdd(&P.stats[4], (unsigned long long)nl * nl); }
-        atomicAdd(&P.stats[5], (unsigned long long)nch);
-        atomicAdd(&P.stats[6], (unsigned long long)chunks_kept);
-        atomicAdd(&P.stats[7], (unsigned long long)members);
+        if constexpr (INDEXED) {
+            atomicAdd(&P.index_stats[0], (unsigned long long)((nch + 63u) / 64u));
+            atomicAdd(&P.index_stats[1], (unsigned long long)groups_kept);
+            atomicAdd(&P.index_stats[2], (unsigned long long)leaf_tests);
+            atomicAdd(&P.index_stats[3], (unsigned long long)chunks_kept);
+            atomicAdd(&P.index_stats[4], (unsigned long long)members);
+        } else {
+            atomicAdd(&P.stats[5], (unsigned long long)nch);
+            atomicAdd(&P.stats[6], (unsigned long long)chunks_kept);
+            atomicAdd(&P.stats[7], (unsigned long long)members);
+        }
     }
 
     // ---- shade: every lane walks its own list; the loops run to the longest list of the wave's short rays ----
@@ -201,7 +285,10 @@ __device__ __forceinline__ float wave_sum(float v)
 // block cull does) into s_list, and beyond RAY_LCAP into this workgroup's scratch slot of N words (entry k at slot[k]), so no
 // list length is refused.  Lane l then takes emitters l, l + 64, ... against all survivors as absorbers (wave-uniform: scalar
 // row loads); the four sums are reduced over the lanes in a fixed order -- another summation order than the reference's.
-template <int EXP, int ERF>
+// INDEXED: the re-cull goes through the Morton index (lane = group, lane = leaf of a kept group, lane = member of a kept leaf) and finds
+// the survivors in Morton order; each sets bit perm[pos] of this workgroup's bitmap (N bits of device memory, all zero between rays),
+// and the list is read off the bitmap in ascending scene order -- the list the unindexed compaction makes.
+template <int EXP, int ERF, bool INDEXED>
 __global__ __launch_bounds__(64) void ray_long_kernel(RayArgs)
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -227,6 +314,45 @@ __global__ __launch_bounds__(64) void ray_long_kernel(RayArgs)
         // ---- cull: 64 chunk spheres at a time (lane = chunk), then the members of the kept ones (lane = Gaussian) ----
         __syncthreads(); // the previous ray's list reads are done
         uint32_t n = 0;
+        if constexpr (INDEXED) {
+            const uint32_t ngr = (nch + 63u) / 64u, nwords = (N + 31u) / 32u;
+            uint32_t *bm = P.bitmap + (size_t)blockIdx.x * nwords;
+            for (uint32_t g0 = 0; g0 < ngr; g0 += 64u) {
+                const uint32_t g = g0 + lane;
+                unsigned long long gmask = __ballot(g < ngr && ray_chunk_keeps(P.groups[min(g, ngr - 1u)], ray));
+                while (gmask) {
+                    const uint32_t lf0 = (g0 + (uint32_t)__builtin_ctzll(gmask)) * 64u, lf = lf0 + lane;
+                    gmask &= gmask - 1ull;
+                    unsigned long long cmask = __ballot(lf < nch && ray_chunk_keeps(P.leaves[min(lf, nch - 1u)], ray));
+                    while (cmask) {
+                        const uint32_t pos = (lf0 + (uint32_t)__builtin_ctzll(cmask)) * 64u + lane;
+                        cmask &= cmask - 1ull;
+                        const uint32_t pc = min(pos, N - 1u);
+                        if (pos < N && ray_member_keeps(P.mu_sig_m[pc], P.gB_m[pc], ray)) {
+                            const uint32_t idx = P.perm[pc];
+                            if (idx < N) atomicOr(&bm[idx >> 5], 1u << (idx & 31u)); // lanes may share a word
+                        }
+                    }
+                }
+            }
+            __threadfence(); // the bits are in memory before they are taken out again
+            // lane = word: take the word and leave zero behind (an atomic: the value in memory, whatever this CU's cache holds of the
+            // last ray), then every lane files its bits from the wave's running count on -- ascending scene index
+            for (uint32_t w0 = 0; w0 < nwords; w0 += 64u) {
+                const uint32_t w = w0 + lane;
+                uint32_t bits = w < nwords ? atomicExch(&bm[w], 0u) : 0u;
+                const uint32_t cnt = (uint32_t)__popc(bits), incl = wave_inclusive_sum(cnt);
+                uint32_t pos = n + incl - cnt;
+                while (bits) {
+                    const uint32_t idx = w * 32u + (uint32_t)__builtin_ctz(bits);
+                    bits &= bits - 1u;
+                    if (pos < (uint32_t)RAY_LCAP) s_list[pos] = idx;
+                    else if (pos < N) slot[pos] = idx;
+                    ++pos;
+                }
+                n += lane_value_u32(incl, 63u);
+            }
+        } else
         for (uint32_t c0 = 0; c0 < nch; c0 += 64u) {
             const uint32_t c = c0 + lane;
             unsigned long long cmask = __ballot(c < nch && ray_chunk_keeps(P.chunks[min(c, nch - 1u)], ray));
@@ -320,15 +446,21 @@ __global__ __launch_bounds__(64) void ray_long_kernel(RayArgs)
 }
 
 template <int EXP, int ERF>
-static void launch_ray_bundle_t(const RayArgs &a, uint32_t long_grid, hipStream_t st)
+static void launch_ray_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
 {
-    hipLaunchKernelGGL((ray_short_kernel<EXP, ERF>), dim3((uint32_t)((a.nrays + 63u) / 64u)), dim3(64), 0, st, a);
-    hipLaunchKernelGGL((ray_long_kernel<EXP, ERF>), dim3(long_grid), dim3(64), 0, st, a);
+    const dim3 short_grid((uint32_t)((a.nrays + 63u) / 64u));
+    if (indexed) {
+        hipLaunchKernelGGL((ray_short_kernel<EXP, ERF, true>), short_grid, dim3(64), 0, st, a);
+        hipLaunchKernelGGL((ray_long_kernel<EXP, ERF, true>), dim3(long_grid), dim3(64), 0, st, a);
+    } else {
+        hipLaunchKernelGGL((ray_short_kernel<EXP, ERF, false>), short_grid, dim3(64), 0, st, a);
+        hipLaunchKernelGGL((ray_long_kernel<EXP, ERF, false>), dim3(long_grid), dim3(64), 0, st, a);
+    }
 }
-void launch_ray_bundle(const RayArgs &a, uint32_t long_grid, int exp_kind, int erf_kind, hipStream_t st)
+void launch_ray_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
 {
     if (!a.nrays || !long_grid) return;
-    VRT_DISPATCH_EXP_ERF(launch_ray_bundle_t, a, long_grid, st);
+    VRT_DISPATCH_EXP_ERF(launch_ray_bundle_t, a, long_grid, indexed, st);
 }
 
 } // namespace vrtk

@@ -1,7 +1,9 @@
 // ray_bundle_example.cpp -- a stereo pair in ONE call of vrt::radiance_rays (the extension of include/vrt/vrt.hpp): the rays of
 // two pinhole eyes, interleaved, each ray with its own origin.  Prints a checksum per eye; with a file name as argument it
 // also writes the rays (origin, direction: 6 floats per ray) there, so that anyone can shade the same rays again.
+// A second call shades the same rays through the Morton index of the scene (vrt::set_ray_index): the same bits, or exit status 2.
 #include <cstdio>
+#include <cstring>
 
 #include "../../include/vrt/vrt.hpp"
 
@@ -34,6 +36,13 @@ int main(int argc, char **argv)
         }
         std::printf("%s eye: radiance sum %.9g pixel hash %08x\n", e ? "right" : "left", sum, hash);
     }
+    std::vector<vec4f_t> L2(L.size());
+    std::vector<u32> px2(px.size());
+    set_ray_index(true);
+    radiance_rays(o.data(), n.data(), o.size(), scene, L2.data(), px2.data());
+    const bool same = !std::memcmp(L.data(), L2.data(), L.size() * sizeof(vec4f_t)) && !std::memcmp(px.data(), px2.data(), px.size() * sizeof(u32));
+    std::fprintf(stderr, "ray index: %s\n", same ? "identical" : "DIFFERENT");
+    if (!same) return 2;
     if (argc > 1) {
         FILE *f = std::fopen(argv[1], "wb");
         if (!f) return 1;

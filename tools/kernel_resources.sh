@@ -9,4 +9,4 @@ case "$1" in
   ray) SRC=vrt_ray_kernel.hip; EXTRA="-mllvm -amdgpu-sched-strategy=max-ilp" ;;
   *) SRC=vrt_kernels.hip; EXTRA="" ;;
 esac
-/opt/rocm/bin/hipcc $FLAGS $EXTRA -c $SRC -o /dev/null 2>&1 | grep -E "Function Name|VGPRs:|SGPRs:|Spill|ScratchSize|Occupancy|LDS Size" | sed 's/^.*remark: //' | paste - - - - - - - - - - | grep -E "${2:-.}" | sed 's/\[-Rpass-analysis=kernel-resource-usage\]//g' | cut -c1-400
+/opt/rocm/bin/hipcc $FLAGS $EXTRA -c $SRC -o /dev/null 2>&1 | grep -E "Function Name|VGPRs:|SGPRs:|Spill|ScratchSize|Occupancy|LDS Size" | sed 's/^.*remark: //' | paste - - - - - - - - | grep -E "${2:-.}" | sed 's/\[-Rpass-analysis=kernel-resource-usage\]//g' | cut -c1-400

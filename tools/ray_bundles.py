@@ -12,6 +12,11 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
   (b), (c): stream events around `--calls` calls enqueued back to back, after warm-up; median and spread over `--repeats` such
   windows; the two paths of (b) alternate.  ray_stats of one bundle says where the time goes: chunk spheres and Gaussians
   tested per ray, list entries and pairs per ray, rays per kernel.
+  (d) 2^20 rays, each from its own point of a sphere around `-g 64` at a random point of the scene; (e) the `-g 16` frame's rays;
+  (f) a 256^2 frame's rays through the teapot (dense: most lit rays go to the one-wave-per-ray kernel).
+  Every bundle is timed with the Morton index (vrt_hip_set_ray_index) off and on in the same run -- two contexts on the same scene,
+  their windows alternating -- with ray_stats / ray_index_stats of one bundle each, and the two results compared bit for bit.  On (b)
+  the indexed call has to be faster than the unindexed one.
 """
 import argparse
 import json
@@ -57,7 +62,18 @@ def part_a(g, repeats_full=3, repeats_rays=50):
     r.set_gaussians(g)
     o, d = centre_rays(g)
     oo = np.ascontiguousarray(np.tile(o, (len(d), 1)))
-    full_ms, rays_ms = [], []
+    full_ms, rays_ms, indexed_ms = [], [], []
+    r.set_ray_index(1)
+    for k in range(3 + repeats_rays):                 # the first calls build the index and warm up
+        t0 = time.perf_counter()
+        indexed = r.radiance_rays(o, d)
+        if k >= 3:
+            indexed_ms.append((time.perf_counter() - t0) * 1e3)
+    r.enable_stats(True)
+    r.radiance_rays(o, d)
+    ist = r.ray_index_stats()
+    r.enable_stats(False)
+    r.set_ray_index(0)
     for _ in range(3):
         rays = r.radiance_rays(o, d)
     for k in range(repeats_rays):
@@ -74,7 +90,9 @@ def part_a(g, repeats_full=3, repeats_rays=50):
     r.close()
     out = {"rays": len(d), "gaussians": len(g), "full_sum_ms": spread(full_ms), "ray_bundle_ms": spread(rays_ms),
            "speedup": round(float(np.median(full_ms) / np.median(rays_ms)), 1),
-           "max_abs_difference": float(np.abs(rays.astype(np.float64) - full).max()), "peak_radiance": float(full.max()), "ray_stats": st}
+           "max_abs_difference": float(np.abs(rays.astype(np.float64) - full).max()), "peak_radiance": float(full.max()), "ray_stats": st,
+           "indexed_ms": spread(indexed_ms), "off_over_on": round(float(np.median(rays_ms) / np.median(indexed_ms)), 2),
+           "identical": bool((indexed == rays).all()), "ray_index_stats": ist}
     return out
 
 
@@ -105,6 +123,66 @@ def per_ray(st):
             "pairs": round(st["lane_pairs"] / max(st["short_rays"], 1), 2), "long_rays": st["long_rays"], "scratch_rays": st["scratch_rays"]}
 
 
+def per_ray_index(ist):
+    n = max(ist["groups_tested"] // max(ist["groups"], 1), 1)
+    return {"leaves": ist["leaves"], "groups": ist["groups"], "groups_kept": round(ist["groups_kept"] / n, 2),
+            "leaves_tested": round(ist["leaves_tested"] / n, 2), "leaves_kept": round(ist["leaves_kept"] / n, 2),
+            "members_tested": round(ist["members_tested"] / n, 1)}
+
+
+def off_and_on(g, nrays, o, origin_per_ray, d, calls, repeats, before=()):
+    """One device bundle timed with the index off and on: two contexts on the same scene, windows alternating (behind `before`, other
+    paths to alternate with).  o, d: host arrays."""
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    ctx = [pkg.Renderer(0), pkg.Renderer(0)]
+    t_o, t_d = torch.from_numpy(np.ascontiguousarray(o, f32)).cuda(), torch.from_numpy(np.ascontiguousarray(d, f32)).cuda()
+    img = [torch.zeros(nrays, dtype=torch.int32, device="cuda") for _ in ctx]
+    rad = [torch.zeros((nrays, 4), dtype=torch.float32, device="cuda") for _ in ctx]
+    for on, r in enumerate(ctx):
+        r.set_gaussians(g)
+        r.set_ray_index(on)
+    torch.cuda.synchronize()
+    run = [lambda k=k: ctx[k].radiance_rays_device(nrays, t_o.data_ptr(), origin_per_ray, t_d.data_ptr(), 0, img[k].data_ptr(), PACK, st) for k in (0, 1)]
+    t = windows(list(before) + run, calls, repeats)
+    stats = []
+    for k, r in enumerate(ctx):
+        r.enable_stats(True)
+        r.radiance_rays_device(nrays, t_o.data_ptr(), origin_per_ray, t_d.data_ptr(), rad[k].data_ptr(), img[k].data_ptr(), PACK, st)
+        stats.append((r.ray_stats(), r.ray_index_stats()))
+    torch.cuda.synchronize()
+    same = bool(torch.equal(rad[0], rad[1]) and torch.equal(img[0], img[1]))
+    lit = int((rad[0][:, :3].sum(1) > 0).sum().item())
+    image = img[0].cpu().numpy().view(np.uint32)
+    for r in ctx:
+        r.close()
+    res = {"rays": nrays, "gaussians": len(g), "off_ms": t[-2], "on_ms": t[-1], "off_over_on": round(t[-2]["median"] / t[-1]["median"], 2),
+           "identical": same, "lit_rays": lit, "per_ray_off": per_ray(stats[0][0]), "per_ray_on": per_ray(stats[1][0]),
+           "per_ray_index": per_ray_index(stats[1][1]), "ray_stats_off": stats[0][0], "ray_stats_on": stats[1][0], "ray_index_stats": stats[1][1]}
+    return res, t[:-2], image
+
+
+def scattered(g, count, seed=5, radius=4.0):
+    rng = np.random.default_rng(seed)
+    mu = g["mu"][:, :3].astype(np.float64)
+    lo, hi = mu.min(0), mu.max(0)
+    v = rng.normal(size=(count, 3))
+    o = ((lo + hi) / 2 + radius * v / np.linalg.norm(v, axis=1, keepdims=True)).astype(f32)
+    dd = rng.uniform(lo, hi, size=(count, 3)) - o
+    return o, np.ascontiguousarray((dd / np.linalg.norm(dd, axis=1, keepdims=True)).astype(f32))
+
+
+def parts_def(g64, calls, repeats):
+    o, d = scattered(g64, 1 << 20)
+    res_d, _, _ = off_and_on(g64, len(d), o, 1, d, calls, repeats)
+    cam, _ = scene.cli_camera(2048, 2048)
+    res_e, _, _ = off_and_on(scene.grid_scene(16), 2048 * 2048, cam.position, 0, directions(cam.plane(), cam.position), calls, repeats)
+    cam, _ = scene.cli_camera(256, 256)
+    teapot = scene.read_obj(os.path.join(ROOT, "tests", "golden", "test-objects", "teapot.obj"))
+    res_f, _, _ = off_and_on(teapot, 256 * 256, cam.position, 0, directions(cam.plane(), cam.position), 2, max(3, repeats // 2))
+    return {"scattered": res_d, "g16": res_e, "teapot": res_f}
+
+
 def parts_bc(g, w, tiles, calls, repeats):
     import torch
     cam, _ = scene.cli_camera(w, w)
@@ -114,13 +192,8 @@ def parts_bc(g, w, tiles, calls, repeats):
     r.set_camera_view(w, w, cam.view)
     frame = r.frame_call(2.0 / tiles, 2.0 / tiles, cam.view, cam.position, PACK)
     img_frame = torch.zeros(w * w, dtype=torch.int32, device="cuda")
-    rb = pkg.Renderer(0)          # the bundles get a context of their own: the two paths alternate without disturbing each other's state
-    rb.set_gaussians(g)
     origin = cam.position
     d = directions(cam.plane(), origin)
-    t_o, t_d = torch.from_numpy(np.ascontiguousarray(origin, f32)).cuda(), torch.from_numpy(d).cuda()
-    img_b = torch.zeros(w * w, dtype=torch.int32, device="cuda")
-    rad_b = torch.zeros((w * w, 4), dtype=torch.float32, device="cuda")
     # (c) two eyes, interleaved: ray 2 p + e is pixel p of the upper half of the frame, seen from eye e
     half = w * (w // 2)
     eyes = np.stack([origin, origin + f32(0.06) * cam.right]).astype(f32)
@@ -129,38 +202,27 @@ def parts_bc(g, w, tiles, calls, repeats):
     d2 = np.empty((2 * half, 3), f32)
     for e in (0, 1):
         d2[e::2] = directions(plane, eyes[e])
-    t_o2, t_d2 = torch.from_numpy(o2).cuda(), torch.from_numpy(d2).cuda()
-    img_c = torch.zeros(2 * half, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
 
     def run_frame():
         frame(img_frame.data_ptr(), st)
 
-    def run_b():
-        rb.radiance_rays_device(w * w, t_o.data_ptr(), 0, t_d.data_ptr(), 0, img_b.data_ptr(), PACK, st)
-
-    def run_c():
-        rb.radiance_rays_device(2 * half, t_o2.data_ptr(), 1, t_d2.data_ptr(), 0, img_c.data_ptr(), PACK, st)
-
-    t_frame, t_b = windows([run_frame, run_b], calls, repeats)
-    (t_c,) = windows([run_c], calls, repeats)
+    # the bundles get contexts of their own: the paths alternate without disturbing each other's state
+    res_b, (t_frame,), img_b = off_and_on(g, w * w, origin, 0, d, calls, repeats, before=[run_frame])
+    res_c, _, _ = off_and_on(g, 2 * half, o2, 1, d2, calls, repeats)
     torch.cuda.synchronize()
     # the same frame?  (the camera path culls through three more levels and prunes: both sit inside the documented bounds)
-    a, b = img_frame.cpu().numpy().view(np.uint32), img_b.cpu().numpy().view(np.uint32)
+    a = img_frame.cpu().numpy().view(np.uint32)
     ch = lambda x: ((x[:, None] >> np.array([0, 8, 16, 24], np.uint32)) & 255).astype(np.int32)  # noqa: E731
-    lsb = int(np.abs(ch(a) - ch(b)).max())
-    rb.enable_stats(True)
-    rb.radiance_rays_device(w * w, t_o.data_ptr(), 0, t_d.data_ptr(), rad_b.data_ptr(), 0, PACK, st)
-    st_b = rb.ray_stats()
-    rb.radiance_rays_device(2 * half, t_o2.data_ptr(), 1, t_d2.data_ptr(), 0, img_c.data_ptr(), PACK, st)
-    st_c = rb.ray_stats()
-    lit = int((rad_b.cpu().numpy()[:, :3].sum(1) > 0).sum())
+    lsb = int(np.abs(ch(a) - ch(img_b)).max())
     r.close()
-    rb.close()
+    t_b, t_c = res_b["off_ms"], res_c["off_ms"]
     return {"rays": w * w, "frame_device_ms": t_frame, "bundle_one_origin_ms": t_b, "bundle_two_eyes_ms": t_c,
             "bundle_over_frame": round(t_b["median"] / t_frame["median"], 2), "two_eyes_over_frame": round(t_c["median"] / t_frame["median"], 2),
-            "max_u8_difference_to_frame": lsb, "lit_rays": lit, "per_ray_one_origin": per_ray(st_b), "per_ray_two_eyes": per_ray(st_c),
-            "ray_stats_one_origin": st_b, "ray_stats_two_eyes": st_c}
+            "indexed_over_frame": round(res_b["on_ms"]["median"] / t_frame["median"], 2),
+            "max_u8_difference_to_frame": lsb, "lit_rays": res_b["lit_rays"], "per_ray_one_origin": res_b["per_ray_off"],
+            "per_ray_two_eyes": res_c["per_ray_off"], "ray_stats_one_origin": res_b["ray_stats_off"], "ray_stats_two_eyes": res_c["ray_stats_off"],
+            "one_origin": res_b, "two_eyes": res_c}
 
 
 def markdown(res):
@@ -189,7 +251,30 @@ The bundle's pixels differ from the frame's by at most {bc['max_u8_difference_to
 Per ray, one origin: {pb['chunks_tested']} chunk spheres tested, {pb['chunks_kept']} kept, {pb['members_tested']} Gaussians tested one by one,
 {pb['list_entries']} list entries and {pb['pairs']} pairs per lane = ray ray, {pb['long_rays']} rays to the one-wave-per-ray kernel.
 Two eyes: {pc['chunks_tested']} / {pc['chunks_kept']} / {pc['members_tested']} / {pc['list_entries']} / {pc['pairs']} / {pc['long_rays']}.
+
+Morton index (`vrt_hip_set_ray_index`) off and on, the same bundle in the same run, windows alternating; ms per call, median (min .. max):
+
+| bundle | rays | N | index off | index on | off / on | same bits | leaves kept per ray (of) | Gaussians tested per ray, off | on | long rays |
+|---|---|---|---|---|---|---|---|---|---|---|
+| (a) 64 rays, host call | {a['rays']} | {a['gaussians']} | {ms(a['ray_bundle_ms'])} | {ms(a['indexed_ms'])} | {a['off_over_on']} | {a['identical']} | {a['ray_index_stats']['leaves_kept'] / a['rays']:.2f} ({a['ray_index_stats']['leaves']}) | {a['ray_stats']['members_tested'] / a['rays']:.0f} | {a['ray_index_stats']['members_tested'] / a['rays']:.0f} | {a['ray_stats']['long_rays']} |
+{index_row('(b) `-g 64` pinhole 2048^2', bc['one_origin'])}
+{index_row('(c) `-g 64` two eyes', bc['two_eyes'])}
+{index_row('(d) `-g 64` scattered origins', res['def']['scattered'])}
+{index_row('(e) `-g 16` pinhole 2048^2', res['def']['g16'])}
+{index_row('(f) teapot pinhole 256^2', res['def']['teapot'])}
+
+Indexed (b) over the camera path: {bc['indexed_over_frame']}.
 """
+
+
+def ms(t):
+    return f"{t['median']} ({t['min']} .. {t['max']})"
+
+
+def index_row(label, r):
+    pi = r["per_ray_index"]
+    return (f"| {label} | {r['rays']} | {r['gaussians']} | {ms(r['off_ms'])} | {ms(r['on_ms'])} | {r['off_over_on']} | {r['identical']} | "
+            f"{pi['leaves_kept']} ({pi['leaves']}) | {r['per_ray_off']['members_tested']} | {pi['members_tested']} | {r['ray_stats_on']['long_rays']} |")
 
 
 def main():
@@ -202,7 +287,7 @@ def main():
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
     res = {"what": "ray bundles against the full sum and against the camera path; see tools/ray_bundles.py",
-           "a": part_a(g), "bc": parts_bc(g, a.width, 16, a.calls, a.repeats)}
+           "a": part_a(g), "bc": parts_bc(g, a.width, 16, a.calls, a.repeats), "def": parts_def(g, a.calls, a.repeats)}
     line = json.dumps(res)
     print(line)
     os.makedirs(a.out_dir, exist_ok=True)
@@ -211,6 +296,8 @@ def main():
     with open(os.path.join(a.out_dir, "ray_bundles.md"), "w") as f:
         f.write(markdown(res))
     assert res["a"]["speedup"] >= 100.0, "the ray bundle call has to be at least 100 times faster than the full sum on the same rays"
+    b = res["bc"]["one_origin"]
+    assert b["on_ms"]["median"] < b["off_ms"]["median"], "the indexed call of the -g 64 pinhole bundle has to be faster than the unindexed call"
 
 
 if __name__ == "__main__":
