@@ -936,8 +936,10 @@ def test_table_mode_stays_inside_the_tolerance(pkg, oracle, renderer, name, step
         _, rad3 = renderer.render(origin)
         st3 = renderer.stats()
         assert st3["table_blocks"] == st["table_empty"] and st3["table_declined"] == st0["dense_blocks"] - st["table_empty"]
-        # (the fallback is the exact kernel's arithmetic over the table kernel's 8 waves per block; the exact launch sums a ray's partial
-        # radiances over 16: VRT_HIP_DENSE_WAVES=8 makes the two bit-equal)
+        # (the fallback is the exact kernel's body over the table kernel's waves per block -- 16 for a frame of this size, 8 from 2^22
+        # rays or with VRT_HIP_TABLE_WAVES=8 -- and the exact launch runs VRT_HIP_DENSE_WAVES = 16 by default: with the same number of
+        # waves on both sides the two are bit-equal, which tests/test_gpu_dense.py asserts for 16 and for 8; with different numbers
+        # a ray's partial radiances are summed in another order)
         assert np.abs(rad3 - exact).max() <= 1e-6
     finally:
         renderer.enable_stats(False)
