@@ -1,12 +1,6 @@
-// vrt_hip_api.cpp -- the C ABI of libvrt_hip.so (see include/vrt_hip.h): context, device-resident
-// scene / tile / ray state, launches.  Compiled with hipcc for gfx950; links only libamdhip64.
-// There is no CPU fallback anywhere in this file: without a GPU vrt_hip_create() fails.
-//
-// Frame pipeline (all on the caller's stream for the *_device entry points):
-//   prep_frame_kernel        only when the origin or the scene changed: oc = mu - origin, |oc|^2
-//   build_tile_lists_kernel  only when tiles / rays / origin / options changed: the reference's tile sets
-//                            (rt.cpp:29-69, or the caller's lists) intersected with a tile-level cull
-//   render_kernel            one wavefront per 8x8 pixel block
+// vrt_hip_api.cpp -- the C ABI of libvrt_hip.so (see include/vrt_hip.h): context, setters, device-resident scene / tile / ray
+// state, shard map and static tables.  The frame pipeline over them is vrt_hip_frame.cpp.  Compiled with hipcc for gfx950;
+// links only libamdhip64.  There is no CPU fallback anywhere in this file: without a GPU vrt_hip_create() fails.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -18,9 +12,7 @@
 
 using namespace vrtk;
 
-namespace {
-std::string g_create_error;
-} // namespace
+static std::string g_create_error;
 
 int fail(vrt_hip_ctx *c, int code, const std::string &msg)
 {
@@ -49,8 +41,6 @@ int quiesce(vrt_hip_ctx *c)
     return VRT_HIP_OK;
 }
 
-namespace {
-
 float exp_floor_x(int exp_kind)
 {
     // Exp(-x) is exactly 0 past this point for the chosen Exp, so such Gaussians contribute nothing:
@@ -70,8 +60,6 @@ bool table_on(const vrt_hip_ctx *c)
     return c->table_hx > 0.f && (c->erf_kind == VRT_ERF_AS || c->erf_kind == VRT_ERF_LIBM) &&
            (c->exp_kind == VRT_EXP_VCL || c->exp_kind == VRT_EXP_LIBM);
 }
-
-} // namespace
 
 int rebuild_tables(vrt_hip_ctx *c)
 {
@@ -131,53 +119,6 @@ int check_ready(vrt_hip_ctx *c)
     return VRT_HIP_OK;
 }
 
-namespace {
-
-int prep_frame(vrt_hip_ctx *c, const float origin[3], hipStream_t st)
-{
-    int rc = rebuild_tables(c);
-    if (rc) return rc;
-    if (c->gA_valid && !memcmp(c->gA_origin, origin, 3 * sizeof(float))) return VRT_HIP_OK;
-    if (c->defer) { // a frame of a batch: one prep launch for all frames (launch_frame_setup_batch)
-        c->defer->do_prep = 1; c->defer->prep_gA = c->gA.p;
-        memcpy(c->defer->prep_origin, origin, 3 * sizeof(float));
-    } else {
-        c->prep_pending = true; // the list kernel of this frame writes the table (BinArgs::prep_gA); flush_prep() launches it if none does
-    }
-    memcpy(c->gA_origin, origin, 3 * sizeof(float));
-    c->cam_seq = c->frame_seq; // the camera moved
-    c->gA_valid = true;
-    c->lists_dirty = true; // the tile-level cull depends on the origin
-    return VRT_HIP_OK;
-}
-
-int flush_prep(vrt_hip_ctx *c, hipStream_t st)
-{
-    if (!c->prep_pending) return VRT_HIP_OK;
-    launch_prep_frame(tables(c), c->gA.p, c->gA_origin, st);
-    HIPCHK(c, hipGetLastError());
-    c->prep_pending = false;
-    return VRT_HIP_OK;
-}
-
-RayGen ray_gen(const vrt_hip_ctx *c, const float origin[3])
-{
-    RayGen r;
-    r.xs = c->plane_mode ? c->xs.p : nullptr; r.ys = c->plane_mode ? c->ys.p : nullptr;
-    r.zs = c->plane_mode ? c->zs.p : nullptr;
-    for (int i = 0; i < 3; ++i) {
-        r.origin[i] = origin[i]; r.pos[i] = c->cam_pos[i]; r.right[i] = c->cam_right[i]; r.up[i] = c->cam_up[i];
-        r.front[i] = c->cam_front[i];
-    }
-    r.focal = c->focal;
-    r.inv_half_w = 1.f / (c->w / 2.f); r.inv_half_h = 1.f / (c->h / 2.f);
-    r.width = c->w; r.height = c->h;
-    r.view_mode = (c->view_mode && !c->plane_mode) ? 1 : 0;
-    for (int i = 0; i < 3; ++i) { r.m0[i] = c->inv_view[i]; r.m1[i] = c->inv_view[4 + i]; r.m3[i] = c->inv_view[12 + i]; }
-    r.half_w = c->w / 2.f; r.half_h = c->h / 2.f;
-    return r;
-}
-
 // (Re)builds the tile-centre arrays when the tile grid changes (the reference's float loops, rt.cpp:47-49).
 int prepare_tile_grid(vrt_hip_ctx *c, float tw, float th)
 {
@@ -212,17 +153,6 @@ int prepare_tile_grid(vrt_hip_ctx *c, float tw, float th)
     return VRT_HIP_OK;
 }
 
-BinArgs bin_args(const vrt_hip_ctx *c)
-{
-    BinArgs a{};
-    a.mu_sig = c->mu_sig.p; a.gA = c->gA.p; a.gB = c->gB.p; a.n = c->n;
-    // the chunk test costs a round trip of its own (the rows can only be asked for after it): worth it where the per-Gaussian pass is long
-    a.chunks = (c->tune.use_chunks == 2 || (c->tune.use_chunks == 1 && c->n > 8192u)) ? c->gChunk.p : nullptr;
-    for (int i = 0; i < 16; ++i) a.V.m[i] = c->view[i];
-    a.xc = c->xc.p; a.yc = c->yc.p; a.tw = c->tw; a.th = c->th; a.tiles_w = c->tiles_w;
-    return a;
-}
-
 // The single-tile "everything" list of the untiled overloads (rt.h:227-228, 315-316).
 int ensure_none_ref_lists(vrt_hip_ctx *c)
 {
@@ -234,6 +164,8 @@ int ensure_none_ref_lists(vrt_hip_ctx *c)
     c->ref_valid = true;
     return VRT_HIP_OK;
 }
+
+namespace {
 
 // Reference-semantics lists of the device binning (what tiles_t would hold), on the context's stream: built by
 // vrt_hip_tile_gaussians, or on demand for queries (get_tile_counts / get_tile_indices).
@@ -261,197 +193,6 @@ int sync_ref_lists(vrt_hip_ctx *c)
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return VRT_HIP_OK;
-}
-
-TileLists work_lists(const vrt_hip_ctx *c);
-
-// Queue counters come in two sets used by alternate list generations: a fused list kernel ADDS to its set
-// (cleared one generation earlier by its predecessor) and clears the other set for its successor -- no memset
-// node on the per-frame path.
-CellGrid cell_grid(const vrt_hip_ctx *c)
-{
-    CellGrid g{};
-    uint32_t *cnt = c->c_counters.p + 8 * (c->list_gen & 1);
-    g.cells_x = c->cells_x; g.cells_y = c->cells_y; g.cstride = c->cstride;
-    g.count = c->c_count.p; g.indices = c->c_indices.p; g.active = c->c_active.p; g.n_cells = c->n_cells;
-    g.dense = c->c_dense.p; g.dense_sorted = c->c_dense_sorted.p; g.scratch = c->c_scratch.p; g.slot = c->c_slot.p;
-    g.n_active = cnt; g.n_dense = cnt + 2;
-    g.n_light = cnt + 1; g.light_threshold = c->lists_light; // as the lists in the buffers were built
-    g.dense_next = cnt + 3;
-    g.overflow = c->c_overflow.p; g.n_overflow = cnt + 4;
-    g.table_hx = table_on(c) ? c->table_hx : 0.f; g.table_budget = c->table_budget; g.table_adapt = c->tune.table_adapt; g.table_room = c->tune.table_room;
-    g.claim_early = c->tune.claim_early;
-    // prune_list sums sigma*mag*exp(-x) in units of the TILE level's eps (cull_x = ln(sigma*mag / eps_eff), rebuild_tables)
-    g.prune_budget = (c->cull_eps > 0.f) ? c->cull_prune * (c->tune.cull_ref_n > 0.f ? c->tune.cull_ref_n : 4096.f / 3.f) * std::max(1.f, (float)c->n / 4096.f) / c->albedo_scale : 0.f;
-    g.dense_threshold = 96; // longer cell lists go straight to the 16-waves-per-block kernel (must be <= PCAP)
-    g.feedback = c->d_fb;
-    g.dense_is_sorted = 1;
-    return g;
-}
-
-// `target`: where this frame is rendered to; when the fused list kernel runs it clears the cells nothing can reach.
-int build_work_lists(vrt_hip_ctx *c, const float origin[3], hipStream_t st, bool use_shard, RenderTarget *target)
-{
-    if (!c->lists_dirty && c->lists_for_shard == (int)use_shard) return VRT_HIP_OK;
-    int rc = ensure_none_ref_lists(c);
-    if (rc) return rc;
-    const TileLists geo = tile_geometry(c);
-    const size_t nt = (size_t)geo.tiles_w * geo.tiles_h;
-    // the tile cone is built from corner rays: needs pinhole rays (always true for in-kernel ray generation)
-    // ... and tiles that are rectangles of the image: with the reference's truncated tile size the row stride
-    // tile_w*tiles_w can differ from the width (rt.h:364-365), a tile's rows then drift sideways and wrap around the
-    // image edge, and its rays are no cone around its corner rays (found by tests/fuzz_parity.py: 33x100, 5 tiles)
-    const bool refine = (!c->plane_mode || c->plane_affine) && geo.stride == c->w;
-
-    // geometry of the second level and its buffers
-    uint32_t n_local = (uint32_t)nt;
-    const uint32_t *tile_map = nullptr;
-    if (use_shard) {
-        if ((rc = rebuild_shard(c))) return rc;
-        n_local = c->n_local; tile_map = c->tile_map.p;
-    }
-    c->cells_x = (geo.tile_w + CELL - 1) / CELL; c->cells_y = (geo.tile_h + CELL - 1) / CELL;
-    c->n_cells = n_local * c->cells_x * c->cells_y;
-    if (c->n_cells > ACTIVE_CELL_MASK) return fail(c, VRT_HIP_ERR_INVALID, "tile grid: more than 2^24 cells of 32 x 32 pixels on one device");
-    c->cstride = std::max(1u, std::min(c->n, 4096u));
-    HIPCHK(c, c->c_count.reserve(c->n_cells)); HIPCHK(c, c->c_active.reserve(c->n_cells));
-    HIPCHK(c, c->c_dense.reserve(c->n_cells));
-    HIPCHK(c, c->c_dense_sorted.reserve(c->n_cells));
-    HIPCHK(c, c->c_slot.reserve(c->n_cells));
-    HIPCHK(c, c->c_scratch.reserve((size_t)c->num_cus * 4 * c->cstride)); // one slot per dense workgroup (<= 4 per CU)
-    HIPCHK(c, c->c_overflow.reserve((size_t)c->n_cells * 16));
-    HIPCHK(c, c->c_indices.reserve((size_t)c->n_cells * c->cstride));
-    if (!c->c_counters.p) {
-        HIPCHK(c, c->c_counters.reserve(16));
-        HIPCHK(c, hipMemsetAsync(c->c_counters.p, 0, 16 * sizeof(uint32_t), st));
-    }
-    ++c->list_gen; // this build fills counter set (list_gen & 1)
-    if (c->tile_mode == TILES_DEVICE && c->grid_n != c->n) { // the scene was replaced after tile_gaussians()
-        HIPCHK(c, hipStreamSynchronize(st));
-        if ((rc = prepare_tile_grid(c, c->tw, c->th))) return rc;
-        c->last_stream = st;
-    }
-
-    BinArgs a = bin_args(c);
-    a.refine = refine ? 1 : 0;
-    a.cull_ref_n = c->tune.cull_ref_n; a.floor_x = exp_floor_x(c->exp_kind);
-    a.R = ray_gen(c, origin);
-    a.tile_w = geo.tile_w; a.tile_h = geo.tile_h; a.stride = geo.stride;
-    c->work_is_ref = false;
-    if (refine) {
-        std::string key((const char *)&a.R, sizeof a.R);
-        const uint32_t geo_key[6] = { geo.tile_w, geo.tile_h, geo.stride, geo.tiles_w, geo.tiles_h, c->plane_gen };
-        key.append((const char *)geo_key, sizeof geo_key);
-        a.tiles_w = geo.tiles_w;
-        // with the cells' cones when the tile's cells are filtered by the same workgroup (the fused list kernel)
-        const uint32_t cpt = c->cells_x * c->cells_y;
-        const uint32_t cones_cells = cpt <= (uint32_t)MAX_FUSED_CELLS ? cpt : 0u;
-        const size_t rows = nt * (1 + cones_cells);
-        // The table fills itself: a row is valid if it carries the tag of this camera (cone_gen); the list kernel's workgroups build the cones
-        // they do not find and file them (round 3: the table's own launch cost a frame whose camera moved 5 us).  Frames of a batch get
-        // theirs from one launch for the whole batch, as before.
-        bool known = true;
-        if (c->tile_cones.cap < 2 * rows) {
-            HIPCHK(c, c->tile_cones.reserve(2 * rows));
-            HIPCHK(c, hipMemsetAsync(c->tile_cones.p, 0, c->tile_cones.cap * sizeof(float4), st)); // tag 0: no camera's
-            c->cone_key.clear();
-        }
-        if (key != c->cone_key) {
-            if (++c->cone_gen == 0u) c->cone_gen = 1u;
-            a.cone_gen = c->cone_gen;
-            known = false;
-            if (c->defer) { // a frame of a batch: one cone launch for all frames (its BinArgs are the frame's bin row)
-                c->defer->do_cones = 1; c->defer->cones_tiles = a.tiles_w * geo.tiles_h;
-                c->defer->cones_cx = cones_cells ? c->cells_x : 0u; c->defer->cones_cy = cones_cells ? c->cells_y : 0u;
-                c->defer->cones_out = c->tile_cones.p;
-                known = true;
-            }
-            c->cone_key = key;
-        }
-        a.tile_cones = c->tile_cones.p; a.cones_cells = cones_cells; a.cone_gen = c->cone_gen; a.cones_known = known ? 1 : 0;
-    }
-    const bool device_bin = c->tile_mode == TILES_DEVICE;
-    // one fused kernel when a tile's cells fit one workgroup's waves; otherwise tile kernel + one-wave-per-cell kernel
-    const bool fuse = c->cells_x * c->cells_y <= (uint32_t)MAX_FUSED_CELLS && (device_bin || refine);
-    c->lists_light = (fuse && !(target && target->sparse)) ? c->light_cells : 0u;
-    FuseArgs f{};
-    f.enabled = fuse ? 1 : 0;
-    f.tile_map = fuse ? tile_map : nullptr;
-    f.C = cell_grid(c);
-    if (fuse && target) { f.O = *target; f.do_clear = target->sparse ? 0 : 1; }
-    c->timeline_tiles = 0;
-    if (fuse && c->tune.timeline) {
-        c->timeline_tiles = n_local;
-        HIPCHK(c, c->d_timeline_lists.reserve((size_t)n_local * 8));
-        HIPCHK(c, hipMemsetAsync(c->d_timeline_lists.p, 0, (size_t)n_local * 8 * sizeof(unsigned long long), st));
-        f.timeline = c->d_timeline_lists.p;
-    }
-    uint32_t *other_set = c->c_counters.p + 8 * ((c->list_gen + 1) & 1);
-    a.zero8 = fuse ? nullptr : c->c_counters.p + 8 * (c->list_gen & 1);
-    if (device_bin) {
-        a.out_start = c->w_start.p; a.out_indices = c->w_indices.p; a.out_count = c->w_count.p;
-    } else if (refine) {
-        const size_t total = c->tile_mode == TILES_NONE ? c->n : c->ref_indices.cap;
-        HIPCHK(c, c->w_count.reserve(nt)); HIPCHK(c, c->w_indices.reserve(total));
-        a.in_start = c->ref_start.p; a.in_count = c->ref_count.p;
-        a.in_indices = c->tile_mode == TILES_NONE ? c->iota.p : c->ref_indices.p;
-        a.tiles_w = geo.tiles_w;
-        a.out_start = c->ref_start.p; a.out_indices = c->w_indices.p; a.out_count = c->w_count.p;
-    } else {
-        c->work_is_ref = true;
-    }
-    if (fuse) {
-        a.next_zero8 = other_set; // cleared for the next generation by workgroup 0
-        if (n_local && c->defer) {
-            c->defer->bin = a; c->defer->fuse = f;
-            c->deferred.lists = true; c->deferred.from_list = !device_bin; c->deferred.list_grid = n_local;
-        } else if (n_local) {
-            if (c->prep_pending) { a.prep_gA = c->gA.p; c->prep_pending = false; } // a.R.origin is the origin prep_frame() noted
-            launch_build_tile_lists(a, f, !device_bin, n_local, st);
-        } else {
-            // a rank that owns no tile (more ranks than tiles) launches no list kernel: nobody adds to this generation's
-            // counters and nobody clears the next one's -- do both here, or the next render would add to stale counts
-            // (found by tests/fuzz_parity.py: 4 tiles on 5 and 8 ranks)
-            HIPCHK(c, hipMemsetAsync(c->c_counters.p, 0, 16 * sizeof(uint32_t), st));
-        }
-        if (target) target->cleared = 1;
-    } else {
-        if (c->defer) return fail(c, VRT_HIP_ERR_INVALID, "frame batch: tiles of more than 64 cells (or rays that are no pinhole bundle) "
-                                                          "need the two-kernel list path, which is not batched");
-        if (!c->work_is_ref) {
-            if (c->prep_pending) { a.prep_gA = c->gA.p; c->prep_pending = false; }
-            launch_build_tile_lists(a, f, !device_bin, (uint32_t)nt, st);
-        }
-        else HIPCHK(c, hipMemsetAsync(c->c_counters.p + 8 * (c->list_gen & 1), 0, 8 * sizeof(uint32_t), st));
-        HIPCHK(c, hipGetLastError());
-        if ((rc = flush_prep(c, st))) return rc; // the cell kernel reads the per-origin table: if no tile kernel wrote it, now
-        launch_build_cell_lists(tables(c), work_lists(c), cell_grid(c), a.R, tile_map, c->n_cells, refine ? 1 : 0,
-                                (target && target->sparse) ? target->keys : nullptr, st);
-        if (target && target->sparse) target->cleared = 1; // a sparse shard stores no empty cells: nothing to clear
-        // the set the NEXT generation will add to (if it is a fused one) must be clear
-        HIPCHK(c, hipMemsetAsync(other_set, 0, 8 * sizeof(uint32_t), st));
-    }
-    HIPCHK(c, hipGetLastError());
-    c->lists_dirty = false;
-    c->lists_fresh = true;
-    c->lists_for_shard = (int)use_shard;
-    return VRT_HIP_OK;
-}
-
-TileLists work_lists(const vrt_hip_ctx *c)
-{
-    TileLists t = tile_geometry(c);
-    t.cull_ref_n = c->tune.cull_ref_n;
-    t.floor_x = exp_floor_x(c->exp_kind);
-    if (c->tile_mode == TILES_DEVICE) {
-        t.start = c->w_start.p; t.count = c->w_count.p; t.indices = c->w_indices.p;
-    } else if (c->work_is_ref) {
-        t.start = c->ref_start.p; t.count = c->ref_count.p;
-        t.indices = c->tile_mode == TILES_NONE ? c->iota.p : c->ref_indices.p;
-    } else {
-        t.start = c->ref_start.p; t.count = c->w_count.p; t.indices = c->w_indices.p;
-    }
-    return t;
 }
 
 // Owner of tile t = (tx, ty): the ranks form an a x b brick (a * b = world, a >= b as square as the divisors allow) that
@@ -506,182 +247,6 @@ uint32_t sparse_capacity(vrt_hip_ctx *c)
 
 namespace {
 
-enum OutMode { OUT_RASTER = 0, OUT_COMPACT = 1, OUT_SPARSE = 2 };
-
-// CellGrid::claim_early for a block-kernel launch of `grid` waves per frame: the variant that claims its next queue entry early, for
-// frames with (by an earlier frame's report, however old: speed only) at least grid / claim_early more blocks than the grid has waves
-int claim_early_for(const vrt_hip_ctx *c, uint32_t grid)
-{
-    const uint32_t seen_blocks = (c->h_fb.p && !c->stats_on) ? c->h_fb.p[1] : 0u;
-    const bool many = c->tune.claim_early > 0 && seen_blocks > grid && (uint64_t)(seen_blocks - grid) * (uint32_t)c->tune.claim_early >= grid;
-    return many ? c->tune.claim_early : 0;
-}
-
-int render_common(vrt_hip_ctx *c, const float origin[3], int pack_flags, uint32_t *d_image, float4 *d_rad,
-                  hipStream_t st, int out_mode)
-{
-    const bool shard_compact = out_mode != OUT_RASTER; // compact and sparse targets hold this rank's tiles only
-    int rc = check_ready(c);
-    if (rc) return rc;
-    const TileLists geo = tile_geometry(c);
-    if (geo.tile_w == 0 || geo.tile_h == 0) return fail(c, VRT_HIP_ERR_INVALID, "render: tile size is 0 pixels");
-    const bool use_shard = c->world > 1 || shard_compact;
-    wait_for_last_stream(c, st);
-    c->last_stream = st;
-    hipEvent_t *tev = nullptr;
-    const bool timed_frame = !c->defer && c->timing_on && (c->timing_frame++ % c->timing_period) == 0;
-    if (timed_frame) {
-        if ((rc = ensure_timing_ring(c))) return rc;
-        tev = &c->tev[4 * (c->timing_count % vrt_hip_ctx::TIMING_RING)];
-        if (c->timing_full) HIPCHK(c, hipEventRecord(tev[0], st));
-    }
-    if ((rc = prep_frame(c, origin, st))) return rc;
-    RenderTarget o{};
-    o.image = d_image; o.radiance = d_rad; o.pack_flags = pack_flags;
-    o.stats = c->stats_on ? c->d_stats.p : nullptr;
-    o.compact = out_mode == OUT_COMPACT ? 1 : 0;
-    if (use_shard) {
-        if ((rc = rebuild_shard(c))) return rc;
-        o.tile_map = c->tile_map.p; o.n_local_tiles = c->n_local;
-    } else {
-        o.tile_map = nullptr; o.n_local_tiles = geo.tiles_w * geo.tiles_h;
-    }
-    uint32_t sparse_cap = 0;
-    if (out_mode == OUT_SPARSE) {
-        // d_image is a sparse shard buffer: header | keys | pixels of the stored cells (vrt_kernels.h, RenderTarget)
-        sparse_cap = sparse_capacity(c);
-        o.sparse = 1; o.sparse_hdr = d_image; o.keys = d_image + SPARSE_HDR_WORDS;
-        o.image = d_image + sparse_pixel_offset(sparse_cap);
-        o.cleared = 1;
-        c->lists_dirty = true; // the list kernel files the cell keys into THIS buffer
-        o.sparse_cap = sparse_cap;
-    }
-    if (c->retain_next && out_mode == OUT_RASTER && !use_shard && !c->defer) { o.stamp = c->own_stamp.p; o.stamp_seq = c->own_seq; }
-    if ((rc = build_work_lists(c, origin, st, use_shard, &o))) return rc;
-    if ((rc = flush_prep(c, st))) return rc; // no list kernel took the per-origin table along (lists unchanged, caller-made lists used as they are, a batch)
-    if (o.stamp && !o.cleared) c->own_seq = 0; // the list kernel of this frame was not the fused one: nobody kept the stamps
-    const TileLists t = work_lists(c);
-    if (o.stats) {
-        HIPCHK(c, hipMemsetAsync(c->d_stats.p, 0, 32 * sizeof(unsigned long long), st));
-        HIPCHK(c, hipMemsetAsync(c->d_stats.p + 8, 0xFF, sizeof(unsigned long long), st)); // running minimum
-    }
-    c->timeline_items = 0;
-    if (c->tune.timeline) {
-        c->timeline_items = (size_t)c->n_cells * 16;
-        HIPCHK(c, c->d_timeline.reserve(c->timeline_items * 5));
-        HIPCHK(c, hipMemsetAsync(c->d_timeline.p, 0, c->timeline_items * 5 * sizeof(unsigned long long), st));
-        o.timeline = c->d_timeline.p;
-    }
-    const uint32_t bx = (t.tile_w + BLOCK_W - 1) / BLOCK_W, by = (t.tile_h + BLOCK_H - 1) / BLOCK_H;
-    c->last.blocks = (uint64_t)o.n_local_tiles * bx * by;
-    c->last.rays = (uint64_t)o.n_local_tiles * t.tile_w * t.tile_h;
-    // persistent grid: 12 one-wave workgroups per CU (three per SIMD at 145 VGPRs), never more than there are blocks
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)c->n_cells * 16u,
-                                                       c->tune.render_grid_override ? (uint64_t)c->tune.render_grid_override
-                                                                               : (uint64_t)c->num_cus * std::max(1, c->tune.render_waves_per_cu));
-    if (out_mode == OUT_SPARSE && grid == 0) // a rank without cells launches no render kernel: nobody writes the header
-        HIPCHK(c, hipMemsetAsync(d_image, 0, SPARSE_HDR_WORDS * sizeof(uint32_t), st));
-    if (!c->lists_fresh) // a re-render from unchanged lists: only the dense kernel's work counters need a reset
-        HIPCHK(c, hipMemsetAsync(c->c_counters.p + 8 * (c->list_gen & 1) + 3, 0, 4 * sizeof(uint32_t), st));
-    c->lists_fresh = false;
-    // How large a dense launch?  The 16-waves-per-block kernel always runs behind the one-wave kernel (which kernel
-    // shades a block depends on the block alone, so the image never depends on this heuristic); but a full launch --
-    // queue sort + one 1024-thread workgroup per CU -- costs ~12 us even with empty queues.  Frames report
-    // (asynchronously, CellGrid::feedback) what their dense kernel found; once a report has arrived from a frame
-    // launched at least two frames after the last change of scene, rays, camera or options, and it says "nothing",
-    // the launch shrinks to one workgroup and skips the sort.  A wrong guess costs speed only.
-    bool expect_dense = true;
-    bool camera_moved = false;
-    if (c->h_fb.p && !c->stats_on && (int32_t)(c->h_fb.p[3] - c->reset_seq) >= 2) {
-        expect_dense = c->h_fb.p[0] > 0 || c->h_fb.p[2] > 0;
-        camera_moved = (int32_t)(c->h_fb.p[3] - c->cam_seq) < 2;
-    }
-    // Not a guess: which blocks are dense is a function of scene, options, rays, camera, tile grid and shard.  A report
-    // from a frame that was launched AFTER the last change of any of them (sequence number above reset_seq and cam_seq)
-    // and that found no dense cell and no handed-over block says the same of this frame: the dense launch -- 4.7 us of a
-    // 47-us serial frame even for one idle workgroup, which also waits for 61 KB of LDS while other frames' block kernels
-    // fill the CUs -- is left out.  Any change brings it back until a frame of the new state has reported.
-    bool no_dense_work = false;
-    if (c->tune.skip_idle_dense && c->h_fb.p && !c->stats_on) {
-        const uint32_t seen = c->h_fb.p[3]; // read first: what is read after it is at least as new
-        no_dense_work = (int32_t)(seen - c->reset_seq) >= 1 && (int32_t)(seen - c->cam_seq) >= 1 && c->h_fb.p[0] == 0 && c->h_fb.p[2] == 0;
-    }
-    if (no_dense_work) ++c->last.dense_launch_skips;
-    uint32_t dense_grid = no_dense_work ? 0u : (uint32_t)std::min<uint64_t>((uint64_t)c->n_cells * 16u, (uint64_t)c->num_cus * (16 / std::min(c->tune.dense_waves, 16)));
-    if (!expect_dense) dense_grid = std::min(dense_grid, (uint32_t)(camera_moved ? std::max(c->dense_idle_grid, c->num_cus / 4) : c->dense_idle_grid));
-    CellGrid cg = cell_grid(c);
-    cg.claim_early = claim_early_for(c, grid);
-    cg.dense_is_sorted = expect_dense ? 1 : 0;
-    cg.frame_seq = ++c->frame_seq;
-    if (!c->c_rq.p) {
-        HIPCHK(c, c->c_rq.reserve(2 * RQ_N * RQ_STRIDE));
-        HIPCHK(c, hipMemsetAsync(c->c_rq.p, 0, 2 * RQ_N * RQ_STRIDE * sizeof(uint32_t), st));
-    }
-    if (grid) ++c->rq_gen; // a skipped launch clears nothing: the sets must not swap
-    cg.rq = c->c_rq.p + (c->rq_gen & 1) * RQ_N * RQ_STRIDE;
-    cg.rq_next = c->c_rq.p + ((c->rq_gen + 1) & 1) * RQ_N * RQ_STRIDE;
-    if (c->defer) {
-        // a frame of a batch: the launches are made once for all frames by vrt_hip_frame_batch_device
-        FrameArgs &fa = *c->defer;
-        fa.S = tables(c); fa.T = t; fa.C = cg; fa.R = ray_gen(c, origin); fa.O = o;
-        c->deferred.render = true; c->deferred.render_grid = grid; c->deferred.order = expect_dense && !no_dense_work; c->deferred.dense_grid = dense_grid;
-        return VRT_HIP_OK;
-    }
-    if (tev) HIPCHK(c, hipEventRecord(tev[1], st));
-    launch_render(tables(c), t, cg, ray_gen(c, origin), o, grid, c->exp_kind, c->erf_kind, st);
-    if (tev) HIPCHK(c, hipEventRecord(tev[2], st));
-    // dense queue: 16-wave workgroups pull blocks until the queue is empty (they exit at once if it is)
-    if (expect_dense && !no_dense_work) launch_order_dense(cg, st);
-    if (!no_dense_work) {
-        if (table_on(c)) {
-            // table mode (the default): the table kernel takes the whole dense queue; a block it declines it shades exactly itself
-            // (dense_shade_block in its own LDS): ONE dense-path launch per frame (rounds 1-3: an exact launch behind it, idle in
-            // every frame of a moving camera)
-            launch_render_table(tables(c), t, cg, ray_gen(c, origin), o, std::min<uint32_t>(dense_grid, (uint32_t)c->num_cus), c->exp_kind, c->erf_kind, st);
-        } else {
-            launch_render_dense(tables(c), t, cg, ray_gen(c, origin), o, dense_grid, c->tune.dense_waves, c->exp_kind, c->erf_kind, st);
-        }
-    }
-    if (tev) {
-        if (c->timing_full) HIPCHK(c, hipEventRecord(tev[3], st));
-        ++c->timing_count;
-    }
-    HIPCHK(c, hipGetLastError());
-    return VRT_HIP_OK;
-}
-
-// Retained frame buffer (vrt_hip_frame's own buffer; vrt_hip_frame_retained_device for a caller's): `image` still holds this
-// context's previous frame at this geometry, so the list kernel clears only the cells that went dark (RenderTarget::stamp).
-// One history per context, for ONE buffer: another buffer, image size, tile grid or background starts a new one with a
-// full clear.  Sets retain_next for the render_common call that follows.
-int retained_begin(vrt_hip_ctx *c, uint32_t *image, float tw, float th, int pack_flags, hipStream_t st)
-{
-    const size_t npix = (size_t)c->w * c->h;
-    const uint32_t tiles_w = (uint32_t)std::ceil(2.f / tw), tiles_h = (uint32_t)std::ceil(2.f / th);
-    const uint32_t tile_w = (uint32_t)(uint64_t)(c->w * tw / 2.f), tile_h = (uint32_t)(uint64_t)(c->h * th / 2.f);
-    const uint32_t cx = (tile_w + CELL - 1) / CELL, cy = (tile_h + CELL - 1) / CELL;
-    const size_t cells = (size_t)tiles_w * tiles_h * cx * cy;
-    vrt_hip_ctx::OwnGeometry sig;
-    sig.w = c->w; sig.h = c->h; sig.tiles_w = tiles_w; sig.tiles_h = tiles_h; sig.tile_w = tile_w; sig.tile_h = tile_h;
-    sig.background = (pack_flags & VRT_ALPHA_COMPUTED) ? 0u : 0xFF000000u; sig.image = image;
-    c->retain_next = c->tune.retain_frame && cells > 0 && cells < (1u << 28) && tiles_w <= 4096 && tiles_h <= 4096 && c->world == 1;
-    if (!c->retain_next) { c->own_seq = 0; return VRT_HIP_OK; }
-    // the previous frame's list and block kernels may still be writing the stamps and the image that the memsets below reset on
-    // THIS stream (render_common's own hand-over comes after this function)
-    wait_for_last_stream(c, st);
-    if (!(sig == c->own_sig) || c->own_seq == 0 || c->own_seq >= 0xFFFFFFF0u || c->own_stamp.cap < cells) {
-        if (c->own_stamp.cap < cells) { int rc = quiesce(c); if (rc) return rc; } // frames in flight write the old stamp buffer
-        HIPCHK(c, c->own_stamp.reserve(cells));
-        HIPCHK(c, hipMemsetAsync(c->own_stamp.p, 0, cells * sizeof(uint32_t), st));
-        if (!(sig == c->own_sig)) HIPCHK(c, hipMemsetAsync(image, 0, npix * 4, st)); // pixels no tile of the NEW grid covers read 0
-        c->own_sig = sig;
-        c->own_seq = 1; // stamps of 0 = "never lit": with seq 1 every empty cell compares against 0 = seq - 1 and is cleared
-    } else {
-        ++c->own_seq;
-    }
-    return VRT_HIP_OK;
-}
-
 // Are the plane arrays an affine function of (row, column)?  Then rays are a pinhole bundle and the
 // corner rays of a tile bound its cone.  Anything else disables the tile-level cull (the per-block cull
 // works from the actual lane rays and stays exact for arbitrary arrays).
@@ -702,6 +267,10 @@ bool plane_is_affine(uint32_t w, uint32_t h, const float *xs, const float *ys, c
     }
     return true;
 }
+
+// Caller-made lists index the scene they were validated against (set_tiles checks every index < n): they do not survive another
+// scene -- back to untiled until set_tiles / tile_gaussians is called again
+void untile(vrt_hip_ctx *c) { c->tile_mode = TILES_NONE; c->tw = c->th = 2.f; c->tiles_w = c->tiles_h = 1; }
 
 // The one place the host runtime reads the environment: every VRT_HIP_* setting (Tuning), at vrt_hip_create.  Values out
 // of range keep the default.
@@ -728,21 +297,6 @@ Tuning read_tuning()
 }
 
 } // namespace
-
-int frame_own_image(vrt_hip_ctx *c, float tw, float th, const float view[16], const float origin[3], int pack_flags)
-{
-    int rc = check_ready(c);
-    if (rc) return rc;
-    const size_t npix = (size_t)c->w * c->h;
-    if (c->d_image.cap < npix) { // first frame at this size: pixels no tile covers read 0
-        HIPCHK(c, c->d_image.reserve(npix));
-        HIPCHK(c, hipMemsetAsync(c->d_image.p, 0, npix * 4, c->stream));
-        c->own_seq = 0;
-    }
-    // Retained frame buffer: d_image is written by nothing but this function and vrt_hip_render (which ends the history), so
-    // an empty cell that was empty in the previous frame already holds the background.
-    return vrt_hip_frame_retained_device(c, tw, th, view, origin, pack_flags, c->d_image.p, c->stream);
-}
 
 extern "C" {
 
@@ -824,12 +378,7 @@ int vrt_hip_set_gaussians(vrt_hip_ctx *c, size_t n, const float *mu_x, const flo
     c->reset_seq = c->frame_seq;
     c->tables_dirty = true;
     c->lists_dirty = true;
-    if (c->tile_mode == TILES_HOST) {
-        // caller-made lists index the scene they were validated against (set_tiles checks every index < n): they do
-        // not carry over to another scene -- back to untiled until set_tiles / tile_gaussians is called again
-        c->tile_mode = TILES_NONE; c->tw = c->th = 2.f; c->tiles_w = c->tiles_h = 1;
-        c->shard_dirty = true;
-    }
+    if (c->tile_mode == TILES_HOST) { untile(c); c->shard_dirty = true; }
     c->ref_valid = false;
     return VRT_HIP_OK;
 }
@@ -880,7 +429,7 @@ int vrt_hip_copy_state(vrt_hip_ctx *dst, const vrt_hip_ctx *src)
     dst->ray_index = src->ray_index; // the mirror builds the same index with its tables: the order is a function of the scene alone
     dst->tables_dirty = true; dst->lists_dirty = true; dst->shard_dirty = true; dst->ref_valid = false;
     dst->reset_seq = dst->frame_seq;
-    if (dst->tile_mode == TILES_HOST) { dst->tile_mode = TILES_NONE; dst->tw = dst->th = 2.f; dst->tiles_w = dst->tiles_h = 1; }
+    if (dst->tile_mode == TILES_HOST) untile(dst);
     ++dst->state_gen;
     return VRT_HIP_OK;
 }
@@ -944,7 +493,7 @@ int vrt_hip_clear_tiles(vrt_hip_ctx *c)
 {
     if (!c) return VRT_HIP_ERR_INVALID;
     if (c->tile_mode != TILES_NONE) c->reset_seq = c->frame_seq;
-    c->tile_mode = TILES_NONE; c->tw = c->th = 2.f; c->tiles_w = c->tiles_h = 1;
+    untile(c);
     c->shard_dirty = true; c->lists_dirty = true; c->ref_valid = false;
     return VRT_HIP_OK;
 }
@@ -967,7 +516,7 @@ int vrt_hip_set_tiles(vrt_hip_ctx *c, float tw, float th, uint64_t tiles_w, uint
         if (indices[k] >= c->n) return fail(c, VRT_HIP_ERR_INVALID, "set_tiles: index out of range (upload the scene first)");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = quiesce(c); if (rc) return rc; }
-    c->ref_indices = {}; // exact-size index buffer: build_work_lists sizes its output from ref_indices.cap
+    c->ref_indices = {}; // exact-size index buffer: plan_lists (vrt_hip_frame.cpp) sizes its output from ref_indices.cap
     HIPCHK(c, c->ref_start.reserve(nt)); HIPCHK(c, c->ref_count.reserve(nt)); HIPCHK(c, c->ref_indices.reserve(total));
     HIPCHK(c, hipMemcpy(c->ref_start.p, start.data(), nt * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->ref_count.p, count.data(), nt * 4, hipMemcpyHostToDevice));
@@ -1097,80 +646,11 @@ int vrt_hip_set_camera_view(vrt_hip_ctx *c, uint32_t w, uint32_t h, const float 
 
 size_t vrt_hip_image_pixels(const vrt_hip_ctx *c) { return (c && c->rays_set) ? (size_t)c->w * c->h : 0; }
 
-int vrt_hip_render_device(vrt_hip_ctx *c, const float origin[3], int pack_flags, uint32_t *d_image, float *d_radiance,
-                          void *hip_stream)
-{
-    if (!c || !origin) return VRT_HIP_ERR_INVALID;
-    return render_common(c, origin, pack_flags, d_image, (float4 *)d_radiance, (hipStream_t)hip_stream, OUT_RASTER);
-}
-
-int vrt_hip_frame_device(vrt_hip_ctx *c, float tw, float th, const float view[16], const float origin[3], int pack_flags,
-                         uint32_t *d_out, int shard, void *hip_stream)
-{
-    if (!c || !origin || !d_out) return VRT_HIP_ERR_INVALID;
-    int rc = vrt_hip_tile_gaussians_device(c, tw, th, view, hip_stream);
-    if (rc) return rc;
-    return render_common(c, origin, pack_flags, d_out, nullptr, (hipStream_t)hip_stream, shard ? OUT_COMPACT : OUT_RASTER);
-}
-
-int vrt_hip_frame_retained_device(vrt_hip_ctx *c, float tw, float th, const float view[16], const float origin[3], int pack_flags,
-                                  uint32_t *d_out, void *hip_stream)
-{
-    if (!c || !origin || !d_out) return VRT_HIP_ERR_INVALID;
-    int rc = check_ready(c);
-    if (rc) return rc;
-    if ((rc = retained_begin(c, d_out, tw, th, pack_flags, (hipStream_t)hip_stream))) return rc;
-    rc = vrt_hip_frame_device(c, tw, th, view, origin, pack_flags, d_out, 0, hip_stream);
-    c->retain_next = false;
-    if (rc) c->own_seq = 0;
-    return rc;
-}
-
-int vrt_hip_frame(vrt_hip_ctx *c, float tw, float th, const float view[16], const float origin[3], int pack_flags,
-                  uint32_t *image_out, int wait)
-{
-    if (!c || !origin || !view) return VRT_HIP_ERR_INVALID;
-    int rc = frame_own_image(c, tw, th, view, origin, pack_flags);
-    if (rc) return rc;
-    const size_t npix = (size_t)c->w * c->h;
-    if (image_out) HIPCHK(c, hipMemcpyAsync(image_out, c->d_image.p, npix * 4, hipMemcpyDeviceToHost, c->stream));
-    if (image_out || wait) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VRT_HIP_OK;
-}
-
 int vrt_hip_sync(vrt_hip_ctx *c)
 {
     if (!c) return VRT_HIP_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VRT_HIP_OK;
-}
-
-int vrt_hip_render(vrt_hip_ctx *c, const float origin[3], int pack_flags, uint32_t *image_out, float *radiance_out)
-{
-    if (!c || !origin) return VRT_HIP_ERR_INVALID;
-    int rc = check_ready(c);
-    if (rc) return rc;
-    const size_t npix = (size_t)c->w * c->h;
-    HIPCHK(c, c->d_image.reserve(npix));
-    c->own_seq = 0; // the library's frame buffer gets another image: vrt_hip_frame's retained history of it ends
-    if (radiance_out) HIPCHK(c, c->d_rad.reserve(npix));
-    HIPCHK(c, hipMemsetAsync(c->d_image.p, 0, npix * 4, c->stream));
-    if (radiance_out) HIPCHK(c, hipMemsetAsync(c->d_rad.p, 0, npix * 16, c->stream));
-    // tables / frame prep outside the timed window (list building is part of a frame, like the reference's tiling)
-    if ((rc = prep_frame(c, origin, c->stream))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    rc = render_common(c, origin, pack_flags, c->d_image.p, radiance_out ? c->d_rad.p : nullptr, c->stream, OUT_RASTER);
-    if (rc) return rc;
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->last.kernel_ms = ms;
-    if (c->stats_on && (rc = read_stats(c))) return rc;
-    if (c->timeline_items) print_timeline(c);
-    if (image_out) HIPCHK(c, hipMemcpy(image_out, c->d_image.p, npix * 4, hipMemcpyDeviceToHost));
-    if (radiance_out) HIPCHK(c, hipMemcpy(radiance_out, c->d_rad.p, npix * 16, hipMemcpyDeviceToHost));
     return VRT_HIP_OK;
 }
 
@@ -1192,12 +672,6 @@ size_t vrt_hip_shard_pixels(const vrt_hip_ctx *cc)
     return (size_t)c->n_slots * t.tile_w * t.tile_h;
 }
 
-int vrt_hip_render_shard_device(vrt_hip_ctx *c, const float origin[3], int pack_flags, uint32_t *d_shard, void *hip_stream)
-{
-    if (!c || !origin || !d_shard) return VRT_HIP_ERR_INVALID;
-    return render_common(c, origin, pack_flags, d_shard, nullptr, (hipStream_t)hip_stream, OUT_COMPACT);
-}
-
 // ---- sparse shards: only the cells some Gaussian reaches travel (multi-GPU transport) ------------------------------
 size_t vrt_hip_sparse_shard_words(const vrt_hip_ctx *cc)
 {
@@ -1206,116 +680,5 @@ size_t vrt_hip_sparse_shard_words(const vrt_hip_ctx *cc)
     const uint32_t cap = sparse_capacity(c);
     return sparse_pixel_offset(cap) + (size_t)cap * CELL * CELL;
 }
-
-int vrt_hip_frame_sparse_device(vrt_hip_ctx *c, float tw, float th, const float view[16], const float origin[3], int pack_flags,
-                                uint32_t *d_sparse, void *hip_stream)
-{
-    if (!c || !origin || !d_sparse) return VRT_HIP_ERR_INVALID;
-    if ((uintptr_t)d_sparse % 16) return fail(c, VRT_HIP_ERR_INVALID, "frame_sparse: the shard buffer must be 16-byte aligned");
-    int rc = vrt_hip_tile_gaussians_device(c, tw, th, view, hip_stream);
-    if (rc) return rc;
-    return render_common(c, origin, pack_flags, d_sparse, nullptr, (hipStream_t)hip_stream, OUT_SPARSE);
-}
-
-int vrt_hip_frame_batch_device(vrt_hip_ctx *const *ctxs, int n, float tw, float th, const float *views, const float *origins,
-                               int pack_flags, uint32_t *const *d_out, int out_kind, void *hip_stream)
-{
-    if (!ctxs || n < 1 || !ctxs[0]) return VRT_HIP_ERR_INVALID;
-    vrt_hip_ctx *c0 = ctxs[0];
-    if (!views || !origins || !d_out) return fail(c0, VRT_HIP_ERR_INVALID, "frame_batch: null argument");
-    if (n > 64) return fail(c0, VRT_HIP_ERR_INVALID, "frame_batch: at most 64 frames per batch");
-    if (out_kind < OUT_RASTER || out_kind > OUT_SPARSE) return fail(c0, VRT_HIP_ERR_INVALID, "frame_batch: out_kind is 0 (frame), 1 (compact shard) or 2 (sparse shard)");
-    hipStream_t st = (hipStream_t)hip_stream;
-    for (int i = 0; i < n; ++i) {
-        vrt_hip_ctx *c = ctxs[i];
-        if (!c || !d_out[i]) return fail(c0, VRT_HIP_ERR_INVALID, "frame_batch: null context or output");
-        for (int k = 0; k < i; ++k)
-            if (ctxs[k] == c) return fail(c0, VRT_HIP_ERR_INVALID, "frame_batch: a context holds ONE frame's lists and queues -- every frame of a batch needs its own");
-        if (c->device != c0->device || c->exp_kind != c0->exp_kind || c->erf_kind != c0->erf_kind || c->tune.dense_waves != c0->tune.dense_waves ||
-            c->table_hx != c0->table_hx || c->table_budget != c0->table_budget || c->cull_prune != c0->cull_prune || c->cull_eps != c0->cull_eps)
-            return fail(c0, VRT_HIP_ERR_INVALID, "frame_batch: the contexts differ in device or in Exp / Erf / dense-kernel / table options");
-        if (c->w != c0->w || c->h != c0->h || c->n != c0->n || c->rank != c0->rank || c->world != c0->world)
-            return fail(c0, VRT_HIP_ERR_INVALID, "frame_batch: the frames differ in image size, scene size or shard");
-        if (out_kind == OUT_SPARSE && (uintptr_t)d_out[i] % 16) return fail(c0, VRT_HIP_ERR_INVALID, "frame_batch: sparse shard buffers must be 16-byte aligned");
-    }
-    HIPCHK(c0, hipSetDevice(c0->device));
-    // argument rows: slot (batch_seq % BATCH_SLOTS) of the pinned ring, copied to the same slot of the device ring
-    if ((size_t)n > c0->batch_cap) {
-        int rc = quiesce(c0);
-        if (rc) return rc;
-        HIPCHK(c0, hipStreamSynchronize(st));
-        c0->batch_cap = 0;
-        const size_t cap = std::max<size_t>(16, (size_t)n);
-        HIPCHK(c0, c0->batch_host.alloc(cap * vrt_hip_ctx::BATCH_SLOTS, hipHostMallocDefault));
-        HIPCHK(c0, c0->batch_dev.reserve(cap * vrt_hip_ctx::BATCH_SLOTS));
-        c0->batch_cap = cap;
-        for (auto &e : c0->batch_copied) if (!e) HIPCHK(c0, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const uint32_t slot = c0->batch_seq++ % vrt_hip_ctx::BATCH_SLOTS;
-    if (c0->batch_seq > (uint32_t)vrt_hip_ctx::BATCH_SLOTS) HIPCHK(c0, hipEventSynchronize(c0->batch_copied[slot])); // the copy that last read this slot
-    FrameArgs *rows = c0->batch_host.p + (size_t)slot * c0->batch_cap;
-    FrameArgs *d_rows = c0->batch_dev.p + (size_t)slot * c0->batch_cap;
-
-    // every frame's host work, memsets and per-origin table kernel as for a single frame; its three launches recorded
-    int failed = VRT_HIP_OK, touched = 0;
-    for (int i = 0; i < n && !failed; ++i) {
-        vrt_hip_ctx *c = ctxs[i];
-        c->defer = &rows[i];
-        rows[i].do_prep = rows[i].do_cones = rows[i].do_order = 0;
-        c->deferred = vrt_hip_ctx::Deferred{};
-        touched = i + 1;
-        int rc = vrt_hip_tile_gaussians_device(c, tw, th, views + 16 * (size_t)i, hip_stream);
-        if (!rc) rc = render_common(c, origins + 3 * (size_t)i, pack_flags, d_out[i], nullptr, st, out_kind);
-        c->defer = nullptr;
-        if (rc) {
-            if (c != c0) fail(c0, rc, std::string("frame_batch: frame ") + std::to_string(i) + ": " + c->err);
-            failed = rc;
-            break;
-        }
-        const auto &d = c->deferred, &d0 = c0->deferred;
-        if (!d.render || d.lists != d0.lists || d.from_list != d0.from_list || d.list_grid != d0.list_grid || d.render_grid != d0.render_grid)
-            failed = fail(c0, VRT_HIP_ERR_INVALID, "frame_batch: the frames differ in image size, tile grid, shard or scene size");
-    }
-    if (failed) {
-        // The contexts prepared so far have advanced their list and queue generations for kernels that will not run: the
-        // counter sets those kernels would have cleared for the next frame are stale.  Clear them and make the next frame
-        // rebuild its lists.
-        for (int i = 0; i < touched; ++i) {
-            vrt_hip_ctx *c = ctxs[i];
-            if (c->c_counters.p && hipMemsetAsync(c->c_counters.p, 0, 16 * sizeof(uint32_t), st) != hipSuccess) (void)hipGetLastError();
-            if (c->c_rq.p && hipMemsetAsync(c->c_rq.p, 0, 2 * RQ_N * RQ_STRIDE * sizeof(uint32_t), st) != hipSuccess) (void)hipGetLastError();
-            c->lists_dirty = true; c->lists_fresh = false;
-            c->gA_valid = false; c->cone_key.clear(); // their deferred set-up launches were never made
-        }
-        return failed;
-    }
-    for (int i = 0; i < n; ++i) rows[i].do_order = ctxs[i]->deferred.order ? 1 : 0;
-    // one-wave kernel: the persistent grid of ONE frame fills the GPU; n frames share it -- so a frame of a batch has 1/n of the waves and
-    // that many more queue entries: the variant that claims them early is chosen against the per-frame grid
-    const uint32_t full_grid = c0->deferred.render_grid;
-    const uint32_t rgrid = full_grid ? std::min(full_grid, std::max(1u, (full_grid + (uint32_t)n - 1) / (uint32_t)n)) : 0u;
-    bool claim = false;
-    for (int i = 0; i < n; ++i) {
-        rows[i].C.claim_early = claim_early_for(ctxs[i], rgrid);
-        claim = claim || rows[i].C.claim_early;
-    }
-    HIPCHK(c0, hipMemcpyAsync(d_rows, rows, (size_t)n * sizeof(FrameArgs), hipMemcpyHostToDevice, st));
-    HIPCHK(c0, hipEventRecord(c0->batch_copied[slot], st));
-    launch_frame_setup_batch(d_rows, rows, (uint32_t)n, st); // per-origin tables and cone tables of the frames that need new ones
-    const auto &d0 = c0->deferred;
-    if (d0.lists) launch_build_tile_lists_batch(d_rows, (uint32_t)n, d0.from_list, !d0.from_list && rows[0].bin.chunks && rows[0].bin.refine, d0.list_grid, st); // (same scene size and geometry in every frame: checked above)
-    launch_render_batch(d_rows, (uint32_t)n, rgrid, claim, c0->exp_kind, c0->erf_kind, st);
-    uint32_t dgrid = 0;
-    for (int i = 0; i < n; ++i) dgrid = std::max(dgrid, ctxs[i]->deferred.dense_grid);
-    launch_order_dense_batch(d_rows, rows, (uint32_t)n, st);
-    if (table_on(c0))
-        launch_render_table_batch(d_rows, (uint32_t)n, std::min<uint32_t>(dgrid, (uint32_t)c0->num_cus), (uint64_t)rows[0].R.width * rows[0].R.height,
-                                  c0->exp_kind, c0->erf_kind, st);
-    else
-        launch_render_dense_batch(d_rows, (uint32_t)n, dgrid, c0->tune.dense_waves, c0->exp_kind, c0->erf_kind, st);
-    HIPCHK(c0, hipGetLastError());
-    return VRT_HIP_OK;
-}
-
 
 } // extern "C"

@@ -1,6 +1,6 @@
 // vrt_hip_ctx.hpp -- internal to libvrt_hip.so: the context behind the C ABI (include/vrt_hip.h), the owning buffer types and
-// what the host runtime's translation units share (vrt_hip_api.cpp: context, setters, frame pipeline, shard map;
-// vrt_hip_assembly.cpp: shard assembly; vrt_hip_query.cpp: point queries; vrt_hip_rays.cpp: ray bundles; vrt_hip_diag.cpp: stats, kernel timing, timelines).
+// what the host runtime's translation units share (vrt_hip_api.cpp: context, setters, tiles, shard map, tables;
+// vrt_hip_frame.cpp: frame pipeline; vrt_hip_assembly.cpp: shard assembly; vrt_hip_query.cpp: point queries; vrt_hip_rays.cpp: ray bundles; vrt_hip_diag.cpp: stats, kernel timing, timelines).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -107,13 +107,7 @@ struct vrt_hip_ctx {
     DevBuf<uint32_t> ref_start, ref_count, ref_indices;
     bool ref_valid = false;
     DevBuf<uint32_t> w_start, w_count, w_indices;
-    // frame batches (vrt_hip_frame_batch_device): while `defer` is set the three per-frame launches are recorded, not made
-    vrtk::FrameArgs *defer = nullptr;
-    struct Deferred {
-        bool lists = false, from_list = false, render = false, order = false;
-        uint32_t list_grid = 0, render_grid = 0, dense_grid = 0;
-    } deferred;
-    // the context a batch is issued through keeps the argument rows: a ring of pinned host slots and device slots
+    // frame batches (vrt_hip_frame_batch_device): the context a batch is issued through keeps the argument rows: a ring of pinned host slots and device slots
     static constexpr int BATCH_SLOTS = 4;
     PinnedBuf<vrtk::FrameArgs> batch_host;
     DevBuf<vrtk::FrameArgs> batch_dev;
@@ -146,8 +140,6 @@ struct vrt_hip_ctx {
     uint32_t rq_gen = 0;      // render launches: selects the work-queue counter set (CellGrid::rq)
     uint32_t cells_x = 1, cells_y = 1, cstride = 1, n_cells = 0;
     int lists_for_shard = -1; // sharding mode the cell lists were built for
-    bool prep_pending = false; // the per-origin table (gA) of gA_origin is still to be written: by the next list kernel, or by flush_prep()
-    bool lists_fresh = false; // the queue counters were zeroed by the list build of this very call
     uint32_t list_gen = 0;    // list generation: selects the counter set (see cell_grid)
     // dense-launch feedback (CellGrid::feedback): host-mapped, read frames later
     PinnedBuf<volatile uint32_t> h_fb;
@@ -205,7 +197,6 @@ struct vrt_hip_ctx {
                    background == o.background && image == o.image;
         }
     } own_sig;
-    bool retain_next = false; // set by vrt_hip_frame around its render_common call
     // A caller's host frame buffer (vrt_hip_host_register): page-locked and mapped while its holder lives.  history[cell] = 1: the
     // buffer holds that cell of a frame in which it was lit (anything else holds background); valid for `sig` (own_sig without the
     // image pointer) once a delivery with stamps has recorded it.  slot: its word in h_cells (the cells its last finished delivery
@@ -292,7 +283,13 @@ int build_ray_index(vrt_hip_ctx *c); // vrt_hip_rays.cpp: the tables are built a
 int rebuild_shard(vrt_hip_ctx *c);
 vrtk::SceneTables tables(const vrt_hip_ctx *c);
 vrtk::TileLists tile_geometry(const vrt_hip_ctx *c);
+float exp_floor_x(int exp_kind);
+bool table_on(const vrt_hip_ctx *c);
+int prepare_tile_grid(vrt_hip_ctx *c, float tw, float th);
+int ensure_none_ref_lists(vrt_hip_ctx *c);
 uint32_t sparse_capacity(vrt_hip_ctx *c); // cells a sparse shard of this context can hold (the same on every rank)
+// vrt_hip_frame.cpp
+vrtk::BinArgs bin_args(const vrt_hip_ctx *c); // the tile binning's part of a list kernel's arguments
 // the frame of vrt_hip_frame into the context's own buffer d_image, on its stream (vrt_hip_frame, vrt_hip_frame_host)
 int frame_own_image(vrt_hip_ctx *c, float tw, float th, const float view[16], const float origin[3], int pack_flags);
 // vrt_hip_diag.cpp

@@ -78,6 +78,23 @@ def test_batch_equals_single_frames(pkg, renderer, name, w, h, tiles_n, n, table
         torch.cuda.synchronize()
         for i in range(m):
             np.testing.assert_array_equal(outs[i].cpu().numpy().view(np.uint32), want[n + i])
+        if (name, table) in (("g16", None), ("cube", 0.0)):
+            # single frames through contexts that have just been frames of a batch, at cameras they have not seen, nothing waited
+            # for in between; then a batch again: what a frame plans (per-origin table, cone tag, counter and queue generations)
+            # must carry over from a batch to a single frame and back
+            singles = [(0, n - 1), (0, 2 * n - 1), (1, n - 2), (1, 2 * n - 2)]
+            for (k, j), o in zip(singles, outs):
+                ctxs[k].set_camera_view(w, h, cams[j].view)
+                ctxs[k].frame_call(tw, th, cams[j].view, cams[j].position, pack)(o.data_ptr(), st)
+            torch.cuda.synchronize()
+            for (k, j), o in zip(singles, outs):
+                np.testing.assert_array_equal(o.cpu().numpy().view(np.uint32), want[j], err_msg=f"single frame, context {k} camera {j}")
+            for r, c in zip(ctxs, cams[:n]):
+                r.set_camera_view(w, h, c.view)
+            ctxs[0].frame_batch_call(ctxs[1:], tw, th, [c.view for c in cams[:n]], [c.position for c in cams[:n]], pack)(ptrs, st)
+            torch.cuda.synchronize()
+            for i in range(n):
+                np.testing.assert_array_equal(outs[i].cpu().numpy().view(np.uint32), want[i], err_msg=f"batch after single frames, frame {i}")
     finally:
         for r in ctxs:
             r.close()

@@ -324,7 +324,14 @@ def test_tiles_of_64_and_of_more_cells(pkg, oracle, renderer, w, h, fused):
         else:
             with pytest.raises(pkg.VrtHipError, match=r"\(-1\).*64 cells"):
                 call([out.data_ptr()], st)
+            # the batch was refused by its planning, after the context had advanced its generations: a single frame through the
+            # same context right behind it is still right
+            r.frame_call(2.0, 2.0, sc.view, sc.origin, pkg.PACK_ROUND | pkg.ALPHA_COMPUTED)(out.data_ptr(), st)
             torch.cuda.synchronize()
+            r.tile_gaussians(2.0, 2.0, sc.view)
+            ref, _ = r.render(sc.origin, want_radiance=False)
+            np.testing.assert_array_equal(out.cpu().numpy().view(np.uint32), ref.reshape(-1))
+            assert (ref.reshape(-1)[sc.pixels] >> 24).min() > 0
     finally:
         r.close()
 
