@@ -69,7 +69,7 @@ static_assert(sizeof(gaussian_t) == 40, "gaussian_t must match the reference's A
 //      AVX2); here a lane is a ray of a wave64, so W = 64 and simd::Vec<simd::Float> is a plain array of 64 floats.
 //      They exist so that callers of broadcast_transmittance / broadcast_radiance (rt.h:102-103, 205-206) compile:
 //      the arithmetic on them happens on the GPU, one lane per ray.  (simd_gaussian_t::pdf has no host evaluator: the
-//      density is evaluated inside the kernels, types.h:299-302 <-> emission_term in csrc/vrt_kernels.hip.) ---------
+//      density is evaluated inside the kernels, types.h:299-302 <-> emission_term in csrc/vrt_kernels_common.hpp.) ---------
 constexpr u64 SIMD_FLOATS = 64;
 namespace simd {
 struct Float {};

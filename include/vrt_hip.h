@@ -389,7 +389,7 @@ int vrt_hip_eval_exp(vrt_hip_ctx *ctx, int exp_kind, const float *x, size_t n, f
  * equidistant nodes along it and interpolate the 5 n sample points (n * G erf terms per ray instead of 5 n^2).
  * `step` = requested node spacing in units of sqrt2 * sigma of the narrowest Gaussian of the block (default 0.05; 0 = off:
  * the exact kernels only, which reproduce the reference's per-term sums).  Every ray's worst-case radiance change --
- * sum over its samples of |term| * (0.0212 u^2 * K + 0.36 u^4 * S_all), see render_table_body in csrc/vrt_kernels.hip --
+ * sum over its samples of |term| * (0.0212 u^2 * K + 0.36 u^4 * S_all), see render_table_body in csrc/vrt_table_kernel.hip --
  * must stay below the budget (default 2.5e-5), or the block is redone at 0.6 of the spacing and then shaded exactly; so
  * are blocks with more than 2048 survivors.
  * Applies to the Exp / Erf pairs {vcl_exp, expf} x {A&S erf, erff}; other pairs are always exact. */

@@ -351,7 +351,7 @@ __device__ __forceinline__ void render_body(const SceneTables &S, const TileList
                 keep = cone_keeps(cone, a, make_float4(bq.x, bq.y, bq.z, slack_cull_x(bq.w, slack, T.floor_x)));
             }
             const unsigned long long mask = __ballot(keep);
-            const uint32_t pos = cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+            const uint32_t pos = cnt + lane_rank(mask);
             if (keep && pos < PCAP) { s_A[pos] = a; s_B[pos] = bq; s_M[pos] = ms; s_C[pos] = alb; s_q[pos] = q; }
             cnt += (uint32_t)__popcll(mask);
         }

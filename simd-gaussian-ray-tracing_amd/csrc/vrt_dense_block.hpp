@@ -1,5 +1,5 @@
 // vrt_dense_block.hpp -- one dense 8x8 block shaded exactly by a workgroup of DW waves: the body of the exact dense kernel
-// (vrt_kernels.hip) and, since round 4, the fallback INSIDE the table kernel for the blocks it declines (vrt_table_kernel.hip) --
+// (vrt_dense_kernel.hip) and, since round 4, the fallback INSIDE the table kernel for the blocks it declines (vrt_table_kernel.hip) --
 // a frame then needs one dense-path launch, not two.  Which arithmetic shades a block is a function of the block alone either way.
 #pragma once
 #include "vrt_kernels_common.hpp"
@@ -54,7 +54,7 @@ __device__ __forceinline__ void dense_shade_block(const SceneTables &S, const Ti
         const uint32_t tx = p.t % T.tiles_w, ty = p.t / T.tiles_w;
         bool valid = p.pxt < T.tile_w && p.pyt < T.tile_h;
         const uint32_t pxc = min(p.pxt, T.tile_w - 1), pyc = min(p.pyt, T.tile_h - 1);
-        uint64_t pix = (uint64_t)(tx * T.tile_w + pxc) + (uint64_t)T.stride * (ty * T.tile_h + pyc);
+        uint64_t pix = tile_pixel(T.tile_w, T.tile_h, T.stride, tx, ty, pxc, pyc);
         if (pix >= npix) { valid = false; pix = npix - 1; }
         const uint32_t n_active_cells = *C.n_active;
         const uint64_t out = out_index(T, C, O, cell, bi, lane, p, pix, n_active_cells);
@@ -100,7 +100,7 @@ __device__ __forceinline__ void dense_shade_block(const SceneTables &S, const Ti
                 before += (wv < wave) ? c : 0;
                 chunk += c;
             }
-            const uint32_t pos = cnt + before + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+            const uint32_t pos = cnt + before + lane_rank(mask);
             if (keep && pos < DCAP) {
                 s_idx0[pos] = idx;
                 s_key[pos] = a.x * cone.cx + a.y * cone.cy + a.z * cone.cz; // depth along the block's axis

@@ -54,7 +54,7 @@ float exp_floor_x(int exp_kind)
     }
 }
 
-// table mode applies to the Exp / Erf pairs its error bound covers (vrt_kernels.hip, VRT_DISPATCH_TABLE)
+// table mode applies to the Exp / Erf pairs its error bound covers (vrt_table_kernel.hip, VRT_DISPATCH_TABLE)
 bool table_on(const vrt_hip_ctx *c)
 {
     return c->table_hx > 0.f && (c->erf_kind == VRT_ERF_AS || c->erf_kind == VRT_ERF_LIBM) &&

@@ -4,6 +4,7 @@
 // device frame) and the cells lit at that delivery that are dark now (background).  Everything else in the buffer already
 // holds this frame's pixels.  The rest of the frame pipeline stays as it is: this unit only reads its buffers.
 #include "vrt_host_frame.h"
+#include "vrt_kernels_common.hpp"
 
 namespace vrtk {
 
@@ -16,7 +17,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // re-reads it on the GPU).  Rows that are not 16-byte aligned (tile width not a multiple of 4) go out as dwords.
 __device__ __forceinline__ void deliver_cell(HostFrameArgs a, uint32_t key, uint32_t lane, bool lit)
 {
-    // cell key -> raster rectangle, as scatter_sparse_body (vrt_kernels.hip) maps it
+    // cell key -> raster rectangle, as scatter_sparse_body (vrt_assembly_kernel.hip) maps it
     const uint32_t cpt = a.cells_x * a.cells_y;
     const uint32_t t = key / cpt, ci = key % cpt;
     const uint32_t tx = t % a.T.tiles_w, ty = t / a.T.tiles_w;
@@ -30,7 +31,7 @@ __device__ __forceinline__ void deliver_cell(HostFrameArgs a, uint32_t key, uint
     for (uint32_t row = lane / 8; row < CELL; row += 8) {
         const uint32_t pyt = (ci / a.cells_x) * CELL + row;
         if (pyt >= a.T.tile_h) break;
-        const uint64_t pix = (uint64_t)(tx * a.T.tile_w + pxt) + (uint64_t)a.T.stride * (ty * a.T.tile_h + pyt);
+        const uint64_t pix = tile_pixel(a.T.tile_w, a.T.tile_h, a.T.stride, tx, ty, pxt, pyt);
         if (vec) {
             if (pix >= npix) break;
             const u32x4 v = lit ? *reinterpret_cast<const u32x4 *>(a.image + pix) : bg4;

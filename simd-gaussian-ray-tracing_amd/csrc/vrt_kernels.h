@@ -1,5 +1,5 @@
 // vrt_kernels.h -- launch interface between the C-ABI host code (vrt_hip_api.cpp) and the
-// gfx950 kernels (vrt_kernels.hip).
+// gfx950 kernels (the vrt_*kernel*.hip units and vrt_host_frame.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,8 +1,9 @@
-// vrt_kernels_common.hpp -- device code shared by the four kernel translation units of libvrt_hip.so (csrc/Makefile):
+// vrt_kernels_common.hpp -- device code shared by the kernel translation units of libvrt_hip.so (csrc/Makefile):
 //   vrt_block_kernel.hip   the one-wave "block kernel" (sparse scenes), scheduled for instruction-level parallelism
-//   vrt_table_kernel.hip   the table kernel (default path of dense blocks)
+//   vrt_table_kernel.hip   the table kernel (default path of dense blocks);  vrt_dense_kernel.hip  the exact dense kernel
 //   vrt_ray_kernel.hip     ray bundles: caller-given rays, culled per ray (no camera, no tiles)
-//   vrt_kernels.hip        everything else: exact dense kernel, list kernels, scene tables, frame assembly, point queries
+//   vrt_kernels.hip        the frame's set-up: scene tables, tile cones, list kernels
+//   vrt_assembly_kernel.hip, vrt_query_kernel.hip, vrt_host_frame.hip   frame assembly, point queries, host delivery (tile_pixel)
 // Hand-written for gfx950 (CDNA4, wave64).  No MFMA: the path is VALU + quarter-rate transcendental bound (one v_rcp_f32 per
 // Abramowitz-Stegun erf term); Gaussian parameters reach the inner loops through LDS rows or wave-uniform scalar loads.
 //
@@ -98,6 +99,8 @@ __device__ __forceinline__ uint32_t lane_value_u32(uint32_t v, uint32_t l)
 }
 // lane `l` (a constant) of a full wave's register, through the scalar unit (__shfl is a ds_bpermute_b32)
 __device__ __forceinline__ float lane_value(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+// this lane's rank among the lanes of a ballot: how many lanes below it are set in `mask`
+__device__ __forceinline__ uint32_t lane_rank(unsigned long long mask) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0)); }
 
 __device__ __forceinline__ uint32_t pack_pixel(float r, float g, float b, float a, int flags)
 {
@@ -380,6 +383,26 @@ __device__ __forceinline__ Cone rect_cone(At at, uint32_t x0, uint32_t y0, uint3
     Cone cone = make_cone(c.nx, c.ny, c.nz, wave_min(co), wave_max(si));
     cone.sin_t += 1e-4f; // the centre pixel is up to half a pixel off the rectangle's centre
     return cone;
+}
+// raster index of pixel (x, y) of tile (tx, ty); scalars, so that BinArgs and TileLists both feed it
+__device__ __forceinline__ uint64_t tile_pixel(uint32_t tile_w, uint32_t tile_h, uint32_t stride, uint32_t tx, uint32_t ty, uint32_t x, uint32_t y)
+{
+    return (uint64_t)(tx * tile_w + x) + (uint64_t)stride * (ty * tile_h + y);
+}
+// cone of cell ci of tile (tx, ty), the tile cut into cells of SIZE x SIZE pixels, cells_x to a row, the last ones clipped to the tile;
+// pixels past the image count as its last pixel.  G: BinArgs or TileLists, for tile_w, tile_h and stride
+template <uint32_t SIZE, typename G>
+__device__ __forceinline__ Cone tile_cell_cone(const RayGen &R, const G &g, uint32_t tx, uint32_t ty, uint32_t ci, uint32_t cells_x, uint32_t lane)
+{
+    const uint64_t npix = (uint64_t)R.width * R.height;
+    const uint32_t x0 = (ci % cells_x) * SIZE, y0 = (ci / cells_x) * SIZE;
+    const uint32_t x1 = min(x0 + SIZE, g.tile_w) - 1, y1 = min(y0 + SIZE, g.tile_h) - 1;
+    auto at = [&](uint32_t x, uint32_t y) {
+        uint64_t pix = tile_pixel(g.tile_w, g.tile_h, g.stride, tx, ty, x, y);
+        if (pix >= npix) pix = npix - 1;
+        return cone_ray(R, pix);
+    };
+    return rect_cone(at, x0, y0, x1, y1, lane);
 }
 __device__ __forceinline__ bool cone_keeps(const Cone &k, float4 a /*oc,|oc|^2*/, float4 bq /*r,1/2s^2,qK,cull_x*/)
 {

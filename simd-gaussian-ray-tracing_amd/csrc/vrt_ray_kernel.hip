@@ -362,7 +362,7 @@ __global__ __launch_bounds__(64) void ray_long_kernel(RayArgs)
                 const uint32_t ic = min(idx, N - 1u);
                 const bool keep = idx < N && ray_member_keeps(S.mu_sig[ic], S.gB[ic], ray);
                 const unsigned long long mask = __ballot(keep);
-                const uint32_t pos = n + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+                const uint32_t pos = n + lane_rank(mask);
                 if (keep) {
                     if (pos < (uint32_t)RAY_LCAP) s_list[pos] = idx;
                     else if (pos < N) slot[pos] = idx;

@@ -1,4 +1,4 @@
-"""Where does a kernel's register-spill code sit?  Compiles csrc/vrt_kernels.hip to gfx950 assembly, finds the loops of one
+"""Where does a kernel's register-spill code sit?  Compiles one kernel translation unit (default: csrc/vrt_dense_kernel.hip) to gfx950 assembly, finds the loops of one
 kernel (backward branches) and lists, per loop that holds erf terms (v_rcp_f32) or scratch accesses, its size, its VALU
 instruction count and its scratch loads / stores.  Round-1 verdict: "render_dense_kernel spills 9 VGPRs to scratch --
 nobody checked whether the spill code sits in the absorber loop".
@@ -13,8 +13,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 want = sys.argv[1] if len(sys.argv) > 1 else "render_dense_kernelILi1ELi1ELi6ELi16ELb1"
-# the kernel's translation unit: vrt_kernels.hip (exact dense kernel, list kernels), vrt_table_kernel.hip, vrt_block_kernel.hip
-unit = sys.argv[2] if len(sys.argv) > 2 else "vrt_kernels.hip"
+# the kernel's translation unit: vrt_dense_kernel.hip (exact dense kernel), vrt_kernels.hip (list kernels), vrt_table_kernel.hip, vrt_block_kernel.hip, ...
+unit = sys.argv[2] if len(sys.argv) > 2 else "vrt_dense_kernel.hip"
 src = os.path.join(ROOT, "simd-gaussian-ray-tracing_amd", "csrc", unit)
 extra = ["-DVRT_RENDER_ECMAX=6", "-DVRT_RENDER_WPE=3", "-mllvm", "-amdgpu-sched-strategy=max-ilp"] if "block" in unit else []
 with tempfile.TemporaryDirectory() as d:

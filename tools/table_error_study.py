@@ -1,4 +1,4 @@
-"""Interpolation error of the table kernel (csrc/vrt_kernels.hip, render_table_body): a unit Abramowitz-Stegun erf
+"""Interpolation error of the table kernel (csrc/vrt_table_kernel.hip, render_table_body): a unit Abramowitz-Stegun erf
 (approx.cpp:90-110 of the reference) tabulated at node spacing u and read off by 4-point Lagrange interpolation.
 
 The A&S erf is the odd extension of a rational function: its second derivative jumps by 0.586 at 0 (a "kink").  For a
