@@ -452,6 +452,35 @@ void radiance_rays_device(const f32 *d_origins, bool origin_per_ray, const f32 *
     d.check(vrt_hip_radiance_rays_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_radiance, d_image, pack_flags, hip_stream),
             "vrt_hip_radiance_rays_device");
 }
+// Transmittance bundles: broadcast_transmittance for ANY number of rays at ns depths each in ONE call, under the same per-ray cull
+// (vrt_hip_transmittance_bundle in include/vrt_hip.h: the exponent moves by less than 0.8 * cull_eps * min(N, 4096) = 3.3e-6 at the
+// defaults).  s: ns sample distances shared by all rays (s_per_ray = false) or nrays * ns, [r * ns + k]; T_out[r * ns + k].  Shadow
+// rays are ns = 1; a depth profile along a ray is one call.  vrt::broadcast_transmittance above stays the reference's full sum.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void transmittance_bundle(const vec4f_t *o, const vec4f_t *n, size_t nrays, const f32 *s, size_t ns, bool s_per_ray, const gaussians_t &gaussians,
+                          f32 *T_out)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    std::vector<f32> oo(3 * nrays), nn(3 * nrays);
+    for (size_t r = 0; r < nrays; ++r) {
+        oo[3 * r] = o[r].x; oo[3 * r + 1] = o[r].y; oo[3 * r + 2] = o[r].z;
+        nn[3 * r] = n[r].x; nn[3 * r + 1] = n[r].y; nn[3 * r + 2] = n[r].z;
+    }
+    d.check(vrt_hip_transmittance_bundle(d.ctx, nrays, oo.data(), 1, nn.data(), s, ns, s_per_ray ? 1 : 0, T_out), "vrt_hip_transmittance_bundle");
+}
+// The same for rays, samples and results that live on the device: enqueued on hip_stream, nothing waits.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void transmittance_bundle_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const f32 *d_s, size_t ns, bool s_per_ray,
+                                 const gaussians_t &gaussians, f32 *d_T, void *hip_stream)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    d.check(vrt_hip_transmittance_bundle_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_s, ns, s_per_ray ? 1 : 0, d_T, hip_stream),
+            "vrt_hip_transmittance_bundle_device");
+}
 // Ray bundles cull through the Morton index of the scene from the next call on (vrt_hip_set_ray_index in include/vrt_hip.h: off by
 // default, the same radiance and the same pixels bit for bit either way; the index is made once per scene).
 inline void set_ray_index(bool on)

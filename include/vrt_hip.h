@@ -336,6 +336,33 @@ int vrt_hip_radiance_rays_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_
                                  void *hip_stream);
 int vrt_hip_radiance_rays(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
                           float *radiance_out, uint32_t *image_out, int pack_flags);        /* host pointers, waits */
+/* -------- transmittance bundles: broadcast_transmittance (rt.h:102-127) for ANY rays at ANY number of depths, as a fast path --
+ * T[r * ns + k] = Exp(sum_j term_j(s[r, k])) over the Gaussians ray r keeps under the cull rule of the ray bundles above (the same
+ * cull_x, the same eps_eff, the same code); term_j is the reference's term in the reference's operations and order (unfused, exact
+ * divides), as in vrt_hip_transmittance_rays.  A ray that keeps nothing gets Exp(0) of the selected kind.
+ * origins, origin_per_ray, dirs: as in vrt_hip_radiance_rays_device.  s: ns sample distances shared by all rays (s_per_ray == 0) or
+ * nrays * ns of them, [r * ns + k] (s_per_ray != 0).  Any ns >= 1: the kernels loop.  s must be finite; a negative s is allowed
+ * and gives T > 1, as the point query does.  Shadow rays are ns = 1; a depth profile of a ray is one call.
+ * Cull bound: a dropped Gaussian has sigma mag exp(-x) < eps_eff, and its term is at most 2 / sqrt(2 pi) times that, so the
+ * exponent moves by less than 0.8 * cull_eps * min(N, 4096) = 3.3e-6 at the defaults -- and for s >= 0, where T <= 1, T moves by
+ * less than that.  cull_eps = 0 keeps everything that Exp does not flush to exactly 0.
+ * Rays with at most 32 kept Gaussians are summed lane = ray in ascending scene order (the reference's sum without what the cull
+ * dropped); longer lists by one wave per ray, which sums in another (fixed) order.  A result is a function of (ray, s, scene,
+ * options) alone, whatever else is in the bundle and however many samples the call carries.
+ * Uses the scene, every Exp / Erf pair, cull_eps and the Morton index when vrt_hip_set_ray_index is on (the same bits either way);
+ * ignores tiles, the rays of set_plane / set_camera*, shard, table settings and cull_prune.
+ * The rules are the radiance bundle's: everything is enqueued on hip_stream, without host synchronisation and without allocation
+ * once a bundle of at least this size has been seen (nrays, and nrays * ns for s and T of the host form); the call counts as a
+ * frame in flight.  It shares the context's long-ray queue, counters, scratch slots and bitmap with the radiance bundles: two
+ * bundles of one context are ordered by the stream they share.  nrays == 0 or ns == 0 returns VRT_HIP_OK with nothing launched;
+ * NULL dirs, origins, s or T with work to do, or more rays than the u32 queue holds: VRT_HIP_ERR_INVALID, nothing enqueued.
+ * vrt_hip_get_ray_stats / vrt_hip_get_ray_index_stats report the last bundle of either kind; for the same rays, scene and options
+ * every field is what a radiance bundle reports.  vrt_hip_transmittance_rays stays the full sum. */
+int vrt_hip_transmittance_bundle_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_origins, int origin_per_ray,
+                                        const float *d_dirs, const float *d_s, size_t ns, int s_per_ray, float *d_T,
+                                        void *hip_stream);
+int vrt_hip_transmittance_bundle(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                                 const float *s, size_t ns, int s_per_ray, float *T_out);       /* host pointers, waits */
 typedef struct {
     uint64_t rays;           /* rays of the bundle                                                                  */
     uint64_t short_rays;     /* shaded lane = ray (list of at most 32)                                              */

@@ -120,6 +120,8 @@ SYMBOLS = {
     "vrt_hip_radiance": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p, _f32p]),
     "vrt_hip_radiance_rays_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     "vrt_hip_radiance_rays": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _u32p, C.c_int]),
+    "vrt_hip_transmittance_bundle_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int, _vp, _vp]),
+    "vrt_hip_transmittance_bundle": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p]),
     "vrt_hip_get_ray_stats": (C.c_int, [_vp, C.POINTER(RayStats)]),
     "vrt_hip_set_ray_index": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_ray_index_stats": (C.c_int, [_vp, C.POINTER(RayIndexStats)]),
@@ -507,6 +509,33 @@ class Renderer:
                                                   d_radiance or None, d_image or None, int(pack), stream or None)
         if rc != 0:
             self._chk(rc, "radiance_rays_device")
+
+    def transmittance_bundle(self, origins, dirs, s, s_per_ray=None):
+        """vrt_hip_transmittance_bundle: T at sample distances along the rays, culled per ray like radiance_rays.  origins [3] (one for
+        the bundle) or [nrays, 3], dirs [nrays, 3] unit length; s [ns] (the same samples for every ray) or [nrays, ns] (per ray;
+        s_per_ray says which when the shape does not).  Returns T f32 [nrays, ns]."""
+        origins = np.ascontiguousarray(origins, np.float32)
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        s = np.ascontiguousarray(s, np.float32)
+        per_ray = origins.size != 3
+        if per_ray:
+            assert origins.size == dirs.size
+        if s_per_ray is None:
+            s_per_ray = s.ndim == 2
+        ns = s.size // len(dirs) if s_per_ray and len(dirs) else s.size
+        if s_per_ray:
+            assert s.size == len(dirs) * ns
+        out = np.zeros((len(dirs), ns), np.float32)
+        self._chk(self._L.vrt_hip_transmittance_bundle(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(s), ns, int(bool(s_per_ray)),
+                                                       _fp(out)), "transmittance_bundle")
+        return out
+
+    def transmittance_bundle_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_s, ns, s_per_ray, d_T, stream=0):
+        """vrt_hip_transmittance_bundle_device: device pointers, everything enqueued on `stream`."""
+        rc = self._L.vrt_hip_transmittance_bundle_device(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None,
+                                                         d_s or None, int(ns), int(bool(s_per_ray)), d_T or None, stream or None)
+        if rc != 0:
+            self._chk(rc, "transmittance_bundle_device")
 
     def ray_stats(self):
         """Counts of the last bundle (enable_stats first): see vrt_hip_ray_stats in include/vrt_hip.h."""

@@ -1,6 +1,6 @@
 // vrt_hip_ctx.hpp -- internal to libvrt_hip.so: the context behind the C ABI (include/vrt_hip.h), the owning buffer types and
 // what the host runtime's translation units share (vrt_hip_api.cpp: context, setters, tiles, shard map, tables;
-// vrt_hip_frame.cpp: frame pipeline; vrt_hip_assembly.cpp: shard assembly; vrt_hip_query.cpp: point queries; vrt_hip_rays.cpp: ray bundles; vrt_hip_diag.cpp: stats, kernel timing, timelines).
+// vrt_hip_frame.cpp: frame pipeline; vrt_hip_assembly.cpp: shard assembly; vrt_hip_query.cpp: point queries; vrt_hip_rays.cpp: ray and transmittance bundles; vrt_hip_diag.cpp: stats, kernel timing, timelines).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -239,6 +239,7 @@ struct vrt_hip_ctx {
     DevBuf<uint32_t> ray_queue, ray_counters, ray_scratch;
     DevBuf<unsigned long long> ray_stats;
     DevBuf<float> rays_in[2];
+    DevBuf<float> rays_s, rays_T; // transmittance bundles: sample distances and results of the host-pointer form
     DevBuf<float4> rays_rad;
     DevBuf<uint32_t> rays_img;
     bool ray_stats_valid = false; // ray_stats holds the counts of the last bundle (stats were on for it)

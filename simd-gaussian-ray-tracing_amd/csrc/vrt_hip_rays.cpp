@@ -1,8 +1,9 @@
-// vrt_hip_rays.cpp -- ray bundles of libvrt_hip.so (vrt_hip_radiance_rays*): radiance of caller-given rays, culled per ray
-// (vrt_ray_kernel.hip).  The scene tables and the chunk spheres are the frame pipeline's; the long-ray queue, its counters and the
+// vrt_hip_rays.cpp -- ray bundles of libvrt_hip.so (vrt_hip_radiance_rays*, vrt_hip_transmittance_bundle*): radiance of caller-given
+// rays, or transmittance at sample distances along them, culled per ray (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip).  The scene tables and the chunk spheres are the frame pipeline's; the long-ray queue, its counters and the
 // long kernel's scratch slots belong to the context and only grow.
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <numeric>
 
@@ -60,6 +61,59 @@ std::vector<uint32_t> morton_order(const std::vector<float4> &ms)
     return perm;
 }
 
+// What a bundle of either kind (radiance, transmittance) enqueues before its two kernels: the tables brought up to date, the Morton
+// index when it is on and out of date, the queue / counters / scratch / statistics buffers at their size for nrays, the counters (and
+// statistics) cleared on the stream, and the kernels' arguments but for the outputs, which the caller fills in.
+struct Bundle {
+    RayArgs a{};
+    uint32_t grid = 0;
+    bool indexed = false;
+};
+int enqueue_bundle(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs, hipStream_t st, Bundle &b)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = rebuild_tables(c); if (rc) return rc; }
+    const bool indexed = c->ray_index;
+    if (indexed && c->ray_index_dirty) { // switched on after the tables were made
+        { int rc = quiesce(c); if (rc) return rc; }
+        { int rc = build_ray_index(c); if (rc) return rc; }
+    }
+    wait_for_last_stream(c, st); // a bundle in flight on another stream uses the queue and the scratch slots
+    c->last_stream = st;
+    const uint32_t grid = long_grid(c);
+    // (a buffer that grows is freed first, which waits for the device: no bundle in flight loses its memory)
+    HIPCHK(c, c->ray_queue.reserve(nrays));
+    HIPCHK(c, c->ray_counters.reserve(2));
+    HIPCHK(c, c->ray_scratch.reserve((size_t)grid * c->n));
+    constexpr size_t stats_words = RAY_STATS_WORDS + RAY_INDEX_STATS_WORDS;
+    HIPCHK(c, c->ray_stats.reserve(stats_words));
+    const uint32_t bitmap_words = (c->n + 31u) / 32u;
+    if (indexed && c->ri_bitmap.cap < (size_t)grid * bitmap_words) { // new memory: all zero once, every ray leaves it so
+        HIPCHK(c, c->ri_bitmap.reserve((size_t)grid * bitmap_words));
+        HIPCHK(c, hipMemsetAsync(c->ri_bitmap.p, 0, c->ri_bitmap.cap * sizeof(uint32_t), st));
+    }
+    HIPCHK(c, hipMemsetAsync(c->ray_counters.p, 0, 2 * sizeof(uint32_t), st));
+    if (c->stats_on) HIPCHK(c, hipMemsetAsync(c->ray_stats.p, 0, stats_words * sizeof(unsigned long long), st));
+    c->ray_stats_valid = c->stats_on;
+    c->ray_indexed_last = indexed; c->ri_last_leaves = (c->n + 63u) / 64u; c->ri_last_groups = (c->ri_last_leaves + 63u) / 64u;
+    RayArgs &a = b.a;
+    a.S = tables(c);
+    a.chunks = c->gChunk.p;
+    a.origins = d_origins; a.dirs = d_dirs; a.origin_per_ray = origin_per_ray ? 1 : 0;
+    a.nrays = nrays;
+    a.queue = c->ray_queue.p; a.queue_cap = (uint32_t)nrays;
+    a.counters = c->ray_counters.p;
+    a.scratch = c->ray_scratch.p;
+    a.stats = c->stats_on ? c->ray_stats.p : nullptr;
+    if (indexed) {
+        a.perm = c->ri_perm.p; a.mu_sig_m = c->ri_mu_sig.p; a.gB_m = c->ri_gB.p; a.leaves = c->ri_leaves.p; a.groups = c->ri_groups.p;
+        a.bitmap = c->ri_bitmap.p;
+        a.index_stats = c->stats_on ? c->ray_stats.p + RAY_STATS_WORDS : nullptr;
+    }
+    b.grid = grid; b.indexed = indexed;
+    return VRT_HIP_OK;
+}
+
 } // namespace
 
 // The Morton index of the ray bundles (include/vrt_hip.h, vrt_hip_set_ray_index).  Key of a Gaussian: its centre quantised to 10 bits
@@ -115,48 +169,11 @@ int vrt_hip_radiance_rays_device(vrt_hip_ctx *c, size_t nrays, const float *d_or
     if (!d_origins || !d_dirs) return fail(c, VRT_HIP_ERR_INVALID, "radiance_rays: NULL origins or directions");
     if (!d_radiance && !d_image) return fail(c, VRT_HIP_ERR_INVALID, "radiance_rays: no output buffer");
     if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "radiance_rays: more than 2^32 - 16 rays in one bundle");
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    { int rc = rebuild_tables(c); if (rc) return rc; }
-    const bool indexed = c->ray_index;
-    if (indexed && c->ray_index_dirty) { // switched on after the tables were made
-        { int rc = quiesce(c); if (rc) return rc; }
-        { int rc = build_ray_index(c); if (rc) return rc; }
-    }
-    wait_for_last_stream(c, st); // a bundle in flight on another stream uses the queue and the scratch slots
-    c->last_stream = st;
-    const uint32_t grid = long_grid(c);
-    // (a buffer that grows is freed first, which waits for the device: no bundle in flight loses its memory)
-    HIPCHK(c, c->ray_queue.reserve(nrays));
-    HIPCHK(c, c->ray_counters.reserve(2));
-    HIPCHK(c, c->ray_scratch.reserve((size_t)grid * c->n));
-    constexpr size_t stats_words = RAY_STATS_WORDS + RAY_INDEX_STATS_WORDS;
-    HIPCHK(c, c->ray_stats.reserve(stats_words));
-    const uint32_t bitmap_words = (c->n + 31u) / 32u;
-    if (indexed && c->ri_bitmap.cap < (size_t)grid * bitmap_words) { // new memory: all zero once, every ray leaves it so
-        HIPCHK(c, c->ri_bitmap.reserve((size_t)grid * bitmap_words));
-        HIPCHK(c, hipMemsetAsync(c->ri_bitmap.p, 0, c->ri_bitmap.cap * sizeof(uint32_t), st));
-    }
-    HIPCHK(c, hipMemsetAsync(c->ray_counters.p, 0, 2 * sizeof(uint32_t), st));
-    if (c->stats_on) HIPCHK(c, hipMemsetAsync(c->ray_stats.p, 0, stats_words * sizeof(unsigned long long), st));
-    c->ray_stats_valid = c->stats_on;
-    c->ray_indexed_last = indexed; c->ri_last_leaves = (c->n + 63u) / 64u; c->ri_last_groups = (c->ri_last_leaves + 63u) / 64u;
-    RayArgs a{};
-    a.S = tables(c);
-    a.chunks = c->gChunk.p;
-    a.origins = d_origins; a.dirs = d_dirs; a.origin_per_ray = origin_per_ray ? 1 : 0;
-    a.nrays = nrays;
-    a.radiance = (float4 *)d_radiance; a.image = d_image; a.pack_flags = pack_flags;
-    a.queue = c->ray_queue.p; a.queue_cap = (uint32_t)nrays;
-    a.counters = c->ray_counters.p;
-    a.scratch = c->ray_scratch.p;
-    a.stats = c->stats_on ? c->ray_stats.p : nullptr;
-    if (indexed) {
-        a.perm = c->ri_perm.p; a.mu_sig_m = c->ri_mu_sig.p; a.gB_m = c->ri_gB.p; a.leaves = c->ri_leaves.p; a.groups = c->ri_groups.p;
-        a.bitmap = c->ri_bitmap.p;
-        a.index_stats = c->stats_on ? c->ray_stats.p + RAY_STATS_WORDS : nullptr;
-    }
-    launch_ray_bundle(a, grid, indexed, c->exp_kind, c->erf_kind, st);
+    Bundle b;
+    { int rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b); if (rc) return rc; }
+    b.a.radiance = (float4 *)d_radiance; b.a.image = d_image; b.a.pack_flags = pack_flags;
+    launch_ray_bundle(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
     HIPCHK(c, hipGetLastError());
     return VRT_HIP_OK;
 }
@@ -182,6 +199,51 @@ int vrt_hip_radiance_rays(vrt_hip_ctx *c, size_t nrays, const float *origins, in
     if (rc) return rc;
     if (radiance_out) HIPCHK(c, hipMemcpyAsync(radiance_out, c->rays_rad.p, nrays * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     if (image_out) HIPCHK(c, hipMemcpyAsync(image_out, c->rays_img.p, nrays * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_transmittance_bundle_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                        const float *d_s, size_t ns, int s_per_ray, float *d_T, void *hip_stream)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    if (nrays == 0 || ns == 0) return VRT_HIP_OK;
+    if (!d_origins || !d_dirs) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: NULL origins or directions");
+    if (!d_s || !d_T) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: NULL samples or result");
+    if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: more than 2^32 - 16 rays in one bundle");
+    if (ns > (SIZE_MAX / sizeof(float)) / nrays) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: nrays * ns does not fit");
+    hipStream_t st = (hipStream_t)hip_stream;
+    Bundle b;
+    { int rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b); if (rc) return rc; }
+    b.a.s = d_s; b.a.ns = ns; b.a.s_per_ray = s_per_ray ? 1 : 0; b.a.T = d_T;
+    launch_ray_trans_bundle(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
+    HIPCHK(c, hipGetLastError());
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_transmittance_bundle(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *s,
+                                 size_t ns, int s_per_ray, float *T_out)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    if (nrays == 0 || ns == 0) return VRT_HIP_OK;
+    if (!origins || !dirs) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: NULL origins or directions");
+    if (!s || !T_out) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: NULL samples or result");
+    if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: more than 2^32 - 16 rays in one bundle");
+    if (ns > (SIZE_MAX / sizeof(float)) / nrays) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: nrays * ns does not fit");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // the staging buffers may still be read by an earlier bundle
+    const size_t no = (origin_per_ray ? nrays : 1) * 3, nsamples = (s_per_ray ? nrays : 1) * ns;
+    HIPCHK(c, c->rays_in[0].reserve(no));
+    HIPCHK(c, c->rays_in[1].reserve(nrays * 3));
+    HIPCHK(c, c->rays_s.reserve(nsamples));
+    HIPCHK(c, c->rays_T.reserve(nrays * ns));
+    HIPCHK(c, hipMemcpyAsync(c->rays_in[0].p, origins, no * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rays_in[1].p, dirs, nrays * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rays_s.p, s, nsamples * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    int rc = vrt_hip_transmittance_bundle_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->rays_s.p, ns, s_per_ray, c->rays_T.p,
+                                                 c->stream);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(T_out, c->rays_T.p, nrays * ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return VRT_HIP_OK;
 }

@@ -2,6 +2,7 @@
 //   vrt_block_kernel.hip   the one-wave "block kernel" (sparse scenes), scheduled for instruction-level parallelism
 //   vrt_table_kernel.hip   the table kernel (default path of dense blocks);  vrt_dense_kernel.hip  the exact dense kernel
 //   vrt_ray_kernel.hip     ray bundles: caller-given rays, culled per ray (no camera, no tiles)
+//   vrt_ray_trans_kernel.hip  transmittance bundles: T at sample distances along such rays (both over vrt_ray_cull.hpp)
 //   vrt_kernels.hip        the frame's set-up: scene tables, tile cones, list kernels
 //   vrt_assembly_kernel.hip, vrt_query_kernel.hip, vrt_host_frame.hip   frame assembly, point queries, host delivery (tile_pixel)
 // Hand-written for gfx950 (CDNA4, wave64).  No MFMA: the path is VALU + quarter-rate transcendental bound (one v_rcp_f32 per
@@ -461,6 +462,25 @@ __device__ __forceinline__ uint64_t out_index(const TileLists &T, const CellGrid
         return (uint64_t)slot * (CELL * CELL) + ((bi >> 2) * BLOCK_H + (lane >> 3)) * CELL + (bi & 3) * BLOCK_W + (lane & 7);
     }
     return O.compact ? ((uint64_t)p.lt * T.tile_h + p.pyt) * T.tile_w + p.pxt : pix;
+}
+
+// Gaussian q's term of the transmittance exponent from origin o along direction n up to the sample point s: rt.h:36-52, same operations
+// in the same order, unfused (see dot3_ref)
+template <int EXP, int ERF>
+__device__ __forceinline__ float transmittance_term(const SceneTables &S, uint32_t q, float ox, float oy, float oz, float nx, float ny, float nz,
+                                                    float s)
+{
+    const float4 g = S.mu_sig[q];
+    const float mag = S.gD[q].z;
+    const float cx = sub_ref(g.x, ox), cy = sub_ref(g.y, oy), cz = sub_ref(g.z, oz);
+    const float mu_bar = dot3_ref(cx, cy, cz, nx, ny, nz);
+    const float oc_sq = dot3_ref(cx, cy, cz, cx, cy, cz);
+    const float inv_2_sigma2 = 1.f / mul_ref(mul_ref(2.f, g.w), g.w);
+    const float c_bar = mul_ref(mag, vexp<EXP>(-mul_ref(sub_ref(oc_sq, mul_ref(mu_bar, mu_bar)), inv_2_sigma2)));
+    const float sqrt_2_sig = mul_ref(SQRT_2, g.w);
+    const float mu_bar_n = mu_bar / sqrt_2_sig;
+    const float s_n = s / sqrt_2_sig;
+    return mul_ref(mul_ref(mul_ref(g.w, c_bar), INV_SQRT_2_PI), sub_ref(verf<ERF>(-mu_bar_n), verf<ERF>(sub_ref(s_n, mu_bar_n))));
 }
 
 #define VRT_DISPATCH_EXP_ERF(FN, ...)                                                              \

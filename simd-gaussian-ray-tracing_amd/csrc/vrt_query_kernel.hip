@@ -5,24 +5,7 @@
 namespace vrtk {
 
 // API parity with rt.h:32-54, rt.cpp:8-27, rt.h:146-223; not performance paths.
-// Gaussian q's term of the transmittance exponent from origin o along direction n up to the sample point s: rt.h:36-52, same operations
-// in the same order, unfused (see dot3_ref)
-template <int EXP, int ERF>
-__device__ __forceinline__ float transmittance_term(const SceneTables &S, uint32_t q, float ox, float oy, float oz, float nx, float ny, float nz,
-                                                    float s)
-{
-    const float4 g = S.mu_sig[q];
-    const float mag = S.gD[q].z;
-    const float cx = sub_ref(g.x, ox), cy = sub_ref(g.y, oy), cz = sub_ref(g.z, oz);
-    const float mu_bar = dot3_ref(cx, cy, cz, nx, ny, nz);
-    const float oc_sq = dot3_ref(cx, cy, cz, cx, cy, cz);
-    const float inv_2_sigma2 = 1.f / mul_ref(mul_ref(2.f, g.w), g.w);
-    const float c_bar = mul_ref(mag, vexp<EXP>(-mul_ref(sub_ref(oc_sq, mul_ref(mu_bar, mu_bar)), inv_2_sigma2)));
-    const float sqrt_2_sig = mul_ref(SQRT_2, g.w);
-    const float mu_bar_n = mu_bar / sqrt_2_sig;
-    const float s_n = s / sqrt_2_sig;
-    return mul_ref(mul_ref(mul_ref(g.w, c_bar), INV_SQRT_2_PI), sub_ref(verf<ERF>(-mu_bar_n), verf<ERF>(sub_ref(s_n, mu_bar_n))));
-}
+// (transmittance_term: vrt_kernels_common.hpp)
 template <int EXP, int ERF>
 __global__ void transmittance_kernel(SceneTables S, float ox, float oy, float oz, float nx, float ny, float nz,
                                      const float *s_in, size_t ns, float *T_out)

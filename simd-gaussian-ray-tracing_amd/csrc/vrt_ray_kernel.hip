@@ -11,34 +11,9 @@
 // the same ascending scene order: the sphere tests only ever drop what the member test drops, so no bit of a result moves.
 // Compiled like the block kernel with -mllvm -amdgpu-sched-strategy=max-ilp (see the note at the top of vrt_block_kernel.hip):
 // the pair loops are the same independent erf terms.
-#include "vrt_kernels_common.hpp"
+#include "vrt_ray_cull.hpp"
 
 namespace vrtk {
-
-// The chunk's sphere (centre, radius incl. its members' reach: build_chunks_kernel) against the LINE of one ray.  A member
-// is kept by the ray criterion only within its reach of the line, and the distance to a line is 1-Lipschitz in the point,
-// so a line farther than the radius from the centre keeps no member.  The d^2 - t^2 cancellation is guarded on the keeping
-// side, as in chunk_keeps.  Unfused: both kernels must decide alike.
-__device__ __forceinline__ bool ray_chunk_keeps(float4 ch, const LaneRay &ray)
-{
-    const float ax = sub_ref(ch.x, ray.ox), ay = sub_ref(ch.y, ray.oy), az = sub_ref(ch.z, ray.oz);
-    const float d2 = dot3_ref(ax, ay, az, ax, ay, az);
-    const float t = dot3_ref(ax, ay, az, ray.nx, ray.ny, ray.nz);
-    const float dperp = __builtin_sqrtf(fmaxf(0.f, sub_ref(sub_ref(d2, mul_ref(t, t)), mul_ref(8e-6f, d2))));
-    return !(mul_ref(dperp, 0.9999f) > ch.w);
-}
-// x = (|oc|^2 - mubar^2) / (2 sigma^2) of one ray and one Gaussian in the reference's order (ray_gaussian<false>); kept iff !(x > cull_x)
-__device__ __forceinline__ bool ray_member_keeps(float4 ms, float4 bq, const LaneRay &ray)
-{
-    const float cx = ms.x - ray.ox, cy = ms.y - ray.oy, cz = ms.z - ray.oz;
-    const float mubar = dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz);
-    const float x = mul_ref(sub_ref(dot3_ref(cx, cy, cz, cx, cy, cz), mul_ref(mubar, mubar)), bq.y);
-    return !(x > bq.w);
-}
-
-// Uniform (scalar) 4-byte load, as uload
-typedef const uint32_t __attribute__((address_space(4))) *cu32ptr;
-__device__ __forceinline__ uint32_t uload_u32(const uint32_t *base, uint32_t idx) { return ((cu32ptr)(const void *)base)[idx]; }
 
 // Group spheres of the Morton index: lane = leaf sphere of the group, one wave per group.  Centre = mid-point of the box of the leaf
 // centres, radius = the farthest leaf centre plus that leaf's radius, widened by build_chunks_kernel's margins: a line farther from the
@@ -68,14 +43,6 @@ void launch_build_ray_groups(uint32_t nleaves, const float4 *leaves, float4 *gro
     if (ngr) hipLaunchKernelGGL(build_ray_groups_kernel, dim3((ngr + 3u) / 4u), dim3(256), 0, st, nleaves, leaves, groups);
 }
 
-__device__ __forceinline__ LaneRay load_ray(const RayArgs &P, uint64_t r)
-{
-    const uint64_t ro = P.origin_per_ray ? r : 0ull;
-    LaneRay ray;
-    ray.ox = P.origins[3 * ro]; ray.oy = P.origins[3 * ro + 1]; ray.oz = P.origins[3 * ro + 2];
-    ray.nx = P.dirs[3 * r]; ray.ny = P.dirs[3 * r + 1]; ray.nz = P.dirs[3 * r + 2];
-    return ray;
-}
 __device__ __forceinline__ void store_ray(const RayArgs &P, uint64_t r, float Lr, float Lg, float Lb, float La)
 {
     if (P.image) P.image[r] = pack_pixel(Lr, Lg, Lb, La, P.pack_flags);
@@ -171,87 +138,12 @@ __global__ __launch_bounds__(64) void ray_short_kernel(RayArgs) // read through 
     const bool valid = r < P.nrays; // the grid has no wave without a valid ray
     const LaneRay ray = load_ray(P, valid ? r : P.nrays - 1);
 
-    // ---- cull: chunk spheres per lane, members of the chunks some lane keeps with a wave-uniform index ----
+    // ---- cull (vrt_ray_cull.hpp): chunk spheres per lane, members of the chunks some lane keeps with a wave-uniform index ----
     const uint32_t N = S.n, nch = (N + 63u) / 64u;
-    uint32_t nl = 0, chunks_kept = 0, members = 0;
-    [[maybe_unused]] uint32_t groups_kept = 0, leaf_tests = 0;
-    if constexpr (INDEXED) {
-        // ---- the same cull through the Morton index: group spheres, the leaf spheres of the groups some lane keeps, the members of the
-        // leaves some lane keeps -- all three with a wave-uniform index (scalar loads of consecutive permuted rows).  The leaf spheres
-        // take the place of the chunk spheres (nch of them, 64 consecutive Morton positions each).
-        const uint32_t ngr = (nch + 63u) / 64u;
-        for (uint32_t g = 0; g < ngr; ++g) {
-            const bool kg = valid && ray_chunk_keeps(uload(P.groups, g), ray);
-            if (__ballot(kg) == 0ull) continue;
-            groups_kept += kg ? 1u : 0u;
-            const uint32_t lf0 = g * 64u, lf1 = min(lf0 + 64u, nch);
-            leaf_tests += lf1 - lf0;
-            for (uint32_t lf = lf0; lf < lf1; ++lf) {
-                // a lane files only what its OWN group and leaf tests admit
-                const bool kc = kg && ray_chunk_keeps(uload(P.leaves, lf), ray);
-                if (__ballot(kc) == 0ull) continue;
-                chunks_kept += kc ? 1u : 0u;
-                const uint32_t first = lf * 64u, last = min(first + 64u, N);
-                members += last - first;
-#pragma unroll 2
-                for (uint32_t pos = first; pos < last; ++pos) {
-                    const bool km = ray_member_keeps(uload(P.mu_sig_m, pos), uload(P.gB_m, pos), ray);
-                    if (kc && km) {
-                        if (nl < (uint32_t)RAY_PL) {
-                            // entries arrive in Morton order: filed at their place in ascending SCENE order, the order the shading sums in
-                            const uint32_t idx = uload_u32(P.perm, pos);
-                            uint32_t k = nl;
-                            while (k > 0u) {
-                                const uint32_t prev = s_list[(k - 1u) * 64u + lane];
-                                if (prev < idx) break;
-                                s_list[k * 64u + lane] = prev;
-                                --k;
-                            }
-                            s_list[k * 64u + lane] = idx;
-                        }
-                        ++nl; // the count runs on: such a ray's list is not used
-                    }
-                }
-            }
-        }
-    } else
-    for (uint32_t c = 0; c < nch; ++c) {
-        const bool kc = valid && ray_chunk_keeps(uload(P.chunks, c), ray);
-        if (__ballot(kc) == 0ull) continue;
-        chunks_kept += kc ? 1u : 0u;
-        const uint32_t first = c * 64u, last = min(first + 64u, N);
-        members += last - first;
-#pragma unroll 4
-        for (uint32_t idx = first; idx < last; ++idx) {
-            // a lane files only what its OWN chunk test admits: its list does not depend on its wave-mates
-            const bool km = ray_member_keeps(uload(S.mu_sig, idx), uload(S.gB, idx), ray);
-            if (kc && km) {
-                if (nl < (uint32_t)RAY_PL) s_list[nl * 64u + lane] = idx; // ascending; the count runs on
-                ++nl;
-            }
-        }
-    }
+    RayCullCounts cnt;
+    uint32_t nl = ray_short_cull<INDEXED>(&P, &S, N, nch, s_list, lane, valid, ray, cnt);
     const bool is_long = nl > (uint32_t)RAY_PL;
-    if (is_long) { // to the one-wave-per-ray kernel behind this one
-        const uint32_t pos = atomicAdd(&P.counters[0], 1u);
-        if (pos < P.queue_cap) P.queue[pos] = (uint32_t)r;
-    }
-    if (P.stats && valid) {
-        atomicAdd(&P.stats[0], 1ull);
-        atomicAdd(&P.stats[is_long ? 2 : 1], 1ull);
-        if (!is_long) { atomicAdd(&P.stats[3], (unsigned long long)nl); atomicAdd(&P.stats[4], (unsigned long long)nl * nl); }
-        if constexpr (INDEXED) {
-            atomicAdd(&P.index_stats[0], (unsigned long long)((nch + 63u) / 64u));
-            atomicAdd(&P.index_stats[1], (unsigned long long)groups_kept);
-            atomicAdd(&P.index_stats[2], (unsigned long long)leaf_tests);
-            atomicAdd(&P.index_stats[3], (unsigned long long)chunks_kept);
-            atomicAdd(&P.index_stats[4], (unsigned long long)members);
-        } else {
-            atomicAdd(&P.stats[5], (unsigned long long)nch);
-            atomicAdd(&P.stats[6], (unsigned long long)chunks_kept);
-            atomicAdd(&P.stats[7], (unsigned long long)members);
-        }
-    }
+    ray_short_file<INDEXED>(&P, nch, r, valid, is_long, nl, cnt); // to the one-wave-per-ray kernel behind this one; statistics
 
     // ---- shade: every lane walks its own list; the loops run to the longest list of the wave's short rays ----
     if (is_long) nl = 0;
@@ -266,19 +158,6 @@ __global__ __launch_bounds__(64) void ray_short_kernel(RayArgs) // read through 
         else ray_shade_chunk<EXP, ERF, 1>(S, s_list, nl, nmax, lane, ray, i0, Lr, Lg, Lb, La);
     }
     if (valid && !is_long) store_ray(P, r, Lr, Lg, Lb, La);
-}
-
-// sum over the 64 lanes of a full wave in a fixed order, on the DPP path (wave_inclusive_sum's steps on floats; zeros are shifted in)
-#define VRT_DPP_ZERO(v, ctrl, rows, bound) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, rows, 0xf, bound))
-__device__ __forceinline__ float wave_sum(float v)
-{
-    v = add_ref(v, VRT_DPP_ZERO(v, 0x111, 0xf, true));  // row_shr:1
-    v = add_ref(v, VRT_DPP_ZERO(v, 0x112, 0xf, true));  // row_shr:2
-    v = add_ref(v, VRT_DPP_ZERO(v, 0x114, 0xf, true));  // row_shr:4
-    v = add_ref(v, VRT_DPP_ZERO(v, 0x118, 0xf, true));  // row_shr:8
-    v = add_ref(v, VRT_DPP_ZERO(v, 0x142, 0xa, false)); // row_bcast:15 into rows 1 and 3
-    v = add_ref(v, VRT_DPP_ZERO(v, 0x143, 0xc, false)); // row_bcast:31 into rows 2 and 3
-    return lane_value(v, 63);
 }
 
 // One wave per long ray, lane = emitter.  The ray is wave-uniform: its survivors are compacted in index order (ballot / mbcnt, as the
@@ -302,10 +181,7 @@ __global__ __launch_bounds__(64) void ray_long_kernel(RayArgs)
     constexpr int EC = 2;
 
     while (true) {
-        // Every lane executes the atomic (lane 0 adds 1, the others 0: one wave-level atomic after the compiler's atomic optimizer).
-        // With `if (lane == 0) k = atomicAdd(..)` the compiler threaded lane 0's store at the end of the loop body into this claim and
-        // left the other 63 lanes in a loop of their own, reading k = 0 for ever: a claim must not sit behind a branch on the lane.
-        const uint32_t k = __builtin_amdgcn_readfirstlane(atomicAdd(&P.counters[1], lane == 0 ? 1u : 0u));
+        const uint32_t k = ray_long_claim(&P, lane); // every lane executes the atomic: see there
         if (k >= n_long) break;
         const uint64_t r = P.queue[k];
         if (r >= P.nrays) continue;
@@ -313,64 +189,7 @@ __global__ __launch_bounds__(64) void ray_long_kernel(RayArgs)
 
         // ---- cull: 64 chunk spheres at a time (lane = chunk), then the members of the kept ones (lane = Gaussian) ----
         __syncthreads(); // the previous ray's list reads are done
-        uint32_t n = 0;
-        if constexpr (INDEXED) {
-            const uint32_t ngr = (nch + 63u) / 64u, nwords = (N + 31u) / 32u;
-            uint32_t *bm = P.bitmap + (size_t)blockIdx.x * nwords;
-            for (uint32_t g0 = 0; g0 < ngr; g0 += 64u) {
-                const uint32_t g = g0 + lane;
-                unsigned long long gmask = __ballot(g < ngr && ray_chunk_keeps(P.groups[min(g, ngr - 1u)], ray));
-                while (gmask) {
-                    const uint32_t lf0 = (g0 + (uint32_t)__builtin_ctzll(gmask)) * 64u, lf = lf0 + lane;
-                    gmask &= gmask - 1ull;
-                    unsigned long long cmask = __ballot(lf < nch && ray_chunk_keeps(P.leaves[min(lf, nch - 1u)], ray));
-                    while (cmask) {
-                        const uint32_t pos = (lf0 + (uint32_t)__builtin_ctzll(cmask)) * 64u + lane;
-                        cmask &= cmask - 1ull;
-                        const uint32_t pc = min(pos, N - 1u);
-                        if (pos < N && ray_member_keeps(P.mu_sig_m[pc], P.gB_m[pc], ray)) {
-                            const uint32_t idx = P.perm[pc];
-                            if (idx < N) atomicOr(&bm[idx >> 5], 1u << (idx & 31u)); // lanes may share a word
-                        }
-                    }
-                }
-            }
-            __threadfence(); // the bits are in memory before they are taken out again
-            // lane = word: take the word and leave zero behind (an atomic: the value in memory, whatever this CU's cache holds of the
-            // last ray), then every lane files its bits from the wave's running count on -- ascending scene index
-            for (uint32_t w0 = 0; w0 < nwords; w0 += 64u) {
-                const uint32_t w = w0 + lane;
-                uint32_t bits = w < nwords ? atomicExch(&bm[w], 0u) : 0u;
-                const uint32_t cnt = (uint32_t)__popc(bits), incl = wave_inclusive_sum(cnt);
-                uint32_t pos = n + incl - cnt;
-                while (bits) {
-                    const uint32_t idx = w * 32u + (uint32_t)__builtin_ctz(bits);
-                    bits &= bits - 1u;
-                    if (pos < (uint32_t)RAY_LCAP) s_list[pos] = idx;
-                    else if (pos < N) slot[pos] = idx;
-                    ++pos;
-                }
-                n += lane_value_u32(incl, 63u);
-            }
-        } else
-        for (uint32_t c0 = 0; c0 < nch; c0 += 64u) {
-            const uint32_t c = c0 + lane;
-            unsigned long long cmask = __ballot(c < nch && ray_chunk_keeps(P.chunks[min(c, nch - 1u)], ray));
-            while (cmask) {
-                const uint32_t idx = (c0 + (uint32_t)__builtin_ctzll(cmask)) * 64u + lane;
-                cmask &= cmask - 1ull;
-                const uint32_t ic = min(idx, N - 1u);
-                const bool keep = idx < N && ray_member_keeps(S.mu_sig[ic], S.gB[ic], ray);
-                const unsigned long long mask = __ballot(keep);
-                const uint32_t pos = n + lane_rank(mask);
-                if (keep) {
-                    if (pos < (uint32_t)RAY_LCAP) s_list[pos] = idx;
-                    else if (pos < N) slot[pos] = idx;
-                }
-                n += (uint32_t)__popcll(mask);
-            }
-        }
-        n = min(n, N);
+        const uint32_t n = ray_long_cull<INDEXED>(&P, &S, N, nch, (lds_u32 *)s_list, slot, lane, ray);
         __syncthreads(); // list and scratch writes of this wave are visible to it
         if (P.stats && lane == 0 && n > (uint32_t)RAY_LCAP) atomicAdd(&P.stats[8], 1ull);
         auto entry = [&](uint32_t p) -> uint32_t { return p < (uint32_t)RAY_LCAP ? s_list[p] : slot[p]; };

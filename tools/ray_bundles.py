@@ -17,6 +17,10 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
   Every bundle is timed with the Morton index (vrt_hip_set_ray_index) off and on in the same run -- two contexts on the same scene,
   their windows alternating -- with ray_stats / ray_index_stats of one bundle each, and the two results compared bit for bit.  On (b)
   the indexed call has to be faster than the unindexed one.
+  (t) transmittance bundles (vrt_hip_transmittance_bundle): 4096 rays aimed at Gaussians of `-g 64`, host pointers, with ns = 1 and
+      ns = 16 samples per ray, index off and on, and vrt_hip_transmittance_rays (the full sum, one sample per ray) on the same rays in
+      the same run; host clock around the calls, as in (a).  The ns = 1 bundle has to be faster than the full-sum call.
+      `--transmittance-only` runs (t) alone and prints its JSON line without touching the files.
 """
 import argparse
 import json
@@ -94,6 +98,71 @@ def part_a(g, repeats_full=3, repeats_rays=50):
            "indexed_ms": spread(indexed_ms), "off_over_on": round(float(np.median(rays_ms) / np.median(indexed_ms)), 2),
            "identical": bool((indexed == rays).all()), "ray_index_stats": ist}
     return out
+
+
+def aimed_rays(g, count=4096, seed=11, origin=(0.0, 0.0, -4.0)):
+    """ray k aims at the centre of a Gaussian with a jitter of about sigma (tests/ray_bundle_scenes.coherent_rays)"""
+    rng = np.random.default_rng(seed)
+    pick = rng.choice(len(g), size=count, replace=count > len(g))
+    target = g["mu"][pick, :3].astype(np.float64) + rng.normal(size=(count, 3)) * g["sigma"][pick, None]
+    o = np.asarray(origin, f32)
+    d = target - o.astype(np.float64)
+    return o, np.ascontiguousarray((d / np.linalg.norm(d, axis=1, keepdims=True)).astype(f32))
+
+
+def part_t(g, repeats=20, repeats_full=5):
+    r = pkg.Renderer(0)
+    r.set_gaussians(g)
+    o, d = aimed_rays(g)
+    oo = np.ascontiguousarray(np.tile(o, (len(d), 1)))
+    s16 = np.linspace(0.5, 8.0, 16).astype(f32)
+    s1 = s16[-1:]
+    s1_rays = np.full(len(d), s1[0], f32)
+    ms_, T = {}, {}
+    for on in (0, 1):
+        r.set_ray_index(on)
+        for label, s in (("ns1", s1), ("ns16", s16)):
+            key = f"{label}_{'on' if on else 'off'}"
+            for k in range(3 + repeats):                # the first calls build the index and warm up
+                t0 = time.perf_counter()
+                T[key] = r.transmittance_bundle(o, d, s)
+                if k >= 3:
+                    ms_.setdefault(key, []).append((time.perf_counter() - t0) * 1e3)
+            if on == 0 and label == "ns1":                # the full sum in the same run, behind the bundle it is compared with
+                for k in range(1 + repeats_full):
+                    t0 = time.perf_counter()
+                    full = r.transmittance_rays(oo, d, s1_rays)
+                    if k >= 1:
+                        ms_.setdefault("full_sum", []).append((time.perf_counter() - t0) * 1e3)
+    r.set_ray_index(0)
+    r.enable_stats(True)
+    r.transmittance_bundle(o, d, s1)
+    st = r.ray_stats()
+    r.close()
+    return {"rays": len(d), "gaussians": len(g), "ms": {k: spread(v) for k, v in ms_.items()},
+            "full_over_ns1": round(float(np.median(ms_["full_sum"]) / np.median(ms_["ns1_off"])), 1),
+            "max_abs_difference_to_full_sum": float(np.abs(T["ns1_off"][:, 0].astype(np.float64) - full).max()),
+            "identical_index_on_off": bool((T["ns1_on"] == T["ns1_off"]).all() and (T["ns16_on"] == T["ns16_off"]).all()),
+            "T_min": float(T["ns16_off"].min()), "ray_stats": st}
+
+
+def check_t(t):
+    assert t["ms"]["ns1_off"]["median"] < t["ms"]["full_sum"]["median"], "the ns = 1 transmittance bundle has to be faster than the full-sum call on the same rays"
+
+
+def markdown_t(t):
+    m = t["ms"]
+    return f"""
+(t) transmittance bundles: {t['rays']} rays aimed at Gaussians of `-g 64` (N = {t['gaussians']}), host pointers, call returns after completion; ms per call, median (min .. max):
+
+| call | index off | index on |
+|---|---|---|
+| `vrt_hip_transmittance_bundle`, ns = 1 | {ms(m['ns1_off'])} | {ms(m['ns1_on'])} |
+| `vrt_hip_transmittance_bundle`, ns = 16 | {ms(m['ns16_off'])} | {ms(m['ns16_on'])} |
+| `vrt_hip_transmittance_rays` (full sum, one sample per ray) | {ms(m['full_sum'])} | |
+
+Full sum over the ns = 1 bundle: {t['full_over_ns1']}; largest difference of a T {t['max_abs_difference_to_full_sum']:.2e}; index on = off bit for bit: {t['identical_index_on_off']}.
+"""
 
 
 def windows(fns, calls, repeats, warm=3):
@@ -284,20 +353,27 @@ def main():
     ap.add_argument("--width", type=int, default=2048)
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--transmittance-only", action="store_true")
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
+    if a.transmittance_only:
+        t = part_t(g)
+        print(json.dumps({"t": t}))
+        check_t(t)
+        return
     res = {"what": "ray bundles against the full sum and against the camera path; see tools/ray_bundles.py",
-           "a": part_a(g), "bc": parts_bc(g, a.width, 16, a.calls, a.repeats), "def": parts_def(g, a.calls, a.repeats)}
+           "a": part_a(g), "bc": parts_bc(g, a.width, 16, a.calls, a.repeats), "def": parts_def(g, a.calls, a.repeats), "t": part_t(g)}
     line = json.dumps(res)
     print(line)
     os.makedirs(a.out_dir, exist_ok=True)
     with open(os.path.join(a.out_dir, "ray_bundles.json"), "w") as f:
         f.write(line + "\n")
     with open(os.path.join(a.out_dir, "ray_bundles.md"), "w") as f:
-        f.write(markdown(res))
+        f.write(markdown(res) + markdown_t(res["t"]))
     assert res["a"]["speedup"] >= 100.0, "the ray bundle call has to be at least 100 times faster than the full sum on the same rays"
     b = res["bc"]["one_origin"]
     assert b["on_ms"]["median"] < b["off_ms"]["median"], "the indexed call of the -g 64 pinhole bundle has to be faster than the unindexed call"
+    check_t(res["t"])
 
 
 if __name__ == "__main__":
