@@ -481,6 +481,36 @@ void transmittance_bundle_device(const f32 *d_origins, bool origin_per_ray, cons
     d.check(vrt_hip_transmittance_bundle_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_s, ns, s_per_ray ? 1 : 0, d_T, hip_stream),
             "vrt_hip_transmittance_bundle_device");
 }
+// Depth bundles: the distance along ANY number of rays at which their transmittance falls to nt levels each, in ONE call under the same
+// per-ray cull (vrt_hip_depth_bundle in include/vrt_hip.h): depth_out[r * nt + k] is 0 where ray r starts at or below the level, +inf
+// where it never gets there, and otherwise the upper end of a bracket around the crossing no wider than max(ulp, s_end * 2^-24) --
+// transmittance_bundle at that depth returns a T <= tau.  tau: nt levels shared by all rays (tau_per_ray = false) or nrays * nt,
+// [r * nt + k].  tau = 0.5 is a median-depth map; a first hit to start shadow rays from is one call (host/first_hit_example.cpp).
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void depth_bundle(const vec4f_t *o, const vec4f_t *n, size_t nrays, const f32 *tau, size_t nt, bool tau_per_ray, const gaussians_t &gaussians,
+                  f32 *depth_out)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    std::vector<f32> oo(3 * nrays), nn(3 * nrays);
+    for (size_t r = 0; r < nrays; ++r) {
+        oo[3 * r] = o[r].x; oo[3 * r + 1] = o[r].y; oo[3 * r + 2] = o[r].z;
+        nn[3 * r] = n[r].x; nn[3 * r + 1] = n[r].y; nn[3 * r + 2] = n[r].z;
+    }
+    d.check(vrt_hip_depth_bundle(d.ctx, nrays, oo.data(), 1, nn.data(), tau, nt, tau_per_ray ? 1 : 0, depth_out), "vrt_hip_depth_bundle");
+}
+// The same for rays, levels and results that live on the device: enqueued on hip_stream, nothing waits.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void depth_bundle_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const f32 *d_tau, size_t nt, bool tau_per_ray,
+                         const gaussians_t &gaussians, f32 *d_depth, void *hip_stream)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    d.check(vrt_hip_depth_bundle_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_tau, nt, tau_per_ray ? 1 : 0, d_depth, hip_stream),
+            "vrt_hip_depth_bundle_device");
+}
 // Ray bundles cull through the Morton index of the scene from the next call on (vrt_hip_set_ray_index in include/vrt_hip.h: off by
 // default, the same radiance and the same pixels bit for bit either way; the index is made once per scene).
 inline void set_ray_index(bool on)

@@ -363,6 +363,36 @@ int vrt_hip_transmittance_bundle_device(vrt_hip_ctx *ctx, size_t nrays, const fl
                                         void *hip_stream);
 int vrt_hip_transmittance_bundle(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
                                  const float *s, size_t ns, int s_per_ray, float *T_out);       /* host pointers, waits */
+/* -------- depth bundles: the distance along ANY rays at which T falls to a level -- the inverse of the transmittance bundles ----
+ * depth[r * nt + k] = where ray r's transmittance reaches the level tau[k] (tau_per_ray == 0: nt levels shared by all rays) or
+ * tau[r * nt + k] (tau_per_ray != 0): a first-hit distance (tau = 0.5: the median depth), a depth map at any level for compositing,
+ * the free-flight distance of a path tracer ("the s with T(s) = xi").  Any nt >= 1: the kernels loop.
+ * That(r, s) is what vrt_hip_transmittance_bundle returns for ray r at distance s under the same scene and options: the same cull,
+ * the same terms, the same summation order, the selected Exp and Erf -- bit for bit.  s_end(r) = max over the Gaussians the ray
+ * keeps of mubar_j + 6 sqrt(2) sigma_j, at least 0: every Erf is saturated there.  With tau the level:
+ *   tau is NaN                                        NaN
+ *   That(r, 0) <= tau  (every tau >= 1: That(r, 0) = Exp(0))   0
+ *   the ray keeps nothing, or That(r, s_end) > tau    +inf: the ray never gets that dark (every tau <= 0 that That does not reach)
+ *   otherwise                                         the upper end hi of a bracket lo < hi with That(r, hi) <= tau < That(r, lo), both
+ *                                                     ends evaluated by the kernel, narrowed by bisection from [0, s_end] until
+ *                                                     hi - lo <= max(ulp(hi), s_end * 2^-24)
+ * The comparison is made in T with the selected Exp (not in the exponent against ln tau): vrt_hip_transmittance_bundle at s = depth
+ * on the same context returns a T <= tau, exactly.  With magnitudes >= 0 T does not increase along a ray and the crossing is
+ * unique up to that resolution and the rounding of That; with negative magnitudes the result is still such a bracket, around one of
+ * the crossings.  A result is a function of (ray, tau, scene, options) alone, whatever else is in the bundle, however many levels the
+ * call carries and whether the Morton index is on.
+ * Cost: per ray two walks of its list (s_end with That(0), That(s_end)), then one walk per halving -- 23 to 25 -- for every group of
+ * up to 4 levels; the cull is paid once.
+ * origins, origin_per_ray, dirs, the stream rules, the buffers that only grow (nrays, and nrays * nt for tau and depth of the host
+ * form), the shared queue / counters / scratch slots / bitmap and the statistics are the transmittance bundle's: two bundles of one
+ * context are ordered by the stream they share; vrt_hip_get_ray_stats / vrt_hip_get_ray_index_stats report the last bundle of any of
+ * the three kinds, and for the same rays, scene and options every field is what a radiance bundle reports.  nrays == 0 or nt == 0
+ * returns VRT_HIP_OK with nothing launched; NULL origins, dirs, tau or depth with work to do, more than 2^32 - 16 rays, or an
+ * nrays * nt that does not fit: VRT_HIP_ERR_INVALID, nothing enqueued. */
+int vrt_hip_depth_bundle_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                const float *d_tau, size_t nt, int tau_per_ray, float *d_depth, void *hip_stream);
+int vrt_hip_depth_bundle(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                         const float *tau, size_t nt, int tau_per_ray, float *depth_out);           /* host pointers, waits */
 typedef struct {
     uint64_t rays;           /* rays of the bundle                                                                  */
     uint64_t short_rays;     /* shaded lane = ray (list of at most 32)                                              */

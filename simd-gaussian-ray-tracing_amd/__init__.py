@@ -122,6 +122,8 @@ SYMBOLS = {
     "vrt_hip_radiance_rays": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _u32p, C.c_int]),
     "vrt_hip_transmittance_bundle_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int, _vp, _vp]),
     "vrt_hip_transmittance_bundle": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p]),
+    "vrt_hip_depth_bundle_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int, _vp, _vp]),
+    "vrt_hip_depth_bundle": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p]),
     "vrt_hip_get_ray_stats": (C.c_int, [_vp, C.POINTER(RayStats)]),
     "vrt_hip_set_ray_index": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_ray_index_stats": (C.c_int, [_vp, C.POINTER(RayIndexStats)]),
@@ -536,6 +538,34 @@ class Renderer:
                                                          d_s or None, int(ns), int(bool(s_per_ray)), d_T or None, stream or None)
         if rc != 0:
             self._chk(rc, "transmittance_bundle_device")
+
+    def depth_bundle(self, origins, dirs, tau, tau_per_ray=None):
+        """vrt_hip_depth_bundle: the distance along each ray at which its transmittance falls to the levels tau -- 0 where it starts at
+        or below a level, +inf where it never gets there (include/vrt_hip.h has the contract).  origins [3] (one for the bundle) or
+        [nrays, 3], dirs [nrays, 3] unit length; tau [nt] (the same levels for every ray) or [nrays, nt] (per ray; tau_per_ray says
+        which when the shape does not).  Returns the depths f32 [nrays, nt]."""
+        origins = np.ascontiguousarray(origins, np.float32)
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        tau = np.ascontiguousarray(tau, np.float32)
+        per_ray = origins.size != 3
+        if per_ray:
+            assert origins.size == dirs.size
+        if tau_per_ray is None:
+            tau_per_ray = tau.ndim == 2
+        nt = tau.size // len(dirs) if tau_per_ray and len(dirs) else tau.size
+        if tau_per_ray:
+            assert tau.size == len(dirs) * nt
+        out = np.zeros((len(dirs), nt), np.float32)
+        self._chk(self._L.vrt_hip_depth_bundle(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(tau), nt, int(bool(tau_per_ray)),
+                                               _fp(out)), "depth_bundle")
+        return out
+
+    def depth_bundle_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_tau, nt, tau_per_ray, d_depth, stream=0):
+        """vrt_hip_depth_bundle_device: device pointers, everything enqueued on `stream`."""
+        rc = self._L.vrt_hip_depth_bundle_device(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None,
+                                                 d_tau or None, int(nt), int(bool(tau_per_ray)), d_depth or None, stream or None)
+        if rc != 0:
+            self._chk(rc, "depth_bundle_device")
 
     def ray_stats(self):
         """Counts of the last bundle (enable_stats first): see vrt_hip_ray_stats in include/vrt_hip.h."""

@@ -1,6 +1,8 @@
-// vrt_hip_rays.cpp -- ray bundles of libvrt_hip.so (vrt_hip_radiance_rays*, vrt_hip_transmittance_bundle*): radiance of caller-given
-// rays, or transmittance at sample distances along them, culled per ray (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip).  The scene tables and the chunk spheres are the frame pipeline's; the long-ray queue, its counters and the
-// long kernel's scratch slots belong to the context and only grow.
+// vrt_hip_rays.cpp -- ray bundles of libvrt_hip.so (vrt_hip_radiance_rays*, vrt_hip_transmittance_bundle*, vrt_hip_depth_bundle*):
+// radiance of caller-given rays, transmittance at sample distances along them, or the distance at which their transmittance falls to
+// given levels, culled per ray (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip).  The scene tables and the
+// chunk spheres are the frame pipeline's; the long-ray queue, its counters and the long kernel's scratch slots belong to the context
+// and only grow.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -61,7 +63,7 @@ std::vector<uint32_t> morton_order(const std::vector<float4> &ms)
     return perm;
 }
 
-// What a bundle of either kind (radiance, transmittance) enqueues before its two kernels: the tables brought up to date, the Morton
+// What a bundle of any kind (radiance, transmittance, depth) enqueues before its two kernels: the tables brought up to date, the Morton
 // index when it is on and out of date, the queue / counters / scratch / statistics buffers at their size for nrays, the counters (and
 // statistics) cleared on the stream, and the kernels' arguments but for the outputs, which the caller fills in.
 struct Bundle {
@@ -244,6 +246,50 @@ int vrt_hip_transmittance_bundle(vrt_hip_ctx *c, size_t nrays, const float *orig
                                                  c->stream);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(T_out, c->rays_T.p, nrays * ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_depth_bundle_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs, const float *d_tau,
+                                size_t nt, int tau_per_ray, float *d_depth, void *hip_stream)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    if (nrays == 0 || nt == 0) return VRT_HIP_OK;
+    if (!d_origins || !d_dirs) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: NULL origins or directions");
+    if (!d_tau || !d_depth) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: NULL levels or result");
+    if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: more than 2^32 - 16 rays in one bundle");
+    if (nt > (SIZE_MAX / sizeof(float)) / nrays) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: nrays * nt does not fit");
+    hipStream_t st = (hipStream_t)hip_stream;
+    Bundle b;
+    { int rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b); if (rc) return rc; }
+    b.a.tau = d_tau; b.a.nt = nt; b.a.tau_per_ray = tau_per_ray ? 1 : 0; b.a.depth = d_depth;
+    launch_ray_depth_bundle(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
+    HIPCHK(c, hipGetLastError());
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_depth_bundle(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *tau, size_t nt,
+                         int tau_per_ray, float *depth_out)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    if (nrays == 0 || nt == 0) return VRT_HIP_OK;
+    if (!origins || !dirs) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: NULL origins or directions");
+    if (!tau || !depth_out) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: NULL levels or result");
+    if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: more than 2^32 - 16 rays in one bundle");
+    if (nt > (SIZE_MAX / sizeof(float)) / nrays) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: nrays * nt does not fit");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // the staging buffers may still be read by an earlier bundle
+    const size_t no = (origin_per_ray ? nrays : 1) * 3, nlevels = (tau_per_ray ? nrays : 1) * nt;
+    HIPCHK(c, c->rays_in[0].reserve(no));
+    HIPCHK(c, c->rays_in[1].reserve(nrays * 3));
+    HIPCHK(c, c->rays_s.reserve(nlevels));
+    HIPCHK(c, c->rays_T.reserve(nrays * nt));
+    HIPCHK(c, hipMemcpyAsync(c->rays_in[0].p, origins, no * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rays_in[1].p, dirs, nrays * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rays_s.p, tau, nlevels * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    int rc = vrt_hip_depth_bundle_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->rays_s.p, nt, tau_per_ray, c->rays_T.p, c->stream);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(depth_out, c->rays_T.p, nrays * nt * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return VRT_HIP_OK;
 }

@@ -1,7 +1,7 @@
-// vrt_ray_cull.hpp -- the per-ray cull of the ray bundles, shared by vrt_ray_kernel.hip (radiance) and vrt_ray_trans_kernel.hip
-// (transmittance): the sphere and member tests, the lane = ray cull into per-lane lists in LDS, the one-wave-per-ray re-cull into
+// vrt_ray_cull.hpp -- the per-ray cull of the ray bundles, shared by vrt_ray_kernel.hip (radiance), vrt_ray_trans_kernel.hip
+// (transmittance) and vrt_ray_depth_kernel.hip (depth): the sphere and member tests, the lane = ray cull into per-lane lists in LDS, the one-wave-per-ray re-cull into
 // LDS + scratch slot, both with and without the Morton index, the queue of the long rays and the statistics words.  One text for
-// both translation units: the same rays keep the same Gaussians, go to the same kernel and count the same statistics.
+// all three translation units: the same rays keep the same Gaussians, go to the same kernel and count the same statistics.
 #pragma once
 #include "vrt_kernels_common.hpp"
 
@@ -62,7 +62,7 @@ __device__ __forceinline__ float wave_sum(float v)
 // that the whole structure may be read ahead of the branches that guard a read, and it then lifts the argument loads out of the loops --
 // other machine code than the kernels had with this text in their bodies, with more registers live (one instantiation lost a wave per SIMD).
 // ---------------------------------------------------------------------------------------------
-// lane = ray (ray_short_kernel, ray_short_trans_kernel)
+// lane = ray (ray_short_kernel, ray_short_trans_kernel, ray_short_depth_kernel)
 // ---------------------------------------------------------------------------------------------
 // What the cull of one lane counted for the statistics
 struct RayCullCounts { uint32_t chunks_kept, members, groups_kept, leaf_tests; };
@@ -166,7 +166,7 @@ __device__ __forceinline__ void ray_short_file(const RayArgs *Pp, uint32_t nch, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// one wave per ray (ray_long_kernel, ray_long_trans_kernel)
+// one wave per ray (ray_long_kernel, ray_long_trans_kernel, ray_long_depth_kernel)
 // ---------------------------------------------------------------------------------------------
 // The next entry of the long-ray queue for this wave.
 // Every lane executes the atomic (lane 0 adds 1, the others 0: one wave-level atomic after the compiler's atomic optimizer).

@@ -9,37 +9,9 @@
 // A dropped Gaussian has sigma mag exp(-x) < eps_eff and its term is at most 2 / sqrt(2 pi) times that: the exponent moves by less than
 // 0.8 cull_eps min(N, 4096).
 // Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
-#include "vrt_ray_cull.hpp"
+#include "vrt_ray_trans.hpp" // trans_entry, trans_sample, RAY_SG, long_list_entry: shared with vrt_ray_depth_kernel.hip
 
 namespace vrtk {
-
-// samples a lane (short kernel) or a wave (long kernel) carries through one walk of a list
-constexpr int RAY_SG = 4;
-
-// transmittance_term (vrt_kernels_common.hpp) cut in two: what depends on (ray, Gaussian) alone, and what a sample adds to it.  The same
-// operations on the same operands in the same order -- nothing re-associated, nothing fused, exact divides.
-struct TransEntry { float w /* sigma cbar / sqrt(2 pi) */, erf0 /* Erf(-mubar_n) */, mu_bar_n, sqrt_2_sig; };
-template <int EXP, int ERF>
-__device__ __forceinline__ TransEntry trans_entry(float4 g /* mu, sigma */, float mag, const LaneRay &ray)
-{
-    const float cx = sub_ref(g.x, ray.ox), cy = sub_ref(g.y, ray.oy), cz = sub_ref(g.z, ray.oz);
-    const float mu_bar = dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz);
-    const float oc_sq = dot3_ref(cx, cy, cz, cx, cy, cz);
-    const float inv_2_sigma2 = 1.f / mul_ref(mul_ref(2.f, g.w), g.w);
-    const float c_bar = mul_ref(mag, vexp<EXP>(-mul_ref(sub_ref(oc_sq, mul_ref(mu_bar, mu_bar)), inv_2_sigma2)));
-    TransEntry t;
-    t.sqrt_2_sig = mul_ref(SQRT_2, g.w);
-    t.mu_bar_n = mu_bar / t.sqrt_2_sig;
-    t.w = mul_ref(mul_ref(g.w, c_bar), INV_SQRT_2_PI);
-    t.erf0 = verf<ERF>(-t.mu_bar_n);
-    return t;
-}
-template <int ERF>
-__device__ __forceinline__ float trans_sample(const TransEntry &t, float s)
-{
-    const float s_n = s / t.sqrt_2_sig;
-    return mul_ref(t.w, sub_ref(t.erf0, verf<ERF>(sub_ref(s_n, t.mu_bar_n))));
-}
 
 template <int EXP, int ERF, bool INDEXED>
 __global__ __launch_bounds__(64) void ray_short_trans_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
@@ -99,12 +71,6 @@ __global__ __launch_bounds__(64) void ray_short_trans_kernel(RayArgs) // read th
         for (int g = 0; g < RAY_SG; ++g)
             if (writes && k0 + g < ns) Tp[k0 + g] = vexp<EXP>(acc[g]);
     }
-}
-
-// entry p of a long ray's list: the first RAY_LCAP in LDS, the rest in the workgroup's scratch slot
-__device__ __forceinline__ uint32_t long_list_entry(const uint32_t *s_list, const uint32_t *slot, uint32_t p)
-{
-    return p < (uint32_t)RAY_LCAP ? s_list[p] : slot[p];
 }
 
 // One wave per long ray.  Claim, re-cull and list are the radiance long kernel's (vrt_ray_cull.hpp).  Lane l takes entries l, l + 64, ...

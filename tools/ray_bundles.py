@@ -21,6 +21,13 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
       ns = 16 samples per ray, index off and on, and vrt_hip_transmittance_rays (the full sum, one sample per ray) on the same rays in
       the same run; host clock around the calls, as in (a).  The ns = 1 bundle has to be faster than the full-sum call.
       `--transmittance-only` runs (t) alone and prints its JSON line without touching the files.
+  (depth) depth bundles (vrt_hip_depth_bundle_device): the same 4096 aimed rays, device pointers, nt = 1 (tau = 0.99) and nt = 4 levels
+      (0.999, 0.99, 0.98, 0.95: the aimed rays end between T = 0.9 and 0.995), index off and on, against what a caller had before: a
+      bisection of the same resolution around vrt_hip_transmittance_bundle_device with the brackets kept on the device -- T at a
+      scene bound (8.0, behind everything from these origins) for the misses, then 24 halvings of [0, 8], every step one bundle
+      call (a cull and two kernels) and three elementwise updates; no host round trip.  Stream events around each, alternating, after
+      warm-up.  The depth bundle has to be faster in every row.  `--depth-only` runs this part alone; it prints its JSON line and
+      writes ray_depth.json and ray_depth.md (and nothing else) to --out-dir.  (The letter (d) was taken.)
 """
 import argparse
 import json
@@ -163,6 +170,104 @@ def markdown_t(t):
 
 Full sum over the ns = 1 bundle: {t['full_over_ns1']}; largest difference of a T {t['max_abs_difference_to_full_sum']:.2e}; index on = off bit for bit: {t['identical_index_on_off']}.
 """
+
+
+DEPTH_BOUND, DEPTH_HALVINGS = 8.0, 24     # the caller-side bisection: bracket [0, 8] down to 8 * 2^-24, the depth bundle's s_end 2^-24 with s_end ~ 5.4
+
+
+def part_depth(g, repeats=7, calls=2):
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    o, d = aimed_rays(g)
+    nrays = len(d)
+    t_o, t_d = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
+    ctx = [pkg.Renderer(0), pkg.Renderer(0)]
+    for on, r in enumerate(ctx):
+        r.set_gaussians(g)
+        r.set_ray_index(on)
+    rows, out = {}, {}
+    for label, levels in (("nt1", [0.99]), ("nt4", [0.999, 0.99, 0.98, 0.95])):
+        nt = len(levels)
+        tau = torch.tensor(levels, dtype=torch.float32, device="cuda")
+        tau_rows = tau.expand(nrays, nt)
+        depth = [torch.zeros((nrays, nt), dtype=torch.float32, device="cuda") for _ in ctx]
+        base = [torch.zeros((nrays, nt), dtype=torch.float32, device="cuda") for _ in ctx]
+        mid, T = torch.zeros((nrays, nt), dtype=torch.float32, device="cuda"), torch.zeros((nrays, nt), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+
+        def bundle(k):
+            ctx[k].depth_bundle_device(nrays, t_o.data_ptr(), 0, t_d.data_ptr(), tau.data_ptr(), nt, 0, depth[k].data_ptr(), st)
+
+        def bisect(k):
+            mid.fill_(DEPTH_BOUND)
+            ctx[k].transmittance_bundle_device(nrays, t_o.data_ptr(), 0, t_d.data_ptr(), mid.data_ptr(), nt, 1, T.data_ptr(), st)
+            miss = T > tau_rows
+            lo, hi = torch.zeros_like(mid), torch.full_like(mid, DEPTH_BOUND)
+            for _ in range(DEPTH_HALVINGS):
+                torch.add(lo, hi - lo, alpha=0.5, out=mid)
+                ctx[k].transmittance_bundle_device(nrays, t_o.data_ptr(), 0, t_d.data_ptr(), mid.data_ptr(), nt, 1, T.data_ptr(), st)
+                below = T <= tau_rows
+                hi = torch.where(below, mid, hi)
+                lo = torch.where(below, lo, mid)
+            base[k].copy_(torch.where(miss, torch.full_like(hi, float("inf")), hi))
+
+        t = windows([lambda: bundle(0), lambda: bisect(0), lambda: bundle(1), lambda: bisect(1)], calls, repeats, warm=2)
+        torch.cuda.synchronize()
+        dv, bv = [x.cpu().numpy() for x in depth], [x.cpu().numpy() for x in base]
+        fin = np.isfinite(dv[0]) & np.isfinite(bv[0])
+        rows[label] = {"levels": levels, "bundle_off_ms": t[0], "bisection_off_ms": t[1], "bundle_on_ms": t[2], "bisection_on_ms": t[3],
+                       "bisection_over_bundle_off": round(t[1]["median"] / t[0]["median"], 1),
+                       "bisection_over_bundle_on": round(t[3]["median"] / t[2]["median"], 1),
+                       "finite_results": int(np.isfinite(dv[0]).sum()), "of": int(dv[0].size),
+                       "same_misses_as_bisection": bool((np.isfinite(dv[0]) == np.isfinite(bv[0])).all()),
+                       "max_abs_difference_to_bisection": float(np.abs(dv[0][fin] - bv[0][fin]).max()) if fin.any() else 0.0,
+                       "identical_index_on_off": bool((dv[0].view(np.uint32) == dv[1].view(np.uint32)).all())}
+        out[label] = dv[0]
+    ctx[0].enable_stats(True)
+    tau1 = torch.tensor([0.99], dtype=torch.float32, device="cuda")
+    one = torch.zeros((nrays, 1), dtype=torch.float32, device="cuda")
+    ctx[0].depth_bundle_device(nrays, t_o.data_ptr(), 0, t_d.data_ptr(), tau1.data_ptr(), 1, 0, one.data_ptr(), st)
+    stats = ctx[0].ray_stats()
+    torch.cuda.synchronize()
+    for r in ctx:
+        r.close()
+    return {"rays": nrays, "gaussians": len(g), "bisection": {"bound": DEPTH_BOUND, "halvings": DEPTH_HALVINGS, "bundle_calls": DEPTH_HALVINGS + 1},
+            "rows": rows, "nt1_is_column_of_nt4": bool((out["nt1"][:, 0].view(np.uint32) == out["nt4"][:, 1].view(np.uint32)).all()), "ray_stats": stats}
+
+
+def check_depth(z):
+    for label, r in z["rows"].items():
+        assert r["bundle_off_ms"]["median"] < r["bisection_off_ms"]["median"] and r["bundle_on_ms"]["median"] < r["bisection_on_ms"]["median"], \
+            f"{label}: the depth bundle has to be faster than the caller-side bisection through transmittance_bundle_device"
+
+
+def markdown_depth(z):
+    lines = [f"""# Depth bundles (tools/ray_bundles.py --depth-only)
+
+{z['rays']} rays aimed at Gaussians of `-g 64` (N = {z['gaussians']}), device pointers, stream events around back-to-back calls, the paths alternating; ms per
+call, median (min .. max).  The baseline is what a caller had before: T at s = {z['bisection']['bound']} for the misses, then {z['bisection']['halvings']} halvings of [0, {z['bisection']['bound']}] around
+`vrt_hip_transmittance_bundle_device` ({z['bisection']['bundle_calls']} bundle calls, the brackets updated on the device, no host round trip).
+
+| levels | index | `vrt_hip_depth_bundle_device` | caller-side bisection | bisection / bundle | finite results | same misses | largest difference of a depth |
+|---|---|---|---|---|---|---|---|"""]
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            lines.append(f"| {', '.join(str(v) for v in r['levels'])} | {key} | {ms(r[f'bundle_{key}_ms'])} | {ms(r[f'bisection_{key}_ms'])} | {r[f'bisection_over_bundle_{key}']} | "
+                         f"{r['finite_results']} of {r['of']} | {r['same_misses_as_bisection']} | {r['max_abs_difference_to_bisection']:.2e} |")
+    st = z["ray_stats"]
+    lines.append(f"""
+Index on = off bit for bit: {all(r['identical_index_on_off'] for r in z['rows'].values())}; the nt = 1 result is the 0.99 column of the nt = 4 result bit for bit: {z['nt1_is_column_of_nt4']}.
+Of the {st['rays']} rays {st['short_rays']} are searched lane = ray ({st['lane_entries'] / max(st['short_rays'], 1):.2f} list entries each) and {st['long_rays']} one wave per ray.
+""")
+    return "\n".join(lines)
+
+
+def write_depth(z, out_dir):
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "ray_depth.json"), "w") as f:
+        f.write(json.dumps({"what": "depth bundles against a caller-side bisection through transmittance bundles; see tools/ray_bundles.py", "depth": z}) + "\n")
+    with open(os.path.join(out_dir, "ray_depth.md"), "w") as f:
+        f.write(markdown_depth(z))
 
 
 def windows(fns, calls, repeats, warm=3):
@@ -354,6 +459,7 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--transmittance-only", action="store_true")
+    ap.add_argument("--depth-only", action="store_true")
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
     if a.transmittance_only:
@@ -361,8 +467,14 @@ def main():
         print(json.dumps({"t": t}))
         check_t(t)
         return
+    if a.depth_only:
+        z = part_depth(g)
+        print(json.dumps({"depth": z}))
+        write_depth(z, a.out_dir)
+        check_depth(z)
+        return
     res = {"what": "ray bundles against the full sum and against the camera path; see tools/ray_bundles.py",
-           "a": part_a(g), "bc": parts_bc(g, a.width, 16, a.calls, a.repeats), "def": parts_def(g, a.calls, a.repeats), "t": part_t(g)}
+           "a": part_a(g), "bc": parts_bc(g, a.width, 16, a.calls, a.repeats), "def": parts_def(g, a.calls, a.repeats), "t": part_t(g), "depth": part_depth(g)}
     line = json.dumps(res)
     print(line)
     os.makedirs(a.out_dir, exist_ok=True)
@@ -370,10 +482,12 @@ def main():
         f.write(line + "\n")
     with open(os.path.join(a.out_dir, "ray_bundles.md"), "w") as f:
         f.write(markdown(res) + markdown_t(res["t"]))
+    write_depth(res["depth"], a.out_dir)
     assert res["a"]["speedup"] >= 100.0, "the ray bundle call has to be at least 100 times faster than the full sum on the same rays"
     b = res["bc"]["one_origin"]
     assert b["on_ms"]["median"] < b["off_ms"]["median"], "the indexed call of the -g 64 pinhole bundle has to be faster than the unindexed call"
     check_t(res["t"])
+    check_depth(res["depth"])
 
 
 if __name__ == "__main__":
