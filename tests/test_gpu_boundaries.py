@@ -12,6 +12,10 @@ them for the blocks it shades itself (a block it hands over adds nothing there),
 `lane_entries` / `lane_max_entries` (per-ray list lengths summed over rays / the longest per block summed over blocks) are the
 block kernel's alone.  A block of the block kernel can never hold more than PCAP candidates: its cell holds at most
 dense_threshold = PCAP = 96, so `pos < PCAP` / `cnt <= PCAP` there cannot be crossed from inside and no scene tries to.
+
+PRUNE_PL here is the limit alone: WHICH entries the budgeted prune drops (the budget's edge, ties, every instantiation, the budget's
+factors) and which a lane keeps in the first place are held decision by decision in tests/test_gpu_block.py (scenes and model:
+tests/block_scenes.py).
 """
 import numpy as np
 import pytest
