@@ -46,6 +46,7 @@ EPS_TEST, EPS_DEFAULT = 1e-7, 1e-9
 KAPPA = 6.0
 U24, U11 = 2.0 ** -24, 2.0 ** -11
 ERR_D2, ERR_SLACK, ERR_SUM = 16 * U24, 2e-5, 16 * U24
+ERR_RSQ = 2.0 ** -21      # cosine and sine of a cone built from cone_ray's directions (tests/list_scenes.py)
 KEPT, GONE, AMB, ABSENT = 1, 2, 3, 0
 SQRT_2PI = 2.5066282746310002
 WIDE_SIGMA = 200.0        # the faint Gaussians: x <= 6e-4 over the whole image, e constant to 0.06 %
@@ -87,8 +88,11 @@ def edge_margin(b):
 
 
 # ---- what the kernel sees, in float64 ----
-def geometry(sc, eps):
-    key = ("_geom", eps)
+def geometry(sc, eps, floor=FLOOR_VCL, rays=True, scale_n=True):
+    """floor: exp_floor_x of the frame's Exp kind.  rays=False leaves out the per-ray tables x and err_x (npix x n numbers: the list
+    suite's images are large and its model asks for a ray's x cell by cell).  scale_n=False is the list suite's wrong variant of
+    eps_eff, without the 4096 / N."""
+    key = ("_geom", eps) if (floor, rays, scale_n) == (FLOOR_VCL, True, True) else ("_geom", eps, floor, rays, scale_n)
     if key in sc:
         return sc[key]
     f = np.float32
@@ -102,22 +106,24 @@ def geometry(sc, eps):
     inv2s2 = (f(1.0) / (f(2.0) * s32 * s32)).astype(np.float64)
     q = (s32 * m32).astype(f)
     n = len(g)
-    eps_eff = f(eps) * min(f(1.0), f(4096.0) / f(max(n, 1)))
-    cull_x = np.full(n, FLOOR_VCL)
+    eps_eff = f(eps) * (min(f(1.0), f(4096.0) / f(max(n, 1))) if scale_n else f(1.0))
+    cull_x = np.full(n, float(floor))
     with np.errstate(divide="ignore"):
         raw = np.log((np.abs(q) / eps_eff).astype(f).astype(np.float64)) if eps > 0.0 else np.full(n, np.inf)
     err_cull = 2.0 ** -22 * np.maximum(1.0, np.abs(np.where(np.isfinite(raw), raw, 0.0)))
-    assert not (np.abs(raw - FLOOR_VCL) <= err_cull).any()      # at the floor or below it: no scene leaves that to the logarithm's last bit
+    assert not (np.abs(raw - floor) <= err_cull).any()      # at the floor or below it: no scene leaves that to the logarithm's last bit
     cull_x = np.minimum(cull_x, raw)
     cull_x[q == 0] = -np.inf
-    floor = ~(cull_x < FLOOR_VCL)
-    mubar = d @ oc.T
-    x = np.maximum(w2[None, :] - mubar * mubar, 0.0) * inv2s2[None, :]
-    err_x = (ERR_D2 * w2 * inv2s2)[None, :] + 2.0 ** -22 * x
+    at_floor = ~(cull_x < floor)
+    x = err_x = None
+    if rays:
+        mubar = d @ oc.T
+        x = np.maximum(w2[None, :] - mubar * mubar, 0.0) * inv2s2[None, :]
+        err_x = (ERR_D2 * w2 * inv2s2)[None, :] + 2.0 ** -22 * x
     # tied entries: bit-identical centre, sigma and |sigma mag|
     rows = np.concatenate([g["mu"][:, :3].astype(f).view(np.uint32), s32.view(np.uint32)[:, None], np.abs(q).view(np.uint32)[:, None]], 1)
     _, group = np.unique(rows, axis=0, return_inverse=True)
-    sc[key] = Scene(d=d, oc=oc, w2=w2, inv2s2=inv2s2, q=q, cull_x=cull_x, err_cull=err_cull, floor=floor, x=x, err_x=err_x,
+    sc[key] = Scene(d=d, oc=oc, w2=w2, inv2s2=inv2s2, q=q, cull_x=cull_x, err_cull=err_cull, floor=at_floor, x=x, err_x=err_x,
                     group=np.asarray(group).reshape(-1), eps_eff=float(eps_eff))
     return sc[key]
 
@@ -143,14 +149,17 @@ def _rect_cone(sc, G, x0, y0, x1, y1):
     return _cone(corners, at((x0 + x1 + 1) // 2, (y0 + y1 + 1) // 2), 1e-4)
 
 
-def _cone_keeps(G, cone, thr, idx):
-    """cone_keeps for the candidates idx: (keep, sure)."""
+def _cone_keeps(G, cone, thr, idx, rsq=False):
+    """cone_keeps for the candidates idx: (keep, sure).  rsq: the cone comes from cone_ray's directions (the list kernels' tile and
+    cell cones), whose cosine and sine are off by up to ERR_RSQ each -- tests/list_scenes.py derives the term."""
     axis, cos_t, sin_t = cone
     tc = G.oc[idx] @ axis
     dperp = np.sqrt(np.maximum(0.0, G.w2[idx] - tc * tc))
     dmin = np.maximum(0.0, dperp * cos_t - np.abs(tc) * sin_t)
     v = dmin * dmin * G.inv2s2[idx] * 0.999 - 1e-3
     margin = np.where(dmin > 0.0, 2e-3 * (1.0 + np.abs(v)) + 8 * ERR_D2 * G.w2[idx] * G.inv2s2[idx], 0.0) + G.err_cull[idx] + ERR_SLACK
+    if rsq:
+        margin = margin + np.where(dmin > 0.0, 2.0 * dmin * G.inv2s2[idx] * ERR_RSQ * (dperp + np.abs(tc)), 0.0)
     return ~(v > thr[idx]), np.abs(v - thr[idx]) > margin
 
 
