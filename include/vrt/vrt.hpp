@@ -521,6 +521,9 @@ inline void set_ray_index(bool on)
 // ======== end of the extension ==========================================================================================
 
 // ---- rt.cpp:8-27 -----------------------------------------------------------------------------------------------------
+// transmittance_step passes on, like its siblings (detail::device_t::check), the error of vrt_hip_transmittance_step, which refuses the
+// arguments with which the reference's loop `t <= s; t += delta` does not end or runs for long: s = +inf, s >= delta * 2^23, a delta
+// that is no normal positive float, more than 2^23 density evaluations (include/vrt_hip.h).
 inline f32 transmittance_step(const vec4f_t o, const vec4f_t n, const f32 s, const f32 delta, const std::vector<gaussian_t> gaussians)
 {
     auto &d = detail::device_t::get();

@@ -432,7 +432,16 @@ typedef struct {
 } vrt_hip_ray_index_stats;
 int vrt_hip_get_ray_index_stats(vrt_hip_ctx *ctx, vrt_hip_ray_index_stats *out); /* of the last bundle, when vrt_hip_enable_stats is on (waits for it) */
 
-/* Numeric cross-checks of rt.cpp:8-27 (transmittance_step uses fast_exp like the reference). */
+/* Numeric cross-checks of rt.cpp:8-27 (transmittance_step uses fast_exp like the reference).
+ * vrt_hip_transmittance_step runs the reference's float32 loop `for (t = 0; t <= s; t += delta)` per sample point, and refuses with
+ * VRT_HIP_ERR_INVALID (and a reason in vrt_hip_last_error), before anything is uploaded or launched, the arguments with which that loop
+ * does not end or holds the GPU for long:
+ *   - delta that is not a normal positive float (0, negative, NaN, below FLT_MIN);
+ *   - any s[k] = +inf;
+ *   - max finite s[k] >= delta * 2^23: from there on t + delta rounds back to t (delta = 0.01: s >= 83,886.08);
+ *   - ceil(max s[k] / delta) * max(n, 1) > 2^23 density evaluations in one lane, n the number of Gaussians (about a second).
+ * Negative and NaN sample points are accepted and behave as in the reference: zero steps, T = fast_exp(-0).
+ * csrc/vrt_step_guard.hpp has the predicate and the proof that an accepted call ends. */
 int vrt_hip_transmittance_step(vrt_hip_ctx *ctx, const float o[3], const float n[3], const float *s, size_t ns,
                                float delta, float *T_out);
 int vrt_hip_density(vrt_hip_ctx *ctx, size_t npts, const float *pts, float *D_out);

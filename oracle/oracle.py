@@ -187,6 +187,14 @@ def transmittance(o, n, s, g, exp_kind=EXP_LIBM, erf_kind=ERF_LIBM):
 
 
 def transmittance_step(o, n, s, delta, g):
+    """rt.cpp:8-17, the float32 loop `for (t = 0; t <= s; t += delta)`.  Raises ValueError for arguments with which that loop does
+    not end -- the termination condition of csrc/vrt_step_guard.hpp: s = +inf, s >= delta * 2^23 (t + delta rounds back to t before
+    t reaches s), or a delta that is not a normal positive float -- so that no test can spin in the C function."""
+    s32, d32 = float(np.float32(s)), float(np.float32(delta))
+    if not d32 >= 2.0 ** -126:        # FLT_MIN
+        raise ValueError(f"transmittance_step: delta = {delta} is not a normal positive float")
+    if s32 >= 0.0 and (np.isinf(s32) or s32 >= d32 * 2.0 ** 23):
+        raise ValueError(f"transmittance_step: s = {s} is not below delta * 2^23 = {d32 * 2.0 ** 23}: the step loop would never end")
     o, n = vec4(o), vec4(n)
     return lib().oracle_transmittance_step(_fp(o), _fp(n), float(s), float(delta), g.ctypes.data, len(g))
 

@@ -75,9 +75,14 @@ float oracle_spline_erf(float x)
     return 1.0f;
 }
 
+/* The reference is a -ffast-math build: its start-up code makes the CPU read subnormal operands as 0.  This file is built without
+ * -ffast-math, so the two approximations that jump at 0 (spline_erf_mirror, spline_exp) say it themselves. */
+static inline float subnormal_as_zero(float x) { return fabsf(x) < 1.17549435e-38f ? 0.f : x; }
+
 /* approx.cpp:45-55: evaluate the negative half on -|x| and mirror. */
 float oracle_spline_erf_mirror(float x)
 {
+    x = subnormal_as_zero(x);
     const float inv_sign = -sign_of(x);
     x *= inv_sign; /* -|x| */
     if (x <= -2.9f) return -inv_sign;
@@ -164,6 +169,7 @@ static const cubic_piece EXP_PIECES[] = {
 
 float oracle_spline_exp(float x)
 {
+    x = subnormal_as_zero(x);
     if (x <= -9.0f) return 0.0f;
     for (size_t i = 0; i < N_EXP_PIECES; ++i)
         if (x < EXP_PIECES[i].hi) return eval_piece(&EXP_PIECES[i], x);

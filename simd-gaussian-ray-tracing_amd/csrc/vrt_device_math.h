@@ -38,8 +38,31 @@ __device__ __forceinline__ float exp_accurate(float x)
     return __builtin_fmaf(r, e * LN2, r);
 }
 
-// vcl_exp flushes to 0 below -87.3 (vectormath_exp.h:393,447-456) -- never produces denormals.
-__device__ __forceinline__ float exp_vcl(float x) { return (x < -87.3f) ? 0.f : exp_accurate(x); }
+// vcl_exp is 0 from -87.3 down and +inf from +87.3 up (vectormath_exp.h:393,447-456: inrange = |x| < 87.3, so +-87.3f themselves are out) --
+// it never produces denormals.  In range it is exp_accurate(x), the same operations and the same bits.  Out of range the correction factor
+// of the last fma is swapped for max(x, -1):  x <= -87.3 gives r * -1 + r = 0 exactly (r = 2^t is a normal float or 0);  x >= 87.3 gives
+// r * x + r >= 88.3 * 2^125.9 = +inf;  +-inf give +inf and 0;  NaN stays NaN through r.  One compare on |x|, one max and one select where
+// the lower limit alone took a compare and a select -- and without them exp_accurate's own last step is inf * e + inf beyond x = 88.72,
+// a NaN for e <= 0 where the reference has +inf (tests/test_gpu_queries.py::test_vcl_exp_beyond_its_upper_limit).
+__device__ __forceinline__ float exp_vcl(float x)
+{
+    constexpr float L2E_HI = 1.44269504088896340736f;
+    constexpr float L2E_LO = 1.925963033500011e-8f;
+    constexpr float LN2 = 0.6931471805599453f;
+    const float t = x * L2E_HI;
+    float e = __builtin_fmaf(x, L2E_HI, -t);
+    e = __builtin_fmaf(x, L2E_LO, e);
+    const float r = __builtin_amdgcn_exp2f(t);
+    const float c = (__builtin_fabsf(x) < 87.3f) ? e * LN2 : __builtin_fmaxf(x, -1.f);
+    return __builtin_fmaf(r, c, r);
+}
+// expf (the pair nobody times) with its limits: +inf once exp(x) passes FLT_MAX (x > 88.72283), 0 once it is below half the smallest
+// subnormal (x < -103.98) -- exp_accurate alone gives NaN at both infinities and, as described above, past the upper one
+__device__ __forceinline__ float exp_libm(float x) { return (x > 88.72283f) ? __builtin_inff() : (x < -103.98f) ? 0.f : exp_accurate(x); }
+
+// The reference is a -ffast-math build, whose start-up code makes the CPU read subnormal operands as 0.  Only the two approximations that
+// jump at 0 can tell: spline_exp (1.0162 just below 0, 1 from 0 on) and spline_erf_mirror (+-0.0537 either side of 0).
+__device__ __forceinline__ float subnormal_as_zero(float x) { return __builtin_fabsf(x) < 1.17549435e-38f ? 0.f : x; }
 
 // approx.cpp:112-129 fast_exp (Schraudolph), NDEBUG unset => clamped; truncating float->u32.
 __device__ __forceinline__ float exp_fast(float x)
@@ -84,6 +107,7 @@ __device__ __forceinline__ float exp_spline(float x)
         { -0.5f, -0.25f, 0.02860214f, 0.2659771f, 0.60136306f, 0.60653067f },
         { -0.25f, 0.0f, 0.3395703f, 0.52065486f, 0.7980211f, 0.7788008f },
     };
+    x = subnormal_as_zero(x);
     if (x <= -9.0f) return 0.0f;
     float r = 1.0f;
     bool done = false;
@@ -104,7 +128,7 @@ __device__ __forceinline__ float vexp(float x)
     if constexpr (EXP == VRT_EXP_VCL) return exp_vcl(x);
     else if constexpr (EXP == VRT_EXP_FAST) return exp_fast(x);
     else if constexpr (EXP == VRT_EXP_SPLINE) return exp_spline(x);
-    else return exp_accurate(x);
+    else return exp_libm(x);
 }
 
 // two floats in an aligned register pair: the operand of the packed fp32 instructions (v_pk_fma_f32, v_pk_mul_f32, v_pk_add_f32)
@@ -161,6 +185,7 @@ __device__ __forceinline__ float erf_spline(float x)
 __device__ __forceinline__ float erf_spline_mirror(float x)
 {
     constexpr float HI[] = { -2.3f, -1.7f, -1.1f, -0.5f };
+    x = subnormal_as_zero(x);
     const float inv_sign = -(float)((x >= 0) - (x < 0));
     x *= inv_sign;
     if (x <= -2.9f) return -inv_sign;

@@ -3,6 +3,7 @@
 #include <initializer_list>
 
 #include "vrt_hip_ctx.hpp"
+#include "vrt_step_guard.hpp"
 
 using namespace vrtk;
 
@@ -53,6 +54,9 @@ int vrt_hip_transmittance_step(vrt_hip_ctx *c, const float o[3], const float n[3
                                float *T_out)
 {
     if (!c || !o || !n || (ns && (!s || !T_out)) || !(delta > 0.f)) return VRT_HIP_ERR_INVALID;
+    // the kernel runs the reference's float loop `t <= s; t += delta`: only arguments for which it ends, and soon (vrt_step_guard.hpp)
+    const StepGuard guard = step_guard(s, ns, delta, c->n);
+    if (guard.refusal) return fail(c, VRT_HIP_ERR_INVALID, step_refusal_message(guard.refusal));
     return query<float>(c, true, { { s, ns } }, ns, T_out, [&](DevBuf<float> *d, float *T) {
         launch_transmittance_step(tables(c), o, n, d[0].p, ns, delta, T, c->stream);
     });

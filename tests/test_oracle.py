@@ -41,6 +41,32 @@ def test_erf_exp_restatements_match_reference_tables(oracle, gold):
     assert np.abs(oracle.map_scalar("oracle_as_erf", x) - gold["libm_erf"]).max() <= 5e-4
 
 
+def test_erf_exp_restatements_match_the_reference_at_their_edges(oracle):
+    """tests/golden/approx_edges.npz (gen_approx_golden.py): the real approx.cpp at +-0, the smallest normal, a subnormal, every piece border of
+    the splines, |x| = 2 of the Taylor erf, vcl_exp's limits +-87.3 and either side of fast_exp's clamps -- finite inputs only -- held to the
+    constants of the test above.  The reference reads a subnormal as 0 (a -ffast-math build): spline_exp and spline_erf_mirror, which jump at 0,
+    show it.  Where the table holds 0 or inf (vcl_exp beyond +-87.3, fast_exp beyond its clamps) the oracle holds the same."""
+    edges = np.load(os.path.join(GOLDEN, "approx_edges.npz"))
+    x, xe = edges["erf_x"], edges["exp_x"]
+    assert np.isfinite(x).all() and np.isfinite(xe).all()
+    assert ((x.view(np.uint32) & 0x7F800000) == 0).sum() >= 4 and ((xe.view(np.uint32) & 0x7F800000) == 0).sum() >= 6   # +-0 and subnormals
+    assert np.abs(oracle.map_scalar("oracle_as_erf", x) - edges["as_erf"]).max() <= 3e-7
+    assert np.abs(oracle.map_scalar("oracle_spline_erf", x) - edges["spline_erf"]).max() <= 2e-7
+    assert np.abs(oracle.map_scalar("oracle_spline_erf_mirror", x) - edges["spline_erf_mirror"]).max() <= 2e-7
+    assert np.abs(oracle.map_scalar("oracle_taylor_erf", x) - edges["taylor_erf"]).max() <= 6e-7
+    np.testing.assert_array_equal(oracle.map_scalar("oracle_vcl_exp", xe), edges["vcl_exp"])
+    assert np.isinf(edges["vcl_exp"]).sum() >= 4 and (edges["vcl_exp"] == 0).sum() >= 4
+    fe, fg = oracle.map_scalar("oracle_fast_exp", xe), edges["fast_exp"]
+    ends = ~np.isfinite(fg) | (fg == 0)
+    np.testing.assert_array_equal(fe[ends], fg[ends])
+    assert ends.sum() >= 4 and (np.abs(fe[~ends] - fg[~ends]) <= 1e-5 * np.abs(fg[~ends])).all()
+    assert np.abs(oracle.map_scalar("oracle_spline_exp", xe) - edges["spline_exp"]).max() <= 1.2e-7
+    # the jump of spline_erf_mirror sits between -FLT_MIN and the subnormals, that of spline_exp too
+    sub = np.array([1 << 31 | 1 << 9, 1 << 31 | 1 << 23], np.uint32).view(np.float32)       # -2^-140, -FLT_MIN
+    assert oracle.map_scalar("oracle_spline_erf_mirror", sub).tolist() == [np.float32(-0.05368501), np.float32(0.05368501)]
+    assert oracle.map_scalar("oracle_spline_exp", sub).tolist() == [1.0, np.float32(1.0161527)]
+
+
 @pytest.fixture(scope="module")
 def plots():
     """What the REFERENCE ITSELF holds for erf / exp: the output of its accuracy experiment (tests/accuracy.cpp:9-58), kept in the
