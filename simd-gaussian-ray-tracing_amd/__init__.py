@@ -181,6 +181,29 @@ def _f3(v):
     return np.ascontiguousarray(np.asarray(v, np.float32)[:3])
 
 
+def _rays(origins, dirs):
+    """The rays of a bundle as the library takes them: origins f32 [3] (one for the bundle) or [nrays, 3], dirs f32 [nrays, 3], and
+    whether there is an origin per ray."""
+    origins = np.ascontiguousarray(origins, np.float32)
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    per_ray = origins.size != 3
+    if per_ray:
+        assert origins.size == dirs.size
+    return origins, dirs, per_ray
+
+
+def _table(v, nrays, per_ray):
+    """A bundle's table of values, [n] for every ray or [nrays, n] per ray (per_ray says which when the shape does not): the array
+    f32, the values per ray, and whether they are per ray."""
+    v = np.ascontiguousarray(v, np.float32)
+    if per_ray is None:
+        per_ray = v.ndim == 2
+    n = v.size // nrays if per_ray and nrays else v.size
+    if per_ray:
+        assert v.size == nrays * n
+    return v, n, bool(per_ray)
+
+
 class Renderer:
     """One context = one GPU.  Mirrors the reference call set (main.cpp:257-296)."""
 
@@ -493,11 +516,7 @@ class Renderer:
     def radiance_rays(self, origins, dirs, want_image=False, pack=PACK_ROUND | ALPHA_COMPUTED):
         """vrt_hip_radiance_rays: origins [3] (one for the bundle) or [nrays, 3], dirs [nrays, 3] unit length.  Returns the
         radiance f32 [nrays, 4], or (radiance, packed pixels u32 [nrays]) with want_image."""
-        origins = np.ascontiguousarray(origins, np.float32)
-        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
-        per_ray = origins.size != 3
-        if per_ray:
-            assert origins.size == dirs.size
+        origins, dirs, per_ray = _rays(origins, dirs)
         rad = np.zeros((len(dirs), 4), np.float32)
         img = np.zeros(len(dirs), np.uint32) if want_image else None
         self._chk(self._L.vrt_hip_radiance_rays(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(rad),
@@ -512,25 +531,20 @@ class Renderer:
         if rc != 0:
             self._chk(rc, "radiance_rays_device")
 
+    def _profile(self, what, origins, dirs, table, table_per_ray):
+        """vrt_hip_<what>: a table of values, shared or per ray, in; a result f32 [nrays, values per ray] out."""
+        origins, dirs, per_ray = _rays(origins, dirs)
+        table, n, table_per_ray = _table(table, len(dirs), table_per_ray)
+        out = np.zeros((len(dirs), n), np.float32)
+        self._chk(getattr(self._L, "vrt_hip_" + what)(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(table), n, int(table_per_ray),
+                                                      _fp(out)), what)
+        return out
+
     def transmittance_bundle(self, origins, dirs, s, s_per_ray=None):
         """vrt_hip_transmittance_bundle: T at sample distances along the rays, culled per ray like radiance_rays.  origins [3] (one for
         the bundle) or [nrays, 3], dirs [nrays, 3] unit length; s [ns] (the same samples for every ray) or [nrays, ns] (per ray;
         s_per_ray says which when the shape does not).  Returns T f32 [nrays, ns]."""
-        origins = np.ascontiguousarray(origins, np.float32)
-        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
-        s = np.ascontiguousarray(s, np.float32)
-        per_ray = origins.size != 3
-        if per_ray:
-            assert origins.size == dirs.size
-        if s_per_ray is None:
-            s_per_ray = s.ndim == 2
-        ns = s.size // len(dirs) if s_per_ray and len(dirs) else s.size
-        if s_per_ray:
-            assert s.size == len(dirs) * ns
-        out = np.zeros((len(dirs), ns), np.float32)
-        self._chk(self._L.vrt_hip_transmittance_bundle(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(s), ns, int(bool(s_per_ray)),
-                                                       _fp(out)), "transmittance_bundle")
-        return out
+        return self._profile("transmittance_bundle", origins, dirs, s, s_per_ray)
 
     def transmittance_bundle_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_s, ns, s_per_ray, d_T, stream=0):
         """vrt_hip_transmittance_bundle_device: device pointers, everything enqueued on `stream`."""
@@ -544,21 +558,7 @@ class Renderer:
         or below a level, +inf where it never gets there (include/vrt_hip.h has the contract).  origins [3] (one for the bundle) or
         [nrays, 3], dirs [nrays, 3] unit length; tau [nt] (the same levels for every ray) or [nrays, nt] (per ray; tau_per_ray says
         which when the shape does not).  Returns the depths f32 [nrays, nt]."""
-        origins = np.ascontiguousarray(origins, np.float32)
-        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
-        tau = np.ascontiguousarray(tau, np.float32)
-        per_ray = origins.size != 3
-        if per_ray:
-            assert origins.size == dirs.size
-        if tau_per_ray is None:
-            tau_per_ray = tau.ndim == 2
-        nt = tau.size // len(dirs) if tau_per_ray and len(dirs) else tau.size
-        if tau_per_ray:
-            assert tau.size == len(dirs) * nt
-        out = np.zeros((len(dirs), nt), np.float32)
-        self._chk(self._L.vrt_hip_depth_bundle(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(tau), nt, int(bool(tau_per_ray)),
-                                               _fp(out)), "depth_bundle")
-        return out
+        return self._profile("depth_bundle", origins, dirs, tau, tau_per_ray)
 
     def depth_bundle_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_tau, nt, tau_per_ray, d_depth, stream=0):
         """vrt_hip_depth_bundle_device: device pointers, everything enqueued on `stream`."""

@@ -161,21 +161,104 @@ int build_ray_index(vrt_hip_ctx *c)
     return VRT_HIP_OK;
 }
 
+namespace {
+
+// A kind of bundle as its entry points see it: its name and what it calls its tables and results in the messages; for the two kinds
+// that turn a table of values (one for the bundle or one per ray) into a result per ray and value -- sample distances into T, levels into
+// depths -- also what the table's length is called, where the four arguments go in RayArgs and which kernels run.
+struct BundleKind {
+    const char *name, *io_text, *count;
+    const float *RayArgs::*table;
+    uint64_t RayArgs::*n;
+    int RayArgs::*per_ray;
+    float *RayArgs::*out;
+    void (*launch)(const RayArgs &, uint32_t, bool, int, int, hipStream_t);
+};
+const BundleKind RADIANCE = { "radiance_rays", "no output buffer", "", nullptr, nullptr, nullptr, nullptr, launch_ray_bundle };
+const BundleKind TRANSMITTANCE = { "transmittance_bundle", "NULL samples or result", "ns", &RayArgs::s, &RayArgs::ns, &RayArgs::s_per_ray, &RayArgs::T,
+                                   launch_ray_trans_bundle };
+const BundleKind DEPTH = { "depth_bundle", "NULL levels or result", "nt", &RayArgs::tau, &RayArgs::nt, &RayArgs::tau_per_ray, &RayArgs::depth,
+                           launch_ray_depth_bundle };
+
+// What every entry point checks before anything else, host and device form alike.  n: values per ray (1 for radiance); io_ok: the kind's
+// tables and results are there.  True when the call is over, with rc its result: an error, or VRT_HIP_OK for a bundle of nothing.
+bool bundle_over(vrt_hip_ctx *c, const BundleKind &k, size_t nrays, size_t n, const void *origins, const void *dirs, bool io_ok, int &rc)
+{
+    const std::string name = k.name;
+    if (!c) rc = VRT_HIP_ERR_INVALID;
+    else if (nrays == 0 || n == 0) rc = VRT_HIP_OK;
+    else if (!origins || !dirs) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": NULL origins or directions");
+    else if (!io_ok) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": " + k.io_text);
+    else if (nrays > 0xFFFFFFF0ull) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": more than 2^32 - 16 rays in one bundle");
+    else if (n > (SIZE_MAX / sizeof(float)) / nrays) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": nrays * " + k.count + " does not fit");
+    else return false;
+    return true;
+}
+
+// Origins and directions of a host-pointer form into their staging buffers, on the context's stream.  The caller has quiesced (an
+// earlier bundle may still read the staging buffers) and reserved its other staging buffers: no buffer grows behind a copy.
+int stage_rays(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs)
+{
+    const size_t no = (origin_per_ray ? nrays : 1) * 3;
+    HIPCHK(c, c->rays_in[0].reserve(no));
+    HIPCHK(c, c->rays_in[1].reserve(nrays * 3));
+    HIPCHK(c, hipMemcpyAsync(c->rays_in[0].p, origins, no * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rays_in[1].p, dirs, nrays * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return VRT_HIP_OK;
+}
+
+// The device form of a transmittance or depth bundle
+int profile_device(vrt_hip_ctx *c, const BundleKind &k, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs, const float *d_table,
+                   size_t n, int per_ray, float *d_out, hipStream_t st)
+{
+    int rc;
+    if (bundle_over(c, k, nrays, n, d_origins, d_dirs, d_table && d_out, rc)) return rc;
+    Bundle b;
+    rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b);
+    if (rc) return rc;
+    b.a.*k.table = d_table; b.a.*k.n = n; b.a.*k.per_ray = per_ray ? 1 : 0; b.a.*k.out = d_out;
+    k.launch(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
+    HIPCHK(c, hipGetLastError());
+    return VRT_HIP_OK;
+}
+
+// The host form: rays and table staged, the device form on the context's stream, the result copied back and waited for
+int profile_host(vrt_hip_ctx *c, const BundleKind &k, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *table, size_t n,
+                 int per_ray, float *out)
+{
+    int rc;
+    if (bundle_over(c, k, nrays, n, origins, dirs, table && out, rc)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = quiesce(c); // the staging buffers may still be read by an earlier bundle
+    if (rc) return rc;
+    const size_t nvalues = (per_ray ? nrays : 1) * n;
+    HIPCHK(c, c->rays_s.reserve(nvalues));
+    HIPCHK(c, c->rays_T.reserve(nrays * n));
+    rc = stage_rays(c, nrays, origins, origin_per_ray, dirs);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->rays_s.p, table, nvalues * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    rc = profile_device(c, k, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->rays_s.p, n, per_ray, c->rays_T.p, c->stream);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, c->rays_T.p, nrays * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VRT_HIP_OK;
+}
+
+} // namespace
+
 extern "C" {
 
 int vrt_hip_radiance_rays_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
                                  float *d_radiance, uint32_t *d_image, int pack_flags, void *hip_stream)
 {
-    if (!c) return VRT_HIP_ERR_INVALID;
-    if (nrays == 0) return VRT_HIP_OK;
-    if (!d_origins || !d_dirs) return fail(c, VRT_HIP_ERR_INVALID, "radiance_rays: NULL origins or directions");
-    if (!d_radiance && !d_image) return fail(c, VRT_HIP_ERR_INVALID, "radiance_rays: no output buffer");
-    if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "radiance_rays: more than 2^32 - 16 rays in one bundle");
+    int rc;
+    if (bundle_over(c, RADIANCE, nrays, 1, d_origins, d_dirs, d_radiance || d_image, rc)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     Bundle b;
-    { int rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b); if (rc) return rc; }
+    rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b);
+    if (rc) return rc;
     b.a.radiance = (float4 *)d_radiance; b.a.image = d_image; b.a.pack_flags = pack_flags;
-    launch_ray_bundle(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
+    RADIANCE.launch(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
     HIPCHK(c, hipGetLastError());
     return VRT_HIP_OK;
 }
@@ -183,21 +266,17 @@ int vrt_hip_radiance_rays_device(vrt_hip_ctx *c, size_t nrays, const float *d_or
 int vrt_hip_radiance_rays(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
                           float *radiance_out, uint32_t *image_out, int pack_flags)
 {
-    if (!c) return VRT_HIP_ERR_INVALID;
-    if (nrays == 0) return VRT_HIP_OK;
-    if (!origins || !dirs) return fail(c, VRT_HIP_ERR_INVALID, "radiance_rays: NULL origins or directions");
-    if (!radiance_out && !image_out) return fail(c, VRT_HIP_ERR_INVALID, "radiance_rays: no output buffer");
+    int rc;
+    if (bundle_over(c, RADIANCE, nrays, 1, origins, dirs, radiance_out || image_out, rc)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    { int rc = quiesce(c); if (rc) return rc; } // the staging buffers may still be read by an earlier bundle
-    const size_t no = (origin_per_ray ? nrays : 1) * 3;
-    HIPCHK(c, c->rays_in[0].reserve(no));
-    HIPCHK(c, c->rays_in[1].reserve(nrays * 3));
+    rc = quiesce(c); // the staging buffers may still be read by an earlier bundle
+    if (rc) return rc;
     if (radiance_out) HIPCHK(c, c->rays_rad.reserve(nrays));
     if (image_out) HIPCHK(c, c->rays_img.reserve(nrays));
-    HIPCHK(c, hipMemcpyAsync(c->rays_in[0].p, origins, no * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rays_in[1].p, dirs, nrays * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    int rc = vrt_hip_radiance_rays_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, radiance_out ? (float *)c->rays_rad.p : nullptr,
-                                          image_out ? c->rays_img.p : nullptr, pack_flags, c->stream);
+    rc = stage_rays(c, nrays, origins, origin_per_ray, dirs);
+    if (rc) return rc;
+    rc = vrt_hip_radiance_rays_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, radiance_out ? (float *)c->rays_rad.p : nullptr,
+                                      image_out ? c->rays_img.p : nullptr, pack_flags, c->stream);
     if (rc) return rc;
     if (radiance_out) HIPCHK(c, hipMemcpyAsync(radiance_out, c->rays_rad.p, nrays * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     if (image_out) HIPCHK(c, hipMemcpyAsync(image_out, c->rays_img.p, nrays * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -208,90 +287,25 @@ int vrt_hip_radiance_rays(vrt_hip_ctx *c, size_t nrays, const float *origins, in
 int vrt_hip_transmittance_bundle_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
                                         const float *d_s, size_t ns, int s_per_ray, float *d_T, void *hip_stream)
 {
-    if (!c) return VRT_HIP_ERR_INVALID;
-    if (nrays == 0 || ns == 0) return VRT_HIP_OK;
-    if (!d_origins || !d_dirs) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: NULL origins or directions");
-    if (!d_s || !d_T) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: NULL samples or result");
-    if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: more than 2^32 - 16 rays in one bundle");
-    if (ns > (SIZE_MAX / sizeof(float)) / nrays) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: nrays * ns does not fit");
-    hipStream_t st = (hipStream_t)hip_stream;
-    Bundle b;
-    { int rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b); if (rc) return rc; }
-    b.a.s = d_s; b.a.ns = ns; b.a.s_per_ray = s_per_ray ? 1 : 0; b.a.T = d_T;
-    launch_ray_trans_bundle(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
-    HIPCHK(c, hipGetLastError());
-    return VRT_HIP_OK;
+    return profile_device(c, TRANSMITTANCE, nrays, d_origins, origin_per_ray, d_dirs, d_s, ns, s_per_ray, d_T, (hipStream_t)hip_stream);
 }
 
 int vrt_hip_transmittance_bundle(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *s,
                                  size_t ns, int s_per_ray, float *T_out)
 {
-    if (!c) return VRT_HIP_ERR_INVALID;
-    if (nrays == 0 || ns == 0) return VRT_HIP_OK;
-    if (!origins || !dirs) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: NULL origins or directions");
-    if (!s || !T_out) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: NULL samples or result");
-    if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: more than 2^32 - 16 rays in one bundle");
-    if (ns > (SIZE_MAX / sizeof(float)) / nrays) return fail(c, VRT_HIP_ERR_INVALID, "transmittance_bundle: nrays * ns does not fit");
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc = quiesce(c); if (rc) return rc; } // the staging buffers may still be read by an earlier bundle
-    const size_t no = (origin_per_ray ? nrays : 1) * 3, nsamples = (s_per_ray ? nrays : 1) * ns;
-    HIPCHK(c, c->rays_in[0].reserve(no));
-    HIPCHK(c, c->rays_in[1].reserve(nrays * 3));
-    HIPCHK(c, c->rays_s.reserve(nsamples));
-    HIPCHK(c, c->rays_T.reserve(nrays * ns));
-    HIPCHK(c, hipMemcpyAsync(c->rays_in[0].p, origins, no * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rays_in[1].p, dirs, nrays * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rays_s.p, s, nsamples * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    int rc = vrt_hip_transmittance_bundle_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->rays_s.p, ns, s_per_ray, c->rays_T.p,
-                                                 c->stream);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(T_out, c->rays_T.p, nrays * ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VRT_HIP_OK;
+    return profile_host(c, TRANSMITTANCE, nrays, origins, origin_per_ray, dirs, s, ns, s_per_ray, T_out);
 }
 
 int vrt_hip_depth_bundle_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs, const float *d_tau,
                                 size_t nt, int tau_per_ray, float *d_depth, void *hip_stream)
 {
-    if (!c) return VRT_HIP_ERR_INVALID;
-    if (nrays == 0 || nt == 0) return VRT_HIP_OK;
-    if (!d_origins || !d_dirs) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: NULL origins or directions");
-    if (!d_tau || !d_depth) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: NULL levels or result");
-    if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: more than 2^32 - 16 rays in one bundle");
-    if (nt > (SIZE_MAX / sizeof(float)) / nrays) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: nrays * nt does not fit");
-    hipStream_t st = (hipStream_t)hip_stream;
-    Bundle b;
-    { int rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b); if (rc) return rc; }
-    b.a.tau = d_tau; b.a.nt = nt; b.a.tau_per_ray = tau_per_ray ? 1 : 0; b.a.depth = d_depth;
-    launch_ray_depth_bundle(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
-    HIPCHK(c, hipGetLastError());
-    return VRT_HIP_OK;
+    return profile_device(c, DEPTH, nrays, d_origins, origin_per_ray, d_dirs, d_tau, nt, tau_per_ray, d_depth, (hipStream_t)hip_stream);
 }
 
 int vrt_hip_depth_bundle(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *tau, size_t nt,
                          int tau_per_ray, float *depth_out)
 {
-    if (!c) return VRT_HIP_ERR_INVALID;
-    if (nrays == 0 || nt == 0) return VRT_HIP_OK;
-    if (!origins || !dirs) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: NULL origins or directions");
-    if (!tau || !depth_out) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: NULL levels or result");
-    if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: more than 2^32 - 16 rays in one bundle");
-    if (nt > (SIZE_MAX / sizeof(float)) / nrays) return fail(c, VRT_HIP_ERR_INVALID, "depth_bundle: nrays * nt does not fit");
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc = quiesce(c); if (rc) return rc; } // the staging buffers may still be read by an earlier bundle
-    const size_t no = (origin_per_ray ? nrays : 1) * 3, nlevels = (tau_per_ray ? nrays : 1) * nt;
-    HIPCHK(c, c->rays_in[0].reserve(no));
-    HIPCHK(c, c->rays_in[1].reserve(nrays * 3));
-    HIPCHK(c, c->rays_s.reserve(nlevels));
-    HIPCHK(c, c->rays_T.reserve(nrays * nt));
-    HIPCHK(c, hipMemcpyAsync(c->rays_in[0].p, origins, no * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rays_in[1].p, dirs, nrays * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rays_s.p, tau, nlevels * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    int rc = vrt_hip_depth_bundle_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->rays_s.p, nt, tau_per_ray, c->rays_T.p, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(depth_out, c->rays_T.p, nrays * nt * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VRT_HIP_OK;
+    return profile_host(c, DEPTH, nrays, origins, origin_per_ray, dirs, tau, nt, tau_per_ray, depth_out);
 }
 
 int vrt_hip_get_ray_stats(vrt_hip_ctx *c, vrt_hip_ray_stats *out)

@@ -1,7 +1,9 @@
-// vrt_ray_cull.hpp -- the per-ray cull of the ray bundles, shared by vrt_ray_kernel.hip (radiance), vrt_ray_trans_kernel.hip
-// (transmittance) and vrt_ray_depth_kernel.hip (depth): the sphere and member tests, the lane = ray cull into per-lane lists in LDS, the one-wave-per-ray re-cull into
-// LDS + scratch slot, both with and without the Morton index, the queue of the long rays and the statistics words.  One text for
-// all three translation units: the same rays keep the same Gaussians, go to the same kernel and count the same statistics.
+// vrt_ray_cull.hpp -- the skeleton of the ray bundles, shared by vrt_ray_kernel.hip (radiance), vrt_ray_trans_kernel.hip
+// (transmittance) and vrt_ray_depth_kernel.hip (depth): the sphere and member tests, the lane = ray cull into per-lane lists in LDS, the
+// one-wave-per-ray re-cull into LDS + scratch slot, both with and without the Morton index, the queue of the long rays and the
+// statistics words; around them what every kernel pair does before its own middle -- ray_short_begin (a lane's ray, list and filing),
+// ray_long_begin / ray_long_next (a wave's claims of the queue, each with its re-cull) -- and launch_ray_kernels behind them.  One text
+// for all three translation units: the same rays keep the same Gaussians, go to the same kernel and count the same statistics.
 #pragma once
 #include "vrt_kernels_common.hpp"
 
@@ -165,6 +167,35 @@ __device__ __forceinline__ void ray_short_file(const RayArgs *Pp, uint32_t nch, 
     }
 }
 
+// A lane's ray behind its cull, as every lane = ray kernel begins: the ray (a lane past the end of the bundle works on the last ray
+// and writes nothing), its list in s_list[k*64 + lane], filed to the long-ray queue and counted.
+struct ShortRay {
+    uint64_t r, rc;  // the lane's ray id, and the same clamped to the bundle
+    bool valid, is_long, writes /* valid && !is_long: this lane's result is this kernel's to store */;
+    uint32_t nl;     // list length; 0 for a long ray, whose list is not used here
+    uint32_t nmax;   // the longest nl of the wave: its loops run that far, so that the wave stays together
+    LaneRay ray;
+};
+template <bool INDEXED>
+__device__ __forceinline__ ShortRay ray_short_begin(const RayArgs *Pp, const SceneTables *Sp, uint32_t *s_list /*[RAY_PL * 64]*/, uint32_t lane)
+{
+    const RayArgs &P = *Pp;
+    ShortRay R;
+    R.r = (uint64_t)blockIdx.x * 64u + lane;
+    R.valid = R.r < P.nrays; // the grid has no wave without a valid ray
+    R.rc = R.valid ? R.r : P.nrays - 1;
+    R.ray = load_ray(P, R.rc);
+    const uint32_t N = Sp->n, nch = (N + 63u) / 64u;
+    RayCullCounts cnt;
+    R.nl = ray_short_cull<INDEXED>(Pp, Sp, N, nch, s_list, lane, R.valid, R.ray, cnt);
+    R.is_long = R.nl > (uint32_t)RAY_PL;
+    ray_short_file<INDEXED>(Pp, nch, R.r, R.valid, R.is_long, R.nl, cnt); // to the one-wave-per-ray kernel behind this one; statistics
+    if (R.is_long) R.nl = 0;
+    R.nmax = wave_max_u32(R.nl);
+    R.writes = R.valid && !R.is_long;
+    return R;
+}
+
 // ---------------------------------------------------------------------------------------------
 // one wave per ray (ray_long_kernel, ray_long_trans_kernel, ray_long_depth_kernel)
 // ---------------------------------------------------------------------------------------------
@@ -184,7 +215,7 @@ __device__ __forceinline__ uint32_t ray_long_claim(const RayArgs *Pp, uint32_t l
 // INDEXED: the re-cull goes through the Morton index (lane = group, lane = leaf of a kept group, lane = member of a kept leaf) and finds
 // the survivors in Morton order; each sets bit perm[pos] of this workgroup's bitmap (N bits of device memory, all zero between rays),
 // and the list is read off the bitmap in ascending scene order -- the list the unindexed compaction makes.
-// Returns the list length; the caller's barriers stand before (the previous ray's list reads are done) and behind it.
+// Returns the list length; ray_long_next's barriers stand before (the previous ray's list reads are done) and behind it.
 template <bool INDEXED>
 __device__ __forceinline__ uint32_t ray_long_cull(const RayArgs *Pp, const SceneTables *Sp, uint32_t N, uint32_t nch /* (N + 63) / 64 */, lds_u32 *s_list,
                                                   uint32_t *slot, uint32_t lane, const LaneRay &ray)
@@ -249,6 +280,61 @@ __device__ __forceinline__ uint32_t ray_long_cull(const RayArgs *Pp, const Scene
         }
     }
     return min(n, N);
+}
+
+// entry p of a long ray's list: the first RAY_LCAP in LDS, the rest in the workgroup's scratch slot
+__device__ __forceinline__ uint32_t long_list_entry(const uint32_t *s_list, const uint32_t *slot, uint32_t p)
+{
+    return p < (uint32_t)RAY_LCAP ? s_list[p] : slot[p];
+}
+
+// A wave's way through the long-ray queue, as every one-wave-per-ray kernel runs it:
+//     LongRay L = ray_long_begin(&P);
+//     while (ray_long_next<INDEXED>(&P, &S, s_list, lane, L)) { ... L.r, L.ray, the L.n entries long_list_entry(s_list, L.slot, p) ... }
+struct LongRay {
+    uint32_t n_long; // length of the queue
+    uint32_t *slot;  // this workgroup's scratch slot
+    uint32_t N, nch; // Gaussians and chunks of the scene
+    uint64_t r;      // the ray claimed last,
+    LaneRay ray;
+    uint32_t n;      // and the length of its list
+};
+__device__ __forceinline__ LongRay ray_long_begin(const RayArgs *Pp)
+{
+    const RayArgs &P = *Pp;
+    LongRay L;
+    L.n_long = min(P.counters[0], P.queue_cap); // final: the short kernel is done
+    L.slot = P.scratch + (size_t)blockIdx.x * P.S.n;
+    L.N = P.S.n; L.nch = (L.N + 63u) / 64u;
+    return L;
+}
+// Claims the next ray of the queue and culls it again into s_list[RAY_LCAP] / L.slot; false when the queue is empty.  The whole wave
+// calls this (ray_long_claim says why the claim sits behind no branch on the lane) and comes back together.
+// (ray_long_kernel of vrt_ray_kernel.hip runs a text of its own of this loop; the note at the top of that file says why.)
+template <bool INDEXED>
+__device__ __forceinline__ bool ray_long_next(const RayArgs *Pp, const SceneTables *Sp, uint32_t *s_list /*[RAY_LCAP]*/, uint32_t lane, LongRay &L)
+{
+    const RayArgs &P = *Pp;
+    while (true) {
+        const uint32_t k = ray_long_claim(Pp, lane);
+        if (k >= L.n_long) return false;
+        L.r = P.queue[k];
+        if (L.r >= P.nrays) continue;
+        L.ray = load_ray(P, L.r);
+        __syncthreads(); // the previous ray's list reads are done
+        L.n = ray_long_cull<INDEXED>(Pp, Sp, L.N, L.nch, (lds_u32 *)s_list, L.slot, lane, L.ray);
+        __syncthreads(); // list and scratch writes of this wave are visible to it
+        if (P.stats && lane == 0 && L.n > (uint32_t)RAY_LCAP) atomicAdd(&P.stats[8], 1ull);
+        return true;
+    }
+}
+
+// Both kernels of a bundle, always enqueued: lane = ray over all rays, then one wave per queued ray on long_grid workgroups.
+typedef void (*RayKernel)(RayArgs);
+inline void launch_ray_kernels(RayKernel short_kernel, RayKernel long_kernel, const RayArgs &a, uint32_t long_grid, hipStream_t st)
+{
+    hipLaunchKernelGGL(short_kernel, dim3((uint32_t)((a.nrays + 63u) / 64u)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(long_kernel, dim3(long_grid), dim3(64), 0, st, a);
 }
 
 } // namespace vrtk

@@ -1,7 +1,7 @@
 // vrt_ray_depth_kernel.hip -- depth bundles (vrt_hip_depth_bundle*): the distance along caller-given rays at which the transmittance
 // falls to each of nt levels -- the inverse of the transmittance bundles' T(s) (vrt_ray_trans_kernel.hip), which is evaluated here by
-// the same text (vrt_ray_trans.hpp) over the same lists in the same order, so that T(depth) through a transmittance bundle is the very
-// number this search compared with the level.  The cull, the queue of the long rays, the re-cull and the statistics are
+// the walks those kernels call (short_walk, long_walk of vrt_ray_trans.hpp): the same text over the same lists in the same order, so
+// that T(depth) through a transmittance bundle is the very number this search compared with the level.  The cull, the queue of the long rays, the re-cull and the statistics are
 // vrt_ray_cull.hpp's: the same rays keep the same Gaussians and go to the same kind of kernel as in the other two bundles.
 //   ray_short_depth_kernel  lane = ray, per-ray lists of at most RAY_PL scene indices in LDS; every lane searches its own brackets
 //   ray_long_depth_kernel   one wave per ray whose list is longer; lane l takes entries l, l + 64, ..., wave_sum reduces the partial sums
@@ -16,70 +16,6 @@
 namespace vrtk {
 
 constexpr int DEPTH_MAX_WALKS = 64; // of one group's search: never reached by a finite s_end (a bracket halves per walk)
-
-// mu_bar + 6 sqrt(2) sigma of one Gaussian: beyond it every Erf of its term is saturated (Erf(6) rounds to 1); mu_bar in trans_entry's operations
-__device__ __forceinline__ float trans_reach(float4 g /* mu, sigma */, const LaneRay &ray)
-{
-    const float cx = sub_ref(g.x, ray.ox), cy = sub_ref(g.y, ray.oy), cz = sub_ref(g.z, ray.oz);
-    const float mu_bar = dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz);
-    return add_ref(mu_bar, mul_ref(6.f, mul_ref(SQRT_2, g.w)));
-}
-
-// One walk of a lane's list (s_list[k*64 + lane], nl entries; the loop runs to nmax, the longest list of the wave's short rays, and a
-// lane past the end of its list leaves its sums as they are): acc[g] = the exponent at sv[g], in ray_short_trans_kernel's order.
-// REACH: also the largest trans_reach of the list, at least 0.
-template <int EXP, int ERF, int NS, bool REACH>
-__device__ __forceinline__ void short_walk(const SceneTables *Sp, const uint32_t *s_list, uint32_t lane, uint32_t nl, uint32_t nmax, const LaneRay &ray,
-                                           const float (&sv)[NS], float (&acc)[NS], float &reach)
-{
-    const SceneTables &S = *Sp;
-#pragma unroll
-    for (int g = 0; g < NS; ++g) acc[g] = 0.f;
-    if constexpr (REACH) reach = 0.f;
-    if (!nmax) return;
-    uint32_t lj = nl ? s_list[lane] : 0u;
-    float4 a = S.mu_sig[lj];
-    float mag = S.gD[lj].z;
-    for (uint32_t j = 0; j < nmax; ++j) {
-        const float4 ca = a;
-        const float cm = mag;
-        const bool vj = j < nl;
-        if (j + 1 < nmax) { // the next entry's rows, one iteration ahead
-            lj = (j + 1 < nl) ? s_list[(j + 1) * 64 + lane] : 0u;
-            a = S.mu_sig[lj]; mag = S.gD[lj].z;
-        }
-        const TransEntry t = trans_entry<EXP, ERF>(ca, cm, ray);
-        if constexpr (REACH) reach = vj ? fmaxf(reach, trans_reach(ca, ray)) : reach;
-#pragma unroll
-        for (int g = 0; g < NS; ++g) {
-            const float sum = add_ref(acc[g], trans_sample<ERF>(t, sv[g]));
-            acc[g] = vj ? sum : acc[g];
-        }
-    }
-}
-
-// One walk of a long ray's list by its wave: lane l takes entries l, l + 64, ...; total[g] = the exponent at sv[g], the 64 partial sums
-// reduced as in ray_long_trans_kernel (wave-uniform).  The whole wave calls this.
-template <int EXP, int ERF, int NS, bool REACH>
-__device__ __forceinline__ void long_walk(const SceneTables *Sp, const uint32_t *s_list, const uint32_t *slot, uint32_t lane, uint32_t n, const LaneRay &ray,
-                                          const float (&sv)[NS], float (&total)[NS], float &reach)
-{
-    const SceneTables &S = *Sp;
-    float acc[NS], far = 0.f;
-#pragma unroll
-    for (int g = 0; g < NS; ++g) acc[g] = 0.f;
-    for (uint32_t p = lane; p < n; p += 64u) {
-        const uint32_t idx = long_list_entry(s_list, slot, p);
-        const float4 ms = S.mu_sig[idx];
-        const TransEntry t = trans_entry<EXP, ERF>(ms, S.gD[idx].z, ray);
-        if constexpr (REACH) far = fmaxf(far, trans_reach(ms, ray));
-#pragma unroll
-        for (int g = 0; g < NS; ++g) acc[g] = add_ref(acc[g], trans_sample<ERF>(t, sv[g]));
-    }
-#pragma unroll
-    for (int g = 0; g < NS; ++g) total[g] = wave_sum(acc[g]); // the whole wave is here again
-    if constexpr (REACH) reach = wave_max(far);
-}
 
 // The brackets of one group of levels before its search.  A level that needs no search gets lo == hi == its result (NaN for a NaN level,
 // 0 where T(0) <= tau, +inf where T(s_end) > tau -- a miss -- and 0 for a slot past the last level); the others [0, s_end], both ends evaluated.
@@ -109,35 +45,24 @@ __global__ __launch_bounds__(64) void ray_short_depth_kernel(RayArgs) // read th
     const SceneTables &S = P.S;
     __shared__ uint32_t s_list[RAY_PL * 64]; // [k*64 + lane]: consecutive lanes on consecutive banks
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t r = (uint64_t)blockIdx.x * 64u + lane;
-    const bool valid = r < P.nrays; // the grid has no wave without a valid ray
-    const uint64_t rc = valid ? r : P.nrays - 1;
-    const LaneRay ray = load_ray(P, rc);
+    const ShortRay R = ray_short_begin<INDEXED>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
+    const uint32_t nl = R.nl, nmax = R.nmax;
+    const LaneRay &ray = R.ray;
 
-    // ---- cull (vrt_ray_cull.hpp): exactly the radiance kernel's ----
-    const uint32_t N = S.n, nch = (N + 63u) / 64u;
-    RayCullCounts cnt;
-    uint32_t nl = ray_short_cull<INDEXED>(&P, &S, N, nch, s_list, lane, valid, ray, cnt);
-    const bool is_long = nl > (uint32_t)RAY_PL;
-    ray_short_file<INDEXED>(&P, nch, r, valid, is_long, nl, cnt); // to the one-wave-per-ray kernel behind this one; statistics
-
-    if (is_long) nl = 0;
-    const uint32_t nmax = wave_max_u32(nl);
     // ---- the ends: s_end with T(0), then T(s_end); an empty list has s_end = 0 and T = Exp(0) at both ----
-    float s_end, unused;
     float s1[1] = { 0.f }, e1[1];
-    short_walk<EXP, ERF, 1, true>(&S, s_list, lane, nl, nmax, ray, s1, e1, s_end);
+    const float s_end = short_walk<EXP, ERF, 1, true>(&S, s_list, lane, nl, nmax, ray, s1, e1);
     const float T0 = vexp<EXP>(e1[0]);
     s1[0] = s_end;
-    short_walk<EXP, ERF, 1, false>(&S, s_list, lane, nl, nmax, ray, s1, e1, unused);
+    short_walk<EXP, ERF, 1, false>(&S, s_list, lane, nl, nmax, ray, s1, e1);
     const float Tend = vexp<EXP>(e1[0]);
     const float res = mul_ref(s_end, 0x1p-24f);
 
     // ---- levels, RAY_SG at a time: every walk of the lane's list halves the brackets of the whole group ----
     const uint64_t nt = P.nt;
-    const float *tp = P.tau + (P.tau_per_ray ? rc * nt : 0ull);
-    float *dp = P.depth + rc * nt;
-    const bool writes = valid && !is_long;
+    const float *tp = P.tau + (P.tau_per_ray ? R.rc * nt : 0ull);
+    float *dp = P.depth + R.rc * nt;
+    const bool writes = R.writes;
     for (uint64_t k0 = 0; k0 < nt; k0 += RAY_SG) {
         float tau[RAY_SG], lo[RAY_SG], hi[RAY_SG];
 #pragma unroll
@@ -156,7 +81,7 @@ __global__ __launch_bounds__(64) void ray_short_depth_kernel(RayArgs) // read th
                 if (!act[g]) sv[g] = 0.f;
             }
             if (__ballot(any) == 0ull) break; // the loops below run to the wave's longest list: the wave stays together
-            short_walk<EXP, ERF, RAY_SG, false>(&S, s_list, lane, nl, nmax, ray, sv, acc, unused);
+            short_walk<EXP, ERF, RAY_SG, false>(&S, s_list, lane, nl, nmax, ray, sv, acc);
 #pragma unroll
             for (int g = 0; g < RAY_SG; ++g) {
                 const bool below = vexp<EXP>(acc[g]) <= tau[g];
@@ -179,34 +104,24 @@ __global__ __launch_bounds__(64) void ray_long_depth_kernel(RayArgs)
     const SceneTables &S = P.S;
     __shared__ uint32_t s_list[RAY_LCAP];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t n_long = min(P.counters[0], P.queue_cap); // final: the short kernel is done
-    uint32_t *slot = P.scratch + (size_t)blockIdx.x * S.n;
-    const uint32_t N = S.n, nch = (N + 63u) / 64u;
     const uint64_t nt = P.nt;
 
-    while (true) {
-        const uint32_t k = ray_long_claim(&P, lane); // every lane executes the atomic: see there
-        if (k >= n_long) break;
-        const uint64_t r = P.queue[k];
-        if (r >= P.nrays) continue;
-        const LaneRay ray = load_ray(P, r);
+    LongRay L = ray_long_begin(&P);
+    while (ray_long_next<INDEXED>(&P, &S, s_list, lane, L)) {
+        const uint32_t *slot = L.slot;
+        const uint32_t n = L.n;
+        const LaneRay &ray = L.ray;
 
-        __syncthreads(); // the previous ray's list reads are done
-        const uint32_t n = ray_long_cull<INDEXED>(&P, &S, N, nch, (lds_u32 *)s_list, slot, lane, ray);
-        __syncthreads(); // list and scratch writes of this wave are visible to it
-        if (P.stats && lane == 0 && n > (uint32_t)RAY_LCAP) atomicAdd(&P.stats[8], 1ull);
-
-        float s_end, unused;
         float s1[1] = { 0.f }, e1[1];
-        long_walk<EXP, ERF, 1, true>(&S, s_list, slot, lane, n, ray, s1, e1, s_end);
+        const float s_end = long_walk<EXP, ERF, 1, true>(&S, s_list, slot, lane, n, ray, s1, e1);
         const float T0 = vexp<EXP>(e1[0]);
         s1[0] = s_end;
-        long_walk<EXP, ERF, 1, false>(&S, s_list, slot, lane, n, ray, s1, e1, unused);
+        long_walk<EXP, ERF, 1, false>(&S, s_list, slot, lane, n, ray, s1, e1);
         const float Tend = vexp<EXP>(e1[0]);
         const float res = mul_ref(s_end, 0x1p-24f);
 
-        const float *tp = P.tau + (P.tau_per_ray ? r * nt : 0ull);
-        float *dp = P.depth + r * nt;
+        const float *tp = P.tau + (P.tau_per_ray ? L.r * nt : 0ull);
+        float *dp = P.depth + L.r * nt;
         for (uint64_t k0 = 0; k0 < nt; k0 += RAY_SG) {
             float tau[RAY_SG], lo[RAY_SG], hi[RAY_SG];
 #pragma unroll
@@ -225,7 +140,7 @@ __global__ __launch_bounds__(64) void ray_long_depth_kernel(RayArgs)
                     if (!act[g]) sv[g] = 0.f;
                 }
                 if (__ballot(any) == 0ull) break; // wave-uniform either way
-                long_walk<EXP, ERF, RAY_SG, false>(&S, s_list, slot, lane, n, ray, sv, total, unused);
+                long_walk<EXP, ERF, RAY_SG, false>(&S, s_list, slot, lane, n, ray, sv, total);
 #pragma unroll
                 for (int g = 0; g < RAY_SG; ++g) {
                     const bool below = vexp<EXP>(total[g]) <= tau[g];
@@ -243,14 +158,8 @@ __global__ __launch_bounds__(64) void ray_long_depth_kernel(RayArgs)
 template <int EXP, int ERF>
 static void launch_ray_depth_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
 {
-    const dim3 short_grid((uint32_t)((a.nrays + 63u) / 64u));
-    if (indexed) {
-        hipLaunchKernelGGL((ray_short_depth_kernel<EXP, ERF, true>), short_grid, dim3(64), 0, st, a);
-        hipLaunchKernelGGL((ray_long_depth_kernel<EXP, ERF, true>), dim3(long_grid), dim3(64), 0, st, a);
-    } else {
-        hipLaunchKernelGGL((ray_short_depth_kernel<EXP, ERF, false>), short_grid, dim3(64), 0, st, a);
-        hipLaunchKernelGGL((ray_long_depth_kernel<EXP, ERF, false>), dim3(long_grid), dim3(64), 0, st, a);
-    }
+    if (indexed) launch_ray_kernels(ray_short_depth_kernel<EXP, ERF, true>, ray_long_depth_kernel<EXP, ERF, true>, a, long_grid, st);
+    else launch_ray_kernels(ray_short_depth_kernel<EXP, ERF, false>, ray_long_depth_kernel<EXP, ERF, false>, a, long_grid, st);
 }
 void launch_ray_depth_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
 {

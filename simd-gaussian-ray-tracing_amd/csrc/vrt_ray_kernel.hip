@@ -9,6 +9,11 @@
 // Both kernels come in a second, INDEXED form (vrt_hip_set_ray_index): the cull walks the scene in the Morton order of its centres --
 // group spheres (64 leaves), leaf spheres (64 consecutive Morton positions), members -- and hands the shading code the SAME list in
 // the same ascending scene order: the sphere tests only ever drop what the member test drops, so no bit of a result moves.
+// What a lane = ray kernel does before it shades (ray, cull, list, filing: ray_short_begin) and how the pair is launched
+// (launch_ray_kernels) is vrt_ray_cull.hpp's, the text the transmittance and depth bundles run.  ray_long_kernel keeps its OWN text of
+// the claim loop (ray_long_next there), of the list entry (long_list_entry there) and of the emitter set-up and emission it has in common
+// with ray_shade_chunk: under max-ilp each of the shared forms moved its pair loop's schedule, and the build with them was slower on
+// the bundle that lives in this kernel (profiles/ray_bundle_refactor.md).  A change to ray_long_next is a change to that loop as well.
 // Compiled like the block kernel with -mllvm -amdgpu-sched-strategy=max-ilp (see the note at the top of vrt_block_kernel.hip):
 // the pair loops are the same independent erf terms.
 #include "vrt_ray_cull.hpp"
@@ -134,20 +139,12 @@ __global__ __launch_bounds__(64) void ray_short_kernel(RayArgs) // read through 
     const SceneTables &S = P.S;
     __shared__ uint32_t s_list[RAY_PL * 64]; // [k*64 + lane]: consecutive lanes on consecutive banks
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t r = (uint64_t)blockIdx.x * 64u + lane;
-    const bool valid = r < P.nrays; // the grid has no wave without a valid ray
-    const LaneRay ray = load_ray(P, valid ? r : P.nrays - 1);
-
-    // ---- cull (vrt_ray_cull.hpp): chunk spheres per lane, members of the chunks some lane keeps with a wave-uniform index ----
-    const uint32_t N = S.n, nch = (N + 63u) / 64u;
-    RayCullCounts cnt;
-    uint32_t nl = ray_short_cull<INDEXED>(&P, &S, N, nch, s_list, lane, valid, ray, cnt);
-    const bool is_long = nl > (uint32_t)RAY_PL;
-    ray_short_file<INDEXED>(&P, nch, r, valid, is_long, nl, cnt); // to the one-wave-per-ray kernel behind this one; statistics
+    // ---- ray, cull, list (vrt_ray_cull.hpp) ----
+    const ShortRay R = ray_short_begin<INDEXED>(&P, &S, s_list, lane);
+    const uint32_t nl = R.nl, nmax = R.nmax;
+    const LaneRay &ray = R.ray;
 
     // ---- shade: every lane walks its own list; the loops run to the longest list of the wave's short rays ----
-    if (is_long) nl = 0;
-    const uint32_t nmax = wave_max_u32(nl);
     float Lr = 0.f, Lg = 0.f, Lb = 0.f, La = 0.f;
     constexpr int EC = 4;
     for (uint32_t i0 = 0; i0 < nmax; i0 += EC) {
@@ -157,7 +154,7 @@ __global__ __launch_bounds__(64) void ray_short_kernel(RayArgs) // read through 
         else if (rem == 2) ray_shade_chunk<EXP, ERF, 2>(S, s_list, nl, nmax, lane, ray, i0, Lr, Lg, Lb, La);
         else ray_shade_chunk<EXP, ERF, 1>(S, s_list, nl, nmax, lane, ray, i0, Lr, Lg, Lb, La);
     }
-    if (valid && !is_long) store_ray(P, r, Lr, Lg, Lb, La);
+    if (R.writes) store_ray(P, R.r, Lr, Lg, Lb, La);
 }
 
 // One wave per long ray, lane = emitter.  The ray is wave-uniform: its survivors are compacted in index order (ballot / mbcnt, as the
@@ -267,14 +264,8 @@ __global__ __launch_bounds__(64) void ray_long_kernel(RayArgs)
 template <int EXP, int ERF>
 static void launch_ray_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
 {
-    const dim3 short_grid((uint32_t)((a.nrays + 63u) / 64u));
-    if (indexed) {
-        hipLaunchKernelGGL((ray_short_kernel<EXP, ERF, true>), short_grid, dim3(64), 0, st, a);
-        hipLaunchKernelGGL((ray_long_kernel<EXP, ERF, true>), dim3(long_grid), dim3(64), 0, st, a);
-    } else {
-        hipLaunchKernelGGL((ray_short_kernel<EXP, ERF, false>), short_grid, dim3(64), 0, st, a);
-        hipLaunchKernelGGL((ray_long_kernel<EXP, ERF, false>), dim3(long_grid), dim3(64), 0, st, a);
-    }
+    if (indexed) launch_ray_kernels(ray_short_kernel<EXP, ERF, true>, ray_long_kernel<EXP, ERF, true>, a, long_grid, st);
+    else launch_ray_kernels(ray_short_kernel<EXP, ERF, false>, ray_long_kernel<EXP, ERF, false>, a, long_grid, st);
 }
 void launch_ray_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
 {

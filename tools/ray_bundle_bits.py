@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""The raw float32 bits of all three kinds of ray bundle, for comparing two builds of the library.  Needs the GPU.
+
+    VRT_HIP_LIB=<build A>/libvrt_hip.so python tools/ray_bundle_bits.py --out a.npz
+    VRT_HIP_LIB=<build B>/libvrt_hip.so python tools/ray_bundle_bits.py --out b.npz
+    cmp a.npz b.npz            (python tools/ray_bundle_bits.py --out b.npz --against a.npz names the results that differ)
+
+Radiance, transmittance and depth bundles of 130 rays (three waves, the last with two rays) through the scenes of
+tests/ray_bundle_scenes.py that sit on the kernels' capacities: stack_with_side at RAY_PL and RAY_PL + 1 (lane = ray lists full and
+one over), wide_stack at RAY_LCAP and RAY_LCAP + 1 (one wave per ray: the list in LDS, and one entry in the scratch slot), and
+scattered rays through `-g 16` (lists from a handful to far beyond RAY_PL in one wave).  Every bundle with one origin and with an origin
+per ray, the Morton index off and on, under every Exp / Erf pair the kernels are instantiated for; the tables of the transmittance and
+depth bundles shared and per ray, with 1, 4 and 7 values per ray (either side of the 4 that ride on one walk of a list).  The file
+holds the same bytes whenever the results do: the members are stored in name order with a fixed date."""
+import argparse
+import io
+import os
+import sys
+import zipfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
+import __graft_entry__ as ge  # noqa: E402
+import oracle  # noqa: E402  (its scene constructor alone: nothing of it is compiled or loaded)
+import ray_bundle_scenes as S  # noqa: E402
+
+pkg = ge._load_pkg()
+from sgrt_amd import scene  # noqa: E402
+
+NRAYS = 130
+PAIRS = [(0, 0), (0, 1), (1, 0), (1, 1), (2, 1), (3, 1), (1, 2), (1, 3), (1, 4)]   # VRT_DISPATCH_EXP_ERF (csrc/vrt_kernels_common.hpp)
+COUNTS = (1, 4, 7)
+f32 = np.float32
+
+
+def near_axis_rays():
+    """wide_rays() and more of their kind: every one keeps the whole wide stack."""
+    rng = np.random.default_rng(77)
+    target = np.concatenate([[[0.0, 0.0, 1.0], [0.05, 0.02, 1.0], [-0.03, 0.06, 1.0]],
+                             np.column_stack([rng.normal(size=(NRAYS - 3, 2)) * 0.04, np.ones(NRAYS - 3)])])
+    return S.STACK_ORIGIN, S.normalise(target - S.STACK_ORIGIN.astype(np.float64))
+
+
+def cases():
+    """(name, scene, origin [3], origins [NRAYS, 3], dirs [NRAYS, 3])"""
+    grid = scene.grid_scene(16)
+    so, sd = S.scattered_rays(grid, count=NRAYS)
+    out = [("stack%d" % k, S.stack_with_side(oracle, k), *S.stack_rays(nmiss=NRAYS - 2)) for k in (S.RAY_PL, S.RAY_PL + 1)]
+    out += [("wide%d" % n, S.wide_stack(oracle, S.RAY_LCAP, n).g, *near_axis_rays()) for n in (S.RAY_LCAP, S.RAY_LCAP + 1)]
+    out = [(name, g, o, np.ascontiguousarray(np.tile(o, (NRAYS, 1))), d) for name, g, o, d in out]
+    return out + [("scattered", grid, so[0].copy(), so, sd)]
+
+
+def tables(n):
+    """{'shared' / 'per_ray': (sample distances, transmittance levels)} with n values per ray"""
+    s = np.linspace(0.5, 6.0, n).astype(f32)
+    tau = np.linspace(0.97, 0.35, n).astype(f32)
+    k = (1.0 + 0.003 * np.arange(NRAYS))[:, None]
+    return {"shared": (s, tau), "per_ray": ((s[None, :] * k).astype(f32), np.clip(tau[None, :] / k, 0.0, 1.0).astype(f32))}
+
+
+def run():
+    res = {}
+    r = pkg.Renderer(0)
+    for name, g, o1, on, d in cases():
+        assert len(d) == NRAYS and on.shape == (NRAYS, 3)
+        r.set_gaussians(g)
+        r.set_options(1, 1, S.CULL_EPS)
+        r.set_ray_index(0)
+        r.enable_stats(True)
+        r.radiance_rays(on, d)
+        st = r.ray_stats()
+        r.enable_stats(False)
+        print(f"{name}: {len(g)} Gaussians, {st['short_rays']} rays lane = ray, {st['long_rays']} one wave per ray, {st['scratch_rays']} of them past RAY_LCAP")
+        for exp_kind, erf_kind in PAIRS:
+            r.set_options(exp_kind, erf_kind, S.CULL_EPS)
+            for index in (0, 1):
+                r.set_ray_index(index)
+                for form, o in (("one_origin", o1), ("origin_per_ray", on)):
+                    key = f"{name}/exp{exp_kind}_erf{erf_kind}/index{index}/{form}"
+                    res[key + "/radiance"] = r.radiance_rays(o, d)
+                    for n in COUNTS:
+                        for which, (s, tau) in tables(n).items():
+                            res[f"{key}/transmittance/{n}_{which}"] = r.transmittance_bundle(o, d, s)
+                            res[f"{key}/depth/{n}_{which}"] = r.depth_bundle(o, d, tau)
+    r.close()
+    return {k: np.ascontiguousarray(v, f32).view(np.uint32) for k, v in res.items()}
+
+
+def write(path, arrays):
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:
+        for name in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, arrays[name], allow_pickle=False)
+            z.writestr(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--against", help="an earlier --out file: name the results whose bits differ, exit 1 if any does")
+    a = ap.parse_args()
+    arrays = run()
+    write(a.out, arrays)
+    finite = sum(int(np.isfinite(v.view(f32)).sum()) for v in arrays.values())
+    print(f"{len(arrays)} results, {sum(v.size for v in arrays.values())} values ({finite} finite) from {pkg.LIB_PATH} -> {a.out}")
+    if a.against:
+        other = np.load(a.against)
+        bad = [k for k in sorted(set(arrays) | set(other.files)) if k not in arrays or k not in other.files or not np.array_equal(arrays[k], other[k])]
+        for k in bad:
+            print("differs", k)
+        print(f"{len(bad)} of {len(arrays)} results differ from {a.against}")
+        sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
