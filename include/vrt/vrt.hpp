@@ -452,6 +452,37 @@ void radiance_rays_device(const f32 *d_origins, bool origin_per_ray, const f32 *
     d.check(vrt_hip_radiance_rays_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_radiance, d_image, pack_flags, hip_stream),
             "vrt_hip_radiance_rays_device");
 }
+// Gradient bundles: given grad_radiance[r] = d(loss) / d(out[r] of radiance_rays) for the same rays, the derivative of the loss with
+// respect to the Gaussians (vrt_hip_radiance_rays_grad in include/vrt_hip.h has the function, the fixed kept lists and the supported
+// pairs: {vcl, libm} x {abramowitz_stegun, libm}; any other pair throws).  grad_out: gaussians.size() rows of VRT_HIP_GRAD_STRIDE
+// floats, OVERWRITTEN: [0..3] d albedo, [4..6] d mu, [7] d sigma, [8] d magnitude, [9..11] 0.  Summed with float atomics on the
+// device: not bitwise reproducible.  No gradient with respect to the rays.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void radiance_rays_grad(const vec4f_t *o, const vec4f_t *n, size_t nrays, const gaussians_t &gaussians, const vec4f_t *grad_radiance, f32 *grad_out)
+{
+    static_assert(sizeof(vec4f_t) == 4 * sizeof(f32), "grad_radiance is handed to the library as 4 floats per ray");
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    std::vector<f32> oo(3 * nrays), nn(3 * nrays);
+    for (size_t r = 0; r < nrays; ++r) {
+        oo[3 * r] = o[r].x; oo[3 * r + 1] = o[r].y; oo[3 * r + 2] = o[r].z;
+        nn[3 * r] = n[r].x; nn[3 * r + 1] = n[r].y; nn[3 * r + 2] = n[r].z;
+    }
+    d.check(vrt_hip_radiance_rays_grad(d.ctx, nrays, oo.data(), 1, nn.data(), grad_radiance ? &grad_radiance[0].x : nullptr, grad_out),
+            "vrt_hip_radiance_rays_grad");
+}
+// The same on the device: ADDS into d_grad (the caller clears it), enqueued on hip_stream, nothing waits.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void radiance_rays_grad_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const gaussians_t &gaussians,
+                               const f32 *d_grad_radiance, f32 *d_grad, void *hip_stream)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    d.check(vrt_hip_radiance_rays_grad_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_grad_radiance, d_grad, hip_stream),
+            "vrt_hip_radiance_rays_grad_device");
+}
 // Transmittance bundles: broadcast_transmittance for ANY number of rays at ns depths each in ONE call, under the same per-ray cull
 // (vrt_hip_transmittance_bundle in include/vrt_hip.h: the exponent moves by less than 0.8 * cull_eps * min(N, 4096) = 3.3e-6 at the
 // defaults).  s: ns sample distances shared by all rays (s_per_ray = false) or nrays * ns, [r * ns + k]; T_out[r * ns + k].  Shadow

@@ -393,6 +393,34 @@ int vrt_hip_depth_bundle_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_o
                                 const float *d_tau, size_t nt, int tau_per_ray, float *d_depth, void *hip_stream);
 int vrt_hip_depth_bundle(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
                          const float *tau, size_t nt, int tau_per_ray, float *depth_out);           /* host pointers, waits */
+/* -------- gradient bundles: d(loss) / d(Gaussians) from d(loss) / d(radiance) of ANY rays -------------------------------------
+ * The function that is differentiated is what vrt_hip_radiance_rays computes for the same rays, scene and options:
+ *   L(r) = sum_{i in K} a_i sum_{k=-4..0} sigma_i m_i exp(-d2_i / (2 sigma_i^2) - k^2 / 2) T(mubar_i + k sigma_i),
+ *   T(s) = Exp(sum_{j in K} A_j (Erf(-mubar_j r_j) - Erf((s - mubar_j) r_j))),  A_j = sigma_j m_j exp(-d2_j / (2 sigma_j^2)) / 0.79788456,
+ * with K the list ray r keeps under the cull rule of the ray bundles above (the same cull_x, the same eps_eff, the same code) HELD
+ * FIXED: the cull is piecewise constant in the parameters, so a Gaussian that a ray drops gets nothing from that ray -- in
+ * particular one of magnitude 0, which every ray drops.  Given grad_radiance[4 * r ..] = d(loss) / d(L(r)), row j of the table gets
+ *   [0..3] d(loss) / d(albedo rgba of j)   [4..6] d / d(mu xyz)   [7] d / d(sigma)   [8] d / d(magnitude)   [9..11] never touched
+ * summed over the rays that keep j.  Exp and Erf in L and T are the selected pair's; their derivatives are the analytic ones
+ * (Exp' = Exp, Erf'(x) = 2 / sqrt(pi) exp(-x^2)), also for the Abramowitz-Stegun Erf.  Supported pairs: {vcl_exp, expf} x
+ * {A&S erf, erff}; under any other pair the call returns VRT_HIP_ERR_INVALID with a message and enqueues nothing (the piecewise
+ * approximations have jumps).  Gradients with respect to the rays (origins, directions) are not computed.
+ * The _device form ADDS into d_grad (N rows of VRT_HIP_GRAD_STRIDE floats, N = Gaussians of the scene) with float atomics: the
+ * caller clears the table, and may let several bundles add into it.  A row of a Gaussian that no ray keeps is not written at all.
+ * The sums depend on the arrival order of the atomic adds: results are NOT bitwise reproducible from run to run.  d_grad_radiance
+ * is 16-byte aligned, as d_radiance of vrt_hip_radiance_rays_device.  The host form overwrites grad_out (columns 9..11 with 0).
+ * Everything else is the radiance bundle's: origins, origin_per_ray, dirs, the stream rules, the buffers that only grow, the shared
+ * queue / counters / scratch slots / bitmap, the Morton index (the same kept lists either way), "counts as a frame in flight";
+ * vrt_hip_get_ray_stats / vrt_hip_get_ray_index_stats report for the same rays every field a radiance bundle reports, and the
+ * same rays go to the same kind of kernel.  nrays == 0 or a scene of no Gaussians returns VRT_HIP_OK with nothing launched and the
+ * table untouched; NULL origins, dirs, grad_radiance or table with work to do, more than 2^32 - 16 rays, or an unsupported pair:
+ * VRT_HIP_ERR_INVALID, nothing enqueued. */
+enum { VRT_HIP_GRAD_STRIDE = 12 };  /* floats per row: [0..3] d albedo rgba, [4..6] d mu xyz, [7] d sigma, [8] d magnitude, [9..11] never touched */
+int vrt_hip_radiance_rays_grad_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                      const float *d_grad_radiance /* 4 per ray */, float *d_grad /* N rows, ACCUMULATED into */,
+                                      void *hip_stream);
+int vrt_hip_radiance_rays_grad(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                               const float *grad_radiance, float *grad_out /* N rows, OVERWRITTEN; columns 9..11 written as 0 */);
 typedef struct {
     uint64_t rays;           /* rays of the bundle                                                                  */
     uint64_t short_rays;     /* shaded lane = ray (list of at most 32)                                              */

@@ -22,6 +22,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 EXP_LIBM, EXP_VCL, EXP_FAST, EXP_SPLINE = 0, 1, 2, 3
 ERF_LIBM, ERF_AS, ERF_SPLINE, ERF_SPLINE_MIRROR, ERF_TAYLOR = 0, 1, 2, 3, 4
+GRAD_STRIDE = 12            # VRT_HIP_GRAD_STRIDE: floats per row of a gradient bundle's table
 TABLE_STEP_DEFAULT = 0.05   # vrt_hip_set_table_step: the library's default (0 = exact kernels only)
 PACK_TRUNC, PACK_ROUND, ALPHA_OPAQUE, ALPHA_COMPUTED = 0, 1, 0, 2
 
@@ -124,6 +125,8 @@ SYMBOLS = {
     "vrt_hip_transmittance_bundle": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p]),
     "vrt_hip_depth_bundle_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int, _vp, _vp]),
     "vrt_hip_depth_bundle": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p]),
+    "vrt_hip_radiance_rays_grad_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "vrt_hip_radiance_rays_grad": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _f32p]),
     "vrt_hip_get_ray_stats": (C.c_int, [_vp, C.POINTER(RayStats)]),
     "vrt_hip_set_ray_index": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_ray_index_stats": (C.c_int, [_vp, C.POINTER(RayIndexStats)]),
@@ -202,6 +205,11 @@ def _table(v, nrays, per_ray):
     if per_ray:
         assert v.size == nrays * n
     return v, n, bool(per_ray)
+
+
+def grad_columns(table):
+    """The columns of a gradient bundle's table [N, GRAD_STRIDE] (numpy array or torch tensor) by name: views, not copies."""
+    return {"albedo": table[:, 0:4], "mu": table[:, 4:7], "sigma": table[:, 7], "magnitude": table[:, 8]}
 
 
 class Renderer:
@@ -566,6 +574,27 @@ class Renderer:
                                                  d_tau or None, int(nt), int(bool(tau_per_ray)), d_depth or None, stream or None)
         if rc != 0:
             self._chk(rc, "depth_bundle_device")
+
+    def radiance_rays_grad(self, origins, dirs, grad_radiance):
+        """vrt_hip_radiance_rays_grad: the derivative of a loss with respect to the Gaussians, given its derivative grad_radiance
+        [nrays, 4] with respect to what radiance_rays returns for the same rays (the kept lists held fixed; no gradient for the rays).
+        Returns {"albedo": [N, 4], "mu": [N, 3], "sigma": [N], "magnitude": [N]}, float32.  The sums are float atomics on the device:
+        not bitwise reproducible."""
+        origins, dirs, per_ray = _rays(origins, dirs)
+        g = np.ascontiguousarray(grad_radiance, np.float32).reshape(-1, 4)
+        assert len(g) == len(dirs)
+        out = np.zeros((self.n, GRAD_STRIDE), np.float32)
+        self._chk(self._L.vrt_hip_radiance_rays_grad(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(g), _fp(out)),
+                  "radiance_rays_grad")
+        return grad_columns(out)
+
+    def radiance_rays_grad_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_grad_radiance, d_grad, stream=0):
+        """vrt_hip_radiance_rays_grad_device: device pointers, everything enqueued on `stream`; ADDS into d_grad ([N, GRAD_STRIDE]
+        float32: grad_columns names its columns)."""
+        rc = self._L.vrt_hip_radiance_rays_grad_device(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None,
+                                                       d_grad_radiance or None, d_grad or None, stream or None)
+        if rc != 0:
+            self._chk(rc, "radiance_rays_grad_device")
 
     def ray_stats(self):
         """Counts of the last bundle (enable_stats first): see vrt_hip_ray_stats in include/vrt_hip.h."""

@@ -131,6 +131,15 @@ __device__ __forceinline__ float vexp(float x)
     else return exp_libm(x);
 }
 
+// exp(-x^2): Erf'(x) = 2 / sqrt(pi) times this.  The gradient bundles (vrt_ray_grad_kernel.hip) take the derivative of every Erf variant
+// they accept from here -- the analytic one, also where Erf itself is the Abramowitz-Stegun form (whose 7.1.27 is a rational function: it
+// forms no exponential that could be handed out).
+template <int EXP>
+__device__ __forceinline__ float exp_neg_sq(float x)
+{
+    return vexp<EXP>(-(x * x));
+}
+
 // two floats in an aligned register pair: the operand of the packed fp32 instructions (v_pk_fma_f32, v_pk_mul_f32, v_pk_add_f32)
 typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }

@@ -1,6 +1,7 @@
-// vrt_hip_rays.cpp -- ray bundles of libvrt_hip.so (vrt_hip_radiance_rays*, vrt_hip_transmittance_bundle*, vrt_hip_depth_bundle*):
-// radiance of caller-given rays, transmittance at sample distances along them, or the distance at which their transmittance falls to
-// given levels, culled per ray (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip).  The scene tables and the
+// vrt_hip_rays.cpp -- ray bundles of libvrt_hip.so (vrt_hip_radiance_rays*, vrt_hip_transmittance_bundle*, vrt_hip_depth_bundle*,
+// vrt_hip_radiance_rays_grad*): radiance of caller-given rays, transmittance at sample distances along them, the distance at which their
+// transmittance falls to given levels, or the derivative of their radiance with respect to the Gaussians, culled per ray
+// (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip, vrt_ray_grad_kernel.hip).  The scene tables and the
 // chunk spheres are the frame pipeline's; the long-ray queue, its counters and the long kernel's scratch slots belong to the context
 // and only grow.
 #include <algorithm>
@@ -63,7 +64,7 @@ std::vector<uint32_t> morton_order(const std::vector<float4> &ms)
     return perm;
 }
 
-// What a bundle of any kind (radiance, transmittance, depth) enqueues before its two kernels: the tables brought up to date, the Morton
+// What a bundle of any kind (radiance, transmittance, depth, gradient) enqueues before its two kernels: the tables brought up to date, the Morton
 // index when it is on and out of date, the queue / counters / scratch / statistics buffers at their size for nrays, the counters (and
 // statistics) cleared on the stream, and the kernels' arguments but for the outputs, which the caller fills in.
 struct Bundle {
@@ -179,6 +180,7 @@ const BundleKind TRANSMITTANCE = { "transmittance_bundle", "NULL samples or resu
                                    launch_ray_trans_bundle };
 const BundleKind DEPTH = { "depth_bundle", "NULL levels or result", "nt", &RayArgs::tau, &RayArgs::nt, &RayArgs::tau_per_ray, &RayArgs::depth,
                            launch_ray_depth_bundle };
+const BundleKind GRADIENT = { "radiance_rays_grad", "NULL grad_radiance or gradient table", "", nullptr, nullptr, nullptr, nullptr, launch_ray_grad_bundle };
 
 // What every entry point checks before anything else, host and device form alike.  n: values per ray (1 for radiance); io_ok: the kind's
 // tables and results are there.  True when the call is over, with rc its result: an error, or VRT_HIP_OK for a bundle of nothing.
@@ -192,6 +194,16 @@ bool bundle_over(vrt_hip_ctx *c, const BundleKind &k, size_t nrays, size_t n, co
     else if (nrays > 0xFFFFFFF0ull) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": more than 2^32 - 16 rays in one bundle");
     else if (n > (SIZE_MAX / sizeof(float)) / nrays) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": nrays * " + k.count + " does not fit");
     else return false;
+    return true;
+}
+
+// What a gradient bundle checks on top of bundle_over (one "value" per ray when the scene has Gaussians, none when it has not: a bundle
+// of nothing): the Exp / Erf pair has kernels.
+bool grad_over(vrt_hip_ctx *c, size_t nrays, const void *origins, const void *dirs, bool io_ok, int &rc)
+{
+    if (bundle_over(c, GRADIENT, nrays, c && c->n == 0 ? 0 : 1, origins, dirs, io_ok, rc)) return true;
+    if (ray_grad_pair_supported(c->exp_kind, c->erf_kind)) return false;
+    rc = fail(c, VRT_HIP_ERR_INVALID, std::string(GRADIENT.name) + ": the derivative is taken under {vcl_exp, expf} x {A&S erf, erff} only; the selected pair has jumps");
     return true;
 }
 
@@ -280,6 +292,45 @@ int vrt_hip_radiance_rays(vrt_hip_ctx *c, size_t nrays, const float *origins, in
     if (rc) return rc;
     if (radiance_out) HIPCHK(c, hipMemcpyAsync(radiance_out, c->rays_rad.p, nrays * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     if (image_out) HIPCHK(c, hipMemcpyAsync(image_out, c->rays_img.p, nrays * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_radiance_rays_grad_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                      const float *d_grad_radiance, float *d_grad, void *hip_stream)
+{
+    int rc;
+    if (grad_over(c, nrays, d_origins, d_dirs, d_grad_radiance && d_grad, rc)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    Bundle b;
+    rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b);
+    if (rc) return rc;
+    b.a.grad_radiance = (const float4 *)d_grad_radiance; b.a.grad = d_grad;
+    GRADIENT.launch(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
+    HIPCHK(c, hipGetLastError());
+    return VRT_HIP_OK;
+}
+
+// The host form: rays and grad_radiance staged, a cleared table of the scene's size, the device form on the context's stream, the table
+// copied back and waited for
+int vrt_hip_radiance_rays_grad(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                               const float *grad_radiance, float *grad_out)
+{
+    int rc;
+    if (grad_over(c, nrays, origins, dirs, grad_radiance && grad_out, rc)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = quiesce(c); // the staging buffers may still be read by an earlier bundle
+    if (rc) return rc;
+    const size_t table = (size_t)c->n * VRT_HIP_GRAD_STRIDE;
+    HIPCHK(c, c->rays_s.reserve(nrays * 4));
+    HIPCHK(c, c->rays_T.reserve(table));
+    rc = stage_rays(c, nrays, origins, origin_per_ray, dirs);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->rays_s.p, grad_radiance, nrays * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->rays_T.p, 0, table * sizeof(float), c->stream));
+    rc = vrt_hip_radiance_rays_grad_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->rays_s.p, c->rays_T.p, c->stream);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(grad_out, c->rays_T.p, table * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return VRT_HIP_OK;
 }

@@ -270,7 +270,7 @@ void launch_clear_stale_cells(const uint32_t *stamp, uint32_t seq, uint32_t n_ce
 constexpr uint32_t SPARSE_HDR_WORDS = 4; // [0] cells stored, [1] capacity (cells), [2] cells per tile, [3] reserved
 __host__ __device__ inline size_t sparse_pixel_offset(uint32_t cap) { return (SPARSE_HDR_WORDS + (size_t)cap + 3) / 4 * 4; }
 
-// Ray bundles (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip): caller-given rays, culled per ray, no camera and no tiles.
+// Ray bundles (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip, vrt_ray_grad_kernel.hip): caller-given rays, culled per ray, no camera and no tiles.
 #ifndef VRT_RAY_PL
 #define VRT_RAY_PL 32
 #endif
@@ -315,6 +315,9 @@ struct RayArgs {
     uint64_t nt;
     int tau_per_ray;
     float *depth;                // [r * nt + k]
+    // Gradient bundles (vrt_ray_grad_kernel.hip; behind everything the other kernels read)
+    const float4 *grad_radiance; // [r] d(loss) / d(radiance of ray r)
+    float *grad;                 // [S.n * VRT_HIP_GRAD_STRIDE] the caller's table, added to with float atomics
 };
 constexpr int RAY_STATS_WORDS = 9, RAY_INDEX_STATS_WORDS = 5; // one device buffer: the index's words follow the nine
 void launch_ray_bundle(const RayArgs &a, uint32_t long_grid /* one-wave workgroups of the long kernel */, bool indexed, int exp_kind, int erf_kind,
@@ -323,6 +326,10 @@ void launch_ray_bundle(const RayArgs &a, uint32_t long_grid /* one-wave workgrou
 void launch_ray_trans_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
 // the same cull, then the distance at which T falls to each of a.nt levels per ray (vrt_ray_depth_kernel.hip)
 void launch_ray_depth_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+// the same cull, then d(loss) / d(Gaussians) from a.grad_radiance, added into a.grad (vrt_ray_grad_kernel.hip).  Only the pairs
+// ray_grad_pair_supported names have kernels; any other enqueues nothing.
+void launch_ray_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+bool ray_grad_pair_supported(int exp_kind, int erf_kind);
 // group spheres of the Morton index: one per 64 consecutive leaf spheres, bounding them
 void launch_build_ray_groups(uint32_t nleaves, const float4 *leaves, float4 *groups, hipStream_t st);
 

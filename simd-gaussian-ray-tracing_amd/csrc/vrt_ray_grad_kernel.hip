@@ -1,0 +1,439 @@
+// vrt_ray_grad_kernel.hip -- gradient bundles (vrt_hip_radiance_rays_grad*): d(loss) / d(albedo, mu, sigma, magnitude) of every Gaussian,
+// given d(loss) / d(radiance) of caller-given rays.  The rays, the cull, the lists, the queue of the long rays, the re-cull and the
+// statistics are vrt_ray_cull.hpp's, the text the radiance kernels of vrt_ray_kernel.hip run: the same rays keep the same Gaussians and
+// go to the same kind of kernel.  The kept list K of a ray is held fixed (the cull is piecewise constant in the parameters).
+//
+// The function ("Gradient bundles"; K = 1 / 0.79788456 as everywhere in this library, C = 2 / sqrt(pi)):
+//   A_j = K sigma_j m_j exp(-d2_j / (2 sigma_j^2)),  x_ikj = (mubar_i + k sigma_i - mubar_j) r_j,  D_ikj = Erf(-mubar_j r_j) - Erf(x_ikj),
+//   T_ik = Exp(sum_j A_j D_ikj),  L = sum_i a_i sum_k sigma_i m_i exp(-d2_i / (2 sigma_i^2) - k^2 / 2) T_ik,           k = -4..0
+// and with g = dl/dL, G_i = g . a_i, w_ik = G_i (the ik term of L), W = sum_ik w_ik and per absorber j the three sums
+//   P_j = sum_ik w_ik D_ikj,   Q_j = sum_ik w_ik e2_ikj,   R_j = sum_ik w_ik e2_ikj x_ikj,      e2 = exp(-x^2), e1_j = exp(-(mubar_j r_j)^2)
+// the contributions (to the emitter, to the emitter through its sample points, to every absorber) collapse to
+//   d m_j     = M_j            = (A_j / m_j) P_j + G_j V_j                         V_j = sum_k (the jk term of L) / m_j, formed without m_j
+//   d mu_j    = -m_j M_j c_perp_j / sigma_j^2 + [A_j C r_j (Q_j - e1_j W) + Z_j] n        Z_j = sum_k w_jk S_jk = -sum_i C A_i r_i sum_k w_jk e2_jki
+//   d sigma_j = m_j M_j (1 / sigma_j + d2_j / sigma_j^3) + A_j C (e1_j mubar_j r_j W + R_j) / sigma_j + Y_j          Y_j = sum_k k w_jk S_jk
+//   d a_j     = g m_j V_j
+// Two passes over the pair loop per emitter chunk: the first is the radiance kernels' (the exponents of T, then w_ik); the second
+// evaluates D and e2 again and deals w_ik out to the absorbers (P, Q, R) and, through the same products, back to the emitter (Z, Y).
+// Nothing of size 5 n is stored: a chunk's w_ik live in registers between its two passes.
+//   ray_short_grad_kernel  lane = ray.  Three running sums per list position and lane in LDS (M, the n coefficient, the sigma sum:
+//                          24 KB next to the 8 KB of lists) take the chunks' shares; when all chunks are through, W is known and every
+//                          position is dealt to the caller's table once: 9 atomic adds per (ray, kept Gaussian) -- 4 (albedo) behind the
+//                          emitter's chunk, 5 at the end.  Where a position holds the same scene index in every lane that has one (a
+//                          coherent bundle), the values are summed over the wave (wave_sum) and ONE row segment is added.
+//   ray_long_grad_kernel   one wave per ray, lane = emitter, the absorber wave-uniform: P, Q, R are summed over the wave per (round of
+//                          128 emitters, absorber) and lanes 0..4 add one row segment; the emitter's own terms are per-lane adds (every
+//                          lane another row); the terms in W follow in a last walk of the list.
+// Exp / Erf of the forward quantities are the selected pair's; e1 and e2 are exp_neg_sq<EXP>.  Only {vcl, libm} x {A&S, libm} are
+// instantiated: the piecewise approximations have jumps, and the entry point refuses them.
+// The sums in the caller's table depend on the arrival order of the atomic adds: not bitwise reproducible.
+// Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
+#include "vrt_ray_cull.hpp"
+
+namespace vrtk {
+
+constexpr float ERF_SLOPE = 1.1283791670955126f; // 2 / sqrt(pi): Erf'(x) = ERF_SLOPE exp(-x^2)
+constexpr int GRAD_STRIDE = VRT_HIP_GRAD_STRIDE; // floats per row of the caller's table
+
+// a - b as an unevaluated sum hi + lo, exactly (Knuth's two-sum on a and -b)
+__device__ __forceinline__ void exact_diff(float a, float b, float &hi, float &lo)
+{
+    hi = sub_ref(a, b);
+    const float bb = sub_ref(hi, a);
+    lo = sub_ref(sub_ref(a, sub_ref(hi, bb)), add_ref(b, bb));
+}
+
+// One Gaussian against one ray, as both passes and the last walk need it.  d2 is formed from c_perp = c - mubar n itself, not as
+// |c|^2 - mubar^2: the vector is needed anyway and its norm has no cancellation.  c = mu - o keeps the low part its rounding drops: the
+// exponent d2 / (2 sigma^2) of a small Gaussian far from the origin otherwise carries ulp(|c|) |c_perp| / sigma^2 of error, 1e-4 of a
+// row's every entry in the grid scene seen from four units away (a rounding error of mubar only moves c_perp along n: second order).  `on` = false (a lane past the end of its list):
+// a harmless row takes the place of whatever was loaded, and the weights are exact zeros.
+struct GradGauss {
+    float mubar, d2, px, py, pz; // c . n, |c_perp|^2, c_perp
+    float r, inv_s, inv_s2;      // 1 / (sqrt2 sigma), 1 / sigma, 1 / sigma^2
+    float A, Am, Ar;             // A_j, A_j / m_j (formed without m_j), A_j C r_j
+    float m, E;                  // mubar r, Erf(-mubar r)
+};
+template <int EXP, int ERF>
+__device__ __forceinline__ GradGauss grad_gauss(const ErfEval<ERF> &erf, float4 ms, float4 b, bool on, const LaneRay &ray)
+{
+    if (!on) { ms = make_float4(ray.ox, ray.oy, ray.oz, 1.f); b = make_float4(0.70710678f, 0.5f, 0.f, 0.f); }
+    GradGauss q;
+    float cx, cy, cz, lx, ly, lz;
+    exact_diff(ms.x, ray.ox, cx, lx); exact_diff(ms.y, ray.oy, cy, ly); exact_diff(ms.z, ray.oz, cz, lz);
+    // mubar = c . n as hi + lo (products split by fma, sums by two-sum, the low part of c included): a rounding error of mubar moves
+    // c_perp along n -- second order in d2, but first order in a component of c_perp that is small against |c| |n's component|
+    const float p1 = mul_ref(cx, ray.nx), p2 = mul_ref(cy, ray.ny), p3 = mul_ref(cz, ray.nz);
+    const float e1 = __builtin_fmaf(cx, ray.nx, -p1), e2 = __builtin_fmaf(cy, ray.ny, -p2), e3 = __builtin_fmaf(cz, ray.nz, -p3);
+    float s12, r12, s123, r123;
+    exact_diff(p1, -p2, s12, r12);
+    exact_diff(s12, -p3, s123, r123);
+    const float tail = add_ref(add_ref(add_ref(add_ref(e1, e2), e3), add_ref(r12, r123)), dot3_ref(lx, ly, lz, ray.nx, ray.ny, ray.nz));
+    q.mubar = add_ref(s123, tail);
+    const float mlo = add_ref(sub_ref(s123, q.mubar), tail);
+    q.px = add_ref(__builtin_fmaf(-mlo, ray.nx, __builtin_fmaf(-q.mubar, ray.nx, cx)), lx);
+    q.py = add_ref(__builtin_fmaf(-mlo, ray.ny, __builtin_fmaf(-q.mubar, ray.ny, cy)), ly);
+    q.pz = add_ref(__builtin_fmaf(-mlo, ray.nz, __builtin_fmaf(-q.mubar, ray.nz, cz)), lz);
+    q.d2 = dot3_ref(q.px, q.py, q.pz, q.px, q.py, q.pz);
+    const float ex = vexp<EXP>(-(q.d2 * b.y));
+    q.r = b.x; q.inv_s = b.x * SQRT_2; q.inv_s2 = 2.f * b.y;
+    q.A = b.z * ex;
+    q.Am = on ? (INV_SQRT_2_PI * ms.w) * ex : 0.f;
+    q.Ar = q.A * ERF_SLOPE * b.x;
+    q.m = q.mubar * b.x;
+    q.E = erf(-q.m);
+    return q;
+}
+
+// NV values per lane for columns col0.. of row idx of the caller's table; `on`: this lane has something to add.  The whole wave calls
+// this.  When every lane that is on names the same row, the values are summed over the wave and lanes 0..NV-1 add one segment.
+template <int NV>
+__device__ __forceinline__ void grad_deposit(float *table, uint32_t idx, bool on, const float (&v)[NV], uint32_t col0, uint32_t lane)
+{
+    const unsigned long long mask = __ballot(on);
+    if (mask == 0ull) return;
+    const uint32_t first = lane_value_u32(idx, (uint32_t)__builtin_ctzll(mask));
+    const bool shared = __ballot(on && idx == first) == mask && (mask & (mask - 1ull)) != 0ull; // one row, more than one adder
+    if (shared) {
+        float mine = 0.f;
+#pragma unroll
+        for (int c = 0; c < NV; ++c) {
+            const float s = wave_sum(on ? v[c] : 0.f);
+            if (lane == (uint32_t)c) mine = s;
+        }
+        if (lane < (uint32_t)NV) atomicAdd(&table[(size_t)first * GRAD_STRIDE + col0 + lane], mine);
+    } else if (on) {
+#pragma unroll
+        for (int c = 0; c < NV; ++c) atomicAdd(&table[(size_t)idx * GRAD_STRIDE + col0 + c], v[c]);
+    }
+}
+
+// What an emitter contributes once the exponents of its five samples are known: t_k = sigma exp(acc_k - d2 / (2 sigma^2) - k^2 / 2)
+// (the ik term of L without m_i), V = sum_k t_k, w_k = G m t_k.
+template <int EXP>
+__device__ __forceinline__ float grad_emitter(bool on, float sigma, float d2, float inv2s2, float Gm, const float (&acc)[5], float (&w)[5])
+{
+    float V = 0.f;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const float kf = (float)(k - 4);
+        const float t = sigma * vexp<EXP>(acc[k] - d2 * inv2s2 - 0.5f * kf * kf);
+        V += t;
+        w[k] = on ? Gm * t : 0.f;
+    }
+    return on ? V : 0.f; // a lane without this emitter: exact zeros, whatever its exponents came to
+}
+
+// s_acc: three sums per list position and lane, [(c * RAY_PL + pos) * 64 + lane]: c = 0 M, 1 the coefficient of n, 2 the sigma sum
+__device__ __forceinline__ float &grad_acc(float *s_acc, int c, uint32_t pos, uint32_t lane) { return s_acc[((uint32_t)c * RAY_PL + pos) * 64u + lane]; }
+
+// One chunk of EC emitters (list positions i0 .. i0+EC-1 of every lane) against the lane's whole list, both passes.
+template <int EXP, int ERF, int EC>
+__device__ __forceinline__ void ray_grad_chunk(const RayArgs *Pp, const SceneTables *Sp, const uint32_t *s_list /*[k*64 + lane]*/, float *s_acc, uint32_t nl,
+                                               uint32_t nmax, uint32_t lane, const LaneRay &ray, uint32_t i0, float4 g, float &W)
+{
+    const SceneTables &S = *Sp;
+    const ErfEval<ERF> erf;
+    float e_mubar[EC], e_sigma[EC];
+#pragma unroll
+    for (int e = 0; e < EC; ++e) {
+        const bool on = i0 + e < nl;
+        const uint32_t idx = on ? s_list[(i0 + e) * 64 + lane] : 0u;
+        const float4 ms = S.mu_sig[idx];
+        const float cx = ms.x - ray.ox, cy = ms.y - ray.oy, cz = ms.z - ray.oz;
+        e_mubar[e] = on ? dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz) : 0.f;
+        e_sigma[e] = on ? ms.w : 1.f;
+    }
+
+    // ---- pass 1: the exponents of T at the chunk's 5 EC sample points (the radiance kernel's pair loop) ----
+    float acc[EC][5];
+#pragma unroll
+    for (int e = 0; e < EC; ++e)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) acc[e][k] = 0.f;
+    uint32_t lj = nl ? s_list[lane] : 0u;
+    float4 a = S.mu_sig[lj], b = S.gB[lj];
+    for (uint32_t j = 0; j < nmax; ++j) {
+        const float4 ca = a, cb = b;
+        const bool vj = j < nl;
+        if (j + 1 < nmax) {
+            lj = (j + 1 < nl) ? s_list[(j + 1) * 64 + lane] : 0u;
+            a = S.mu_sig[lj]; b = S.gB[lj];
+        }
+        const GradGauss q = grad_gauss<EXP, ERF>(erf, ca, cb, vj, ray);
+#pragma unroll
+        for (int e = 0; e < EC; ++e) {
+            const float base = __builtin_fmaf(e_mubar[e], q.r, -q.m);
+            const float step = e_sigma[e] * q.r;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const float x = __builtin_fmaf((float)(k - 4), step, base);
+                acc[e][k] = __builtin_fmaf(q.A, q.E - erf(x), acc[e][k]);
+            }
+        }
+    }
+
+    // ---- the emitters: w_ik, V_i; the albedo rows leave here ----
+    float w[EC][5], GV[EC];
+#pragma unroll
+    for (int e = 0; e < EC; ++e) {
+        const bool on = i0 + e < nl;
+        const uint32_t idx = on ? s_list[(i0 + e) * 64 + lane] : 0u;
+        const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], on, ray);
+        const float4 alb = S.gC[idx];
+        const float mag = on ? S.gD[idx].z : 0.f;
+        const float G = on ? g.x * alb.x + g.y * alb.y + g.z * alb.z + g.w * alb.w : 0.f;
+        const float V = grad_emitter<EXP>(on, e_sigma[e], q.d2, 0.5f * q.inv_s2, G * mag, acc[e], w[e]);
+        GV[e] = G * V;
+        W = __builtin_fmaf(GV[e], mag, W);
+        const float mV = mag * V;
+        const float da[4] = { g.x * mV, g.y * mV, g.z * mV, g.w * mV };
+        grad_deposit<4>(Pp->grad, idx, on, da, 0u, lane);
+    }
+
+    // ---- pass 2: the same pairs again; w_ik to the absorbers (P, Q, R) and through w e2 A C r back to the emitters (Z, Y) ----
+    float z[EC], y[EC];
+#pragma unroll
+    for (int e = 0; e < EC; ++e) z[e] = y[e] = 0.f;
+    lj = nl ? s_list[lane] : 0u;
+    a = S.mu_sig[lj]; b = S.gB[lj];
+    for (uint32_t j = 0; j < nmax; ++j) {
+        const float4 ca = a, cb = b;
+        const bool vj = j < nl;
+        if (j + 1 < nmax) {
+            lj = (j + 1 < nl) ? s_list[(j + 1) * 64 + lane] : 0u;
+            a = S.mu_sig[lj]; b = S.gB[lj];
+        }
+        const GradGauss q = grad_gauss<EXP, ERF>(erf, ca, cb, vj, ray);
+        float Pj = 0.f, Qj = 0.f, Rj = 0.f;
+#pragma unroll
+        for (int e = 0; e < EC; ++e) {
+            const float base = __builtin_fmaf(e_mubar[e], q.r, -q.m);
+            const float step = e_sigma[e] * q.r;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const float kf = (float)(k - 4);
+                const float x = __builtin_fmaf(kf, step, base);
+                const float we = w[e][k] * exp_neg_sq<EXP>(x);
+                Pj = __builtin_fmaf(w[e][k], q.E - erf(x), Pj);
+                Qj += we;
+                Rj = __builtin_fmaf(we, x, Rj);
+                const float t = q.Ar * we;
+                z[e] += t;
+                y[e] = __builtin_fmaf(kf, t, y[e]);
+            }
+        }
+        grad_acc(s_acc, 0, j, lane) += q.Am * Pj;
+        grad_acc(s_acc, 1, j, lane) += q.Ar * Qj;
+        grad_acc(s_acc, 2, j, lane) += q.Ar * Rj * SQRT_2;
+    }
+#pragma unroll
+    for (int e = 0; e < EC; ++e) {
+        if (i0 + e < nl) {
+            grad_acc(s_acc, 0, i0 + e, lane) += GV[e];
+            grad_acc(s_acc, 1, i0 + e, lane) -= z[e];
+            grad_acc(s_acc, 2, i0 + e, lane) -= y[e];
+        }
+    }
+}
+
+template <int EXP, int ERF, bool INDEXED>
+__global__ __launch_bounds__(64) void ray_short_grad_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
+{
+    const RayArgs &P = kernel_args<RayArgs>();
+    const SceneTables &S = P.S;
+    __shared__ uint32_t s_list[RAY_PL * 64]; // [k*64 + lane]: consecutive lanes on consecutive banks
+    __shared__ float s_acc[3 * RAY_PL * 64];
+    const uint32_t lane = threadIdx.x & 63u;
+    const ShortRay R = ray_short_begin<INDEXED>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
+    const uint32_t nl = R.nl, nmax = R.nmax;
+    const LaneRay &ray = R.ray;
+    const float4 g = P.grad_radiance[R.rc];
+
+    for (uint32_t p = 0; p < nmax; ++p)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) grad_acc(s_acc, c, p, lane) = 0.f;
+
+    float W = 0.f;
+    constexpr int EC = 4;
+    for (uint32_t i0 = 0; i0 < nmax; i0 += EC) {
+        const uint32_t rem = nmax - i0;
+        if (rem >= (uint32_t)EC) ray_grad_chunk<EXP, ERF, EC>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
+        else if (rem == 3) ray_grad_chunk<EXP, ERF, 3>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
+        else if (rem == 2) ray_grad_chunk<EXP, ERF, 2>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
+        else ray_grad_chunk<EXP, ERF, 1>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
+    }
+
+    // ---- every list position to the table once, now that W is known ----
+    const ErfEval<ERF> erf;
+    for (uint32_t p = 0; p < nmax; ++p) {
+        const bool on = p < nl; // nl is 0 in a lane without a ray of this kernel
+        const uint32_t idx = on ? s_list[p * 64 + lane] : 0u;
+        const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], on, ray);
+        const float mag = on ? S.gD[idx].z : 0.f;
+        const float M = grad_acc(s_acc, 0, p, lane), mM = mag * M;
+        const float ArE = q.Ar * exp_neg_sq<EXP>(q.m);
+        const float alpha = -mM * q.inv_s2;
+        const float beta = __builtin_fmaf(-ArE, W, grad_acc(s_acc, 1, p, lane));
+        const float dsig = mM * (q.inv_s + q.d2 * q.inv_s * q.inv_s2) + grad_acc(s_acc, 2, p, lane) + ArE * q.m * SQRT_2 * W;
+        const float d[5] = { __builtin_fmaf(alpha, q.px, beta * ray.nx), __builtin_fmaf(alpha, q.py, beta * ray.ny),
+                             __builtin_fmaf(alpha, q.pz, beta * ray.nz), dsig, M };
+        grad_deposit<5>(P.grad, idx, on, d, 4u, lane);
+    }
+}
+
+// One wave per long ray, lane = emitter (EC rounds of 64 at a time), the absorber wave-uniform.
+template <int EXP, int ERF, bool INDEXED>
+__global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
+{
+    const RayArgs &P = kernel_args<RayArgs>();
+    const SceneTables &S = P.S;
+    __shared__ uint32_t s_list[RAY_LCAP];
+    const uint32_t lane = threadIdx.x & 63u;
+    const ErfEval<ERF> erf;
+    constexpr int EC = 2;
+
+    LongRay L = ray_long_begin(&P);
+    while (ray_long_next<INDEXED>(&P, &S, s_list, lane, L)) {
+        const LaneRay ray = L.ray;
+        const uint32_t n = L.n;
+        const float4 g = P.grad_radiance[L.r];
+        float W = 0.f; // this lane's emitters; summed over the wave behind the rounds
+        for (uint32_t e0 = 0; e0 < n; e0 += 64u * EC) {
+            float e_mubar[EC], e_sigma[EC];
+            uint32_t e_idx[EC];
+            bool e_on[EC];
+#pragma unroll
+            for (int e = 0; e < EC; ++e) {
+                const uint32_t p = e0 + (uint32_t)e * 64u + lane;
+                e_on[e] = p < n;
+                e_idx[e] = long_list_entry(s_list, L.slot, e_on[e] ? p : 0u);
+                const float4 ms = S.mu_sig[e_idx[e]];
+                const float cx = ms.x - ray.ox, cy = ms.y - ray.oy, cz = ms.z - ray.oz;
+                e_mubar[e] = e_on[e] ? dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz) : 0.f;
+                e_sigma[e] = e_on[e] ? ms.w : 1.f;
+            }
+            // ---- pass 1 ----
+            float acc[EC][5];
+#pragma unroll
+            for (int e = 0; e < EC; ++e)
+#pragma unroll
+                for (int k = 0; k < 5; ++k) acc[e][k] = 0.f;
+            for (uint32_t j = 0; j < n; ++j) {
+                const uint32_t idx = __builtin_amdgcn_readfirstlane(long_list_entry(s_list, L.slot, j));
+                const GradGauss q = grad_gauss<EXP, ERF>(erf, uload(S.mu_sig, idx), uload(S.gB, idx), true, ray);
+#pragma unroll
+                for (int e = 0; e < EC; ++e) {
+                    const float base = __builtin_fmaf(e_mubar[e], q.r, -q.m);
+                    const float step = e_sigma[e] * q.r;
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) {
+                        const float x = __builtin_fmaf((float)(k - 4), step, base);
+                        acc[e][k] = __builtin_fmaf(q.A, q.E - erf(x), acc[e][k]);
+                    }
+                }
+            }
+            // ---- the emitters ----
+            float w[EC][5], GV[EC], e_mag[EC];
+#pragma unroll
+            for (int e = 0; e < EC; ++e) {
+                const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[e_idx[e]], S.gB[e_idx[e]], e_on[e], ray);
+                const float4 alb = S.gC[e_idx[e]];
+                e_mag[e] = e_on[e] ? S.gD[e_idx[e]].z : 0.f;
+                const float G = e_on[e] ? g.x * alb.x + g.y * alb.y + g.z * alb.z + g.w * alb.w : 0.f;
+                const float V = grad_emitter<EXP>(e_on[e], e_sigma[e], q.d2, 0.5f * q.inv_s2, G * e_mag[e], acc[e], w[e]);
+                GV[e] = G * V;
+                W = __builtin_fmaf(GV[e], e_mag[e], W);
+                if (e_on[e]) {
+                    const float mV = e_mag[e] * V;
+                    float *row = P.grad + (size_t)e_idx[e] * GRAD_STRIDE;
+                    atomicAdd(row + 0, g.x * mV); atomicAdd(row + 1, g.y * mV); atomicAdd(row + 2, g.z * mV); atomicAdd(row + 3, g.w * mV);
+                }
+            }
+            // ---- pass 2: per absorber P, Q, R over the wave, one row segment by lanes 0..4 ----
+            float z[EC], y[EC];
+#pragma unroll
+            for (int e = 0; e < EC; ++e) z[e] = y[e] = 0.f;
+            for (uint32_t j = 0; j < n; ++j) {
+                const uint32_t idx = __builtin_amdgcn_readfirstlane(long_list_entry(s_list, L.slot, j));
+                const GradGauss q = grad_gauss<EXP, ERF>(erf, uload(S.mu_sig, idx), uload(S.gB, idx), true, ray);
+                float Pj = 0.f, Qj = 0.f, Rj = 0.f;
+#pragma unroll
+                for (int e = 0; e < EC; ++e) {
+                    const float base = __builtin_fmaf(e_mubar[e], q.r, -q.m);
+                    const float step = e_sigma[e] * q.r;
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) {
+                        const float kf = (float)(k - 4);
+                        const float x = __builtin_fmaf(kf, step, base);
+                        const float we = w[e][k] * exp_neg_sq<EXP>(x);
+                        Pj = __builtin_fmaf(w[e][k], q.E - erf(x), Pj);
+                        Qj += we;
+                        Rj = __builtin_fmaf(we, x, Rj);
+                        const float t = q.Ar * we;
+                        z[e] += t;
+                        y[e] = __builtin_fmaf(kf, t, y[e]);
+                    }
+                }
+                Pj = wave_sum(Pj); Qj = wave_sum(Qj); Rj = wave_sum(Rj);
+                const float mag = uload(S.gD, idx).z;
+                const float M = q.Am * Pj, mM = mag * M, alpha = -mM * q.inv_s2, beta = q.Ar * Qj;
+                const float dsig = mM * (q.inv_s + q.d2 * q.inv_s * q.inv_s2) + q.Ar * Rj * SQRT_2;
+                const float dx = __builtin_fmaf(alpha, q.px, beta * ray.nx), dy = __builtin_fmaf(alpha, q.py, beta * ray.ny),
+                            dz = __builtin_fmaf(alpha, q.pz, beta * ray.nz);
+                const float mine = lane == 0 ? dx : lane == 1 ? dy : lane == 2 ? dz : lane == 3 ? dsig : M;
+                if (lane < 5u) atomicAdd(&P.grad[(size_t)idx * GRAD_STRIDE + 4u + lane], mine);
+            }
+            // ---- the emitters' own terms: every lane another row ----
+#pragma unroll
+            for (int e = 0; e < EC; ++e) {
+                if (e_on[e]) {
+                    const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[e_idx[e]], S.gB[e_idx[e]], true, ray);
+                    const float M = GV[e], mM = e_mag[e] * M, alpha = -mM * q.inv_s2, beta = -z[e];
+                    float *row = P.grad + (size_t)e_idx[e] * GRAD_STRIDE;
+                    atomicAdd(row + 4, __builtin_fmaf(alpha, q.px, beta * ray.nx));
+                    atomicAdd(row + 5, __builtin_fmaf(alpha, q.py, beta * ray.ny));
+                    atomicAdd(row + 6, __builtin_fmaf(alpha, q.pz, beta * ray.nz));
+                    atomicAdd(row + 7, mM * (q.inv_s + q.d2 * q.inv_s * q.inv_s2) - y[e]);
+                    atomicAdd(row + 8, M);
+                }
+            }
+        }
+        // ---- the terms in W = sum_ik w_ik, lane = list position ----
+        W = wave_sum(W);
+        for (uint32_t p0 = 0; p0 < n; p0 += 64u) {
+            const uint32_t p = p0 + lane;
+            if (p < n) {
+                const uint32_t idx = long_list_entry(s_list, L.slot, p);
+                const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], true, ray);
+                const float ArEW = q.Ar * exp_neg_sq<EXP>(q.m) * W;
+                float *row = P.grad + (size_t)idx * GRAD_STRIDE;
+                atomicAdd(row + 4, -ArEW * ray.nx); atomicAdd(row + 5, -ArEW * ray.ny); atomicAdd(row + 6, -ArEW * ray.nz);
+                atomicAdd(row + 7, ArEW * q.m * SQRT_2);
+            }
+        }
+    }
+}
+
+template <int EXP, int ERF>
+static void launch_ray_grad_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
+{
+    if (indexed) launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, true>, ray_long_grad_kernel<EXP, ERF, true>, a, long_grid, st);
+    else launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, false>, ray_long_grad_kernel<EXP, ERF, false>, a, long_grid, st);
+}
+bool ray_grad_pair_supported(int exp_kind, int erf_kind)
+{
+    return (exp_kind == VRT_EXP_VCL || exp_kind == VRT_EXP_LIBM) && (erf_kind == VRT_ERF_AS || erf_kind == VRT_ERF_LIBM);
+}
+void launch_ray_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
+{
+    if (!a.nrays || !long_grid || !ray_grad_pair_supported(exp_kind, erf_kind)) return;
+    switch (exp_kind * 8 + erf_kind) {
+    case VRT_EXP_LIBM * 8 + VRT_ERF_LIBM: launch_ray_grad_bundle_t<VRT_EXP_LIBM, VRT_ERF_LIBM>(a, long_grid, indexed, st); break;
+    case VRT_EXP_LIBM * 8 + VRT_ERF_AS: launch_ray_grad_bundle_t<VRT_EXP_LIBM, VRT_ERF_AS>(a, long_grid, indexed, st); break;
+    case VRT_EXP_VCL * 8 + VRT_ERF_LIBM: launch_ray_grad_bundle_t<VRT_EXP_VCL, VRT_ERF_LIBM>(a, long_grid, indexed, st); break;
+    default: launch_ray_grad_bundle_t<VRT_EXP_VCL, VRT_ERF_AS>(a, long_grid, indexed, st); break;
+    }
+}
+
+} // namespace vrtk

@@ -28,6 +28,16 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
       call (a cull and two kernels) and three elementwise updates; no host round trip.  Stream events around each, alternating, after
       warm-up.  The depth bundle has to be faster in every row.  `--depth-only` runs this part alone; it prints its JSON line and
       writes ray_depth.json and ray_depth.md (and nothing else) to --out-dir.  (The letter (d) was taken.)
+  (g) gradient bundles (vrt_hip_radiance_rays_grad_device): the 4096 rays of a 64 x 64 pinhole frame of the CLI camera (one origin, but
+      these rays pass between the Gaussians), the 4096 rays of a 64 x 64 pinhole frame zoomed onto 0.03 x 0.03 of the grid around one
+      Gaussian (one origin, every wave's lanes keep the same few Gaussians: the wave-reduced adds) and the 2^20 scattered rays of (d)
+      (per-lane adds), device pointers, index off and on, each against
+      vrt_hip_radiance_rays_device (radiance out) of the same rays in the same run, windows alternating.  The ratio is gradient time over
+      radiance time; there is no pass / fail ratio.  With it the atomic bytes of one call (36 B per entry of a lane = ray list before
+      the wave reduction; the long rays' share is not counted by ray_stats) and the time they would take at 1.3 TB/s.
+      `--grad-only` runs this part alone, prints its JSON line and writes ray_grad.json and ray_grad.md (and nothing else) to --out-dir;
+      the .md ends with the text of <out-dir>/ray_grad_resources.txt when that file is there (the output of
+      `tools/kernel_resources.sh raygrad`, which needs the compiler and no GPU).
 """
 import argparse
 import json
@@ -270,6 +280,75 @@ def write_depth(z, out_dir):
         f.write(markdown_depth(z))
 
 
+ATOMIC_RATE = 1.3e12   # bytes of float atomic adds per second, chip-wide
+
+
+def part_grad(g, calls=3, repeats=5):
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    rows = {}
+    cam, _ = scene.cli_camera(64, 64)
+    pinhole = (np.asarray(cam.position, f32)[:3], directions(cam.plane(), cam.position))
+    centre = g["mu"][len(g) // 2 + int(round(len(g) ** 0.5)) // 2, :3].astype(np.float64)
+    u = (np.arange(64) - 31.5) / 64 * 0.03
+    target = centre[None, :] + np.stack([np.tile(u, 64), np.repeat(u, 64), np.zeros(4096)], 1)
+    dz = target - np.asarray(cam.position, np.float64)[:3]
+    zoom = (pinhole[0], np.ascontiguousarray((dz / np.linalg.norm(dz, axis=1, keepdims=True)).astype(f32)))
+    for label, (o, d), per in (("pinhole_64x64", pinhole, 0), ("zoom_64x64", zoom, 0), ("scattered_2^20", scattered(g, 1 << 20), 1)):
+        nrays = len(d)
+        t_o, t_d = torch.from_numpy(np.ascontiguousarray(o, f32)).cuda(), torch.from_numpy(np.ascontiguousarray(d, f32)).cuda()
+        t_g = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, size=(nrays, 4)).astype(f32)).cuda()
+        ctx = [pkg.Renderer(0), pkg.Renderer(0)]
+        for on, r in enumerate(ctx):
+            r.set_gaussians(g)
+            r.set_ray_index(on)
+        rad = [torch.zeros((nrays, 4), dtype=torch.float32, device="cuda") for _ in ctx]
+        table = [torch.zeros((len(g), pkg.GRAD_STRIDE), dtype=torch.float32, device="cuda") for _ in ctx]
+        torch.cuda.synchronize()
+        fns = []
+        for k in (0, 1):
+            fns.append(lambda k=k: ctx[k].radiance_rays_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), rad[k].data_ptr(), 0, PACK, st))
+            fns.append(lambda k=k: ctx[k].radiance_rays_grad_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_g.data_ptr(), table[k].data_ptr(), st))
+        t = windows(fns, calls, repeats, warm=2)
+        ctx[0].enable_stats(True)
+        table[0].zero_()
+        ctx[0].radiance_rays_grad_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_g.data_ptr(), table[0].data_ptr(), st)
+        stats = ctx[0].ray_stats()
+        torch.cuda.synchronize()
+        finite = bool(torch.isfinite(table[0]).all().item())
+        for r in ctx:
+            r.close()
+        atomic_bytes = 36 * stats["lane_entries"]
+        rows[label] = {"rays": nrays, "radiance_off_ms": t[0], "grad_off_ms": t[1], "radiance_on_ms": t[2], "grad_on_ms": t[3],
+                       "grad_over_radiance_off": round(t[1]["median"] / t[0]["median"], 2), "grad_over_radiance_on": round(t[3]["median"] / t[2]["median"], 2),
+                       "atomic_bytes_short_rays_before_reduction": atomic_bytes, "ms_at_atomic_rate": round(atomic_bytes / ATOMIC_RATE * 1e3, 5),
+                       "finite": finite, "per_ray": per_ray(stats), "ray_stats": stats}
+    return {"gaussians": len(g), "rows": rows}
+
+
+def markdown_grad(z, resources=""):
+    lines = [f"""# Gradient bundles (tools/ray_bundles.py --grad-only)
+
+`vrt_hip_radiance_rays_grad_device` against `vrt_hip_radiance_rays_device` (radiance out) of the same rays in the same run: `-g 64`
+(N = {z['gaussians']}), device pointers, stream events around back-to-back calls, the four paths (radiance / gradient, Morton index off / on: two
+contexts) alternating; ms per call, median (min .. max).  There is no pass / fail ratio.  Atomic bytes: 36 B (9 adds) per entry of a
+lane = ray list, before the wave reduction takes any away; the adds of the one-wave-per-ray kernel are not counted by ray_stats (not taken).
+
+| bundle | rays | index | radiance | gradient | gradient / radiance | list entries (pairs) per lane = ray ray | long rays | atomic bytes | ms at 1.3 TB/s |
+|---|---|---|---|---|---|---|---|---|---|"""]
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            lines.append(f"| {label} | {r['rays']} | {key} | {ms(r[f'radiance_{key}_ms'])} | {ms(r[f'grad_{key}_ms'])} | {r[f'grad_over_radiance_{key}']} | "
+                         f"{r['per_ray']['list_entries']} ({r['per_ray']['pairs']}) | {r['per_ray']['long_rays']} | {r['atomic_bytes_short_rays_before_reduction']} | {r['ms_at_atomic_rate']} |")
+    lines.append("""
+Not taken: a profile under rocprofv3 (counters, the atomic request count), the host-pointer form, any scene but `-g 64`, the max-ilp
+scheduler on this unit, variants of the LDS layout.
+""")
+    if resources:
+        lines.append("Resources (`tools/kernel_resources.sh raygrad`; template arguments: Exp (0 libm, 1 vcl), Erf (0 libm, 1 A&S), INDEXED):\n\n```\n" + resources.rstrip() + "\n```\n")
+    return "\n".join(lines)
+
+
 def windows(fns, calls, repeats, warm=3):
     """ms per call of each fn: `repeats` windows of `calls` back-to-back calls between two stream events, the fns alternating."""
     import torch
@@ -460,12 +539,23 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--transmittance-only", action="store_true")
     ap.add_argument("--depth-only", action="store_true")
+    ap.add_argument("--grad-only", action="store_true")
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
     if a.transmittance_only:
         t = part_t(g)
         print(json.dumps({"t": t}))
         check_t(t)
+        return
+    if a.grad_only:
+        z = part_grad(g)
+        os.makedirs(a.out_dir, exist_ok=True)
+        with open(os.path.join(a.out_dir, "ray_grad.json"), "w") as f:
+            f.write(json.dumps({"what": "gradient bundles against radiance bundles of the same rays; see tools/ray_bundles.py (g)", "grad": z}) + "\n")
+        res = os.path.join(a.out_dir, "ray_grad_resources.txt")
+        with open(os.path.join(a.out_dir, "ray_grad.md"), "w") as f:
+            f.write(markdown_grad(z, open(res).read() if os.path.exists(res) else ""))
+        print(json.dumps({"grad": z}))
         return
     if a.depth_only:
         z = part_depth(g)
