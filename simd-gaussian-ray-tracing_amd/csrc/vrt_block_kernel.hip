@@ -319,16 +319,7 @@ __device__ __forceinline__ void render_body(const SceneTables &S, const TileList
         ray.ox = pin_vgpr(ray.ox); ray.oy = pin_vgpr(ray.oy); ray.oz = pin_vgpr(ray.oz);
 
         // ---- block cone: axis = mean of the four centre rays, angle = farthest lane ----
-        float cx = lane_value(ray.nx, 27) + lane_value(ray.nx, 28) + lane_value(ray.nx, 35) + lane_value(ray.nx, 36);
-        float cy = lane_value(ray.ny, 27) + lane_value(ray.ny, 28) + lane_value(ray.ny, 35) + lane_value(ray.ny, 36);
-        float cz = lane_value(ray.nz, 27) + lane_value(ray.nz, 28) + lane_value(ray.nz, 35) + lane_value(ray.nz, 36);
-        {
-            const float inv = __builtin_amdgcn_rsqf(cx * cx + cy * cy + cz * cz);
-            cx *= inv; cy *= inv; cz *= inv;
-        }
-        float co, si;
-        cos_sin(ray.nx, ray.ny, ray.nz, cx, cy, cz, co, si);
-        const Cone cone = make_cone(cx, cy, cz, wave_min(co), wave_max(si));
+        const Cone cone = block_cone<true>(ray);
 
         // ---- block cull over the cell's list (ballot compaction, order preserving) ----
         __syncthreads(); // previous item's LDS reads are done
@@ -389,9 +380,9 @@ __device__ __forceinline__ void render_body(const SceneTables &S, const TileList
             continue;
         }
         if (O.stats && first) {
-            atomicAdd(&O.stats[0], (unsigned long long)cnt);
-            atomicAdd(&O.stats[1], (unsigned long long)n_list);
-            atomicAdd(&O.stats[5], 1ull);
+            atomicAdd(&O.stats[STAT_BLOCK_CANDIDATES], (unsigned long long)cnt);
+            atomicAdd(&O.stats[STAT_TILE_ENTRIES], (unsigned long long)n_list);
+            atomicAdd(&O.stats[STAT_SHADED_BLOCKS], 1ull);
         }
         uint32_t nmax = wave_max_u32(nl);
         if (C.prune_budget > 0.f && nmax <= PRUNE_PL) {
@@ -417,7 +408,7 @@ __device__ __forceinline__ void render_body(const SceneTables &S, const TileList
             unsigned long long sq = (unsigned long long)nl * nl; // this ray's (emitter, absorber) pairs: 5 erf terms each
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) sq += (unsigned long long)(uint32_t)__shfl_xor((int)sq, off, 64);
-            if (lane == 0) { atomicAdd(&O.stats[3], tot); atomicAdd(&O.stats[4], (unsigned long long)nmax); atomicAdd(&O.stats[12], sq); }
+            if (lane == 0) { atomicAdd(&O.stats[STAT_LANE_ENTRIES], tot); atomicAdd(&O.stats[STAT_LANE_MAX_ENTRIES], (unsigned long long)nmax); atomicAdd(&O.stats[STAT_LANE_PAIRS], sq); }
         }
         const unsigned long long tl2 = O.timeline ? wall_clock64() : 0ull;
         if constexpr (CLAIM) {

@@ -28,6 +28,56 @@ struct DenseLds {
 // work; written out only when statistics are on)
 struct DenseVisits { uint32_t full = 0, zero = 0, common = 0; };
 
+// ---- cooperative block cull, order preserving across the DW waves: thread k of the workgroup tests list entry base + k against the cone
+//      (with the slack of the level that n_list candidates enter), the waves' counts meet in `wave_cnt` (LDS), and a kept candidate's
+//      position is the number of kept ones before it in the list.  store(keep, pos, idx, a), called by every thread: what the caller
+//      keeps of a candidate if `keep`, positions not clipped (a = its row of S.gA, by value: through a reference the depth key's products
+//      were contracted the other way round).  Returns the number of survivors; two barriers per DW * 64 entries. ----
+template <int DW, typename Store>
+__device__ __forceinline__ uint32_t block_cull(const SceneTables &S, const TileLists &T, uint32_t (&wave_cnt)[DW], const uint32_t *list,
+                                               uint32_t n_list, const Cone &cone, Store store)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t cnt = 0;
+    for (uint32_t base = 0; base < n_list; base += DW * 64) {
+        const uint32_t k = base + tid;
+        bool keep = false; uint32_t idx = 0; float4 a, bq;
+        if (k < n_list) {
+            idx = list[k];
+            a = S.gA[idx]; bq = S.gB[idx];
+            bq.w = slack_cull_x(bq.w, level_slack(T.cull_ref_n, n_list), T.floor_x);
+            keep = cone_keeps(cone, a, bq);
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(mask);
+        __syncthreads();
+        uint32_t before = 0, chunk = 0;
+#pragma unroll
+        for (uint32_t wv = 0; wv < DW; ++wv) {
+            const uint32_t c = wave_cnt[wv];
+            before += (wv < wave) ? c : 0;
+            chunk += c;
+        }
+        const uint32_t pos = cnt + before + lane_rank(mask);
+        store(keep, pos, idx, a);
+        cnt += chunk;
+        __syncthreads();
+    }
+    return cnt;
+}
+// the sum of the DW waves' partial radiances of lane `lane`, in wave order: deterministic, no float atomics
+template <int DW>
+__device__ __forceinline__ float4 wave_order_sum(const float4 (&L)[DW][64], uint32_t lane)
+{
+    float4 sum = L[0][lane];
+#pragma unroll
+    for (int w = 1; w < DW; ++w) {
+        const float4 v = L[w][lane];
+        sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
+    }
+    return sum;
+}
+
 // Block `bi` of `cell`, all DW * 64 threads of the workgroup; `scratch`: this workgroup's slot of C.scratch; `file_key`: the block
 // is the first of a dense cell of a sparse shard (its key is filed here).  The caller's barrier separates it from the previous use
 // of `lds`.
@@ -43,7 +93,6 @@ __device__ __forceinline__ void dense_shade_block(const SceneTables &S, const Ti
     float(&s_key)[DCAP] = lds.key;
     uint32_t(&s_wave_cnt)[DW] = lds.wave_cnt;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t npix = (uint64_t)R.width * R.height;
     constexpr float SAT = erf_saturation<ERF>();
     constexpr float SAT_M = SAT + 1e-3f; // the range bounds are re-associated forms of the arguments: keep a margin
     const ErfEval<ERF> erf;
@@ -51,66 +100,19 @@ __device__ __forceinline__ void dense_shade_block(const SceneTables &S, const Ti
     {
         const BlockPos p = block_of(T, C, O, cell, bi, lane);
         if (!p.inside) return;
-        const uint32_t tx = p.t % T.tiles_w, ty = p.t / T.tiles_w;
-        bool valid = p.pxt < T.tile_w && p.pyt < T.tile_h;
-        const uint32_t pxc = min(p.pxt, T.tile_w - 1), pyc = min(p.pyt, T.tile_h - 1);
-        uint64_t pix = tile_pixel(T.tile_w, T.tile_h, T.stride, tx, ty, pxc, pyc);
-        if (pix >= npix) { valid = false; pix = npix - 1; }
-        const uint32_t n_active_cells = *C.n_active;
-        const uint64_t out = out_index(T, C, O, cell, bi, lane, p, pix, n_active_cells);
-        if (O.sparse && file_key && bi == 0 && tid == 0) // a dense cell's key (the active cells' are filed by the list kernel)
-            O.keys[n_active_cells + (C.slot[cell] & 0x7FFFFFFFu)] = p.t * (C.cells_x * C.cells_y) + cell % (C.cells_x * C.cells_y);
-
-        uint32_t n_list = C.count[cell];
-        const uint32_t *list = C.indices + (size_t)cell * C.cstride;
-        if (n_list == 0xFFFFFFFFu) { n_list = T.count[p.t]; list = T.indices + T.start[p.t]; }
-
-        const LaneRay ray = pixel_ray(R, pix); // every wave holds the same 64 rays
-        float cx = __shfl(ray.nx, 27, 64) + __shfl(ray.nx, 28, 64) + __shfl(ray.nx, 35, 64) + __shfl(ray.nx, 36, 64);
-        float cy = __shfl(ray.ny, 27, 64) + __shfl(ray.ny, 28, 64) + __shfl(ray.ny, 35, 64) + __shfl(ray.ny, 36, 64);
-        float cz = __shfl(ray.nz, 27, 64) + __shfl(ray.nz, 28, 64) + __shfl(ray.nz, 35, 64) + __shfl(ray.nz, 36, 64);
-        {
-            const float inv = __builtin_amdgcn_rsqf(cx * cx + cy * cy + cz * cz);
-            cx *= inv; cy *= inv; cz *= inv;
-        }
-        float co, si;
-        cos_sin(ray.nx, ray.ny, ray.nz, cx, cy, cz, co, si);
-        const Cone cone = make_cone(cx, cy, cz, wave_min_bpermute(co), wave_max_bpermute(si)); // (not the DPP forms: vrt_kernels_common.hpp)
-
-        // ---- cooperative block cull, order preserving across the 16 waves ----
-        uint32_t cnt = 0;
-        for (uint32_t base = 0; base < n_list; base += DW * 64) {
-            const uint32_t k = base + tid;
-            bool keep = false;
-            uint32_t idx = 0;
-            float4 a, bq;
-            if (k < n_list) {
-                idx = list[k];
-                a = S.gA[idx]; bq = S.gB[idx];
-                bq.w = slack_cull_x(bq.w, level_slack(T.cull_ref_n, n_list), T.floor_x);
-                keep = cone_keeps(cone, a, bq);
-            }
-            const unsigned long long mask = __ballot(keep);
-            if (lane == 0) s_wave_cnt[wave] = (uint32_t)__popcll(mask);
-            __syncthreads();
-            uint32_t before = 0, chunk = 0;
-#pragma unroll
-            for (uint32_t wv = 0; wv < DW; ++wv) {
-                const uint32_t c = s_wave_cnt[wv];
-                before += (wv < wave) ? c : 0;
-                chunk += c;
-            }
-            const uint32_t pos = cnt + before + lane_rank(mask);
+        const BlockRays blk = block_rays(T, C, R, O, cell, bi, file_key, p);
+        const uint32_t n_list = blk.n_list, *list = blk.list;
+        const LaneRay &ray = blk.ray;
+        const Cone cone = block_cone<false>(ray);
+        // the survivors: in list order into LDS with their depth key, and into this workgroup's slot of global scratch -- should they
+        // outgrow LDS, the fallback below streams THEM (cnt^2 pairs) and not the whole cell list (n_list^2)
+        const uint32_t cnt = block_cull<DW>(S, T, s_wave_cnt, list, n_list, cone, [&](bool keep, uint32_t pos, uint32_t idx, float4 a) {
             if (keep && pos < DCAP) {
                 s_idx0[pos] = idx;
                 s_key[pos] = a.x * cone.cx + a.y * cone.cy + a.z * cone.cz; // depth along the block's axis
             }
-            // the survivors also go to this workgroup's slot of global scratch: should they outgrow LDS, the fallback
-            // below streams THEM (cnt^2 pairs) and not the whole cell list (n_list^2)
             if (keep && pos < C.cstride) scratch[pos] = idx;
-            cnt += chunk;
-            __syncthreads();
-        }
+        });
         // ---- sort the candidates by depth (rank sort: every thread ranks one candidate against all keys) so
         //      that the emitters of a chunk are neighbours in depth and whole absorbers saturate for them ----
         if (cnt <= DCAP) {
@@ -127,10 +129,10 @@ __device__ __forceinline__ void dense_shade_block(const SceneTables &S, const Ti
         }
         __syncthreads();
         if (O.stats && tid == 0) {
-            atomicAdd(&O.stats[0], (unsigned long long)(cnt <= C.cstride ? cnt : n_list));
-            atomicAdd(&O.stats[1], (unsigned long long)n_list);
-            if (cnt > DCAP) atomicAdd(&O.stats[2], 1ull);
-            atomicAdd(&O.stats[6], 1ull);
+            atomicAdd(&O.stats[STAT_BLOCK_CANDIDATES], (unsigned long long)(cnt <= C.cstride ? cnt : n_list));
+            atomicAdd(&O.stats[STAT_TILE_ENTRIES], (unsigned long long)n_list);
+            if (cnt > DCAP) atomicAdd(&O.stats[STAT_DENSE_OVER_DCAP], 1ull);
+            atomicAdd(&O.stats[STAT_DENSE_BLOCKS], 1ull);
         }
 
         float Lr = 0.f, Lg = 0.f, Lb = 0.f, La = 0.f;
@@ -223,15 +225,10 @@ __device__ __forceinline__ void dense_shade_block(const SceneTables &S, const Ti
         // ---- sum the waves' partial radiances in wave order ----
         s_L[wave][lane] = make_float4(Lr, Lg, Lb, La);
         __syncthreads();
-        if (wave == 0 && valid) {
-            float4 sum = s_L[0][lane];
-#pragma unroll
-            for (int w = 1; w < DW; ++w) {
-                const float4 v = s_L[w][lane];
-                sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
-            }
-            if (O.image) O.image[out] = pack_pixel(sum.x, sum.y, sum.z, sum.w, O.pack_flags);
-            if (O.radiance) O.radiance[out] = sum;
+        if (wave == 0 && blk.valid) {
+            const float4 sum = wave_order_sum<DW>(s_L, lane);
+            if (O.image) O.image[blk.out] = pack_pixel(sum.x, sum.y, sum.z, sum.w, O.pack_flags);
+            if (O.radiance) O.radiance[blk.out] = sum;
         }
     }
 }

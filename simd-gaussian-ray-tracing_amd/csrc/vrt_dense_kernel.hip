@@ -30,13 +30,13 @@ __device__ __forceinline__ void render_dense_body(const SceneTables &S, const Ti
         const uint32_t item = s_item;
         if (item >= n_items) {
             if (O.stats && lane == 0) {
-                atomicAdd(&O.stats[13], (unsigned long long)visits.full); atomicAdd(&O.stats[14], (unsigned long long)visits.zero);
-                atomicAdd(&O.stats[15], (unsigned long long)visits.common);
+                atomicAdd(&O.stats[STAT_DENSE_VISITS_FULL], (unsigned long long)visits.full); atomicAdd(&O.stats[STAT_DENSE_VISITS_ZERO], (unsigned long long)visits.zero);
+                atomicAdd(&O.stats[STAT_DENSE_VISITS_COMMON], (unsigned long long)visits.common);
             }
             if (O.stats && tid == 0) { // workgroup timeline: how long the queue kept this workgroup busy
                 const unsigned long long t_end = wall_clock64();
-                atomicMin(&O.stats[8], t_start); atomicMax(&O.stats[9], t_end);
-                atomicAdd(&O.stats[10], t_end - t_start); atomicAdd(&O.stats[11], 1ull);
+                atomicMin(&O.stats[STAT_DENSE_T_FIRST], t_start); atomicMax(&O.stats[STAT_DENSE_T_LAST], t_end);
+                atomicAdd(&O.stats[STAT_DENSE_BUSY_TICKS], t_end - t_start); atomicAdd(&O.stats[STAT_DENSE_WORKGROUPS], 1ull);
             }
             break;
         }

@@ -328,7 +328,7 @@ int vrt_hip_create(int device, vrt_hip_ctx **out)
     c->ray_index = c->tune.ray_index;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-        c->d_stats.reserve(32) != hipSuccess) {
+        c->d_stats.reserve(STAT_WORDS) != hipSuccess) {
         vrt_hip_destroy(c);
         return fail(nullptr, VRT_HIP_ERR_HIP, "create: stream/event creation failed");
     }

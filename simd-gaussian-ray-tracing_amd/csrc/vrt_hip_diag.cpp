@@ -20,21 +20,26 @@ int ensure_timing_ring(vrt_hip_ctx *c)
 // vrt_hip_render with stats on: the counters its kernels summed (d_stats) into vrt_hip_stats
 int read_stats(vrt_hip_ctx *c)
 {
-    unsigned long long st[32];
+    using namespace vrtk;
+    unsigned long long st[STAT_WORDS];
     HIPCHK(c, hipMemcpy(st, c->d_stats.p, sizeof st, hipMemcpyDeviceToHost));
-    c->last.table_nodes = st[16]; c->last.table_retries = st[17]; c->last.table_skips = st[18]; c->last.table_declined = st[19]; c->last.table_coarser = st[20]; c->last.table_empty = st[21];
-    for (int k = 0; k < 8; ++k) c->last.table_phase_ticks[k] = st[24 + k];
-    if (c->tune.table_diag && st[7]) // the table phase split by the first wave's clock: staging | node loops | waiting at the chunk barriers (note: [21] is table_empty)
+    c->last.table_nodes = st[STAT_TABLE_NODES]; c->last.table_retries = st[STAT_TABLE_RETRIES]; c->last.table_skips = st[STAT_TABLE_SKIPS];
+    c->last.table_declined = st[STAT_TABLE_DECLINED]; c->last.table_coarser = st[STAT_TABLE_COARSER]; c->last.table_empty = st[STAT_TABLE_EMPTY];
+    for (int k = 0; k < 8; ++k) c->last.table_phase_ticks[k] = st[STAT_TABLE_PHASE + k];
+    if (c->tune.table_diag && st[STAT_TABLE_BLOCKS]) // the table phase split by every wave's clock: staging | node loops | waiting at the chunk barriers
         fprintf(stderr, "[vrt_hip] table kernel, us per block of its table phase (%.1f): node loops %.1f, waiting at the chunk barriers %.1f, staging the rest (mean over the 16 waves)\n",
-                st[24 + 5] * 0.01 / st[7], st[22] * 0.01 / 16 / st[7], st[23] * 0.01 / 16 / st[7]);
-    c->last.lane_pairs = st[12];
-    c->last.dense_visits_full = st[13]; c->last.dense_visits_zero = st[14]; c->last.dense_visits_common = st[15];
-    c->last.dense_busy_frac = (st[11] && st[9] > st[8]) ? (double)st[10] / ((double)st[11] * (double)(st[9] - st[8])) : 0.0;
-    c->last.shaded_blocks = st[5] + st[6];
-    c->last.dense_blocks = st[6];
-    c->last.table_blocks = st[7];
-    c->last.list_entries = st[0]; c->last.tile_entries = st[1]; c->last.overflow_blocks = st[2];
-    c->last.lane_entries = st[3]; c->last.lane_max_entries = st[4];
+                st[STAT_TABLE_PHASE + 5] * 0.01 / st[STAT_TABLE_BLOCKS], st[STAT_TABLE_NODE_TICKS] * 0.01 / 16 / st[STAT_TABLE_BLOCKS],
+                st[STAT_TABLE_WAIT_TICKS] * 0.01 / 16 / st[STAT_TABLE_BLOCKS]);
+    c->last.lane_pairs = st[STAT_LANE_PAIRS];
+    c->last.dense_visits_full = st[STAT_DENSE_VISITS_FULL]; c->last.dense_visits_zero = st[STAT_DENSE_VISITS_ZERO]; c->last.dense_visits_common = st[STAT_DENSE_VISITS_COMMON];
+    c->last.dense_busy_frac = (st[STAT_DENSE_WORKGROUPS] && st[STAT_DENSE_T_LAST] > st[STAT_DENSE_T_FIRST])
+                                  ? (double)st[STAT_DENSE_BUSY_TICKS] / ((double)st[STAT_DENSE_WORKGROUPS] * (double)(st[STAT_DENSE_T_LAST] - st[STAT_DENSE_T_FIRST]))
+                                  : 0.0;
+    c->last.shaded_blocks = st[STAT_SHADED_BLOCKS] + st[STAT_DENSE_BLOCKS];
+    c->last.dense_blocks = st[STAT_DENSE_BLOCKS];
+    c->last.table_blocks = st[STAT_TABLE_BLOCKS];
+    c->last.list_entries = st[STAT_BLOCK_CANDIDATES]; c->last.tile_entries = st[STAT_TILE_ENTRIES]; c->last.overflow_blocks = st[STAT_DENSE_OVER_DCAP];
+    c->last.lane_entries = st[STAT_LANE_ENTRIES]; c->last.lane_max_entries = st[STAT_LANE_MAX_ENTRIES];
     return VRT_HIP_OK;
 }
 

@@ -329,8 +329,8 @@ int plan_frame(vrt_hip_ctx *c, const float origin[3], int pack_flags, uint32_t *
     if (o.stamp && !o.cleared) c->own_seq = 0; // the list kernel of this frame was not the fused one: nobody kept the stamps
     const TileLists &t = fa.T = work_lists(c);
     if (o.stats) { // the list kernels keep no statistics: these words belong to the block kernel and the dense kernels
-        HIPCHK(c, hipMemsetAsync(c->d_stats.p, 0, 32 * sizeof(unsigned long long), st));
-        HIPCHK(c, hipMemsetAsync(c->d_stats.p + 8, 0xFF, sizeof(unsigned long long), st)); // running minimum
+        HIPCHK(c, hipMemsetAsync(c->d_stats.p, 0, STAT_WORDS * sizeof(unsigned long long), st));
+        HIPCHK(c, hipMemsetAsync(c->d_stats.p + STAT_DENSE_T_FIRST, 0xFF, sizeof(unsigned long long), st)); // running minimum
     }
     c->timeline_items = 0;
     if (c->tune.timeline) { // the block kernel's stamps; the list kernel's go to a buffer of their own (d_timeline_lists)

@@ -149,15 +149,37 @@ struct RenderTarget {
     int sparse;
     uint32_t *keys, *sparse_hdr;
     uint32_t sparse_cap;      // capacity (cells) of the shard buffer: header word 1, locates the pixel region
-    unsigned long long *stats; // nullable: [0]=block candidates [1]=tile entries [2]=dense blocks with more than DCAP survivors
-                               // [3]=sum of lane list lengths [4]=sum over blocks of the longest lane list [5]=shaded blocks
-                               // [6]=dense blocks [7]=table blocks [8..11]=dense workgroup timeline [12]=sum over rays of (lane list length)^2
-                               // [13..15]=dense kernel: (emitter chunk, absorber) visits evaluated in full / exactly zero / exactly -2A
-                               // [16]=table kernel: sum of node counts over its blocks [17]=blocks it did at the reduced spacing
-                               // [18]=(absorber, wave) visits it settled by saturation [19]=blocks it declined [20]=blocks it did at a coarser spacing
-                               // than requested [21]=blocks of its queue that no Gaussian reaches
-                               // [24..31]=table kernel: 10-ns ticks per phase, summed over blocks   (32 words in all)
+    unsigned long long *stats; // nullable: STAT_WORDS words, indexed by RenderStat below
     unsigned long long *timeline; // nullable diagnostics: 4 wall_clock64 stamps + the hardware id per one-wave work item (5 words)
+};
+// The words of RenderTarget::stats (the kernels add to them, read_stats() in vrt_hip_diag.cpp turns them into vrt_hip_stats)
+enum RenderStat {
+    STAT_BLOCK_CANDIDATES = 0,    // survivors of the block culls
+    STAT_TILE_ENTRIES = 1,        // list entries the block culls looked at
+    STAT_DENSE_OVER_DCAP = 2,     // dense blocks with more than DCAP survivors
+    STAT_LANE_ENTRIES = 3,        // block kernel: sum of lane list lengths
+    STAT_LANE_MAX_ENTRIES = 4,    // ... sum over blocks of the longest lane list
+    STAT_SHADED_BLOCKS = 5,       // ... blocks it shaded
+    STAT_DENSE_BLOCKS = 6,        // blocks of the dense path (table kernel and exact body)
+    STAT_TABLE_BLOCKS = 7,        // ... of these, by the table kernel
+    STAT_DENSE_T_FIRST = 8,       // exact dense kernel, workgroup timeline: earliest start (running minimum) ...
+    STAT_DENSE_T_LAST = 9,        // ... latest end,
+    STAT_DENSE_BUSY_TICKS = 10,   // ... summed ticks between a workgroup's start and end,
+    STAT_DENSE_WORKGROUPS = 11,   // ... workgroups
+    STAT_LANE_PAIRS = 12,         // block kernel: sum over rays of (lane list length)^2
+    STAT_DENSE_VISITS_FULL = 13,  // exact body: (emitter chunk, absorber) visits evaluated in full,
+    STAT_DENSE_VISITS_ZERO = 14,  // ... exactly zero,
+    STAT_DENSE_VISITS_COMMON = 15, // ... exactly -2A
+    STAT_TABLE_NODES = 16,        // table kernel: sum of node counts over its blocks
+    STAT_TABLE_RETRIES = 17,      // ... blocks it did at the reduced spacing
+    STAT_TABLE_SKIPS = 18,        // ... (absorber, wave) visits it settled by saturation
+    STAT_TABLE_DECLINED = 19,     // ... blocks it declined
+    STAT_TABLE_COARSER = 20,      // ... blocks it did at a coarser spacing than requested
+    STAT_TABLE_EMPTY = 21,        // ... blocks of its queue that no Gaussian reaches
+    STAT_TABLE_NODE_TICKS = 22,   // ... 10-ns ticks in the node loops, summed over waves and blocks
+    STAT_TABLE_WAIT_TICKS = 23,   // ... and waiting at the staging groups' barriers
+    STAT_TABLE_PHASE = 24,        // ... 10-ns ticks per phase, summed over blocks: eight words (vrt_hip_stats::table_phase_ticks)
+    STAT_WORDS = 32
 };
 
 void launch_prep_frame(const SceneTables &s, float4 *gA_out, const float origin[3], hipStream_t st);

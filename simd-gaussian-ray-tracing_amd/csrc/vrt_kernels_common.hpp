@@ -465,6 +465,49 @@ __device__ __forceinline__ uint64_t out_index(const TileLists &T, const CellGrid
     }
     return O.compact ? ((uint64_t)p.lt * T.tile_h + p.pyt) * T.tile_w + p.pxt : pix;
 }
+// One block's rays, lane = ray: the lane's pixel clipped to the tile and the image (`valid`: it is a pixel of its own), where the lane
+// writes, the cell's candidate list (or, if that overflowed its slot, the tile's) and the ray.  p = block_of(cell, bi), inside its tile:
+// that (wave-uniform) test stays with the caller -- a return from in here moved every register of the exact dense kernels.  file_key: the
+// block belongs to a dense cell of a sparse shard, whose first block files the cell's key (the active cells': the list kernel).
+struct BlockRays { bool valid; uint64_t pix, out; uint32_t n_list; const uint32_t *list; LaneRay ray; };
+__device__ __forceinline__ BlockRays block_rays(const TileLists &T, const CellGrid &C, const RayGen &R, const RenderTarget &O, uint32_t cell,
+                                                uint32_t bi, bool file_key, const BlockPos &p)
+{
+    BlockRays b;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint64_t npix = (uint64_t)R.width * R.height;
+    const uint32_t tx = p.t % T.tiles_w, ty = p.t / T.tiles_w;
+    b.valid = p.pxt < T.tile_w && p.pyt < T.tile_h;
+    const uint32_t pxc = min(p.pxt, T.tile_w - 1), pyc = min(p.pyt, T.tile_h - 1);
+    b.pix = tile_pixel(T.tile_w, T.tile_h, T.stride, tx, ty, pxc, pyc);
+    if (b.pix >= npix) { b.valid = false; b.pix = npix - 1; }
+    const uint32_t n_active_cells = *C.n_active;
+    b.out = out_index(T, C, O, cell, bi, lane, p, b.pix, n_active_cells);
+    if (O.sparse && file_key && bi == 0 && tid == 0)
+        O.keys[n_active_cells + (C.slot[cell] & 0x7FFFFFFFu)] = p.t * (C.cells_x * C.cells_y) + cell % (C.cells_x * C.cells_y);
+    b.n_list = C.count[cell];
+    b.list = C.indices + (size_t)cell * C.cstride;
+    if (b.n_list == 0xFFFFFFFFu) { b.n_list = T.count[p.t]; b.list = T.indices + T.start[p.t]; }
+    b.ray = pixel_ray(R, b.pix); // every wave of a workgroup holds the same 64 rays
+    return b;
+}
+// The block cone: axis = mean of the four centre rays, angle = the farthest lane's.  DPP: lanes and extremes through the scalar unit and
+// the DPP path; otherwise through ds_bpermute_b32 (the exact dense body: the measured reason is at wave_min_bpermute above)
+template <bool DPP>
+__device__ __forceinline__ Cone block_cone(const LaneRay &ray)
+{
+    auto at = [](float v, int l) { return DPP ? lane_value(v, l) : __shfl(v, l, 64); };
+    float cx = at(ray.nx, 27) + at(ray.nx, 28) + at(ray.nx, 35) + at(ray.nx, 36);
+    float cy = at(ray.ny, 27) + at(ray.ny, 28) + at(ray.ny, 35) + at(ray.ny, 36);
+    float cz = at(ray.nz, 27) + at(ray.nz, 28) + at(ray.nz, 35) + at(ray.nz, 36);
+    {
+        const float inv = __builtin_amdgcn_rsqf(cx * cx + cy * cy + cz * cz);
+        cx *= inv; cy *= inv; cz *= inv;
+    }
+    float co, si;
+    cos_sin(ray.nx, ray.ny, ray.nz, cx, cy, cz, co, si);
+    return make_cone(cx, cy, cz, DPP ? wave_min(co) : wave_min_bpermute(co), DPP ? wave_max(si) : wave_max_bpermute(si));
+}
 
 // Gaussian q's term of the transmittance exponent from origin o along direction n up to the sample point s: rt.h:36-52, same operations
 // in the same order, unfused (see dot3_ref)

@@ -1,9 +1,7 @@
 // vrt_table_kernel.hip -- the table kernel: dense blocks through a per-ray table of the transmittance exponent.  A translation unit
 // of its own (the three kernel units compile side by side); the default scheduler (csrc/Makefile has the measurement).
 // gfx950 only: TableLds takes 145 KB of the CU's 160 KB of LDS (static_assert below).
-// Diagnostic builds (never the product): -DVRT_TABLE_FORCE=1|2|3 sends every (wave, absorber) visit down one form of the term (timing only,
-// wrong images), -DVRT_TABLE_FINE moves the phase clock's slots 1-4 inside the kink pass, -DVRT_TABLE_COUNT_CLASSES counts the one-sign and
-// the general visits into the statistics words of VRT_HIP_TABLE_DIAG (profiles/r04_experiments.md).
+// The body is a driver (render_table_body) over named phases; the diagnostic builds of round 4 are tools/experiments/table_diag_builds.patch.
 #include "vrt_dense_block.hpp"
 
 namespace vrtk {
@@ -74,10 +72,20 @@ struct TableLds {
 static_assert(sizeof(TableLds<16>) + 512 <= 160 * 1024, "TableLds must fit the 160 KB of LDS of a gfx950 CU");
 static_assert(sizeof(TableLds<8>) + 512 <= 80 * 1024, "two 8-wave workgroups share the 160 KB of LDS of a gfx950 CU");
 
+// The phase clock (statistics runs only; wall_clock64 ticks are 10 ns): the time since its last reading goes into a statistics word
+// (stamp: the phases of a block, thread 0's clock) or into a sum the caller keeps (lap: table_nodes, every wave's clock)
+struct PhaseClock {
+    unsigned long long *stats; bool live; unsigned long long t_last; // stats: RenderTarget::stats
+    __device__ __forceinline__ PhaseClock(unsigned long long *stats_, bool mine) : stats(stats_), live(stats_ && mine), t_last(live ? wall_clock64() : 0ull) {}
+    __device__ __forceinline__ unsigned long long tick() { const unsigned long long t = wall_clock64(), d = t - t_last; t_last = t; return d; }
+    __device__ __forceinline__ void stamp(int phase) { if (live) atomicAdd(&stats[STAT_TABLE_PHASE + phase], tick()); }
+    __device__ __forceinline__ void lap(unsigned long long &acc) { if (live) acc += tick(); }
+};
+
 // The rows (gA, gB) of the survivors a wave works on in one pass -- survivors first, first + 16, ... (at most 64 of them) -- fetched with ONE
-// gather, lane i loading the rows of survivor first + 16 i, and handed to the loop iteration by v_readlane_b32 (the passes used to fetch a
-// survivor's rows by scalar loads one iteration ahead).  Measured neutral (profiles/r04_experiments.md): the fixed phases are not waiting
-// for those loads, they issue ~90 instructions per survivor on four waves per SIMD; kept because the loops lose their lgkmcnt waits.
+// gather, lane i loading the rows of survivor first + 16 i, and handed to the loop iteration by v_readlane_b32.  Measured neutral against
+// scalar loads one iteration ahead (profiles/r04_experiments.md): the fixed phases issue ~90 instructions per survivor on four waves per
+// SIMD and do not wait for those loads; kept because the loops lose their lgkmcnt waits.
 template <int TB_DW>
 struct WaveRows {
     float4 a, b;
@@ -131,16 +139,11 @@ __device__ __forceinline__ void pair_terms(const Erf &erf, v2f (&acc)[NT / 2], v
 
 // one pass over the survivors for the NT nodes [g0, g0 + NT) of this wave; tab[g] = sum_j A_j (E_j - Erf(x_gj))
 //
-// Round 4, second half: what a wave does with an absorber -- nothing but one add (its Erf is saturated on all of the wave's nodes on all
-// 64 rays), the one-sign form of the term, or the general form -- used to be asked absorber by absorber inside the node loop: four vector
-// compares, their way to the scalar unit, a three-way branch whose arms the register allocator joined with a copy of every accumulator.
-// With the arms compiled in unconditionally the same loop ran 15-25 % faster than with the questions in it (VRT_TABLE_FORCE experiments,
-// profiles/r04_experiments.md).  Now the questions are asked ONCE per wave and group of 64 staged absorbers, with LANE = ABSORBER, from
-// two wave-uniform numbers per absorber that the staging pass leaves in LDS (the smallest and the largest argument offset over the 64
-// rays): five ballots give five bit masks, and five tight loops walk their set bits -- no question, no branch between forms, every
-// accumulator updated in place.  The one-sign loops run on the packed fp32 pipe (v_pk_fma_f32 / v_pk_mul_f32: two nodes per
-// instruction; 26.5 cycles per term against 36.3, tools/ubench/erf_term.hip, profiles/r04_erf_term_packed.txt) and keep
-// A (E -+ 1) out of the node sums (one fma per absorber instead of one add per term).
+// The three forms of a visit and how a wave picks one with lane = absorber: "Work split" above.  Asked inside the node loop the questions
+// cost 15-25 % of it (the forced-form experiments, profiles/r04_experiments.md): five ballots give five bit masks, and
+// five tight loops walk their set bits -- no question, no branch between forms, every accumulator updated in place.  The one-sign loops
+// run on the packed fp32 pipe (v_pk_fma_f32 / v_pk_mul_f32; 26.5 cycles per term against 36.3, tools/ubench/erf_term.hip,
+// profiles/r04_erf_term_packed.txt) and keep A (E -+ 1) out of the node sums (one fma per absorber instead of one add per term).
 //
 // The sums: tab[g] = [sum over the saturated and one-sign absorbers of A (E -+ 1)] + [sum of +-A R(|x_g|)] + [general terms]; the first
 // bracket is common to the wave's nodes.  Rounding is at the magnitude of sum |A_j| (< 60, or the block is shaded exactly) times 2^-24 per
@@ -149,15 +152,11 @@ template <int EXP, int ERF, int NT, int TB_DW>
 __device__ __forceinline__ void table_nodes(const SceneTables &S, TableLds<TB_DW> &lds, uint32_t cnt, const LaneRay &ray,
                                             float s_seg /* node 0 of this segment's table on this lane's ray */, float h, uint32_t g0,
                                             uint32_t wave, uint32_t lane, uint32_t &n_skip,
-                                            unsigned long long *diag /* nullable: statistics runs */)
+                                            unsigned long long *stats /* RenderTarget::stats, nullable: statistics runs */)
 {
-    // diagnostics (statistics runs, every wave's clock; stats words 22, 23): ticks in the node loops and waiting at the group barriers
-    unsigned long long d_stage = 0, d_loop = 0, d_wait = 0, d_t = diag ? wall_clock64() : 0ull;
-#ifdef VRT_TABLE_COUNT_CLASSES
-    auto lap = [&](unsigned long long &) {};
-#else
-    auto lap = [&](unsigned long long &acc) { if (diag) { const unsigned long long t = wall_clock64(); acc += t - d_t; d_t = t; } };
-#endif
+    // diagnostics (statistics runs, every wave's clock): ticks in the node loops and waiting at the group barriers
+    unsigned long long d_stage = 0, d_loop = 0, d_wait = 0;
+    PhaseClock clock(stats, true);
     constexpr float SAT_M = table_saturation<ERF>() + 1e-3f;
     constexpr bool AS = ERF == VRT_ERF_AS;
     constexpr int TB_GMAX = TableCfg<TB_DW>::GMAX, TB_STAGE = TableCfg<TB_DW>::STAGE;
@@ -173,10 +172,9 @@ __device__ __forceinline__ void table_nodes(const SceneTables &S, TableLds<TB_DW
     const float s_first = __builtin_fmaf((float)g0, h, s_seg);        // this lane's position of node g0
     // Staging: the per-(ray, absorber) values (A, m, E) of up to TB_STAGE = 128 absorbers at a time go into the memory of the TABLE itself
     // -- it is written only at the end of this function, and until then its 96 KB are free: three [128][64] float arrays.  Wave w stages
-    // absorbers w, w + 16, ... of the group, one barrier, then every wave walks the whole group without another barrier (rounds 1-3
-    // staged 16 at a time, a barrier per 16: the waves of a SIMD do not run in step -- the arbiter favours the oldest -- so every barrier
-    // had early finishers idling).  Per absorber also r and the range [cmin, cmax] over the 64 rays of c = s_seg r - m: the argument of
-    // node g on a ray is c + g h r.
+    // absorbers w, w + 16, ... of the group, one barrier, then every wave walks the whole group without another barrier (the waves of a SIMD
+    // do not run in step -- the arbiter favours the oldest -- so every barrier has early finishers idling).  Per absorber also r and the
+    // range [cmin, cmax] over the 64 rays of c = s_seg r - m: the argument of node g on a ray is c + g h r.
     static_assert(TB_GMAX * 64 == 3 * TB_STAGE * 64, "three staging arrays fill the table exactly");
     float(*stA)[64] = reinterpret_cast<float(*)[64]>(&lds.tab[0][0]);
     float(*stM)[64] = stA + TB_STAGE;
@@ -197,9 +195,9 @@ __device__ __forceinline__ void table_nodes(const SceneTables &S, TableLds<TB_DW
             const float c_lo = wave_min(c), c_hi = wave_max(c);
             if (lane == 0) { lds.st_r[jj] = pb.x; lds.st_cmin[jj] = c_lo; lds.st_cmax[jj] = c_hi; }
         }
-        lap(d_stage);
+        clock.lap(d_stage);
         __syncthreads();
-        lap(d_wait);
+        clock.lap(d_wait);
         for (uint32_t half = 0; half < nb; half += 64) {
             // ---- the questions, lane = absorber: is Erf saturated (-1: the absorber lies behind the wave's nodes, +1: in front) on all
             //      nodes and rays?  Is the argument of one sign on all of them (all but the absorbers whose kink lies inside the range)?
@@ -212,20 +210,12 @@ __device__ __forceinline__ void table_nodes(const SceneTables &S, TableLds<TB_DW
                 const bool in = j < nb;
                 const uint32_t jc = in ? j : 0u;
                 const float r_j = lds.st_r[jc], x_lo = __builtin_fmaf(g0h, r_j, lds.st_cmin[jc]), x_hi = __builtin_fmaf(g1h, r_j, lds.st_cmax[jc]);
-#if defined(VRT_TABLE_FORCE)   /* timing experiments only (wrong images): every visit on one form */
-                const bool b_lo = in && VRT_TABLE_FORCE == 3, b_hi = false, b_pos = in && VRT_TABLE_FORCE == 1, b_neg = false;
-#else
                 const bool b_lo = in && x_hi <= -SAT_M, b_hi = in && x_lo >= SAT_M;
                 const bool b_pos = AS && in && !b_hi && x_lo >= 0.f, b_neg = AS && in && !b_lo && !b_pos && x_hi <= 0.f;
-#endif
                 m_lo = __ballot(b_lo); m_hi = __ballot(b_hi); m_pos = __ballot(b_pos); m_neg = __ballot(b_neg);
                 m_gen = __ballot(in && !(b_lo | b_hi | b_pos | b_neg));
             }
             n_skip += (uint32_t)__popcll(m_lo) + (uint32_t)__popcll(m_hi);
-#ifdef VRT_TABLE_COUNT_CLASSES   /* diagnostic build: stats words 22 / 23 = one-sign / general (wave, absorber) visits instead of the clocks */
-            d_loop += (unsigned long long)__popcll(m_pos) + (unsigned long long)__popcll(m_neg);
-            d_wait += (unsigned long long)__popcll(m_gen);
-#endif
             // ---- saturated: E - Erf = E + 1 or E - 1 on every node ----
             auto walk_AE = [&](unsigned long long mask, auto &&body) {
                 if (!mask) return;
@@ -277,27 +267,321 @@ __device__ __forceinline__ void table_nodes(const SceneTables &S, TableLds<TB_DW
                 }
             });
         }
-        lap(d_loop);
+        clock.lap(d_loop);
         __syncthreads(); // everyone is done with the staged values: the next group, or the table itself, goes into their memory
-        lap(d_wait);
+        clock.lap(d_wait);
     }
-    if (diag && lane == 0) { atomicAdd(&diag[0], d_loop); atomicAdd(&diag[1], d_wait); } // summed over the 16 waves (staging = the rest of the table phase)
+    if (clock.live && lane == 0) { atomicAdd(&stats[STAT_TABLE_NODE_TICKS], d_loop); atomicAdd(&stats[STAT_TABLE_WAIT_TICKS], d_wait); } // summed over the waves (staging = the rest of the table phase)
 #pragma unroll
     for (int t = 0; t < NT; ++t)
         if (g0 + t < (uint32_t)TB_GMAX) lds.tab[g0 + t][lane] = ((t & 1) ? acc[t / 2].y : acc[t / 2].x) + common;
 }
+// ---- The phases of one block, in the order the driver (render_table_body) runs them; all DW * 64 threads call each of them. ----
+// what every phase works on: the block's survivors (lds.idx[0, cnt), in list order) and this lane's ray
+template <int DW> struct TableBlock { const SceneTables &S; TableLds<DW> &lds; const LaneRay &ray; uint32_t cnt, wave, lane; };
 
+// Every ray has its own grid of Gtot nodes from its first sample on (two nodes of margin at either end, so that every sample has its
+// four neighbours), all with the block's spacing h (u = h r_max: in units of 1/r of the narrowest Gaussian; lo: this lane's node 0).
+// The table holds TB_GMAX nodes: a deeper range is worked off in nseg segments of SL intervals (+ the margins); a sample belongs to the
+// segment its interval lies in.  Segments in empty space cost next to nothing: every absorber is saturated there.  The waves evaluate
+// NT nodes each, NT from a short menu (G = NT DW nodes per segment): the spacing is then REDUCED until the segments fill them exactly.
+struct TablePlan {
+    float h, u, lo, inv_h;
+    uint32_t nseg, SL, G, NT, Gtot;
+    bool fits; // false: the range needs more than 8 segments at this spacing, or the spacing is beyond the error study's u <= 0.3
+    __device__ __forceinline__ float node0(uint32_t seg) const { return (float)(seg * SL) - 2.f; } // a segment's first node on the ray's grid
+};
+// the plan for the block's longest sample range `range` at (no more than) the spacing ht; s_lo: this lane's first sample
+template <int DW>
+__device__ __forceinline__ TablePlan table_plan(float range, float ht, float s_lo, float r_max)
+{
+    constexpr int TB_GMAX = TableCfg<DW>::GMAX;
+    TablePlan P = {};
+    const float need = ceilf(range / ht); // intervals the samples span
+    if (!(need < 8.f * (float)(TB_GMAX - 8))) return P;
+    P.nseg = max(1u, ((uint32_t)need + (uint32_t)(TB_GMAX - 8) - 1u) / (uint32_t)(TB_GMAX - 8));
+    const uint32_t sl_need = max(1u, ((uint32_t)need + P.nseg - 1u) / P.nseg);
+    const uint32_t nt = (sl_need + 8u + DW - 1) / DW;
+    P.NT = nt <= 4 ? 4 : nt <= 6 ? 6 : nt <= 8 ? 8 : nt <= 12 ? 12 : nt <= 16 ? 16 : nt <= 20 ? 20 : 24;
+    // intervals per segment; nodes in the table: the segment's intervals, two nodes before them, and up to six behind
+    // the last one (the samples' intervals start at 2 and end at Gtot - 4 <= nseg SL + 2, whose stencil ends at nseg SL + 4)
+    P.G = P.NT * DW; P.SL = P.G - 8u;
+    P.h = fminf(ht, range / (float)(P.nseg * P.SL) * 1.00001f);
+    if (!(P.h > 0.f)) P.h = ht; // range == 0: one sample point per ray
+    P.u = P.h * r_max; P.Gtot = P.nseg * P.SL + 6u;
+    P.lo = s_lo - 2.f * P.h; P.inv_h = 1.f / P.h;
+    P.fits = P.u <= 0.3f;
+    return P;
+}
+// the runtime NT of a plan as a template argument: f is called with the menu's entry as a compile-time constant (TableNT<N>::value)
+template <int N> struct TableNT { static constexpr int value = N; };
+template <typename F>
+__device__ __forceinline__ void with_table_nt(uint32_t nt, F &&f)
+{
+    switch (nt) {
+    case 4: f(TableNT<4>()); break;   case 6: f(TableNT<6>()); break;   case 8: f(TableNT<8>()); break;
+    case 12: f(TableNT<12>()); break; case 16: f(TableNT<16>()); break; case 20: f(TableNT<20>()); break;
+    default: f(TableNT<24>()); break;
+    }
+}
+// ---- sample range: this lane's ray's first and last sample over the survivors, and r_max = r of the block's narrowest Gaussian.  Wave w
+//      looks at survivors w, w + DW, ... (the wave's rows by one gather per 64 DW survivors: WaveRows; here and in the passes below);
+//      the waves' parts meet in lds.red[0], lds.red[1] and s_rmax, free again on return (two barriers). ----
+struct TableRange { float s_lo, s_hi, r_max; };
+template <int DW>
+__device__ __forceinline__ TableRange table_sample_range(const TableBlock<DW> &B, float (&s_rmax)[DW])
+{
+    const SceneTables &S = B.S; TableLds<DW> &lds = B.lds; const LaneRay &ray = B.ray; const uint32_t cnt = B.cnt, wave = B.wave, lane = B.lane;
+    float s_lo = INFINITY, s_hi = -INFINITY, r_max = 0.f;
+    for (uint32_t first = wave; first < cnt; first += 64u * DW) {
+        WaveRows<DW> rows;
+        rows.load(S, lds.idx, first, cnt, lane);
+        const uint32_t n_it = WaveRows<DW>::count(first, cnt);
+        for (uint32_t i = 0; i < n_it; ++i) {
+            const float4 a = rows.A(i);
+            const float r = WaveRows<DW>::rl(rows.b.x, i);
+            const float mubar = dot3_ref(a.x, a.y, a.z, ray.nx, ray.ny, ray.nz);
+            s_hi = fmaxf(s_hi, mubar);
+            s_lo = fminf(s_lo, mubar - 2.8285f / r); // mubar - 4 sigma, sigma = 1/(sqrt2 r), rounded outwards
+            r_max = fmaxf(r_max, r);
+        }
+    }
+    lds.red[0][wave][lane] = s_hi; lds.red[1][wave][lane] = s_lo;
+    if (lane == 0) s_rmax[wave] = r_max;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < DW; ++w) {
+        s_hi = fmaxf(s_hi, lds.red[0][w][lane]); s_lo = fminf(s_lo, lds.red[1][w][lane]);
+        r_max = fmaxf(r_max, s_rmax[w]);
+    }
+    __syncthreads();
+    return { s_lo, s_hi, r_max };
+}
+// ---- kink pass for one segment: wave w takes absorbers w, w + DW, ...: the weight of the kink of j (TB_W0 units, fixed point, rounded
+//      up; integer adds: the order of the atomics does not matter) into the interval of mubar_j and its two neighbours; with `sums` also
+//      S_all = sum |A_j|.  Leaves lds.hist[0, G) (the table's memory) and, with `sums`, lds.red[3]; two barriers, the last one before
+//      the weights are complete for every wave. ----
+template <int EXP, int DW>
+__device__ __forceinline__ void table_kink_pass(const TableBlock<DW> &B, const TablePlan &P, uint32_t seg, bool sums, float &S_all)
+{
+    const SceneTables &S = B.S; TableLds<DW> &lds = B.lds; const LaneRay &ray = B.ray; const uint32_t cnt = B.cnt, wave = B.wave, lane = B.lane, G = P.G;
+    const float lo = P.lo, inv_h = P.inv_h, node0 = P.node0(seg);
+    for (uint32_t g = wave; g < G; g += DW) lds.hist[g][lane] = 0u;
+    __syncthreads();
+    float s_part = 0.f;
+    for (uint32_t first = wave; first < cnt; first += 64u * DW) {
+        WaveRows<DW> rows;
+        rows.load(S, lds.idx, first, cnt, lane);
+        const uint32_t n_it = WaveRows<DW>::count(first, cnt);
+        for (uint32_t i = 0; i < n_it; ++i) {
+            const float4 ca = rows.A(i), cb = rows.B(i);
+            const float mubar = dot3_ref(ca.x, ca.y, ca.z, ray.nx, ray.ny, ray.nz);
+            const float d2 = sub_ref(ca.w, mul_ref(mubar, mubar));
+            const float A = cb.z * vexp<EXP>(-(d2 * cb.y));
+            if (sums) s_part += fabsf(A);
+            const float pos = (mubar - lo) * inv_h;
+            const float gb = floorf(pos);
+            const float th = fminf(fmaxf(pos - gb, 0.f), 1.f);
+            const float a16 = fminf(fabsf(A), 60.f) * 65536.f;
+            const float gl = gb - node0; // interval of the kink in this segment's table
+            if (gl >= 0.f && gl < (float)G) atomicAdd(&lds.hist[(uint32_t)gl][lane], (uint32_t)ceilf(a16 * fminf(1.f, 0.28f + 2.58f * fabsf(th - 0.5f))));
+            if (gl + 1.f >= 0.f && gl + 1.f < (float)G) atomicAdd(&lds.hist[(uint32_t)(gl + 1.f)][lane], (uint32_t)ceilf(a16 * th * th));
+            if (gl - 1.f >= 0.f && gl - 1.f < (float)G) atomicAdd(&lds.hist[(uint32_t)(gl - 1.f)][lane], (uint32_t)ceilf(a16 * (1.f - th) * (1.f - th)));
+        }
+    }
+    if (sums) lds.red[3][wave][lane] = s_part;
+    __syncthreads();
+    if (sums) {
+        S_all = 0.f;
+#pragma unroll
+        for (int w = 0; w < DW; ++w) S_all += lds.red[3][w][lane];
+    }
+}
+// ---- spacing choice (first attempt, CellGrid::table_adapt > 1): how much coarser than requested may the nodes be?  An ESTIMATE of the
+//      bound the emission pass will find, from the kink weights: emission of interval g ~ 1.4 D_g T_g with D_g = K_g / 1.35 the absorber
+//      mass of the interval and T_g = exp(-2 sum of the mass before it); the estimate scales with the spacing like rho^3 (kink part) and
+//      rho^4 (smooth part).  It only picks the spacing: the bound itself is checked by table_bound_store, and a block that fails it is
+//      redone at 0.6 of the spacing.  The weights are taken at the COARSEST spacing the settings and the menu of table sizes allow: 44-48 %
+//      of the blocks of the OBJ scenes keep that spacing, and for them these weights are the final ones; the others scale the estimate
+//      DOWN to the finer candidates.  P: in, the plan at the requested spacing h_target; out, the chosen one.  W: what the passes made
+//      here leave behind.  false: the block is declined.  Works in lds.hist, lds.red[0], lds.red[1], lds.red[3]. ----
+// S_all = sum |A_j| over the survivors, per ray (it does not depend on the spacing), once have_sums; have_kinks: the kink weights of
+// segment 0 at the final spacing are in LDS
+struct TableWeights { float S_all; bool have_kinks, have_sums; };
+template <int EXP, int ERF, int DW>
+__device__ __forceinline__ bool table_choose_spacing(const TableBlock<DW> &B, const CellGrid &C, const RenderTarget &O, float range, const TableRange &rg,
+                                                     float h_target, bool valid, TablePlan &P, TableWeights &W)
+{
+    TableLds<DW> &lds = B.lds; const uint32_t wave = B.wave, lane = B.lane;
+    const float h_r = P.h, u_r = P.u; // the requested spacing, as the menu of table sizes rounds it
+    const uint32_t nodes_r = P.nseg * P.NT;
+    auto menu = [](int c) { return c == 0 ? 3.f : c == 1 ? 2.5f : c == 2 ? 2.f : c == 3 ? 1.6f : 1.3f; };
+    float k_max = 1.f;
+#pragma unroll
+    for (int c = 4; c >= 0; --c)
+        if (menu(c) <= C.table_adapt && menu(c) * u_r <= 0.3f) k_max = menu(c);
+    if (k_max > 1.f && (P = table_plan<DW>(range, h_r * k_max, rg.s_lo, rg.r_max)).fits && P.nseg * P.NT < nodes_r) {
+        const float h_c = P.h;
+        float Pm = 0.f, pin = 0.f, pout = 0.f;
+        for (uint32_t seg = 0; seg < P.nseg; ++seg) {
+            table_kink_pass<EXP>(B, P, seg, seg == 0, W.S_all);
+            const uint32_t ga = seg ? 2u : 0u, gz = min(P.G, P.SL + 2u); // the segment's own intervals
+            const uint32_t wa = min(gz, ga + wave * P.NT), wz = min(gz, wa + P.NT);
+            float mass = 0.f;
+            for (uint32_t g = wa; g < wz; ++g) mass += (float)lds.hist[g][lane];
+            lds.red[0][wave][lane] = mass * (1.f / (1.35f * 65536.f));
+            __syncthreads();
+            float before = Pm, total = 0.f;
+#pragma unroll
+            for (int w = 0; w < DW; ++w) {
+                const float mw = lds.red[0][w][lane];
+                before += (uint32_t)w < wave ? mw : 0.f;
+                total += mw;
+            }
+            for (uint32_t g = wa; g < wz; ++g) {
+                const float Kg = (float)lds.hist[g][lane] * (1.f / 65536.f), D = Kg * (1.f / 1.35f);
+                const float e = 1.4f * D * __expf(-2.f * before);
+                pin = __builtin_fmaf(e, Kg, pin); pout += e;
+                before += D;
+            }
+            Pm += total;
+            __syncthreads(); // red[0] is rewritten by the next segment
+        }
+        W.have_sums = true;
+        lds.red[0][wave][lane] = pin; lds.red[1][wave][lane] = pout;
+        __syncthreads();
+        float pin_t = 0.f, pout_t = 0.f;
+#pragma unroll
+        for (int w = 0; w < DW; ++w) { pin_t += lds.red[0][w][lane]; pout_t += lds.red[1][w][lane]; }
+        const float u = P.u, S_all = W.S_all;
+        const float est_in = 1.01f * TB_W0 * u * u * pin_t, est_out = 1.01f * TB_COUT * (u * u) * (u * u) * S_all * pout_t, est_sat = 1.01f * table_saturation_eps<ERF>() * S_all * pout_t;
+        const float room = C.table_room * C.table_budget;
+        // the coarsest candidate whose estimate leaves room: k_max itself with the weights as they are (rho = 1), the finer
+        // ones by scaling; none: the requested spacing
+        float kappa = 1.f;
+#pragma unroll
+        for (int c = 0; c < 5; ++c) {
+            const float k = menu(c), rho = k == k_max ? 1.f : h_r * k / h_c;
+            if (kappa == 1.f && k <= k_max && rho * rho * rho * (est_in + rho * est_out) + est_sat <= room) kappa = k;
+        }
+        kappa = wave_min(valid ? kappa : k_max); // the same in every wave: they hold the same rays
+        __syncthreads();
+        if (kappa == k_max) W.have_kinks = P.nseg == 1u; // segment 0's weights at this spacing are still in LDS
+        else if (kappa == 1.f || !(P = table_plan<DW>(range, h_r * kappa, rg.s_lo, rg.r_max)).fits || P.nseg * P.NT >= nodes_r) { // (the menu has no smaller table: as requested)
+            if (!(P = table_plan<DW>(range, h_target, rg.s_lo, rg.r_max)).fits) return false;
+        }
+    } else if (!(P = table_plan<DW>(range, h_target, rg.s_lo, rg.r_max)).fits) return false; // no coarser table to be had: no estimate either
+    if (O.stats && threadIdx.x == 0 && P.h != h_r) atomicAdd(&O.stats[STAT_TABLE_COARSER], 1ull);
+    return true;
+}
+// ---- emission for one segment: the emitters are dealt to the waves (emitter i of wave w: w, w + DW, ...; the five rows of the NEXT
+//      emitter are requested before this one's samples); X(s_ik) by 4-point Lagrange interpolation in lds.tab for the samples of this
+//      segment; the error bound's two sums (kink part from lds.s3, smooth part) are accumulated beside the radiance.  No barrier. ----
+struct TableSums { float Lr, Lg, Lb, La, b_in, b_out; };
+template <int EXP, int DW>
+__device__ __forceinline__ void table_emit_segment(const TableBlock<DW> &B, const TablePlan &P, uint32_t seg, TableSums &acc)
+{
+    const SceneTables &S = B.S; TableLds<DW> &lds = B.lds; const LaneRay &ray = B.ray; const uint32_t cnt = B.cnt, wave = B.wave, lane = B.lane, nseg = P.nseg, SL = P.SL, Gtot = P.Gtot;
+    const float lo = P.lo, inv_h = P.inv_h, node0 = P.node0(seg);
+    float &Lr = acc.Lr, &Lg = acc.Lg, &Lb = acc.Lb, &La = acc.La, &b_in = acc.b_in, &b_out = acc.b_out;
+    const float seg_lo = (float)(seg * SL), seg_hi = seg + 1 == nseg ? INFINITY : (float)((seg + 1) * SL);
+    struct Rows { float4 a, ms, alb; float inv2s2, q; } nx = {};
+    auto fetch_rows = [&](uint32_t i) {
+        const uint32_t idx = __builtin_amdgcn_readfirstlane(lds.idx[i]);
+        nx.a = uload(S.gA, idx); nx.ms = uload(S.mu_sig, idx); nx.alb = uload(S.gC, idx);
+        nx.inv2s2 = uload(S.gB, idx).y; nx.q = uload(S.gD, idx).y;
+    };
+    if (wave < cnt) fetch_rows(wave);
+    for (uint32_t i = wave; i < cnt; i += DW) {
+        const Rows cur = nx;
+        if (i + DW < cnt) fetch_rows(i + DW);
+        const float4 a = cur.a, ms = cur.ms, alb = cur.alb;
+        const float inv2s2 = cur.inv2s2, q = cur.q;
+        const float e_mubar = dot3_ref(a.x, a.y, a.z, ray.nx, ray.ny, ray.nz);
+        if (nseg > 1u) { // an emitter none of whose samples lies in this segment on any ray adds exact zeros: skipped
+            const float g_a = floorf((madd_ref(-4.f, ms.w, e_mubar) - lo) * inv_h), g_b = floorf((e_mubar - lo) * inv_h);
+            const float gi_a = fminf(fmaxf(g_a, 2.f), (float)(Gtot - 4)), gi_b = fminf(fmaxf(g_b, 2.f), (float)(Gtot - 4));
+            if (!__any(gi_b >= seg_lo && gi_a < seg_hi)) continue;
+        }
+        float inner = 0.f, inner_abs = 0.f, inner_s3 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const float sk = madd_ref((float)(k - 4), ms.w, e_mubar);
+            const float uu = (sk - lo) * inv_h;
+            const float gi = fminf(fmaxf(floorf(uu), 2.f), (float)(Gtot - 4)); // interval on the ray's grid
+            const bool mine = nseg == 1 || (gi >= seg_lo && gi < seg_hi);
+            const float gfl = mine ? gi - node0 : 2.f; // ... and in the table
+            const float t = uu - (gfl + node0);
+            const uint32_t g = (uint32_t)gfl;
+            const float px = sub_ref(madd_ref(ray.nx, sk, ray.ox), ms.x);
+            const float py = sub_ref(madd_ref(ray.ny, sk, ray.oy), ms.y);
+            const float pz = sub_ref(madd_ref(ray.nz, sk, ray.oz), ms.z);
+            const float dd = dot3_ref(px, py, pz, px, py, pz);
+            const float tm1 = t - 1.f, tm2 = t - 2.f, tp1 = t + 1.f;
+            const float w0 = t * tm1 * tm2 * (-1.f / 6.f), w1 = tp1 * tm1 * tm2 * 0.5f;
+            const float w2 = tp1 * t * tm2 * -0.5f, w3 = tp1 * t * tm1 * (1.f / 6.f);
+            const float X = w0 * lds.tab[g - 1][lane] + w1 * lds.tab[g][lane] + w2 * lds.tab[g + 1][lane] + w3 * lds.tab[g + 2][lane];
+            const float term = mine ? emission_term<EXP>(q, dd * inv2s2, X) : 0.f;
+            inner += term;
+            inner_abs += fabsf(term);
+            inner_s3 = __builtin_fmaf(fabsf(term), (float)lds.s3[g][lane], inner_s3);
+        }
+        Lr = __builtin_fmaf(alb.x, inner, Lr);
+        Lg = __builtin_fmaf(alb.y, inner, Lg);
+        Lb = __builtin_fmaf(alb.z, inner, Lb);
+        La = __builtin_fmaf(alb.w, inner, La);
+        const float amax = fmaxf(fmaxf(fabsf(alb.x), fabsf(alb.y)), fmaxf(fabsf(alb.z), fabsf(alb.w)));
+        b_in = __builtin_fmaf(amax, inner_s3, b_in);
+        b_out = __builtin_fmaf(amax, inner_abs, b_out);
+    }
+}
+// ---- bound and store: the waves' partial radiances (lds.L) and bound sums (the table's memory) are summed in wave order by wave 0, which
+//      forms every ray's bound, stores the block's pixels if ALL its rays keep the budget, and leaves that decision in s_flag.  Two
+//      barriers: behind the partial sums and behind s_flag. ----
+template <int ERF, int DW>
+__device__ __forceinline__ void table_bound_store(const TableBlock<DW> &B, const CellGrid &C, const RenderTarget &O, const BlockRays &blk,
+                                                  const TablePlan &P, float S_all, const TableSums &acc, uint32_t &s_flag)
+{
+    TableLds<DW> &lds = B.lds; const uint32_t wave = B.wave, lane = B.lane; const float u = P.u;
+    lds.L[wave][lane] = make_float4(acc.Lr, acc.Lg, acc.Lb, acc.La);
+    float2 *bparts = reinterpret_cast<float2 *>(&lds.tab[0][0]); // [DW][64]
+    bparts[wave * 64 + lane] = make_float2(acc.b_in, acc.b_out);
+    __syncthreads();
+    if (wave == 0) {
+        const float4 sum = wave_order_sum<DW>(lds.L, lane);
+        float2 bs = bparts[lane];
+#pragma unroll
+        for (int w = 1; w < DW; ++w) {
+            const float2 bv = bparts[w * 64 + lane];
+            bs.x += bv.x; bs.y += bv.y;
+        }
+        // worst-case change of this ray's radiance (header comment); e^dX - 1 <= 1.01 dX for the dX in question
+        const float e_in = TB_W0 * u * u, e_out = TB_COUT * (u * u) * (u * u) + table_saturation_eps<ERF>();
+        const float bound = 1.01f * S_all * (e_in * (1.f / 255.f) * bs.x + e_out * bs.y);
+        // (false for NaN; S_all beyond the fixed-point range of the weights: no bound)
+        const bool good = !blk.valid || (bound <= C.table_budget && S_all < 60.f);
+        const bool all_good = __all(good);
+        if (all_good && blk.valid) {
+            if (O.image) O.image[blk.out] = pack_pixel(sum.x, sum.y, sum.z, sum.w, O.pack_flags);
+            if (O.radiance) O.radiance[blk.out] = sum;
+        }
+        if (lane == 0) s_flag = all_good ? 1u : 0u;
+    }
+    __syncthreads();
+}
+// ---- The driver: persistent DW-wave workgroups pull blocks from the dense queue, shade them phase by phase -- at most two attempts, the second
+//      at 0.6 of the spacing -- and what the table declines exactly, in the table's LDS.  clock.stamp(k) closes slot k of vrt_hip_stats::
+//      table_phase_ticks: 0 set-up, 1 cull, 2 sample range, 3 spacing choice, 4 kink weights, 5 table, 6 emission, 7 bound and store. ----
 template <int EXP, int ERF, int DW>
 __device__ __forceinline__ void render_table_body(const SceneTables &S, const TileLists &T, const CellGrid &C, const RayGen &R,
                                                   const RenderTarget &O)
 {
-    constexpr int TC = TableCfg<DW>::TC, TB_GMAX = TableCfg<DW>::GMAX, TB_DW = DW;
+    constexpr int TC = TableCfg<DW>::TC;
     __shared__ TableLds<DW> lds;
     __shared__ uint32_t s_wave_cnt[DW];
     __shared__ float s_rmax[DW];
     __shared__ uint32_t s_item, s_flag;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t npix = (uint64_t)R.width * R.height;
     const uint32_t n_dense16 = *C.n_dense * 16u, n_items = n_dense16 + *C.n_overflow;
     if (C.feedback && blockIdx.x == 0 && tid == 0) {
         __hip_atomic_store(&C.feedback[2], n_items, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -313,407 +597,92 @@ __device__ __forceinline__ void render_table_body(const SceneTables &S, const Ti
         __syncthreads();
         const uint32_t item = s_item;
         if (item >= n_items) break;
-        // phase clock (statistics runs only): thread 0 adds the time since the last stamp to stats[24 + phase]
-        unsigned long long t_last = (O.stats && tid == 0) ? wall_clock64() : 0ull;
-        auto stamp = [&](int phase) {
-#ifdef VRT_TABLE_FINE   /* diagnostic build: slots 1-4 belong to the inside of kink_pass */
-            if (phase >= 1 && phase <= 4) phase = 0;
-#endif
-            if (O.stats && tid == 0) { const unsigned long long t = wall_clock64(); atomicAdd(&O.stats[24 + phase], t - t_last); t_last = t; }
-        };
+        PhaseClock clock(O.stats, tid == 0);
         uint32_t cell, bi;
         if (item < n_dense16) { cell = dense_queue[item >> 4]; bi = item & 15u; }
         else { const uint32_t packed = C.overflow[item - n_dense16]; cell = packed >> 4; bi = packed & 15u; }
         const BlockPos p = block_of(T, C, O, cell, bi, lane);
         if (!p.inside) continue;
-        const uint32_t tx = p.t % T.tiles_w, ty = p.t / T.tiles_w;
-        bool valid = p.pxt < T.tile_w && p.pyt < T.tile_h;
-        const uint32_t pxc = min(p.pxt, T.tile_w - 1), pyc = min(p.pyt, T.tile_h - 1);
-        uint64_t pix = tile_pixel(T.tile_w, T.tile_h, T.stride, tx, ty, pxc, pyc);
-        if (pix >= npix) { valid = false; pix = npix - 1; }
-        const uint32_t n_active_cells = *C.n_active;
-        const uint64_t out = out_index(T, C, O, cell, bi, lane, p, pix, n_active_cells);
-        if (O.sparse && item < n_dense16 && bi == 0 && tid == 0) // a dense cell's key (the active cells' are filed by the list kernel)
-            O.keys[n_active_cells + (C.slot[cell] & 0x7FFFFFFFu)] = p.t * (C.cells_x * C.cells_y) + cell % (C.cells_x * C.cells_y);
-
-        uint32_t n_list = C.count[cell];
-        const uint32_t *list = C.indices + (size_t)cell * C.cstride;
-        if (n_list == 0xFFFFFFFFu) { n_list = T.count[p.t]; list = T.indices + T.start[p.t]; }
-
-        const LaneRay ray = pixel_ray(R, pix); // every wave holds the same 64 rays
-        float cx = lane_value(ray.nx, 27) + lane_value(ray.nx, 28) + lane_value(ray.nx, 35) + lane_value(ray.nx, 36);
-        float cy = lane_value(ray.ny, 27) + lane_value(ray.ny, 28) + lane_value(ray.ny, 35) + lane_value(ray.ny, 36);
-        float cz = lane_value(ray.nz, 27) + lane_value(ray.nz, 28) + lane_value(ray.nz, 35) + lane_value(ray.nz, 36);
-        {
-            const float inv = __builtin_amdgcn_rsqf(cx * cx + cy * cy + cz * cz);
-            cx *= inv; cy *= inv; cz *= inv;
-        }
-        float co, si;
-        cos_sin(ray.nx, ray.ny, ray.nz, cx, cy, cz, co, si);
-        const Cone cone = make_cone(cx, cy, cz, wave_min(co), wave_max(si));
-        stamp(0);
-
-        // ---- cooperative block cull, order preserving across the 16 waves (as in the exact kernel) ----
-        uint32_t cnt = 0;
-        for (uint32_t base = 0; base < n_list; base += DW * 64) {
-            const uint32_t k = base + tid;
-            bool keep = false;
-            uint32_t idx = 0;
-            if (k < n_list) {
-                idx = list[k];
-                float4 bq = S.gB[idx];
-                bq.w = slack_cull_x(bq.w, level_slack(T.cull_ref_n, n_list), T.floor_x);
-                keep = cone_keeps(cone, S.gA[idx], bq);
-            }
-            const unsigned long long mask = __ballot(keep);
-            if (lane == 0) s_wave_cnt[wave] = (uint32_t)__popcll(mask);
-            __syncthreads();
-            uint32_t before = 0, chunk = 0;
-#pragma unroll
-            for (uint32_t wv = 0; wv < DW; ++wv) {
-                const uint32_t c = s_wave_cnt[wv];
-                before += (wv < wave) ? c : 0;
-                chunk += c;
-            }
-            const uint32_t pos = cnt + before + lane_rank(mask);
+        const BlockRays blk = block_rays(T, C, R, O, cell, bi, item < n_dense16, p);
+        const Cone cone = block_cone<true>(blk.ray);
+        clock.stamp(0);
+        const uint32_t cnt = block_cull<DW>(S, T, s_wave_cnt, blk.list, blk.n_list, cone, [&](bool keep, uint32_t pos, uint32_t idx, float4) {
             if (keep && pos < TC) lds.idx[pos] = idx;
-            cnt += chunk;
-            __syncthreads();
-        }
-
-        stamp(1);
+        });
+        clock.stamp(1);
         if (cnt == 0) { // nothing reaches this block (the rim of a dense cell): background
-            if (wave == 0 && valid) {
-                if (O.image) O.image[out] = pack_pixel(0.f, 0.f, 0.f, 0.f, O.pack_flags);
-                if (O.radiance) O.radiance[out] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (wave == 0 && blk.valid) {
+                if (O.image) O.image[blk.out] = pack_pixel(0.f, 0.f, 0.f, 0.f, O.pack_flags);
+                if (O.radiance) O.radiance[blk.out] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
-            if (O.stats && tid == 0) { atomicAdd(&O.stats[1], (unsigned long long)n_list); atomicAdd(&O.stats[6], 1ull); atomicAdd(&O.stats[7], 1ull); atomicAdd(&O.stats[21], 1ull); }
+            if (O.stats && tid == 0) { atomicAdd(&O.stats[STAT_TILE_ENTRIES], (unsigned long long)blk.n_list); atomicAdd(&O.stats[STAT_DENSE_BLOCKS], 1ull); atomicAdd(&O.stats[STAT_TABLE_BLOCKS], 1ull); atomicAdd(&O.stats[STAT_TABLE_EMPTY], 1ull); }
             continue;
         }
-        // ---- every ray's sample range (wave w looks at survivors w, w + 16, ...), the block's node spacing ----
+        const TableBlock<DW> B = { S, lds, blk.ray, cnt, wave, lane };
         bool ok = cnt <= (uint32_t)TC;
-        float s_lo = INFINITY, s_hi = -INFINITY, r_max = 0.f;
-        if (ok) {
-            // (the wave's rows by one gather per 1024 survivors: WaveRows; here and in the passes below)
-            for (uint32_t first = wave; first < cnt; first += 64u * DW) {
-                WaveRows<DW> rows;
-                rows.load(S, lds.idx, first, cnt, lane);
-                const uint32_t n_it = WaveRows<DW>::count(first, cnt);
-                for (uint32_t i = 0; i < n_it; ++i) {
-                    const float4 a = rows.A(i);
-                    const float r = WaveRows<DW>::rl(rows.b.x, i);
-                    const float mubar = dot3_ref(a.x, a.y, a.z, ray.nx, ray.ny, ray.nz);
-                    s_hi = fmaxf(s_hi, mubar);
-                    s_lo = fminf(s_lo, mubar - 2.8285f / r); // mubar - 4 sigma, sigma = 1/(sqrt2 r), rounded outwards
-                    r_max = fmaxf(r_max, r);
-                }
-            }
-            lds.red[0][wave][lane] = s_hi; lds.red[1][wave][lane] = s_lo;
-            if (lane == 0) s_rmax[wave] = r_max;
-            __syncthreads();
-#pragma unroll
-            for (int w = 0; w < DW; ++w) {
-                s_hi = fmaxf(s_hi, lds.red[0][w][lane]); s_lo = fminf(s_lo, lds.red[1][w][lane]);
-                r_max = fmaxf(r_max, s_rmax[w]);
-            }
-            __syncthreads();
-        }
-        stamp(2);
-        const float range = wave_max(s_hi - s_lo); // the block's longest sample range
-        const float h_req = C.table_hx / r_max;    // requested spacing: table_hx in units of 1/r of the narrowest Gaussian
+        const TableRange rg = ok ? table_sample_range<DW>(B, s_rmax) : TableRange{ INFINITY, -INFINITY, 0.f };
+        clock.stamp(2);
+        const float range = wave_max(rg.s_hi - rg.s_lo); // the block's longest sample range
+        const float h_req = C.table_hx / rg.r_max;       // requested spacing: table_hx in units of 1/r of the narrowest Gaussian
         ok = ok && range >= 0.f && h_req > 0.f && range < INFINITY; // (false for NaN)
         bool done = false;
         float h_target = h_req;
         for (int attempt = 0; ok && !done; ++attempt) {
-            // Every ray has its own grid of Gtot nodes from its first sample on (two nodes of margin at either end, so that
-            // every sample has its four neighbours), all with the block's spacing.  The table holds TB_GMAX nodes: a deeper
-            // range is worked off in segments of SL intervals (+ the margins); a sample belongs to the segment its interval
-            // lies in.  Segments in empty space cost next to nothing: every absorber is saturated there.  The waves evaluate
-            // NT nodes each, NT from a short menu: the spacing is then REDUCED until the segments fill 16 NT nodes exactly.
-            float h = 0.f, u = 0.f, lo = 0.f, inv_h = 0.f;
-            uint32_t nseg = 0, SL = 0, G = 0, NTsel = 0, Gtot = 0;
-            auto plan = [&](float ht) -> bool {
-                const float need = ceilf(range / ht); // intervals the samples span
-                if (!(need < 8.f * (float)(TB_GMAX - 8))) return false;
-                nseg = max(1u, ((uint32_t)need + (uint32_t)(TB_GMAX - 8) - 1u) / (uint32_t)(TB_GMAX - 8));
-                const uint32_t sl_need = max(1u, ((uint32_t)need + nseg - 1u) / nseg);
-                const uint32_t nt = (sl_need + 8u + DW - 1) / DW;
-                NTsel = nt <= 4 ? 4 : nt <= 6 ? 6 : nt <= 8 ? 8 : nt <= 12 ? 12 : nt <= 16 ? 16 : nt <= 20 ? 20 : 24;
-                // intervals per segment; nodes in the table: the segment's intervals, two nodes before them, and up to six behind
-                // the last one (the samples' intervals start at 2 and end at Gtot - 4 <= nseg SL + 2, whose stencil ends at nseg SL + 4)
-                G = NTsel * DW; SL = G - 8u;
-                h = fminf(ht, range / (float)(nseg * SL) * 1.00001f);
-                if (!(h > 0.f)) h = ht; // range == 0: one sample point per ray
-                u = h * r_max;
-                Gtot = nseg * SL + 6u;
-                lo = s_lo - 2.f * h; inv_h = 1.f / h;
-                return u <= 0.3f;
-            };
-            if (!plan(h_target)) { ok = false; break; }
-
-            float S_all = 0.f;
-            // ---- kink pass for one segment: wave w takes absorbers w, w + 16, ...: the weight of the kink of j (TB_W0 units,
-            //      fixed point, rounded up; integer adds: the order of the atomics does not matter) into the interval of mubar_j
-            //      and its two neighbours; with `sums` also S_all = sum |A_j| ----
-            auto kink_pass = [&](uint32_t seg, bool sums) {
-                const float node0 = (float)(seg * SL) - 2.f; // the segment's first node on the ray's grid
-#ifdef VRT_TABLE_FINE
-                auto fine = [&](int k) { if (O.stats && tid == 0) { const unsigned long long t = wall_clock64(); atomicAdd(&O.stats[24 + k], t - t_last); t_last = t; } };
-#else
-                auto fine = [&](int) {};
-#endif
-                fine(0);
-                for (uint32_t g = wave; g < G; g += DW) lds.hist[g][lane] = 0u;
-                __syncthreads();
-                fine(1);
-                float s_part = 0.f;
-                for (uint32_t first = wave; first < cnt; first += 64u * DW) {
-                    WaveRows<DW> rows;
-                    rows.load(S, lds.idx, first, cnt, lane);
-                    const uint32_t n_it = WaveRows<DW>::count(first, cnt);
-                    for (uint32_t i = 0; i < n_it; ++i) {
-                        const float4 ca = rows.A(i), cb = rows.B(i);
-                        const float mubar = dot3_ref(ca.x, ca.y, ca.z, ray.nx, ray.ny, ray.nz);
-                        const float d2 = sub_ref(ca.w, mul_ref(mubar, mubar));
-                        const float A = cb.z * vexp<EXP>(-(d2 * cb.y));
-                        if (sums) s_part += fabsf(A);
-                        const float pos = (mubar - lo) * inv_h;
-                        const float gb = floorf(pos);
-                        const float th = fminf(fmaxf(pos - gb, 0.f), 1.f);
-                        const float a16 = fminf(fabsf(A), 60.f) * 65536.f;
-                        const float gl = gb - node0; // interval of the kink in this segment's table
-                        if (gl >= 0.f && gl < (float)G) atomicAdd(&lds.hist[(uint32_t)gl][lane], (uint32_t)ceilf(a16 * fminf(1.f, 0.28f + 2.58f * fabsf(th - 0.5f))));
-                        if (gl + 1.f >= 0.f && gl + 1.f < (float)G) atomicAdd(&lds.hist[(uint32_t)(gl + 1.f)][lane], (uint32_t)ceilf(a16 * th * th));
-                        if (gl - 1.f >= 0.f && gl - 1.f < (float)G) atomicAdd(&lds.hist[(uint32_t)(gl - 1.f)][lane], (uint32_t)ceilf(a16 * (1.f - th) * (1.f - th)));
-                    }
-                }
-                fine(2);
-                if (sums) lds.red[3][wave][lane] = s_part;
-                __syncthreads();
-                fine(3);
-                if (sums) {
-                    S_all = 0.f;
-#pragma unroll
-                    for (int w = 0; w < DW; ++w) S_all += lds.red[3][w][lane];
-                }
-            };
-
-            // ---- first attempt: how much coarser than requested may the nodes be?  An ESTIMATE of the bound the emission pass
-            //      will find, from the kink weights: emission of interval g ~ 1.4 D_g T_g with D_g = K_g / 1.35 the absorber mass of
-            //      the interval and T_g = exp(-2 sum of the mass before it); the estimate scales with the spacing like rho^3 (kink
-            //      part) and rho^4 (smooth part).  It only picks the spacing: the bound itself is checked below, and a block that
-            //      fails it is redone at 0.6 of the spacing.
-            //      The weights are taken at the COARSEST spacing the settings and the menu of table sizes allow (rounds 3-4 took them
-            //      at the requested spacing -- two or three segments' passes for a teapot block -- and then again at the chosen one):
-            //      44-48 % of the blocks of the OBJ scenes keep that spacing, and for them these weights are the final ones; the
-            //      others scale the estimate DOWN to the finer candidates. ----
-            bool have_kinks = false; // the kink weights of segment 0 at the final spacing are in LDS
-            bool have_sums = false;  // S_all is known (it does not depend on the spacing)
-            if (attempt == 0 && C.table_adapt > 1.f) {
-                const float h_r = h, u_r = u; // the requested spacing, as the menu of table sizes rounds it
-                const uint32_t nodes_r = nseg * NTsel;
-                auto menu = [](int c) { return c == 0 ? 3.f : c == 1 ? 2.5f : c == 2 ? 2.f : c == 3 ? 1.6f : 1.3f; };
-                float k_max = 1.f;
-#pragma unroll
-                for (int c = 4; c >= 0; --c)
-                    if (menu(c) <= C.table_adapt && menu(c) * u_r <= 0.3f) k_max = menu(c);
-                if (k_max > 1.f && plan(h_r * k_max) && nseg * NTsel < nodes_r) {
-                    const float h_c = h;
-                    float P = 0.f, pin = 0.f, pout = 0.f;
-                    for (uint32_t seg = 0; seg < nseg; ++seg) {
-                        kink_pass(seg, seg == 0);
-                        const uint32_t ga = seg ? 2u : 0u, gz = min(G, SL + 2u); // the segment's own intervals
-                        const uint32_t wa = min(gz, ga + wave * NTsel), wz = min(gz, wa + NTsel);
-                        float mass = 0.f;
-                        for (uint32_t g = wa; g < wz; ++g) mass += (float)lds.hist[g][lane];
-                        lds.red[0][wave][lane] = mass * (1.f / (1.35f * 65536.f));
-                        __syncthreads();
-                        float before = P, total = 0.f;
-#pragma unroll
-                        for (int w = 0; w < DW; ++w) {
-                            const float mw = lds.red[0][w][lane];
-                            before += (uint32_t)w < wave ? mw : 0.f;
-                            total += mw;
-                        }
-                        for (uint32_t g = wa; g < wz; ++g) {
-                            const float Kg = (float)lds.hist[g][lane] * (1.f / 65536.f), D = Kg * (1.f / 1.35f);
-                            const float e = 1.4f * D * __expf(-2.f * before);
-                            pin = __builtin_fmaf(e, Kg, pin); pout += e;
-                            before += D;
-                        }
-                        P += total;
-                        __syncthreads(); // red[0] is rewritten by the next segment
-                    }
-                    have_sums = true;
-                    lds.red[0][wave][lane] = pin; lds.red[1][wave][lane] = pout;
-                    __syncthreads();
-                    float pin_t = 0.f, pout_t = 0.f;
-#pragma unroll
-                    for (int w = 0; w < DW; ++w) { pin_t += lds.red[0][w][lane]; pout_t += lds.red[1][w][lane]; }
-                    const float est_in = 1.01f * TB_W0 * u * u * pin_t, est_out = 1.01f * TB_COUT * (u * u) * (u * u) * S_all * pout_t, est_sat = 1.01f * table_saturation_eps<ERF>() * S_all * pout_t;
-                    const float room = C.table_room * C.table_budget;
-                    // the coarsest candidate whose estimate leaves room: k_max itself with the weights as they are (rho = 1), the finer
-                    // ones by scaling; none: the requested spacing
-                    float kappa = 1.f;
-#pragma unroll
-                    for (int c = 0; c < 5; ++c) {
-                        const float k = menu(c), rho = k == k_max ? 1.f : h_r * k / h_c;
-                        if (kappa == 1.f && k <= k_max && rho * rho * rho * (est_in + rho * est_out) + est_sat <= room) kappa = k;
-                    }
-                    kappa = wave_min(valid ? kappa : k_max); // the same in every wave: they hold the same rays
-#ifdef VRT_TABLE_FINE   /* diagnostic build: slot 4 = (sum of 10 kappa) << 32 | blocks that took the coarsest candidate */
-                    if (O.stats && tid == 0) atomicAdd(&O.stats[24 + 4], ((unsigned long long)(kappa * 10.f + 0.5f) << 32) | (kappa == k_max ? 1ull : 0ull));
-#endif
-                    __syncthreads();
-                    if (kappa == k_max) have_kinks = nseg == 1u; // segment 0's weights at this spacing are still in LDS
-                    else if (kappa == 1.f || !plan(h_r * kappa) || nseg * NTsel >= nodes_r) { // (the menu has no smaller table: as requested)
-                        if (!plan(h_target)) { ok = false; break; }
-                    }
-                } else if (!plan(h_target)) { ok = false; break; } // no coarser table to be had: no estimate either
-                if (O.stats && tid == 0 && h != h_r) atomicAdd(&O.stats[20], 1ull);
-            }
-            stamp(3);
-            const uint32_t g0 = wave * NTsel;
-            float Lr = 0.f, Lg = 0.f, Lb = 0.f, La = 0.f, b_in = 0.f, b_out = 0.f;
-
-            for (uint32_t seg = 0; seg < nseg; ++seg) {
-                const float node0 = (float)(seg * SL) - 2.f; // the segment's first node on the ray's grid
-                if (!(seg == 0 && have_kinks)) kink_pass(seg, seg == 0 && !have_sums);
-                const float s3_scale = 255.f / (fmaxf(S_all, 1e-30f) * 65536.f);
-                for (uint32_t g = wave; g < G; g += DW)
+            TablePlan P = table_plan<DW>(range, h_target, rg.s_lo, rg.r_max);
+            if (!P.fits) { ok = false; break; }
+            TableWeights W = { 0.f, false, false };
+            if (attempt == 0 && C.table_adapt > 1.f && !table_choose_spacing<EXP, ERF, DW>(B, C, O, range, rg, h_target, blk.valid, P, W)) { ok = false; break; }
+            clock.stamp(3);
+            const uint32_t g0 = wave * P.NT;
+            TableSums acc = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+            for (uint32_t seg = 0; seg < P.nseg; ++seg) {
+                if (!(seg == 0 && W.have_kinks)) table_kink_pass<EXP, DW>(B, P, seg, seg == 0 && !W.have_sums, W.S_all);
+                const float s3_scale = 255.f / (fmaxf(W.S_all, 1e-30f) * 65536.f); // the weights as one byte per interval, rounded up
+                for (uint32_t g = wave; g < P.G; g += DW)
                     lds.s3[g][lane] = (uint8_t)fminf(floorf((float)lds.hist[g][lane] * s3_scale) + 1.f, 255.f);
                 __syncthreads(); // the weights are read: their memory becomes the table; the partial sums' memory the staging buffers
-                stamp(4);
-
+                clock.stamp(4);
                 // ---- table: wave w evaluates the nodes [w NT, (w+1) NT) of the segment against all survivors ----
-                const float s_seg = __builtin_fmaf(node0, h, lo); // this lane's position of the segment's node 0
-                switch (NTsel) {
-                case 4: table_nodes<EXP, ERF, 4, DW>(S, lds, cnt, ray, s_seg, h, g0, wave, lane, n_skip, O.stats ? O.stats + 22 : nullptr); break;
-                case 6: table_nodes<EXP, ERF, 6, DW>(S, lds, cnt, ray, s_seg, h, g0, wave, lane, n_skip, O.stats ? O.stats + 22 : nullptr); break;
-                case 8: table_nodes<EXP, ERF, 8, DW>(S, lds, cnt, ray, s_seg, h, g0, wave, lane, n_skip, O.stats ? O.stats + 22 : nullptr); break;
-                case 12: table_nodes<EXP, ERF, 12, DW>(S, lds, cnt, ray, s_seg, h, g0, wave, lane, n_skip, O.stats ? O.stats + 22 : nullptr); break;
-                case 16: table_nodes<EXP, ERF, 16, DW>(S, lds, cnt, ray, s_seg, h, g0, wave, lane, n_skip, O.stats ? O.stats + 22 : nullptr); break;
-                case 20: table_nodes<EXP, ERF, 20, DW>(S, lds, cnt, ray, s_seg, h, g0, wave, lane, n_skip, O.stats ? O.stats + 22 : nullptr); break;
-                default: table_nodes<EXP, ERF, 24, DW>(S, lds, cnt, ray, s_seg, h, g0, wave, lane, n_skip, O.stats ? O.stats + 22 : nullptr); break;
-                }
+                const float s_seg = __builtin_fmaf(P.node0(seg), P.h, P.lo); // this lane's position of the segment's node 0
+                with_table_nt(P.NT, [&](auto nt) {
+                    table_nodes<EXP, ERF, decltype(nt)::value, DW>(S, lds, cnt, blk.ray, s_seg, P.h, g0, wave, lane, n_skip, O.stats);
+                });
                 __syncthreads();
-                stamp(5);
-
-                // ---- emission: the emitters are dealt to the waves; X(s_ik) by 4-point Lagrange interpolation for the samples
-                //      of this segment; the error bound is accumulated beside the radiance ----
-                const float seg_lo = (float)(seg * SL), seg_hi = seg + 1 == nseg ? INFINITY : (float)((seg + 1) * SL);
-                // (emitter i of wave w: w, w + 16, ...; the five rows of the NEXT emitter are requested before this one's samples)
-                struct Rows { float4 a, ms, alb; float inv2s2, q; } nx = {};
-                auto fetch_rows = [&](uint32_t i) {
-                    const uint32_t idx = __builtin_amdgcn_readfirstlane(lds.idx[i]);
-                    nx.a = uload(S.gA, idx); nx.ms = uload(S.mu_sig, idx); nx.alb = uload(S.gC, idx);
-                    nx.inv2s2 = uload(S.gB, idx).y; nx.q = uload(S.gD, idx).y;
-                };
-                if (wave < cnt) fetch_rows(wave);
-                for (uint32_t i = wave; i < cnt; i += DW) {
-                    {
-                        const Rows cur = nx;
-                        if (i + DW < cnt) fetch_rows(i + DW);
-                        const float4 a = cur.a, ms = cur.ms, alb = cur.alb;
-                        const float inv2s2 = cur.inv2s2, q = cur.q;
-                        const float e_mubar = dot3_ref(a.x, a.y, a.z, ray.nx, ray.ny, ray.nz);
-                        if (nseg > 1u) { // an emitter none of whose samples lies in this segment on any ray adds exact zeros: skipped
-                            const float g_a = floorf((madd_ref(-4.f, ms.w, e_mubar) - lo) * inv_h), g_b = floorf((e_mubar - lo) * inv_h);
-                            const float gi_a = fminf(fmaxf(g_a, 2.f), (float)(Gtot - 4)), gi_b = fminf(fmaxf(g_b, 2.f), (float)(Gtot - 4));
-                            if (!__any(gi_b >= seg_lo && gi_a < seg_hi)) continue;
-                        }
-                        float inner = 0.f, inner_abs = 0.f, inner_s3 = 0.f;
-#pragma unroll
-                        for (int k = 0; k < 5; ++k) {
-                            const float sk = madd_ref((float)(k - 4), ms.w, e_mubar);
-                            const float uu = (sk - lo) * inv_h;
-                            const float gi = fminf(fmaxf(floorf(uu), 2.f), (float)(Gtot - 4)); // interval on the ray's grid
-                            const bool mine = nseg == 1 || (gi >= seg_lo && gi < seg_hi);
-                            const float gfl = mine ? gi - node0 : 2.f; // ... and in the table
-                            const float t = uu - (gfl + node0);
-                            const uint32_t g = (uint32_t)gfl;
-                            const float px = sub_ref(madd_ref(ray.nx, sk, ray.ox), ms.x);
-                            const float py = sub_ref(madd_ref(ray.ny, sk, ray.oy), ms.y);
-                            const float pz = sub_ref(madd_ref(ray.nz, sk, ray.oz), ms.z);
-                            const float dd = dot3_ref(px, py, pz, px, py, pz);
-                            const float tm1 = t - 1.f, tm2 = t - 2.f, tp1 = t + 1.f;
-                            const float w0 = t * tm1 * tm2 * (-1.f / 6.f), w1 = tp1 * tm1 * tm2 * 0.5f;
-                            const float w2 = tp1 * t * tm2 * -0.5f, w3 = tp1 * t * tm1 * (1.f / 6.f);
-                            const float X = w0 * lds.tab[g - 1][lane] + w1 * lds.tab[g][lane] + w2 * lds.tab[g + 1][lane] + w3 * lds.tab[g + 2][lane];
-                            const float term = mine ? emission_term<EXP>(q, dd * inv2s2, X) : 0.f;
-                            inner += term;
-                            inner_abs += fabsf(term);
-                            inner_s3 = __builtin_fmaf(fabsf(term), (float)lds.s3[g][lane], inner_s3);
-                        }
-                        Lr = __builtin_fmaf(alb.x, inner, Lr);
-                        Lg = __builtin_fmaf(alb.y, inner, Lg);
-                        Lb = __builtin_fmaf(alb.z, inner, Lb);
-                        La = __builtin_fmaf(alb.w, inner, La);
-                        const float amax = fmaxf(fmaxf(fabsf(alb.x), fabsf(alb.y)), fmaxf(fabsf(alb.z), fabsf(alb.w)));
-                        b_in = __builtin_fmaf(amax, inner_s3, b_in);
-                        b_out = __builtin_fmaf(amax, inner_abs, b_out);
-                    }
-                }
+                clock.stamp(5);
+                table_emit_segment<EXP, DW>(B, P, seg, acc);
                 __syncthreads(); // nobody reads the staging buffers or the table any more
-                stamp(6);
+                clock.stamp(6);
             }
-            lds.L[wave][lane] = make_float4(Lr, Lg, Lb, La);
-            float2 *bparts = reinterpret_cast<float2 *>(&lds.tab[0][0]); // [DW][64]
-            bparts[wave * 64 + lane] = make_float2(b_in, b_out);
-            __syncthreads();
-            if (wave == 0) {
-                float4 sum = lds.L[0][lane];
-                float2 bs = bparts[lane];
-#pragma unroll
-                for (int w = 1; w < DW; ++w) {
-                    const float4 v = lds.L[w][lane];
-                    sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
-                    const float2 bv = bparts[w * 64 + lane];
-                    bs.x += bv.x; bs.y += bv.y;
-                }
-                // worst-case change of this ray's radiance (header comment); e^dX - 1 <= 1.01 dX for the dX in question
-                const float e_in = TB_W0 * u * u, e_out = TB_COUT * (u * u) * (u * u) + table_saturation_eps<ERF>();
-                const float bound = 1.01f * S_all * (e_in * (1.f / 255.f) * bs.x + e_out * bs.y);
-                // (false for NaN; S_all beyond the fixed-point range of the weights: no bound)
-                const bool good = !valid || (bound <= C.table_budget && S_all < 60.f);
-                const bool all_good = __all(good);
-                if (all_good && valid) {
-                    if (O.image) O.image[out] = pack_pixel(sum.x, sum.y, sum.z, sum.w, O.pack_flags);
-                    if (O.radiance) O.radiance[out] = sum;
-                }
-                if (lane == 0) s_flag = all_good ? 1u : 0u;
-            }
-            __syncthreads();
-            stamp(7);
+            table_bound_store<ERF, DW>(B, C, O, blk, P, W.S_all, acc, s_flag);
+            clock.stamp(7);
             done = s_flag != 0u;
             if (!done) {
                 if (attempt >= 1) { ok = false; break; }
-                h_target = 0.6f * h;
+                h_target = 0.6f * P.h;
             } else if (O.stats && tid == 0) {
-                atomicAdd(&O.stats[0], (unsigned long long)cnt);
-                atomicAdd(&O.stats[1], (unsigned long long)n_list);
-                atomicAdd(&O.stats[6], 1ull);
-                atomicAdd(&O.stats[7], 1ull);
-                atomicAdd(&O.stats[16], (unsigned long long)Gtot);
-                if (attempt) atomicAdd(&O.stats[17], 1ull);
+                atomicAdd(&O.stats[STAT_BLOCK_CANDIDATES], (unsigned long long)cnt);
+                atomicAdd(&O.stats[STAT_TILE_ENTRIES], (unsigned long long)blk.n_list);
+                atomicAdd(&O.stats[STAT_DENSE_BLOCKS], 1ull);
+                atomicAdd(&O.stats[STAT_TABLE_BLOCKS], 1ull);
+                atomicAdd(&O.stats[STAT_TABLE_NODES], (unsigned long long)P.Gtot);
+                if (attempt) atomicAdd(&O.stats[STAT_TABLE_RETRIES], 1ull);
             }
         }
         if (!ok) { // wave-uniform and the same in every wave
-            // Declined: the block is shaded EXACTLY by this very workgroup, with the exact dense kernel's body in the table's LDS (round 4;
-            // rounds 1-3 queued it for an exact launch behind this one -- a launch every frame of a moving camera paid although nothing
-            // was ever in that queue).  Which arithmetic shades a block is still a function of the block alone.
-            if (O.stats && tid == 0) atomicAdd(&O.stats[19], 1ull);
+            // Declined: the block is shaded EXACTLY by this very workgroup, with the exact dense kernel's body in the table's LDS: a frame
+            // needs one dense-path launch.  Which arithmetic shades a block is still a function of the block alone.
+            if (O.stats && tid == 0) atomicAdd(&O.stats[STAT_TABLE_DECLINED], 1ull);
             __syncthreads(); // everyone is done with the table's LDS
-            static_assert(sizeof(DenseLds<TB_DW>) <= sizeof(TableLds<DW>), "the exact fallback works in the table's LDS");
-            dense_shade_block<EXP, ERF, 6, TB_DW, true>(S, T, C, R, O, *reinterpret_cast<DenseLds<TB_DW> *>(&lds),
-                                                        C.scratch + (size_t)blockIdx.x * C.cstride, cell, bi, false, visits);
+            static_assert(sizeof(DenseLds<DW>) <= sizeof(TableLds<DW>), "the exact fallback works in the table's LDS");
+            dense_shade_block<EXP, ERF, 6, DW, true>(S, T, C, R, O, *reinterpret_cast<DenseLds<DW> *>(&lds),
+                                                     C.scratch + (size_t)blockIdx.x * C.cstride, cell, bi, false, visits);
             continue;
         }
     }
     if (O.stats && lane == 0) {
-        atomicAdd(&O.stats[18], (unsigned long long)n_skip);
-        atomicAdd(&O.stats[13], (unsigned long long)visits.full); atomicAdd(&O.stats[14], (unsigned long long)visits.zero);
-        atomicAdd(&O.stats[15], (unsigned long long)visits.common);
+        atomicAdd(&O.stats[STAT_TABLE_SKIPS], (unsigned long long)n_skip);
+        atomicAdd(&O.stats[STAT_DENSE_VISITS_FULL], (unsigned long long)visits.full); atomicAdd(&O.stats[STAT_DENSE_VISITS_ZERO], (unsigned long long)visits.zero);
+        atomicAdd(&O.stats[STAT_DENSE_VISITS_COMMON], (unsigned long long)visits.common);
     }
 }
 
