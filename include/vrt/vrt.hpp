@@ -542,6 +542,40 @@ void depth_bundle_device(const f32 *d_origins, bool origin_per_ray, const f32 *d
     d.check(vrt_hip_depth_bundle_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_tau, nt, tau_per_ray ? 1 : 0, d_depth, hip_stream),
             "vrt_hip_depth_bundle_device");
 }
+// Transmittance gradient bundles: given grad_T[r * ns + k] = d(loss) / d(T_out[r * ns + k] of transmittance_bundle) for the same rays and
+// samples (wrt = VRT_HIP_TGRAD_T) -- or d(loss) / d(depth_out[r * ns + k] of depth_bundle), with s the depths it returned, s_per_ray = true
+// (wrt = VRT_HIP_TGRAD_DEPTH: the derivative of the ideal crossing; a depth of +inf, 0 or NaN contributes nothing) -- the derivative of the
+// loss with respect to the Gaussians and to the samples or levels (vrt_hip_transmittance_bundle_grad in include/vrt_hip.h has the
+// function, the fixed kept lists and the supported pairs, those of radiance_rays_grad).  grad_out (nullable): gaussians.size() rows of
+// VRT_HIP_GRAD_STRIDE floats, OVERWRITTEN: [4..6] d mu, [7] d sigma, [8] d magnitude, everything else 0.  grad_s_out (nullable): nrays *
+// ns, d(loss) / d(s) or d(loss) / d(tau).  A sample with grad_T == 0 is skipped exactly.  Not bitwise reproducible.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void transmittance_bundle_grad(const vec4f_t *o, const vec4f_t *n, size_t nrays, const f32 *s, size_t ns, bool s_per_ray, const gaussians_t &gaussians,
+                               const f32 *grad_T, int wrt, f32 *grad_out, f32 *grad_s_out)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    std::vector<f32> oo(3 * nrays), nn(3 * nrays);
+    for (size_t r = 0; r < nrays; ++r) {
+        oo[3 * r] = o[r].x; oo[3 * r + 1] = o[r].y; oo[3 * r + 2] = o[r].z;
+        nn[3 * r] = n[r].x; nn[3 * r + 1] = n[r].y; nn[3 * r + 2] = n[r].z;
+    }
+    d.check(vrt_hip_transmittance_bundle_grad(d.ctx, nrays, oo.data(), 1, nn.data(), s, ns, s_per_ray ? 1 : 0, grad_T, wrt, grad_out, grad_s_out),
+            "vrt_hip_transmittance_bundle_grad");
+}
+// The same on the device: ADDS into d_grad (the caller clears it), STORES d_grad_s, enqueued on hip_stream, nothing waits.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void transmittance_bundle_grad_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const f32 *d_s, size_t ns, bool s_per_ray,
+                                      const gaussians_t &gaussians, const f32 *d_grad_T, int wrt, f32 *d_grad, f32 *d_grad_s, void *hip_stream)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    d.check(vrt_hip_transmittance_bundle_grad_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_s, ns, s_per_ray ? 1 : 0, d_grad_T, wrt,
+                                                     d_grad, d_grad_s, hip_stream),
+            "vrt_hip_transmittance_bundle_grad_device");
+}
 // Ray bundles cull through the Morton index of the scene from the next call on (vrt_hip_set_ray_index in include/vrt_hip.h: off by
 // default, the same radiance and the same pixels bit for bit either way; the index is made once per scene).
 inline void set_ray_index(bool on)

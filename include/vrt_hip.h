@@ -421,6 +421,40 @@ int vrt_hip_radiance_rays_grad_device(vrt_hip_ctx *ctx, size_t nrays, const floa
                                       void *hip_stream);
 int vrt_hip_radiance_rays_grad(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
                                const float *grad_radiance, float *grad_out /* N rows, OVERWRITTEN; columns 9..11 written as 0 */);
+/* -------- transmittance gradient bundles: d(loss) / d(Gaussians, samples) from d(loss) / d(T) of ANY rays, and the same for depths ----
+ * The function that is differentiated is what vrt_hip_transmittance_bundle computes for the same rays, samples, scene and options:
+ *   T(r, k) = Exp(E_k),  E_k = sum_{j in K} A_j (Erf(-mubar_j r_j) - Erf((s_k - mubar_j) r_j)),  A_j = sigma_j m_j exp(-d2_j / (2 sigma_j^2)) / 0.79788456,
+ * r_j = 1 / (sqrt2 sigma_j), with K the list ray r keeps under the cull rule of the ray bundles HELD FIXED, as in the gradient bundles
+ * above (a Gaussian of magnitude 0 is dropped by every ray and gets nothing).  S_k = dE_k / ds_k, so that dT / ds = T S.
+ * wrt == VRT_HIP_TGRAD_T: grad_T[r * ns + k] = d(loss) / d(T(r, k)).  Row j of the table gets, summed over the rays that keep j and
+ *   their samples, [4..6] d(loss) / d(mu xyz of j), [7] d / d(sigma), [8] d / d(magnitude); grad_s[r * ns + k] = d(loss) / d(s[r, k]) =
+ *   grad_T T S (with shared samples, s_per_ray == 0, the caller sums it over the rays).
+ * wrt == VRT_HIP_TGRAD_DEPTH: s holds the depths vrt_hip_depth_bundle returned for levels tau (s_per_ray != 0, ns = nt), grad_T[r * ns
+ *   + k] = d(loss) / d(depth[r, k]).  The table gets d(loss) / d(Gaussians) by the implicit function theorem on T(depth, Gaussians) =
+ *   tau: every sample weighs -grad_T / S_k instead of grad_T T_k; grad_s[r * ns + k] = d(loss) / d(tau[r, k]) = grad_T / (T_k S_k).
+ *   This is the derivative of the IDEAL crossing T(depth) = tau, not of the upper end of the bracket the depth bundle returns (the two
+ *   differ by the bracket's width, which the derivative does not see).  A sample whose s is not finite or <= 0, or at which S_k == 0
+ *   -- the depth bundle's +inf, 0 and NaN results -- contributes exactly nothing, and its grad_s is 0.
+ * In both modes a sample with grad_T == 0 is skipped exactly, whatever its s (NaN included), and its grad_s is 0: a caller masks
+ * samples with zeros.  Other values that are not finite propagate as the arithmetic makes them.
+ * Columns 0..3 (albedo: T does not depend on it) and 9..11 of the table are never touched, nor the rows of Gaussians that no ray
+ * keeps: one table may collect a radiance gradient and a mask or depth gradient.  The _device form ADDS into d_grad with float
+ * atomics (not bitwise reproducible) and STORES d_grad_s; either may be NULL, not both.  The host form overwrites grad_out (N rows,
+ * untouched entries 0) and grad_s_out.  Exp and Erf of the forward quantities are the selected pair's, the derivatives the analytic
+ * ones; supported pairs as above: {vcl_exp, expf} x {A&S erf, erff}.  No gradients with respect to the rays.
+ * Everything else is the gradient bundle's contract: origins, origin_per_ray, dirs, the stream rules, the buffers that only grow, the
+ * shared queue / counters / scratch slots / bitmap, the Morton index (the same kept lists either way), the statistics (for the same
+ * rays every field a radiance bundle reports).  nrays == 0, ns == 0 or a scene of no Gaussians returns VRT_HIP_OK with nothing
+ * launched and nothing written; NULL origins, dirs, s or grad_T with work to do, both outputs NULL, wrt outside {0, 1}, an
+ * unsupported pair, more than 2^32 - 16 rays or an nrays * ns that does not fit: VRT_HIP_ERR_INVALID with a message, nothing enqueued. */
+enum { VRT_HIP_TGRAD_T = 0, VRT_HIP_TGRAD_DEPTH = 1 };
+int vrt_hip_transmittance_bundle_grad_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                             const float *d_s, size_t ns, int s_per_ray, const float *d_grad_T /* nrays * ns */, int wrt,
+                                             float *d_grad /* N rows of VRT_HIP_GRAD_STRIDE, ADDED into; may be NULL */,
+                                             float *d_grad_s /* nrays * ns, stored; may be NULL */, void *hip_stream);
+int vrt_hip_transmittance_bundle_grad(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                                      const float *s, size_t ns, int s_per_ray, const float *grad_T, int wrt,
+                                      float *grad_out /* N rows, OVERWRITTEN, or NULL */, float *grad_s_out /* nrays * ns, or NULL */);
 typedef struct {
     uint64_t rays;           /* rays of the bundle                                                                  */
     uint64_t short_rays;     /* shaded lane = ray (list of at most 32)                                              */

@@ -23,6 +23,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 EXP_LIBM, EXP_VCL, EXP_FAST, EXP_SPLINE = 0, 1, 2, 3
 ERF_LIBM, ERF_AS, ERF_SPLINE, ERF_SPLINE_MIRROR, ERF_TAYLOR = 0, 1, 2, 3, 4
 GRAD_STRIDE = 12            # VRT_HIP_GRAD_STRIDE: floats per row of a gradient bundle's table
+TGRAD_T, TGRAD_DEPTH = 0, 1 # VRT_HIP_TGRAD_*: what a transmittance gradient bundle's grad_T is the derivative with respect to
 TABLE_STEP_DEFAULT = 0.05   # vrt_hip_set_table_step: the library's default (0 = exact kernels only)
 PACK_TRUNC, PACK_ROUND, ALPHA_OPAQUE, ALPHA_COMPUTED = 0, 1, 0, 2
 
@@ -127,6 +128,8 @@ SYMBOLS = {
     "vrt_hip_depth_bundle": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p]),
     "vrt_hip_radiance_rays_grad_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "vrt_hip_radiance_rays_grad": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _f32p]),
+    "vrt_hip_transmittance_bundle_grad_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "vrt_hip_transmittance_bundle_grad": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p, C.c_int, _f32p, _f32p]),
     "vrt_hip_get_ray_stats": (C.c_int, [_vp, C.POINTER(RayStats)]),
     "vrt_hip_set_ray_index": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_ray_index_stats": (C.c_int, [_vp, C.POINTER(RayIndexStats)]),
@@ -595,6 +598,35 @@ class Renderer:
                                                        d_grad_radiance or None, d_grad or None, stream or None)
         if rc != 0:
             self._chk(rc, "radiance_rays_grad_device")
+
+    def transmittance_bundle_grad(self, origins, dirs, s, grad_T, wrt=TGRAD_T, s_per_ray=None, want_table=True, want_grad_s=True):
+        """vrt_hip_transmittance_bundle_grad: the derivative of a loss with respect to the Gaussians and the samples, given its
+        derivative grad_T [nrays, ns] with respect to what transmittance_bundle returns for the same rays and samples s (wrt = TGRAD_T)
+        -- or, with wrt = TGRAD_DEPTH, s [nrays, ns] the depths depth_bundle returned and grad_T the derivative with respect to them:
+        the derivative with respect to the Gaussians and the levels tau (of the ideal crossing; a depth of +inf, 0 or NaN contributes
+        nothing).  A sample with grad_T == 0 is skipped exactly.  The kept lists are held fixed; no gradient for the rays.
+        Returns ({"albedo": zeros [N, 4], "mu": [N, 3], "sigma": [N], "magnitude": [N]} or None, grad_s [nrays, ns] or None), float32.
+        The table's sums are float atomics on the device: not bitwise reproducible."""
+        origins, dirs, per_ray = _rays(origins, dirs)
+        s, ns, s_per_ray = _table(s, len(dirs), s_per_ray)
+        g = np.ascontiguousarray(grad_T, np.float32)
+        assert g.size == len(dirs) * ns
+        out = np.zeros((self.n, GRAD_STRIDE), np.float32) if want_table else None
+        gs = np.zeros((len(dirs), ns), np.float32) if want_grad_s else None
+        self._chk(self._L.vrt_hip_transmittance_bundle_grad(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(s), ns, int(s_per_ray), _fp(g),
+                                                            int(wrt), _fp(out) if want_table else None, _fp(gs) if want_grad_s else None),
+                  "transmittance_bundle_grad")
+        return (grad_columns(out) if want_table else None), gs
+
+    def transmittance_bundle_grad_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_s, ns, s_per_ray, d_grad_T, wrt, d_grad=0, d_grad_s=0,
+                                         stream=0):
+        """vrt_hip_transmittance_bundle_grad_device: device pointers, everything enqueued on `stream`; ADDS into columns 4..8 of d_grad
+        ([N, GRAD_STRIDE] float32: grad_columns names its columns) and STORES d_grad_s ([nrays, ns]); either may be 0, not both."""
+        rc = self._L.vrt_hip_transmittance_bundle_grad_device(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None,
+                                                              d_s or None, int(ns), int(bool(s_per_ray)), d_grad_T or None, int(wrt),
+                                                              d_grad or None, d_grad_s or None, stream or None)
+        if rc != 0:
+            self._chk(rc, "transmittance_bundle_grad_device")
 
     def ray_stats(self):
         """Counts of the last bundle (enable_stats first): see vrt_hip_ray_stats in include/vrt_hip.h."""

@@ -1,11 +1,17 @@
-"""torch.autograd face of the ray bundles: radiance of caller-given rays as a differentiable function of the Gaussians.
+"""torch.autograd face of the ray bundles: radiance, transmittance and depth of caller-given rays as differentiable functions of the
+Gaussians.
 
     L = radiance_rays(renderer, mu, albedo, sigma, magnitude, origins, dirs)      # [nrays, 4], on cuda
     loss(L).backward()                                                            # mu.grad, albedo.grad, sigma.grad, magnitude.grad
+    T = transmittance_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, s)      # [nrays, ns]: masks, shadow rays
+    z = depth_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, tau)            # [nrays, nt]: depth maps, first hits
 
 Forward is Renderer.radiance_rays_device, backward Renderer.radiance_rays_grad_device (include/vrt_hip.h, "gradient bundles"): the
 derivative with each ray's kept list held fixed, under {vcl_exp, expf} x {A&S erf, erff} only, summed with float atomics (not bitwise
-reproducible).  No gradient is returned for the rays.
+reproducible).  No gradient is returned for the rays.  transmittance_bundle and depth_bundle run Renderer.transmittance_bundle_device /
+depth_bundle_device forward and Renderer.transmittance_bundle_grad_device backward ("transmittance gradient bundles"), under the same
+rules; they are differentiable in s and tau as well, never in albedo (T does not depend on it).  The depth's derivative is that of the
+ideal crossing T(depth) = tau; a depth of +inf, 0 or NaN gets no gradient.
 
 A Gaussian whose magnitude is exactly 0 is dropped by every ray's cull and therefore receives NO gradient, magnitude.grad included
 (although the true derivative is not 0): initialise magnitudes away from 0.
@@ -17,25 +23,38 @@ library yet; a fitting loop pays that upload once per step.
 import numpy as np
 import torch
 
-from . import GRAD_STRIDE, grad_columns
+from . import GRAD_STRIDE, TGRAD_DEPTH, TGRAD_T, grad_columns
+
+
+def _upload(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs):
+    """What every forward begins with: the scene of `renderer` replaced by the parameters (through the host: the module's known limit),
+    the rays on torch's current device, and in ctx what backward needs of them.  Returns (device, origins, dirs, origin per ray)."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in (mu, albedo, sigma, magnitude)]
+    renderer.set_gaussians_soa(host[0], host[1][:, :3], host[2], host[3], alpha=np.ascontiguousarray(host[1][:, 3]))
+    o = origins.detach().to(dev, torch.float32).contiguous()
+    d = dirs.detach().to(dev, torch.float32).contiguous().reshape(-1, 3)
+    per_ray = o.numel() != 3
+    ctx.renderer, ctx.rays, ctx.n = renderer, (o, d, per_ray), len(host[2])
+    ctx.devices = [t.device for t in (mu, albedo, sigma, magnitude)]
+    ctx.dtypes = [t.dtype for t in (mu, albedo, sigma, magnitude)]
+    return dev, o, d, per_ray
+
+
+def _parameter_grads(ctx, table):
+    """The table's columns as the gradients of (mu, albedo, sigma, magnitude), each on its parameter's device and in its type."""
+    cols = grad_columns(table)
+    return [cols[k].to(dev, dt) for k, dev, dt in zip(("mu", "albedo", "sigma", "magnitude"), ctx.devices, ctx.dtypes)]
 
 
 class _RadianceRays(torch.autograd.Function):
     @staticmethod
     def forward(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs):
-        dev = torch.device("cuda", torch.cuda.current_device())
-        host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in (mu, albedo, sigma, magnitude)]
-        renderer.set_gaussians_soa(host[0], host[1][:, :3], host[2], host[3], alpha=np.ascontiguousarray(host[1][:, 3]))
-        o = origins.detach().to(dev, torch.float32).contiguous()
-        d = dirs.detach().to(dev, torch.float32).contiguous().reshape(-1, 3)
-        per_ray = o.numel() != 3
+        dev, o, d, per_ray = _upload(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs)
         out = torch.empty((d.shape[0], 4), dtype=torch.float32, device=dev)
         if d.shape[0]:
             renderer.radiance_rays_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), d_radiance=out.data_ptr(),
                                           stream=torch.cuda.current_stream(dev).cuda_stream)
-        ctx.renderer, ctx.rays, ctx.n = renderer, (o, d, per_ray), len(host[2])
-        ctx.devices = [t.device for t in (mu, albedo, sigma, magnitude)]
-        ctx.dtypes = [t.dtype for t in (mu, albedo, sigma, magnitude)]
         return out
 
     @staticmethod
@@ -46,9 +65,7 @@ class _RadianceRays(torch.autograd.Function):
         if d.shape[0] and ctx.n:
             ctx.renderer.radiance_rays_grad_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), g.data_ptr(), table.data_ptr(),
                                                    stream=torch.cuda.current_stream(o.device).cuda_stream)
-        cols = grad_columns(table)
-        grads = [cols[k].to(dev, dt) for k, dev, dt in zip(("mu", "albedo", "sigma", "magnitude"), ctx.devices, ctx.dtypes)]
-        return (None, *grads, None, None)
+        return (None, *_parameter_grads(ctx, table), None, None)
 
 
 def radiance_rays(renderer, mu, albedo, sigma, magnitude, origins, dirs):
@@ -57,3 +74,57 @@ def radiance_rays(renderer, mu, albedo, sigma, magnitude, origins, dirs):
     [nrays, 3], unit length.  The scene of `renderer` is REPLACED by the parameters, through the host (see the module's docstring);
     backward must run before the renderer's scene or options change again."""
     return _RadianceRays.apply(renderer, mu, albedo, sigma, magnitude, origins, dirs)
+
+
+class _Profile(torch.autograd.Function):
+    """transmittance_bundle (wrt = TGRAD_T: values = sample distances) and depth_bundle (TGRAD_DEPTH: values = levels)."""
+
+    @staticmethod
+    def forward(ctx, renderer, wrt, mu, albedo, sigma, magnitude, origins, dirs, values):
+        dev, o, d, per_ray = _upload(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs)
+        nrays = d.shape[0]
+        v = values.detach().to(dev, torch.float32).contiguous()
+        v_per_ray = v.dim() == 2
+        n = v.shape[-1] if v.dim() else 1
+        out = torch.empty((nrays, n), dtype=torch.float32, device=dev)
+        if nrays and n:
+            call = renderer.transmittance_bundle_device if wrt == TGRAD_T else renderer.depth_bundle_device
+            call(nrays, o.data_ptr(), per_ray, d.data_ptr(), v.data_ptr(), n, v_per_ray, out.data_ptr(),
+                 stream=torch.cuda.current_stream(dev).cuda_stream)
+        ctx.wrt, ctx.values, ctx.v_per_ray, ctx.v_like = wrt, v, v_per_ray, values
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        o, d, per_ray = ctx.rays
+        (out,) = ctx.saved_tensors
+        nrays, n = out.shape
+        g = grad_out.to(o.device, torch.float32).contiguous()
+        table = torch.zeros((ctx.n, GRAD_STRIDE), dtype=torch.float32, device=o.device)
+        gv = torch.zeros((nrays, n), dtype=torch.float32, device=o.device)
+        if nrays and n and ctx.n:
+            # T mode: at the samples the forward took; depth mode: at the depths the forward returned, one row per ray
+            s, s_per_ray = (ctx.values, ctx.v_per_ray) if ctx.wrt == TGRAD_T else (out, True)
+            ctx.renderer.transmittance_bundle_grad_device(nrays, o.data_ptr(), per_ray, d.data_ptr(), s.data_ptr(), n, s_per_ray, g.data_ptr(), ctx.wrt,
+                                                          d_grad=table.data_ptr(), d_grad_s=gv.data_ptr(),
+                                                          stream=torch.cuda.current_stream(o.device).cuda_stream)
+        if not ctx.v_per_ray:                       # values shared by the rays: their gradient is the sum over the rays
+            gv = gv.sum(0).reshape(ctx.values.shape)
+        grads = _parameter_grads(ctx, table)
+        grads[1] = None                             # albedo
+        return (None, None, *grads, None, None, gv.to(ctx.v_like.device, ctx.v_like.dtype))
+
+
+def transmittance_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, s):
+    """Transmittance [nrays, ns] (a cuda tensor on torch's current device and stream) at the sample distances s ([ns], shared by the
+    rays, or [nrays, ns]) along the rays through the scene of the four parameter tensors, differentiable in mu, sigma, magnitude and
+    s; albedo gets no gradient (None).  Rays, the replaced scene and the order of backward: as radiance_rays."""
+    return _Profile.apply(renderer, TGRAD_T, mu, albedo, sigma, magnitude, origins, dirs, s)
+
+
+def depth_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, tau):
+    """The distance [nrays, nt] along each ray at which its transmittance falls to the levels tau ([nt], shared by the rays, or
+    [nrays, nt]), differentiable in mu, sigma, magnitude and tau (the derivative of the ideal crossing; a result of +inf, 0 or NaN
+    gets and gives no gradient); albedo gets no gradient (None).  Rays, the replaced scene and the order of backward: as radiance_rays."""
+    return _Profile.apply(renderer, TGRAD_DEPTH, mu, albedo, sigma, magnitude, origins, dirs, tau)

@@ -240,6 +240,7 @@ struct vrt_hip_ctx {
     DevBuf<unsigned long long> ray_stats;
     DevBuf<float> rays_in[2];
     DevBuf<float> rays_s, rays_T; // transmittance, depth and gradient bundles: sample distances (levels, d loss / d radiance) and results of the host-pointer form
+    DevBuf<float> rays_g, rays_gs; // transmittance gradient bundles, host-pointer form: d loss / d T (or depth) in, d loss / d samples (or levels) out
     DevBuf<float4> rays_rad;
     DevBuf<uint32_t> rays_img;
     bool ray_stats_valid = false; // ray_stats holds the counts of the last bundle (stats were on for it)

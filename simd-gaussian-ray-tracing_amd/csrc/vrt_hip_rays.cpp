@@ -1,7 +1,8 @@
 // vrt_hip_rays.cpp -- ray bundles of libvrt_hip.so (vrt_hip_radiance_rays*, vrt_hip_transmittance_bundle*, vrt_hip_depth_bundle*,
-// vrt_hip_radiance_rays_grad*): radiance of caller-given rays, transmittance at sample distances along them, the distance at which their
-// transmittance falls to given levels, or the derivative of their radiance with respect to the Gaussians, culled per ray
-// (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip, vrt_ray_grad_kernel.hip).  The scene tables and the
+// vrt_hip_radiance_rays_grad*, vrt_hip_transmittance_bundle_grad*): radiance of caller-given rays, transmittance at sample distances along
+// them, the distance at which their transmittance falls to given levels, or the derivative of their radiance, transmittance or depth with
+// respect to the Gaussians, culled per ray (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip,
+// vrt_ray_grad_kernel.hip, vrt_ray_trans_grad_kernel.hip).  The scene tables and the
 // chunk spheres are the frame pipeline's; the long-ray queue, its counters and the long kernel's scratch slots belong to the context
 // and only grow.
 #include <algorithm>
@@ -181,6 +182,8 @@ const BundleKind TRANSMITTANCE = { "transmittance_bundle", "NULL samples or resu
 const BundleKind DEPTH = { "depth_bundle", "NULL levels or result", "nt", &RayArgs::tau, &RayArgs::nt, &RayArgs::tau_per_ray, &RayArgs::depth,
                            launch_ray_depth_bundle };
 const BundleKind GRADIENT = { "radiance_rays_grad", "NULL grad_radiance or gradient table", "", nullptr, nullptr, nullptr, nullptr, launch_ray_grad_bundle };
+const BundleKind TRANS_GRADIENT = { "transmittance_bundle_grad", "NULL samples or grad_T, or neither a gradient table nor grad_s", "ns", &RayArgs::s, &RayArgs::ns,
+                                    &RayArgs::s_per_ray, &RayArgs::grad_s, launch_ray_trans_grad_bundle };
 
 // What every entry point checks before anything else, host and device form alike.  n: values per ray (1 for radiance); io_ok: the kind's
 // tables and results are there.  True when the call is over, with rc its result: an error, or VRT_HIP_OK for a bundle of nothing.
@@ -199,11 +202,21 @@ bool bundle_over(vrt_hip_ctx *c, const BundleKind &k, size_t nrays, size_t n, co
 
 // What a gradient bundle checks on top of bundle_over (one "value" per ray when the scene has Gaussians, none when it has not: a bundle
 // of nothing): the Exp / Erf pair has kernels.
-bool grad_over(vrt_hip_ctx *c, size_t nrays, const void *origins, const void *dirs, bool io_ok, int &rc)
+bool grad_over(vrt_hip_ctx *c, size_t nrays, const void *origins, const void *dirs, bool io_ok, int &rc, const BundleKind &k = GRADIENT, size_t n = 1)
 {
-    if (bundle_over(c, GRADIENT, nrays, c && c->n == 0 ? 0 : 1, origins, dirs, io_ok, rc)) return true;
+    if (bundle_over(c, k, nrays, c && c->n == 0 ? 0 : n, origins, dirs, io_ok, rc)) return true;
     if (ray_grad_pair_supported(c->exp_kind, c->erf_kind)) return false;
-    rc = fail(c, VRT_HIP_ERR_INVALID, std::string(GRADIENT.name) + ": the derivative is taken under {vcl_exp, expf} x {A&S erf, erff} only; the selected pair has jumps");
+    rc = fail(c, VRT_HIP_ERR_INVALID, std::string(k.name) + ": the derivative is taken under {vcl_exp, expf} x {A&S erf, erff} only; the selected pair has jumps");
+    return true;
+}
+
+// What a transmittance gradient bundle checks: grad_over with ns values per ray, and the mode
+bool trans_grad_over(vrt_hip_ctx *c, size_t nrays, const void *origins, const void *dirs, const void *s, size_t ns, const void *grad_T, int wrt,
+                     const void *grad, const void *grad_s, int &rc)
+{
+    if (grad_over(c, nrays, origins, dirs, s && grad_T && (grad || grad_s), rc, TRANS_GRADIENT, ns)) return true;
+    if (wrt == VRT_HIP_TGRAD_T || wrt == VRT_HIP_TGRAD_DEPTH) return false;
+    rc = fail(c, VRT_HIP_ERR_INVALID, std::string(TRANS_GRADIENT.name) + ": wrt is neither VRT_HIP_TGRAD_T nor VRT_HIP_TGRAD_DEPTH");
     return true;
 }
 
@@ -331,6 +344,53 @@ int vrt_hip_radiance_rays_grad(vrt_hip_ctx *c, size_t nrays, const float *origin
     rc = vrt_hip_radiance_rays_grad_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->rays_s.p, c->rays_T.p, c->stream);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(grad_out, c->rays_T.p, table * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_transmittance_bundle_grad_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                             const float *d_s, size_t ns, int s_per_ray, const float *d_grad_T, int wrt, float *d_grad, float *d_grad_s,
+                                             void *hip_stream)
+{
+    int rc;
+    if (trans_grad_over(c, nrays, d_origins, d_dirs, d_s, ns, d_grad_T, wrt, d_grad, d_grad_s, rc)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const BundleKind &k = TRANS_GRADIENT;
+    Bundle b;
+    rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b);
+    if (rc) return rc;
+    b.a.*k.table = d_s; b.a.*k.n = ns; b.a.*k.per_ray = s_per_ray ? 1 : 0; b.a.*k.out = d_grad_s;
+    b.a.grad_T = d_grad_T; b.a.wrt = wrt; b.a.grad = d_grad;
+    k.launch(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
+    HIPCHK(c, hipGetLastError());
+    return VRT_HIP_OK;
+}
+
+// The host form: rays, samples and grad_T staged, a cleared table of the scene's size, the device form on the context's stream, the
+// table and the per-sample output copied back and waited for
+int vrt_hip_transmittance_bundle_grad(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *s,
+                                      size_t ns, int s_per_ray, const float *grad_T, int wrt, float *grad_out, float *grad_s_out)
+{
+    int rc;
+    if (trans_grad_over(c, nrays, origins, dirs, s, ns, grad_T, wrt, grad_out, grad_s_out, rc)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = quiesce(c); // the staging buffers may still be read by an earlier bundle
+    if (rc) return rc;
+    const size_t table = (size_t)c->n * VRT_HIP_GRAD_STRIDE, nvalues = (s_per_ray ? nrays : 1) * ns;
+    HIPCHK(c, c->rays_s.reserve(nvalues));
+    HIPCHK(c, c->rays_g.reserve(nrays * ns));
+    if (grad_out) HIPCHK(c, c->rays_T.reserve(table));
+    if (grad_s_out) HIPCHK(c, c->rays_gs.reserve(nrays * ns));
+    rc = stage_rays(c, nrays, origins, origin_per_ray, dirs);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->rays_s.p, s, nvalues * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rays_g.p, grad_T, nrays * ns * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (grad_out) HIPCHK(c, hipMemsetAsync(c->rays_T.p, 0, table * sizeof(float), c->stream));
+    rc = vrt_hip_transmittance_bundle_grad_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->rays_s.p, ns, s_per_ray, c->rays_g.p, wrt,
+                                                  grad_out ? c->rays_T.p : nullptr, grad_s_out ? c->rays_gs.p : nullptr, c->stream);
+    if (rc) return rc;
+    if (grad_out) HIPCHK(c, hipMemcpyAsync(grad_out, c->rays_T.p, table * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (grad_s_out) HIPCHK(c, hipMemcpyAsync(grad_s_out, c->rays_gs.p, nrays * ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return VRT_HIP_OK;
 }

@@ -1,0 +1,298 @@
+// vrt_ray_trans_grad_kernel.hip -- transmittance gradient bundles (vrt_hip_transmittance_bundle_grad*): d(loss) / d(mu, sigma,
+// magnitude) of every Gaussian and d(loss) / d(sample), given d(loss) / d(T) at sample distances along caller-given rays -- or, in depth
+// mode, d(loss) / d(Gaussians) and d(loss) / d(level), given d(loss) / d(depth) at the depths a depth bundle returned.  The rays, the
+// cull, the lists, the queue of the long rays, the re-cull and the statistics are vrt_ray_cull.hpp's: the same rays keep the same
+// Gaussians and go to the same kind of kernel as in every other bundle.  The kept list K of a ray is held fixed.
+//
+// The function ("Transmittance gradient bundles"; K = 1 / 0.79788456, C = 2 / sqrt(pi)):
+//   A_j = K sigma_j mag_j exp(-d2_j / (2 sigma_j^2)),  x_kj = (s_k - mubar_j) r_j,  D_kj = Erf(-m_j) - Erf(x_kj),  m_j = mubar_j r_j
+//   E_k = sum_j A_j D_kj,  T_k = Exp(E_k),  S_k = dE_k / ds_k = -sum_j A_j C r_j e2_kj,      e1_j = exp(-m_j^2), e2_kj = exp(-x_kj^2)
+// and with a weight w_k per sample, W = sum_k w_k, P_j = sum_k w_k D_kj, Q_j = sum_k w_k e2_kj, R_j = sum_k w_k e2_kj x_kj:
+//   d mag_j   = (A_j / mag_j) P_j
+//   d mu_j    = -A_j P_j c_perp_j / sigma_j^2 + A_j C r_j (Q_j - e1_j W) n
+//   d sigma_j = A_j P_j (1 / sigma_j + d2_j / sigma_j^3) + A_j C (e1_j m_j W + R_j) / sigma_j
+// wrt == VRT_HIP_TGRAD_T:      g_k = dl / dT_k,      w_k = g_k T_k,    the per-sample output dl / ds_k   = w_k S_k
+// wrt == VRT_HIP_TGRAD_DEPTH:  g_k = dl / ddepth_k,  w_k = -g_k / S_k, the per-sample output dl / dtau_k = g_k / (T_k S_k): the implicit
+//   function theorem on T(depth, theta) = tau with dT / ds = T S -- the derivative of the IDEAL crossing, not of the upper end of the
+//   bracket a depth bundle returns.  A sample whose s_k is not finite or <= 0, or whose S_k == 0 (the depth bundle's +inf, 0 and NaN
+//   results) contributes exactly nothing, and its per-sample output is 0.
+// In both modes a sample with g_k == 0 is skipped exactly (its s_k is never used: no 0 * NaN), per-sample output 0.
+//   ray_short_trans_grad_kernel  lane = ray.  Per group of RAY_SG samples one walk of the lane's list forms E_k and S_k through grad_gauss
+//                                (the compensated c and mubar, not trans_entry's |c|^2 - mubar^2), then w_k, then a second walk deals w_k
+//                                out to P, Q, R of every list position.  Three running sums per list position and lane in LDS (A P / mag,
+//                                the coefficient of n without its W term, the sigma sum without its W term: 24 KB next to the 8 KB of
+//                                lists).  Only W is carried beside them: e1_j comes back from grad_gauss.  After the last group every
+//                                position goes to the table ONCE: 5 adds per (ray, kept Gaussian) whatever ns is, wave-summed where a
+//                                position holds one row in all lanes (grad_deposit).
+//   ray_long_trans_grad_kernel   one wave per queued ray, lane l takes entries l, l + 64, ...  The list has no bound, so no per-entry
+//                                sum waits in LDS: the samples are cut into chunks of NSC = 512.  E_k and S_k of a chunk's samples come
+//                                from wave_sum (w_k is wave-uniform) and go to LDS with their s_k; then every lane runs over its entries
+//                                with the chunk's samples in the inner loop, P, Q, R in registers, and adds its 5 values per entry and
+//                                chunk, the chunk's W terms included: 5 ceil(ns / NSC) adds per entry, every lane another row.
+// The per-sample output is STORED (by the lane; by lane 0 of the long kernel), not added.
+// Exp / Erf of the forward quantities are the selected pair's; e1 and e2 are exp_neg_sq<EXP>.  Only {vcl, libm} x {A&S, libm} are
+// instantiated (ray_grad_pair_supported).  The sums in the caller's table depend on the arrival order of the atomic adds: not bitwise
+// reproducible.  Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
+#include "vrt_ray_grad.hpp"  // grad_gauss, grad_deposit: shared with vrt_ray_grad_kernel.hip
+#include "vrt_ray_trans.hpp" // RAY_SG
+
+namespace vrtk {
+
+constexpr int NSC = 512; // samples per chunk of the long kernel: their w_k and s_k in LDS (4 KB)
+static_assert(NSC >= RAY_SG && NSC % RAY_SG == 0, "a chunk is whole groups");
+
+// What a sample is worth once E_k and S_k = dE_k / ds_k are known: its weight w_k (0: it contributes nothing) and its per-sample output.
+// g == 0: the sample is not live (trans_grad_live), whatever E and S_k came to.
+template <int EXP>
+__device__ __forceinline__ void trans_grad_weight(bool depth_mode, float g, float E, float Sk, float &w, float &gs)
+{
+    const bool live = g != 0.f;
+    const float T = vexp<EXP>(E);
+    if (depth_mode) {
+        const bool ok = live && Sk != 0.f;
+        w = ok ? -g / Sk : 0.f;
+        gs = ok ? g / (T * Sk) : 0.f;
+    } else {
+        w = live ? g * T : 0.f;
+        gs = live ? w * Sk : 0.f;
+    }
+}
+
+// is sample (s, g) live: g_k != 0, and in depth mode s_k finite and > 0.  The kernels carry a sample that is not as g = 0 at s = 0
+// (finite arithmetic, weight exactly 0).
+__device__ __forceinline__ bool trans_grad_live(bool depth_mode, float s, float g)
+{
+    return g != 0.f && (!depth_mode || (s > 0.f && s < __builtin_inff()));
+}
+
+// x_kj = (s_k - mubar_j) r_j, the difference first: s r - m would round at the size of m = mubar r (20 and more for a narrow Gaussian a unit
+// away), and e2 = exp(-x^2) passes an error dx on as 2 |x| dx -- 4e-5 of a far sample's addends on the grid scene, against 5e-6 this way.
+__device__ __forceinline__ float trans_grad_x(float s, const GradGauss &q) { return (s - q.mubar) * q.r; }
+
+// s_acc: three sums per list position and lane, [(c * RAY_PL + pos) * 64 + lane]: c = 0 A P / mag, 1 A C r Q, 2 A C R / sigma
+__device__ __forceinline__ float &tgrad_acc(float *s_acc, int c, uint32_t pos, uint32_t lane) { return s_acc[((uint32_t)c * RAY_PL + pos) * 64u + lane]; }
+
+template <int EXP, int ERF, bool INDEXED>
+__global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
+{
+    const RayArgs &P = kernel_args<RayArgs>();
+    const SceneTables &S = P.S;
+    __shared__ uint32_t s_list[RAY_PL * 64]; // [k*64 + lane]: consecutive lanes on consecutive banks
+    __shared__ float s_acc[3 * RAY_PL * 64];
+    const uint32_t lane = threadIdx.x & 63u;
+    const ShortRay R = ray_short_begin<INDEXED>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
+    const uint32_t nl = R.nl, nmax = R.nmax;
+    const LaneRay &ray = R.ray;
+    const ErfEval<ERF> erf;
+    const bool depth_mode = P.wrt == VRT_HIP_TGRAD_DEPTH;
+    const uint64_t ns = P.ns;
+    const float *sp = P.s + (P.s_per_ray ? R.rc * ns : 0ull);
+    const float *gp = P.grad_T + R.rc * ns;
+    float *gsp = P.grad_s ? P.grad_s + R.rc * ns : nullptr;
+
+    for (uint32_t p = 0; p < nmax; ++p)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) tgrad_acc(s_acc, c, p, lane) = 0.f;
+
+    float W = 0.f;
+    for (uint64_t k0 = 0; k0 < ns; k0 += RAY_SG) {
+        float sv[RAY_SG], gv[RAY_SG], w[RAY_SG];
+#pragma unroll
+        for (int g = 0; g < RAY_SG; ++g) {
+            const bool in = R.writes && k0 + g < ns;
+            const float g_in = in ? gp[k0 + g] : 0.f, s = in ? sp[k0 + g] : 0.f;
+            gv[g] = trans_grad_live(depth_mode, s, g_in) ? g_in : 0.f;
+            sv[g] = gv[g] != 0.f ? s : 0.f;
+        }
+        // ---- walk 1: E_k and S_k ----
+        float accE[RAY_SG], accS[RAY_SG];
+#pragma unroll
+        for (int g = 0; g < RAY_SG; ++g) accE[g] = accS[g] = 0.f;
+        uint32_t lj = nl ? s_list[lane] : 0u;
+        float4 a = S.mu_sig[lj], b = S.gB[lj];
+        for (uint32_t j = 0; j < nmax; ++j) {
+            const float4 ca = a, cb = b;
+            const bool vj = j < nl;
+            if (j + 1 < nmax) { // the next entry's rows, one iteration ahead
+                lj = (j + 1 < nl) ? s_list[(j + 1) * 64 + lane] : 0u;
+                a = S.mu_sig[lj]; b = S.gB[lj];
+            }
+            const GradGauss q = grad_gauss<EXP, ERF>(erf, ca, cb, vj, ray);
+#pragma unroll
+            for (int g = 0; g < RAY_SG; ++g) {
+                const float x = trans_grad_x(sv[g], q);
+                const float e = __builtin_fmaf(q.A, q.E - erf(x), accE[g]);
+                const float t = __builtin_fmaf(-q.Ar, exp_neg_sq<EXP>(x), accS[g]);
+                accE[g] = vj ? e : accE[g];
+                accS[g] = vj ? t : accS[g];
+            }
+        }
+        // ---- the samples: w_k, and what leaves per sample ----
+#pragma unroll
+        for (int g = 0; g < RAY_SG; ++g) {
+            float gs;
+            trans_grad_weight<EXP>(depth_mode, gv[g], accE[g], accS[g], w[g], gs);
+            W += w[g];
+            if (gsp && R.writes && k0 + g < ns) gsp[k0 + g] = gs;
+        }
+        if (!P.grad) continue;
+        // ---- walk 2: the same entries again; w_k to P, Q, R of every position ----
+        lj = nl ? s_list[lane] : 0u;
+        a = S.mu_sig[lj]; b = S.gB[lj];
+        for (uint32_t j = 0; j < nmax; ++j) {
+            const float4 ca = a, cb = b;
+            const bool vj = j < nl;
+            if (j + 1 < nmax) {
+                lj = (j + 1 < nl) ? s_list[(j + 1) * 64 + lane] : 0u;
+                a = S.mu_sig[lj]; b = S.gB[lj];
+            }
+            const GradGauss q = grad_gauss<EXP, ERF>(erf, ca, cb, vj, ray);
+            float Pj = 0.f, Qj = 0.f, Rj = 0.f;
+#pragma unroll
+            for (int g = 0; g < RAY_SG; ++g) {
+                const float x = trans_grad_x(sv[g], q);
+                const float we = w[g] * exp_neg_sq<EXP>(x);
+                Pj = __builtin_fmaf(w[g], q.E - erf(x), Pj);
+                Qj += we;
+                Rj = __builtin_fmaf(we, x, Rj);
+            }
+            if (vj) {
+                tgrad_acc(s_acc, 0, j, lane) += q.Am * Pj;
+                tgrad_acc(s_acc, 1, j, lane) += q.Ar * Qj;
+                tgrad_acc(s_acc, 2, j, lane) += q.Ar * Rj * SQRT_2;
+            }
+        }
+    }
+    if (!P.grad) return;
+
+    // ---- every list position to the table once, now that W is known ----
+    for (uint32_t p = 0; p < nmax; ++p) {
+        const bool on = p < nl; // nl is 0 in a lane without a ray of this kernel
+        const uint32_t idx = on ? s_list[p * 64 + lane] : 0u;
+        const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], on, ray);
+        const float mag = on ? S.gD[idx].z : 0.f;
+        const float M = tgrad_acc(s_acc, 0, p, lane), mM = mag * M;
+        const float ArE = q.Ar * exp_neg_sq<EXP>(q.m);
+        const float alpha = -mM * q.inv_s2;
+        const float beta = __builtin_fmaf(-ArE, W, tgrad_acc(s_acc, 1, p, lane));
+        const float dsig = mM * (q.inv_s + q.d2 * q.inv_s * q.inv_s2) + tgrad_acc(s_acc, 2, p, lane) + ArE * q.m * SQRT_2 * W;
+        const float d[5] = { __builtin_fmaf(alpha, q.px, beta * ray.nx), __builtin_fmaf(alpha, q.py, beta * ray.ny),
+                             __builtin_fmaf(alpha, q.pz, beta * ray.nz), dsig, M };
+        grad_deposit<5>(P.grad, idx, on, d, 4u, lane);
+    }
+}
+
+// One wave per long ray, lane l takes entries l, l + 64, ...; the samples in chunks of NSC.
+template <int EXP, int ERF, bool INDEXED>
+__global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
+{
+    const RayArgs &P = kernel_args<RayArgs>();
+    const SceneTables &S = P.S;
+    __shared__ uint32_t s_list[RAY_LCAP];
+    __shared__ float s_w[NSC], s_s[NSC]; // the chunk's g_k, then its weights w_k, and the distances they are formed at
+    const uint32_t lane = threadIdx.x & 63u;
+    const ErfEval<ERF> erf;
+    const bool depth_mode = P.wrt == VRT_HIP_TGRAD_DEPTH;
+    const uint64_t ns = P.ns;
+
+    LongRay L = ray_long_begin(&P);
+    while (ray_long_next<INDEXED>(&P, &S, s_list, lane, L)) {
+        const LaneRay ray = L.ray;
+        const uint32_t n = L.n;
+        const float *sp = P.s + (P.s_per_ray ? L.r * ns : 0ull);
+        const float *gp = P.grad_T + L.r * ns;
+        float *gsp = P.grad_s ? P.grad_s + L.r * ns : nullptr;
+        for (uint64_t c0 = 0; c0 < ns; c0 += NSC) {
+            const uint32_t nc = (uint32_t)(ns - c0 < (uint64_t)NSC ? ns - c0 : (uint64_t)NSC);
+            // ---- the chunk's samples to LDS, lane = sample (whole groups: what lies past the end is not live) ----
+            for (uint32_t k = lane; k < ((nc + RAY_SG - 1u) & ~(uint32_t)(RAY_SG - 1)); k += 64u) {
+                const bool in = k < nc;
+                const float g_in = in ? gp[c0 + k] : 0.f, s = in ? sp[c0 + k] : 0.f;
+                const float g = trans_grad_live(depth_mode, s, g_in) ? g_in : 0.f;
+                s_w[k] = g; s_s[k] = g != 0.f ? s : 0.f;
+            }
+            __syncthreads();
+            // ---- E_k, S_k and w_k of the chunk's samples, RAY_SG per walk of the list; w_k takes the place of g_k ----
+            float Wc = 0.f;
+            for (uint32_t k0 = 0; k0 < nc; k0 += RAY_SG) {
+                float sv[RAY_SG], gv[RAY_SG], accE[RAY_SG], accS[RAY_SG];
+#pragma unroll
+                for (int g = 0; g < RAY_SG; ++g) {
+                    gv[g] = s_w[k0 + g]; sv[g] = s_s[k0 + g]; // k0 + g < NSC: a chunk is whole groups
+                    accE[g] = accS[g] = 0.f;
+                }
+                for (uint32_t p = lane; p < n; p += 64u) {
+                    const uint32_t idx = long_list_entry(s_list, L.slot, p);
+                    const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], true, ray);
+#pragma unroll
+                    for (int g = 0; g < RAY_SG; ++g) {
+                        const float x = trans_grad_x(sv[g], q);
+                        accE[g] = __builtin_fmaf(q.A, q.E - erf(x), accE[g]);
+                        accS[g] = __builtin_fmaf(-q.Ar, exp_neg_sq<EXP>(x), accS[g]);
+                    }
+                }
+#pragma unroll
+                for (int g = 0; g < RAY_SG; ++g) { // the whole wave is here again
+                    const float E = wave_sum(accE[g]), Sk = wave_sum(accS[g]);
+                    float w, gs;
+                    trans_grad_weight<EXP>(depth_mode, gv[g], E, Sk, w, gs);
+                    Wc += w;
+                    if (lane == 0) {
+                        s_w[k0 + g] = w;
+                        if (gsp && k0 + g < nc) gsp[c0 + k0 + g] = gs;
+                    }
+                }
+            }
+            __syncthreads(); // the chunk's weights are in LDS
+            // ---- every lane its entries, the chunk's samples in the inner loop ----
+            if (P.grad) {
+                for (uint32_t p = lane; p < n; p += 64u) {
+                    const uint32_t idx = long_list_entry(s_list, L.slot, p);
+                    const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], true, ray);
+                    float Pj = 0.f, Qj = 0.f, Rj = 0.f;
+#pragma unroll 4
+                    for (uint32_t k = 0; k < nc; ++k) {
+                        const float w = s_w[k];
+                        const float x = trans_grad_x(s_s[k], q);
+                        const float we = w * exp_neg_sq<EXP>(x);
+                        Pj = __builtin_fmaf(w, q.E - erf(x), Pj);
+                        Qj += we;
+                        Rj = __builtin_fmaf(we, x, Rj);
+                    }
+                    const float mag = S.gD[idx].z;
+                    const float M = q.Am * Pj, mM = mag * M;
+                    const float ArE = q.Ar * exp_neg_sq<EXP>(q.m);
+                    const float alpha = -mM * q.inv_s2;
+                    const float beta = __builtin_fmaf(-ArE, Wc, q.Ar * Qj);
+                    const float dsig = mM * (q.inv_s + q.d2 * q.inv_s * q.inv_s2) + q.Ar * Rj * SQRT_2 + ArE * q.m * SQRT_2 * Wc;
+                    float *row = P.grad + (size_t)idx * GRAD_STRIDE;
+                    atomicAdd(row + 4, __builtin_fmaf(alpha, q.px, beta * ray.nx));
+                    atomicAdd(row + 5, __builtin_fmaf(alpha, q.py, beta * ray.ny));
+                    atomicAdd(row + 6, __builtin_fmaf(alpha, q.pz, beta * ray.nz));
+                    atomicAdd(row + 7, dsig);
+                    atomicAdd(row + 8, M);
+                }
+            }
+            __syncthreads(); // the chunk's weights are read before the next chunk's are written
+        }
+    }
+}
+
+template <int EXP, int ERF>
+static void launch_ray_trans_grad_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
+{
+    if (indexed) launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, true>, ray_long_trans_grad_kernel<EXP, ERF, true>, a, long_grid, st);
+    else launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, false>, ray_long_trans_grad_kernel<EXP, ERF, false>, a, long_grid, st);
+}
+void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
+{
+    if (!a.nrays || !a.ns || !long_grid || !ray_grad_pair_supported(exp_kind, erf_kind)) return;
+    switch (exp_kind * 8 + erf_kind) {
+    case VRT_EXP_LIBM * 8 + VRT_ERF_LIBM: launch_ray_trans_grad_bundle_t<VRT_EXP_LIBM, VRT_ERF_LIBM>(a, long_grid, indexed, st); break;
+    case VRT_EXP_LIBM * 8 + VRT_ERF_AS: launch_ray_trans_grad_bundle_t<VRT_EXP_LIBM, VRT_ERF_AS>(a, long_grid, indexed, st); break;
+    case VRT_EXP_VCL * 8 + VRT_ERF_LIBM: launch_ray_trans_grad_bundle_t<VRT_EXP_VCL, VRT_ERF_LIBM>(a, long_grid, indexed, st); break;
+    default: launch_ray_trans_grad_bundle_t<VRT_EXP_VCL, VRT_ERF_AS>(a, long_grid, indexed, st); break;
+    }
+}
+
+} // namespace vrtk

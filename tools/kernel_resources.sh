@@ -1,6 +1,6 @@
 #!/bin/bash
 # Registers, spills, LDS and occupancy of the kernels of one translation unit (compiler remarks; no GPU needed):
-#   tools/kernel_resources.sh block|table|ray|raytrans|raydepth|raygrad|dense|assembly|query|main [name filter]     (main: vrt_kernels.hip, the frame set-up)
+#   tools/kernel_resources.sh block|table|ray|raytrans|raydepth|raygrad|raytgrad|dense|assembly|query|main [name filter]     (main: vrt_kernels.hip, the frame set-up)
 cd "$(dirname "$0")/../simd-gaussian-ray-tracing_amd/csrc" || exit 1
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-pass-failed -fno-slp-vectorize --cuda-device-only -Rpass-analysis=kernel-resource-usage"
 case "$1" in
@@ -10,6 +10,7 @@ case "$1" in
   raytrans) SRC=vrt_ray_trans_kernel.hip; EXTRA="" ;;
   raydepth) SRC=vrt_ray_depth_kernel.hip; EXTRA="" ;;
   raygrad) SRC=vrt_ray_grad_kernel.hip; EXTRA="" ;;
+  raytgrad) SRC=vrt_ray_trans_grad_kernel.hip; EXTRA="" ;;
   dense|assembly|query) SRC=vrt_$1_kernel.hip; EXTRA="" ;;
   *) SRC=vrt_kernels.hip; EXTRA="" ;;
 esac

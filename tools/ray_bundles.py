@@ -38,6 +38,14 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
       `--grad-only` runs this part alone, prints its JSON line and writes ray_grad.json and ray_grad.md (and nothing else) to --out-dir;
       the .md ends with the text of <out-dir>/ray_grad_resources.txt when that file is there (the output of
       `tools/kernel_resources.sh raygrad`, which needs the compiler and no GPU).
+  (tg) transmittance gradient bundles (vrt_hip_transmittance_bundle_grad_device, table and per-sample output): the 2^20 scattered rays of
+      (d) with ns = 1 (shadow rays, s = 8), the 4096 aimed rays of (t) with ns = 64 (profiles), and the 4096 aimed rays of (depth) in depth
+      mode at the depths of level 0.5 (and, beside it, of level 0.99, which these rays do reach), device pointers, index off and on, each
+      against vrt_hip_transmittance_bundle_device of the same rays and samples in the same run, windows alternating.  A gradient call has
+      to take less time than 10 transmittance bundles (central differences for the five parameters of ONE Gaussian); the ratios are
+      reported as measured.  `--tgrad-only` runs this part alone, prints its JSON line and writes ray_trans_grad.json and
+      ray_trans_grad.md (and nothing else) to --out-dir; the .md ends with the text of <out-dir>/ray_trans_grad_resources.txt when that
+      file is there (the output of `tools/kernel_resources.sh raytgrad`).
 """
 import argparse
 import json
@@ -349,6 +357,93 @@ scheduler on this unit, variants of the LDS layout.
     return "\n".join(lines)
 
 
+TGRAD_LIMIT = 10.0   # transmittance bundles of the same rays: what central differences cost for the five parameters of ONE Gaussian
+
+
+def part_tgrad(g, calls=3, repeats=5):
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    aimed = aimed_rays(g)
+    rows = {}
+    cases = (("shadow_2^20_ns1", scattered(g, 1 << 20), 1, pkg.TGRAD_T, np.array([8.0], f32), None),
+             ("profiles_4096_ns64", aimed, 0, pkg.TGRAD_T, np.linspace(0.5, 8.0, 64).astype(f32), None),
+             ("depth_4096_tau0.5", aimed, 0, pkg.TGRAD_DEPTH, None, 0.5),
+             ("depth_4096_tau0.99", aimed, 0, pkg.TGRAD_DEPTH, None, 0.99))      # beside the case asked for: the aimed rays end between T = 0.9 and 0.995
+    for label, (o, d), per, wrt, s, level in cases:
+        nrays = len(d)
+        t_o, t_d = torch.from_numpy(np.ascontiguousarray(o, f32)).cuda(), torch.from_numpy(np.ascontiguousarray(d, f32)).cuda()
+        ctx = [pkg.Renderer(0), pkg.Renderer(0)]
+        for on, r in enumerate(ctx):
+            r.set_gaussians(g)
+            r.set_ray_index(on)
+        if wrt == pkg.TGRAD_DEPTH:      # the samples are the depths of the level, one per ray
+            tau = torch.tensor([level], dtype=torch.float32, device="cuda")
+            t_s = torch.zeros((nrays, 1), dtype=torch.float32, device="cuda")
+            ctx[0].depth_bundle_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), tau.data_ptr(), 1, 0, t_s.data_ptr(), st)
+            torch.cuda.synchronize()
+            ns, s_per_ray = 1, 1
+            live = int((torch.isfinite(t_s) & (t_s > 0)).sum().item())
+            t_sT = torch.where(torch.isfinite(t_s), t_s, torch.full_like(t_s, 8.0))      # the transmittance bundle wants finite samples
+        else:
+            t_s = torch.from_numpy(s).cuda()
+            ns, s_per_ray, live, t_sT = len(s), 0, nrays * len(s), t_s
+        t_g = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, size=(nrays, ns)).astype(f32)).cuda()
+        T = [torch.zeros((nrays, ns), dtype=torch.float32, device="cuda") for _ in ctx]
+        gs = [torch.zeros((nrays, ns), dtype=torch.float32, device="cuda") for _ in ctx]
+        table = [torch.zeros((len(g), pkg.GRAD_STRIDE), dtype=torch.float32, device="cuda") for _ in ctx]
+        torch.cuda.synchronize()
+        fns = []
+        for k in (0, 1):
+            fns.append(lambda k=k: ctx[k].transmittance_bundle_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_sT.data_ptr(), ns, s_per_ray, T[k].data_ptr(), st))
+            fns.append(lambda k=k: ctx[k].transmittance_bundle_grad_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_s.data_ptr(), ns, s_per_ray, t_g.data_ptr(), wrt,
+                                                                           table[k].data_ptr(), gs[k].data_ptr(), st))
+        t = windows(fns, calls, repeats, warm=2)
+        ctx[0].enable_stats(True)
+        table[0].zero_()
+        fns[1]()
+        stats = ctx[0].ray_stats()
+        torch.cuda.synchronize()
+        finite = bool(torch.isfinite(table[0]).all().item() and torch.isfinite(gs[0]).all().item())
+        for r in ctx:
+            r.close()
+        rows[label] = {"rays": nrays, "ns": ns, "live_samples": live, "trans_off_ms": t[0], "tgrad_off_ms": t[1], "trans_on_ms": t[2], "tgrad_on_ms": t[3],
+                       "tgrad_over_trans_off": round(t[1]["median"] / t[0]["median"], 2), "tgrad_over_trans_on": round(t[3]["median"] / t[2]["median"], 2),
+                       "finite": finite, "per_ray": per_ray(stats), "ray_stats": stats}
+    return {"gaussians": len(g), "limit": TGRAD_LIMIT, "rows": rows}
+
+
+def check_tgrad(z):
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            assert r[f"tgrad_{key}_ms"]["median"] < TGRAD_LIMIT * r[f"trans_{key}_ms"]["median"], \
+                f"{label}, index {key}: a transmittance gradient bundle has to take less time than {TGRAD_LIMIT:.0f} transmittance bundles of the same rays"
+
+
+def markdown_tgrad(z, resources=""):
+    lines = [f"""# Transmittance gradient bundles (tools/ray_bundles.py --tgrad-only)
+
+`vrt_hip_transmittance_bundle_grad_device` (table and per-sample output) against `vrt_hip_transmittance_bundle_device` of the same rays
+and samples in the same run: `-g 64` (N = {z['gaussians']}), device pointers, stream events around back-to-back calls, the four paths
+(transmittance / gradient, Morton index off / on: two contexts) alternating; ms per call, median (min .. max).  The only condition: a
+gradient call takes less time than {z['limit']:.0f} transmittance bundles, what central differences cost for the five parameters of ONE
+Gaussian.  Depth mode runs at the depths `vrt_hip_depth_bundle_device` returned for the level; a ray that never reaches the level has
+depth +inf, which the gradient skips (live samples: finite depths > 0) and the transmittance bundle is given s = 8 for.
+
+| bundle | rays | ns | live samples | index | transmittance | gradient | gradient / transmittance | list entries per lane = ray ray | long rays |
+|---|---|---|---|---|---|---|---|---|---|"""]
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            lines.append(f"| {label} | {r['rays']} | {r['ns']} | {r['live_samples']} | {key} | {ms(r[f'trans_{key}_ms'])} | {ms(r[f'tgrad_{key}_ms'])} | "
+                         f"{r[f'tgrad_over_trans_{key}']} | {r['per_ray']['list_entries']} | {r['per_ray']['long_rays']} |")
+    lines.append("""
+Not taken: a direct-deposit form of the lane = ray kernel without its 24 KB of running sums for ns <= 4 (shadow rays), a profile under
+rocprofv3, the host-pointer form, any scene but `-g 64`, the max-ilp scheduler on this unit, other chunk sizes than NSC = 512.
+""")
+    if resources:
+        lines.append("Resources (`tools/kernel_resources.sh raytgrad`; template arguments: Exp (0 libm, 1 vcl), Erf (0 libm, 1 A&S), INDEXED):\n\n```\n" + resources.rstrip() + "\n```\n")
+    return "\n".join(lines)
+
+
 def windows(fns, calls, repeats, warm=3):
     """ms per call of each fn: `repeats` windows of `calls` back-to-back calls between two stream events, the fns alternating."""
     import torch
@@ -540,6 +635,7 @@ def main():
     ap.add_argument("--transmittance-only", action="store_true")
     ap.add_argument("--depth-only", action="store_true")
     ap.add_argument("--grad-only", action="store_true")
+    ap.add_argument("--tgrad-only", action="store_true")
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
     if a.transmittance_only:
@@ -556,6 +652,17 @@ def main():
         with open(os.path.join(a.out_dir, "ray_grad.md"), "w") as f:
             f.write(markdown_grad(z, open(res).read() if os.path.exists(res) else ""))
         print(json.dumps({"grad": z}))
+        return
+    if a.tgrad_only:
+        z = part_tgrad(g)
+        os.makedirs(a.out_dir, exist_ok=True)
+        with open(os.path.join(a.out_dir, "ray_trans_grad.json"), "w") as f:
+            f.write(json.dumps({"what": "transmittance gradient bundles against transmittance bundles of the same rays; see tools/ray_bundles.py (tg)", "tgrad": z}) + "\n")
+        res = os.path.join(a.out_dir, "ray_trans_grad_resources.txt")
+        with open(os.path.join(a.out_dir, "ray_trans_grad.md"), "w") as f:
+            f.write(markdown_tgrad(z, open(res).read() if os.path.exists(res) else ""))
+        print(json.dumps({"tgrad": z}))
+        check_tgrad(z)
         return
     if a.depth_only:
         z = part_depth(g)
