@@ -252,6 +252,12 @@ class Renderer:
         if rc != 0:
             raise VrtHipError(f"{what} failed ({rc}): {self._L.vrt_hip_last_error(self._h).decode()}")
 
+    def _device(self, what, nrays, d_origins, origin_per_ray, d_dirs, *rest):
+        """vrt_hip_<what>, the device form of a ray bundle: the rays, then the kind's own arguments as ctypes takes them, the stream last."""
+        rc = getattr(self._L, "vrt_hip_" + what)(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None, *rest)
+        if rc != 0:
+            self._chk(rc, what)
+
     # ---- scene ----
     def set_gaussians(self, g):
         """g: structured array with fields albedo[4], mu[4], sigma, magnitude (gaussian_t, types.h:195-200)."""
@@ -537,10 +543,8 @@ class Renderer:
     def radiance_rays_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_radiance=0, d_image=0, pack=PACK_ROUND | ALPHA_COMPUTED,
                              stream=0):
         """vrt_hip_radiance_rays_device: device pointers, everything enqueued on `stream`."""
-        rc = self._L.vrt_hip_radiance_rays_device(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None,
-                                                  d_radiance or None, d_image or None, int(pack), stream or None)
-        if rc != 0:
-            self._chk(rc, "radiance_rays_device")
+        self._device("radiance_rays_device", nrays, d_origins, origin_per_ray, d_dirs, d_radiance or None, d_image or None, int(pack),
+                     stream or None)
 
     def _profile(self, what, origins, dirs, table, table_per_ray):
         """vrt_hip_<what>: a table of values, shared or per ray, in; a result f32 [nrays, values per ray] out."""
@@ -559,10 +563,8 @@ class Renderer:
 
     def transmittance_bundle_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_s, ns, s_per_ray, d_T, stream=0):
         """vrt_hip_transmittance_bundle_device: device pointers, everything enqueued on `stream`."""
-        rc = self._L.vrt_hip_transmittance_bundle_device(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None,
-                                                         d_s or None, int(ns), int(bool(s_per_ray)), d_T or None, stream or None)
-        if rc != 0:
-            self._chk(rc, "transmittance_bundle_device")
+        self._device("transmittance_bundle_device", nrays, d_origins, origin_per_ray, d_dirs, d_s or None, int(ns), int(bool(s_per_ray)),
+                     d_T or None, stream or None)
 
     def depth_bundle(self, origins, dirs, tau, tau_per_ray=None):
         """vrt_hip_depth_bundle: the distance along each ray at which its transmittance falls to the levels tau -- 0 where it starts at
@@ -573,10 +575,8 @@ class Renderer:
 
     def depth_bundle_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_tau, nt, tau_per_ray, d_depth, stream=0):
         """vrt_hip_depth_bundle_device: device pointers, everything enqueued on `stream`."""
-        rc = self._L.vrt_hip_depth_bundle_device(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None,
-                                                 d_tau or None, int(nt), int(bool(tau_per_ray)), d_depth or None, stream or None)
-        if rc != 0:
-            self._chk(rc, "depth_bundle_device")
+        self._device("depth_bundle_device", nrays, d_origins, origin_per_ray, d_dirs, d_tau or None, int(nt), int(bool(tau_per_ray)),
+                     d_depth or None, stream or None)
 
     def radiance_rays_grad(self, origins, dirs, grad_radiance):
         """vrt_hip_radiance_rays_grad: the derivative of a loss with respect to the Gaussians, given its derivative grad_radiance
@@ -594,10 +594,8 @@ class Renderer:
     def radiance_rays_grad_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_grad_radiance, d_grad, stream=0):
         """vrt_hip_radiance_rays_grad_device: device pointers, everything enqueued on `stream`; ADDS into d_grad ([N, GRAD_STRIDE]
         float32: grad_columns names its columns)."""
-        rc = self._L.vrt_hip_radiance_rays_grad_device(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None,
-                                                       d_grad_radiance or None, d_grad or None, stream or None)
-        if rc != 0:
-            self._chk(rc, "radiance_rays_grad_device")
+        self._device("radiance_rays_grad_device", nrays, d_origins, origin_per_ray, d_dirs, d_grad_radiance or None, d_grad or None,
+                     stream or None)
 
     def transmittance_bundle_grad(self, origins, dirs, s, grad_T, wrt=TGRAD_T, s_per_ray=None, want_table=True, want_grad_s=True):
         """vrt_hip_transmittance_bundle_grad: the derivative of a loss with respect to the Gaussians and the samples, given its
@@ -622,11 +620,8 @@ class Renderer:
                                          stream=0):
         """vrt_hip_transmittance_bundle_grad_device: device pointers, everything enqueued on `stream`; ADDS into columns 4..8 of d_grad
         ([N, GRAD_STRIDE] float32: grad_columns names its columns) and STORES d_grad_s ([nrays, ns]); either may be 0, not both."""
-        rc = self._L.vrt_hip_transmittance_bundle_grad_device(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None,
-                                                              d_s or None, int(ns), int(bool(s_per_ray)), d_grad_T or None, int(wrt),
-                                                              d_grad or None, d_grad_s or None, stream or None)
-        if rc != 0:
-            self._chk(rc, "transmittance_bundle_grad_device")
+        self._device("transmittance_bundle_grad_device", nrays, d_origins, origin_per_ray, d_dirs, d_s or None, int(ns), int(bool(s_per_ray)),
+                     d_grad_T or None, int(wrt), d_grad or None, d_grad_s or None, stream or None)
 
     def ray_stats(self):
         """Counts of the last bundle (enable_stats first): see vrt_hip_ray_stats in include/vrt_hip.h."""

@@ -235,14 +235,16 @@ struct vrt_hip_ctx {
     DevBuf<uint32_t> d_image;
     DevBuf<float4> d_rad;
     // ray bundles (vrt_hip_rays.cpp): the long-ray queue, its two counters, the long kernel's scratch slots and the
-    // statistics words grow only; rays_in / rays_rad / rays_img stage the host-pointer form
+    // statistics words grow only; the rays_* buffers stage the host-pointer forms and grow only, each named by what passes through it
     DevBuf<uint32_t> ray_queue, ray_counters, ray_scratch;
     DevBuf<unsigned long long> ray_stats;
-    DevBuf<float> rays_in[2];
-    DevBuf<float> rays_s, rays_T; // transmittance, depth and gradient bundles: sample distances (levels, d loss / d radiance) and results of the host-pointer form
-    DevBuf<float> rays_g, rays_gs; // transmittance gradient bundles, host-pointer form: d loss / d T (or depth) in, d loss / d samples (or levels) out
-    DevBuf<float4> rays_rad;
-    DevBuf<uint32_t> rays_img;
+    DevBuf<float> rays_in[2];     // origins (one or one per ray), directions
+    DevBuf<float> rays_values_in; // a table of values, one for the bundle or one per ray: sample distances, levels
+    DevBuf<float> rays_each_in;   // something per ray and value, in: d loss / d radiance [nrays, 4], d loss / d T (or depth) [nrays, ns]
+    DevBuf<float> rays_each_out;  // something per ray and value, out: T, depths, d loss / d samples (or levels)
+    DevBuf<float> rays_table_out; // the gradient table [n, VRT_HIP_GRAD_STRIDE], cleared ahead of every bundle that adds to it
+    DevBuf<float4> rays_rad;      // radiance per ray, out
+    DevBuf<uint32_t> rays_img;    // packed pixels per ray, out
     bool ray_stats_valid = false; // ray_stats holds the counts of the last bundle (stats were on for it)
     // Morton index of the ray bundles (vrt_hip_set_ray_index; build_ray_index in vrt_hip_rays.cpp): made with the static tables
     // while it is switched on, or by the first bundle after it was switched on; never per bundle

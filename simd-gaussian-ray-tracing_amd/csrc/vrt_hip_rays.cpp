@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <numeric>
 
 #include "vrt_hip_ctx.hpp"
@@ -165,109 +166,126 @@ int build_ray_index(vrt_hip_ctx *c)
 
 namespace {
 
-// A kind of bundle as its entry points see it: its name and what it calls its tables and results in the messages; for the two kinds
-// that turn a table of values (one for the bundle or one per ray) into a result per ray and value -- sample distances into T, levels into
-// depths -- also what the table's length is called, where the four arguments go in RayArgs and which kernels run.
+// A kind of bundle as its entry points see it: its name, what it calls its tables and results and their length in the messages, what
+// its check asks on top of every kind's, and which kernels run.
 struct BundleKind {
     const char *name, *io_text, *count;
-    const float *RayArgs::*table;
-    uint64_t RayArgs::*n;
-    int RayArgs::*per_ray;
-    float *RayArgs::*out;
+    bool gradient; // a derivative: a scene of no Gaussians is a bundle of nothing, and the Exp / Erf pair must have kernels
+    bool modes;    // ... of what `wrt` names
     void (*launch)(const RayArgs &, uint32_t, bool, int, int, hipStream_t);
 };
-const BundleKind RADIANCE = { "radiance_rays", "no output buffer", "", nullptr, nullptr, nullptr, nullptr, launch_ray_bundle };
-const BundleKind TRANSMITTANCE = { "transmittance_bundle", "NULL samples or result", "ns", &RayArgs::s, &RayArgs::ns, &RayArgs::s_per_ray, &RayArgs::T,
-                                   launch_ray_trans_bundle };
-const BundleKind DEPTH = { "depth_bundle", "NULL levels or result", "nt", &RayArgs::tau, &RayArgs::nt, &RayArgs::tau_per_ray, &RayArgs::depth,
-                           launch_ray_depth_bundle };
-const BundleKind GRADIENT = { "radiance_rays_grad", "NULL grad_radiance or gradient table", "", nullptr, nullptr, nullptr, nullptr, launch_ray_grad_bundle };
-const BundleKind TRANS_GRADIENT = { "transmittance_bundle_grad", "NULL samples or grad_T, or neither a gradient table nor grad_s", "ns", &RayArgs::s, &RayArgs::ns,
-                                    &RayArgs::s_per_ray, &RayArgs::grad_s, launch_ray_trans_grad_bundle };
+const BundleKind RADIANCE = { "radiance_rays", "no output buffer", "", false, false, launch_ray_bundle };
+const BundleKind TRANSMITTANCE = { "transmittance_bundle", "NULL samples or result", "ns", false, false, launch_ray_trans_bundle };
+const BundleKind DEPTH = { "depth_bundle", "NULL levels or result", "nt", false, false, launch_ray_depth_bundle };
+const BundleKind GRADIENT = { "radiance_rays_grad", "NULL grad_radiance or gradient table", "", true, false, launch_ray_grad_bundle };
+const BundleKind TRANS_GRADIENT = { "transmittance_bundle_grad", "NULL samples or grad_T, or neither a gradient table nor grad_s", "ns", true, true,
+                                    launch_ray_trans_grad_bundle };
 
-// What every entry point checks before anything else, host and device form alike.  n: values per ray (1 for radiance); io_ok: the kind's
-// tables and results are there.  True when the call is over, with rc its result: an error, or VRT_HIP_OK for a bundle of nothing.
-bool bundle_over(vrt_hip_ctx *c, const BundleKind &k, size_t nrays, size_t n, const void *origins, const void *dirs, bool io_ok, int &rc)
+// The rays of a call, device or host pointers alike
+struct Rays {
+    size_t nrays;
+    const float *origins;
+    int origin_per_ray;
+    const float *dirs;
+};
+
+// What every entry point checks before anything else, host and device form alike.  n: values per ray (1 for radiance and its gradient);
+// io_ok: the kind's tables and results are there; wrt: read by a kind with modes only.  True when the call is over, with rc its result:
+// an error, or VRT_HIP_OK for a bundle of nothing.
+bool bundle_over(vrt_hip_ctx *c, const BundleKind &k, const Rays &r, size_t n, bool io_ok, int wrt, int &rc)
 {
     const std::string name = k.name;
     if (!c) rc = VRT_HIP_ERR_INVALID;
-    else if (nrays == 0 || n == 0) rc = VRT_HIP_OK;
-    else if (!origins || !dirs) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": NULL origins or directions");
+    else if (r.nrays == 0 || n == 0 || (k.gradient && c->n == 0)) rc = VRT_HIP_OK;
+    else if (!r.origins || !r.dirs) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": NULL origins or directions");
     else if (!io_ok) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": " + k.io_text);
-    else if (nrays > 0xFFFFFFF0ull) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": more than 2^32 - 16 rays in one bundle");
-    else if (n > (SIZE_MAX / sizeof(float)) / nrays) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": nrays * " + k.count + " does not fit");
+    else if (r.nrays > 0xFFFFFFF0ull) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": more than 2^32 - 16 rays in one bundle");
+    else if (n > (SIZE_MAX / sizeof(float)) / r.nrays) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": nrays * " + k.count + " does not fit");
+    else if (k.gradient && !ray_grad_pair_supported(c->exp_kind, c->erf_kind))
+        rc = fail(c, VRT_HIP_ERR_INVALID, name + ": the derivative is taken under {vcl_exp, expf} x {A&S erf, erff} only; the selected pair has jumps");
+    else if (k.modes && wrt != VRT_HIP_TGRAD_T && wrt != VRT_HIP_TGRAD_DEPTH)
+        rc = fail(c, VRT_HIP_ERR_INVALID, name + ": wrt is neither VRT_HIP_TGRAD_T nor VRT_HIP_TGRAD_DEPTH");
     else return false;
     return true;
 }
 
-// What a gradient bundle checks on top of bundle_over (one "value" per ray when the scene has Gaussians, none when it has not: a bundle
-// of nothing): the Exp / Erf pair has kernels.
-bool grad_over(vrt_hip_ctx *c, size_t nrays, const void *origins, const void *dirs, bool io_ok, int &rc, const BundleKind &k = GRADIENT, size_t n = 1)
-{
-    if (bundle_over(c, k, nrays, c && c->n == 0 ? 0 : n, origins, dirs, io_ok, rc)) return true;
-    if (ray_grad_pair_supported(c->exp_kind, c->erf_kind)) return false;
-    rc = fail(c, VRT_HIP_ERR_INVALID, std::string(k.name) + ": the derivative is taken under {vcl_exp, expf} x {A&S erf, erff} only; the selected pair has jumps");
-    return true;
-}
-
-// What a transmittance gradient bundle checks: grad_over with ns values per ray, and the mode
-bool trans_grad_over(vrt_hip_ctx *c, size_t nrays, const void *origins, const void *dirs, const void *s, size_t ns, const void *grad_T, int wrt,
-                     const void *grad, const void *grad_s, int &rc)
-{
-    if (grad_over(c, nrays, origins, dirs, s && grad_T && (grad || grad_s), rc, TRANS_GRADIENT, ns)) return true;
-    if (wrt == VRT_HIP_TGRAD_T || wrt == VRT_HIP_TGRAD_DEPTH) return false;
-    rc = fail(c, VRT_HIP_ERR_INVALID, std::string(TRANS_GRADIENT.name) + ": wrt is neither VRT_HIP_TGRAD_T nor VRT_HIP_TGRAD_DEPTH");
-    return true;
-}
-
-// Origins and directions of a host-pointer form into their staging buffers, on the context's stream.  The caller has quiesced (an
-// earlier bundle may still read the staging buffers) and reserved its other staging buffers: no buffer grows behind a copy.
-int stage_rays(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs)
-{
-    const size_t no = (origin_per_ray ? nrays : 1) * 3;
-    HIPCHK(c, c->rays_in[0].reserve(no));
-    HIPCHK(c, c->rays_in[1].reserve(nrays * 3));
-    HIPCHK(c, hipMemcpyAsync(c->rays_in[0].p, origins, no * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rays_in[1].p, dirs, nrays * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    return VRT_HIP_OK;
-}
-
-// The device form of a transmittance or depth bundle
-int profile_device(vrt_hip_ctx *c, const BundleKind &k, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs, const float *d_table,
-                   size_t n, int per_ray, float *d_out, hipStream_t st)
+// The device form of every kind: the check, what every bundle enqueues, the kind's own fields of RayArgs (fill), its two kernels
+template <class Fill>
+int device_bundle(vrt_hip_ctx *c, const BundleKind &k, const Rays &r, size_t n, bool io_ok, int wrt, void *hip_stream, Fill &&fill)
 {
     int rc;
-    if (bundle_over(c, k, nrays, n, d_origins, d_dirs, d_table && d_out, rc)) return rc;
+    if (bundle_over(c, k, r, n, io_ok, wrt, rc)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
     Bundle b;
-    rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b);
+    rc = enqueue_bundle(c, r.nrays, r.origins, r.origin_per_ray, r.dirs, st, b);
     if (rc) return rc;
-    b.a.*k.table = d_table; b.a.*k.n = n; b.a.*k.per_ray = per_ray ? 1 : 0; b.a.*k.out = d_out;
+    fill(b.a);
     k.launch(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
     HIPCHK(c, hipGetLastError());
     return VRT_HIP_OK;
 }
 
-// The host form: rays and table staged, the device form on the context's stream, the result copied back and waited for
-int profile_host(vrt_hip_ctx *c, const BundleKind &k, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *table, size_t n,
-                 int per_ray, float *out)
+// A staging buffer of any element type, as the host path sees it: the path moves bytes
+struct AnyBuf {
+    void *buf;
+    size_t size; // of one element
+    hipError_t (*reserve_fn)(void *, size_t);
+    void *(*data_fn)(void *);
+    template <typename T>
+    AnyBuf(DevBuf<T> &b)
+        : buf(&b), size(sizeof(T)), reserve_fn([](void *p, size_t n) { return ((DevBuf<T> *)p)->reserve(n); }),
+          data_fn([](void *p) -> void * { return ((DevBuf<T> *)p)->p; })
+    {
+    }
+    hipError_t reserve(size_t n) const { return reserve_fn(buf, n); }
+    void *data() const { return data_fn(buf); }
+};
+// What a host-pointer form states: `count` elements at `host` copied into a staging buffer ahead of the device form ...
+struct CopiedIn {
+    AnyBuf buf;
+    const void *host;
+    size_t count;
+};
+// ... and `count` elements brought back from one behind it, the buffer cleared first where the kernels add to it.  A result the caller
+// did not ask for (host == nullptr) is left out altogether.
+struct BroughtBack {
+    AnyBuf buf;
+    void *host;
+    size_t count;
+    bool clear = false;
+};
+
+// The host-pointer form of every kind, behind its check (the lists name buffers of *c): nothing in flight (an earlier bundle may still
+// read the staging buffers), every reservation before any copy (no buffer grows behind a copy), rays and `in` copied in, the results
+// that ask for it cleared, the device form on the context's stream over the staging buffers, `out` copied back and waited for.
+template <class Device>
+int host_bundle(vrt_hip_ctx *c, const Rays &r, std::initializer_list<CopiedIn> in, std::initializer_list<BroughtBack> out, Device &&device)
 {
-    int rc;
-    if (bundle_over(c, k, nrays, n, origins, dirs, table && out, rc)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    rc = quiesce(c); // the staging buffers may still be read by an earlier bundle
+    int rc = quiesce(c);
     if (rc) return rc;
-    const size_t nvalues = (per_ray ? nrays : 1) * n;
-    HIPCHK(c, c->rays_s.reserve(nvalues));
-    HIPCHK(c, c->rays_T.reserve(nrays * n));
-    rc = stage_rays(c, nrays, origins, origin_per_ray, dirs);
+    const size_t no = (r.origin_per_ray ? r.nrays : 1) * 3;
+    for (const CopiedIn &s : in) HIPCHK(c, s.buf.reserve(s.count));
+    for (const BroughtBack &s : out)
+        if (s.host) HIPCHK(c, s.buf.reserve(s.count));
+    HIPCHK(c, c->rays_in[0].reserve(no));
+    HIPCHK(c, c->rays_in[1].reserve(r.nrays * 3));
+    HIPCHK(c, hipMemcpyAsync(c->rays_in[0].p, r.origins, no * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rays_in[1].p, r.dirs, r.nrays * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    for (const CopiedIn &s : in) HIPCHK(c, hipMemcpyAsync(s.buf.data(), s.host, s.count * s.buf.size, hipMemcpyHostToDevice, c->stream));
+    for (const BroughtBack &s : out)
+        if (s.host && s.clear) HIPCHK(c, hipMemsetAsync(s.buf.data(), 0, s.count * s.buf.size, c->stream));
+    rc = device(Rays{ r.nrays, c->rays_in[0].p, r.origin_per_ray, c->rays_in[1].p });
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->rays_s.p, table, nvalues * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    rc = profile_device(c, k, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->rays_s.p, n, per_ray, c->rays_T.p, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->rays_T.p, nrays * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    for (const BroughtBack &s : out)
+        if (s.host) HIPCHK(c, hipMemcpyAsync(s.host, s.buf.data(), s.count * s.buf.size, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return VRT_HIP_OK;
 }
+
+// the staging buffer of a result, or nullptr where the caller did not ask for that result
+template <typename T>
+T *wanted(const void *host, const DevBuf<T> &b) { return host ? b.p : nullptr; }
 
 } // namespace
 
@@ -276,147 +294,115 @@ extern "C" {
 int vrt_hip_radiance_rays_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
                                  float *d_radiance, uint32_t *d_image, int pack_flags, void *hip_stream)
 {
-    int rc;
-    if (bundle_over(c, RADIANCE, nrays, 1, d_origins, d_dirs, d_radiance || d_image, rc)) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
-    Bundle b;
-    rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b);
-    if (rc) return rc;
-    b.a.radiance = (float4 *)d_radiance; b.a.image = d_image; b.a.pack_flags = pack_flags;
-    RADIANCE.launch(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
-    HIPCHK(c, hipGetLastError());
-    return VRT_HIP_OK;
+    return device_bundle(c, RADIANCE, { nrays, d_origins, origin_per_ray, d_dirs }, 1, d_radiance || d_image, 0, hip_stream, [&](RayArgs &a) {
+        a.radiance = (float4 *)d_radiance; a.image = d_image; a.pack_flags = pack_flags;
+    });
 }
 
 int vrt_hip_radiance_rays(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
                           float *radiance_out, uint32_t *image_out, int pack_flags)
 {
+    const Rays r = { nrays, origins, origin_per_ray, dirs };
     int rc;
-    if (bundle_over(c, RADIANCE, nrays, 1, origins, dirs, radiance_out || image_out, rc)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = quiesce(c); // the staging buffers may still be read by an earlier bundle
-    if (rc) return rc;
-    if (radiance_out) HIPCHK(c, c->rays_rad.reserve(nrays));
-    if (image_out) HIPCHK(c, c->rays_img.reserve(nrays));
-    rc = stage_rays(c, nrays, origins, origin_per_ray, dirs);
-    if (rc) return rc;
-    rc = vrt_hip_radiance_rays_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, radiance_out ? (float *)c->rays_rad.p : nullptr,
-                                      image_out ? c->rays_img.p : nullptr, pack_flags, c->stream);
-    if (rc) return rc;
-    if (radiance_out) HIPCHK(c, hipMemcpyAsync(radiance_out, c->rays_rad.p, nrays * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    if (image_out) HIPCHK(c, hipMemcpyAsync(image_out, c->rays_img.p, nrays * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VRT_HIP_OK;
+    if (bundle_over(c, RADIANCE, r, 1, radiance_out || image_out, 0, rc)) return rc;
+    return host_bundle(c, r, {},
+                       { { c->rays_rad, radiance_out, nrays }, { c->rays_img, image_out, nrays } }, [&](const Rays &d) {
+                           return vrt_hip_radiance_rays_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, (float *)wanted(radiance_out, c->rays_rad),
+                                                               wanted(image_out, c->rays_img), pack_flags, c->stream);
+                       });
 }
 
 int vrt_hip_radiance_rays_grad_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
                                       const float *d_grad_radiance, float *d_grad, void *hip_stream)
 {
-    int rc;
-    if (grad_over(c, nrays, d_origins, d_dirs, d_grad_radiance && d_grad, rc)) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
-    Bundle b;
-    rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b);
-    if (rc) return rc;
-    b.a.grad_radiance = (const float4 *)d_grad_radiance; b.a.grad = d_grad;
-    GRADIENT.launch(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
-    HIPCHK(c, hipGetLastError());
-    return VRT_HIP_OK;
+    return device_bundle(c, GRADIENT, { nrays, d_origins, origin_per_ray, d_dirs }, 1, d_grad_radiance && d_grad, 0, hip_stream, [&](RayArgs &a) {
+        a.grad_radiance = (const float4 *)d_grad_radiance; a.grad = d_grad;
+    });
 }
 
-// The host form: rays and grad_radiance staged, a cleared table of the scene's size, the device form on the context's stream, the table
-// copied back and waited for
+// grad_radiance in; a cleared table of the scene's size out
 int vrt_hip_radiance_rays_grad(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
                                const float *grad_radiance, float *grad_out)
 {
+    const Rays r = { nrays, origins, origin_per_ray, dirs };
     int rc;
-    if (grad_over(c, nrays, origins, dirs, grad_radiance && grad_out, rc)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = quiesce(c); // the staging buffers may still be read by an earlier bundle
-    if (rc) return rc;
-    const size_t table = (size_t)c->n * VRT_HIP_GRAD_STRIDE;
-    HIPCHK(c, c->rays_s.reserve(nrays * 4));
-    HIPCHK(c, c->rays_T.reserve(table));
-    rc = stage_rays(c, nrays, origins, origin_per_ray, dirs);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->rays_s.p, grad_radiance, nrays * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->rays_T.p, 0, table * sizeof(float), c->stream));
-    rc = vrt_hip_radiance_rays_grad_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->rays_s.p, c->rays_T.p, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(grad_out, c->rays_T.p, table * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VRT_HIP_OK;
+    if (bundle_over(c, GRADIENT, r, 1, grad_radiance && grad_out, 0, rc)) return rc;
+    return host_bundle(c, r, { { c->rays_each_in, grad_radiance, nrays * 4 } },
+                       { { c->rays_table_out, grad_out, (size_t)c->n * VRT_HIP_GRAD_STRIDE, true } }, [&](const Rays &d) {
+                           return vrt_hip_radiance_rays_grad_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, c->rays_each_in.p, c->rays_table_out.p, c->stream);
+                       });
 }
 
 int vrt_hip_transmittance_bundle_grad_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
                                              const float *d_s, size_t ns, int s_per_ray, const float *d_grad_T, int wrt, float *d_grad, float *d_grad_s,
                                              void *hip_stream)
 {
-    int rc;
-    if (trans_grad_over(c, nrays, d_origins, d_dirs, d_s, ns, d_grad_T, wrt, d_grad, d_grad_s, rc)) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
-    const BundleKind &k = TRANS_GRADIENT;
-    Bundle b;
-    rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b);
-    if (rc) return rc;
-    b.a.*k.table = d_s; b.a.*k.n = ns; b.a.*k.per_ray = s_per_ray ? 1 : 0; b.a.*k.out = d_grad_s;
-    b.a.grad_T = d_grad_T; b.a.wrt = wrt; b.a.grad = d_grad;
-    k.launch(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
-    HIPCHK(c, hipGetLastError());
-    return VRT_HIP_OK;
+    return device_bundle(c, TRANS_GRADIENT, { nrays, d_origins, origin_per_ray, d_dirs }, ns, d_s && d_grad_T && (d_grad || d_grad_s), wrt, hip_stream,
+                         [&](RayArgs &a) {
+                             a.s = d_s; a.ns = ns; a.s_per_ray = s_per_ray ? 1 : 0;
+                             a.grad_T = d_grad_T; a.wrt = wrt; a.grad = d_grad; a.grad_s = d_grad_s;
+                         });
 }
 
-// The host form: rays, samples and grad_T staged, a cleared table of the scene's size, the device form on the context's stream, the
-// table and the per-sample output copied back and waited for
+// samples and grad_T in; a cleared table of the scene's size and the per-sample output out, either where asked for
 int vrt_hip_transmittance_bundle_grad(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *s,
                                       size_t ns, int s_per_ray, const float *grad_T, int wrt, float *grad_out, float *grad_s_out)
 {
+    const Rays r = { nrays, origins, origin_per_ray, dirs };
     int rc;
-    if (trans_grad_over(c, nrays, origins, dirs, s, ns, grad_T, wrt, grad_out, grad_s_out, rc)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = quiesce(c); // the staging buffers may still be read by an earlier bundle
-    if (rc) return rc;
-    const size_t table = (size_t)c->n * VRT_HIP_GRAD_STRIDE, nvalues = (s_per_ray ? nrays : 1) * ns;
-    HIPCHK(c, c->rays_s.reserve(nvalues));
-    HIPCHK(c, c->rays_g.reserve(nrays * ns));
-    if (grad_out) HIPCHK(c, c->rays_T.reserve(table));
-    if (grad_s_out) HIPCHK(c, c->rays_gs.reserve(nrays * ns));
-    rc = stage_rays(c, nrays, origins, origin_per_ray, dirs);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->rays_s.p, s, nvalues * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rays_g.p, grad_T, nrays * ns * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (grad_out) HIPCHK(c, hipMemsetAsync(c->rays_T.p, 0, table * sizeof(float), c->stream));
-    rc = vrt_hip_transmittance_bundle_grad_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->rays_s.p, ns, s_per_ray, c->rays_g.p, wrt,
-                                                  grad_out ? c->rays_T.p : nullptr, grad_s_out ? c->rays_gs.p : nullptr, c->stream);
-    if (rc) return rc;
-    if (grad_out) HIPCHK(c, hipMemcpyAsync(grad_out, c->rays_T.p, table * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (grad_s_out) HIPCHK(c, hipMemcpyAsync(grad_s_out, c->rays_gs.p, nrays * ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VRT_HIP_OK;
+    if (bundle_over(c, TRANS_GRADIENT, r, ns, s && grad_T && (grad_out || grad_s_out), wrt, rc)) return rc;
+    return host_bundle(c, r, { { c->rays_values_in, s, (s_per_ray ? nrays : 1) * ns }, { c->rays_each_in, grad_T, nrays * ns } },
+                       { { c->rays_table_out, grad_out, (size_t)c->n * VRT_HIP_GRAD_STRIDE, true },
+                         { c->rays_each_out, grad_s_out, nrays * ns } },
+                       [&](const Rays &d) {
+                           return vrt_hip_transmittance_bundle_grad_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, c->rays_values_in.p, ns, s_per_ray,
+                                                                           c->rays_each_in.p, wrt, wanted(grad_out, c->rays_table_out),
+                                                                           wanted(grad_s_out, c->rays_each_out), c->stream);
+                       });
 }
 
 int vrt_hip_transmittance_bundle_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
                                         const float *d_s, size_t ns, int s_per_ray, float *d_T, void *hip_stream)
 {
-    return profile_device(c, TRANSMITTANCE, nrays, d_origins, origin_per_ray, d_dirs, d_s, ns, s_per_ray, d_T, (hipStream_t)hip_stream);
+    return device_bundle(c, TRANSMITTANCE, { nrays, d_origins, origin_per_ray, d_dirs }, ns, d_s && d_T, 0, hip_stream, [&](RayArgs &a) {
+        a.s = d_s; a.ns = ns; a.s_per_ray = s_per_ray ? 1 : 0; a.T = d_T;
+    });
 }
 
+// sample distances in; T per ray and sample out
 int vrt_hip_transmittance_bundle(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *s,
                                  size_t ns, int s_per_ray, float *T_out)
 {
-    return profile_host(c, TRANSMITTANCE, nrays, origins, origin_per_ray, dirs, s, ns, s_per_ray, T_out);
+    const Rays r = { nrays, origins, origin_per_ray, dirs };
+    int rc;
+    if (bundle_over(c, TRANSMITTANCE, r, ns, s && T_out, 0, rc)) return rc;
+    return host_bundle(c, r, { { c->rays_values_in, s, (s_per_ray ? nrays : 1) * ns } },
+                       { { c->rays_each_out, T_out, nrays * ns } }, [&](const Rays &d) {
+                           return vrt_hip_transmittance_bundle_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, c->rays_values_in.p, ns, s_per_ray,
+                                                                      c->rays_each_out.p, c->stream);
+                       });
 }
 
 int vrt_hip_depth_bundle_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs, const float *d_tau,
                                 size_t nt, int tau_per_ray, float *d_depth, void *hip_stream)
 {
-    return profile_device(c, DEPTH, nrays, d_origins, origin_per_ray, d_dirs, d_tau, nt, tau_per_ray, d_depth, (hipStream_t)hip_stream);
+    return device_bundle(c, DEPTH, { nrays, d_origins, origin_per_ray, d_dirs }, nt, d_tau && d_depth, 0, hip_stream, [&](RayArgs &a) {
+        a.tau = d_tau; a.nt = nt; a.tau_per_ray = tau_per_ray ? 1 : 0; a.depth = d_depth;
+    });
 }
 
+// levels in; the depth per ray and level out
 int vrt_hip_depth_bundle(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *tau, size_t nt,
                          int tau_per_ray, float *depth_out)
 {
-    return profile_host(c, DEPTH, nrays, origins, origin_per_ray, dirs, tau, nt, tau_per_ray, depth_out);
+    const Rays r = { nrays, origins, origin_per_ray, dirs };
+    int rc;
+    if (bundle_over(c, DEPTH, r, nt, tau && depth_out, 0, rc)) return rc;
+    return host_bundle(c, r, { { c->rays_values_in, tau, (tau_per_ray ? nrays : 1) * nt } },
+                       { { c->rays_each_out, depth_out, nrays * nt } }, [&](const Rays &d) {
+                           return vrt_hip_depth_bundle_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, c->rays_values_in.p, nt, tau_per_ray, c->rays_each_out.p,
+                                                              c->stream);
+                       });
 }
 
 int vrt_hip_get_ray_stats(vrt_hip_ctx *c, vrt_hip_ray_stats *out)

@@ -543,4 +543,13 @@ __device__ __forceinline__ float transmittance_term(const SceneTables &S, uint32
     default: FN<VRT_EXP_VCL, VRT_ERF_AS>(__VA_ARGS__); break;                                      \
     }
 
+// the pairs without jumps, which the derivative kernels are instantiated for: ray_grad_pair_supported (vrt_ray_grad_kernel.hip) names the same four
+#define VRT_DISPATCH_GRAD_PAIR(FN, ...)                                                            \
+    switch (exp_kind * 8 + erf_kind) {                                                             \
+    case VRT_EXP_LIBM * 8 + VRT_ERF_LIBM: FN<VRT_EXP_LIBM, VRT_ERF_LIBM>(__VA_ARGS__); break;      \
+    case VRT_EXP_LIBM * 8 + VRT_ERF_AS: FN<VRT_EXP_LIBM, VRT_ERF_AS>(__VA_ARGS__); break;          \
+    case VRT_EXP_VCL * 8 + VRT_ERF_LIBM: FN<VRT_EXP_VCL, VRT_ERF_LIBM>(__VA_ARGS__); break;        \
+    default: FN<VRT_EXP_VCL, VRT_ERF_AS>(__VA_ARGS__); break;                                      \
+    }
+
 } // namespace vrtk

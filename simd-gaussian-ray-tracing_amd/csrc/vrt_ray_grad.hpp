@@ -1,8 +1,14 @@
 // vrt_ray_grad.hpp -- what the derivative kernels of the ray bundles share: vrt_ray_grad_kernel.hip (d radiance / d Gaussians) and
-// vrt_ray_trans_grad_kernel.hip (d transmittance / d Gaussians and samples, d depth / d Gaussians and levels).  One Gaussian against
-// one ray with the compensated c = mu - o and mubar = c . n that keep d / d mu accurate (grad_gauss), and the deposit of a row segment
-// into the caller's table, wave-summed where every lane names the same row (grad_deposit).  One text for both translation units: the
-// same (ray, Gaussian) gives the same A, c_perp, d2 and Erf(-mubar r) in either kind of gradient.
+// vrt_ray_trans_grad_kernel.hip (d transmittance / d Gaussians and samples, d depth / d Gaussians and levels).  One text each, for both
+// translation units and for the short and the long kernel of either:
+//   grad_gauss        one Gaussian against one ray with the compensated c = mu - o and mubar = c . n that keep d / d mu accurate: the same
+//                     (ray, Gaussian) gives the same A, c_perp, d2 and Erf(-mubar r) in either kind of gradient
+//   grad_deal         one weight dealt to one absorber: P, Q, R
+//   grad_row, _w      the row segment (d mu xyz, d sigma, d magnitude) from M, the coefficient of n and the sigma sum; with the terms in W
+//   grad_deposit      a row segment into the caller's table, wave-summed where every lane names the same row
+//   LaneList, grad_acc, grad_walk_begin / _next, grad_flush_short   lane = ray: a lane's list, the three running sums per list position and lane in LDS, the walk of a
+//                     lane's list with the next entry's rows loaded one iteration ahead, and every position to the table once
+//   grad_emitter_place, grad_pass1, grad_pass2    the radiance gradient's emitter set-up and the bodies of its two pair loops
 #pragma once
 #include "vrt_ray_cull.hpp"
 
@@ -81,6 +87,139 @@ __device__ __forceinline__ void grad_deposit(float *table, uint32_t idx, bool on
     } else if (on) {
 #pragma unroll
         for (int c = 0; c < NV; ++c) atomicAdd(&table[(size_t)idx * GRAD_STRIDE + col0 + c], v[c]);
+    }
+}
+
+// One weight w dealt to one absorber at x = x_ikj (or x_kj), E = Erf(-mubar_j r_j): P += w D, Q += w e2, R += w e2 x.  Returns w e2.
+template <int EXP, int ERF>
+__device__ __forceinline__ float grad_deal(const ErfEval<ERF> &erf, float w, float x, float E, float &P, float &Q, float &R)
+{
+    const float we = w * exp_neg_sq<EXP>(x);
+    P = __builtin_fmaf(w, E - erf(x), P);
+    Q += we;
+    R = __builtin_fmaf(we, x, R);
+    return we;
+}
+
+// The row segment of one Gaussian against one ray: d = (d mu xyz, d sigma, d magnitude) from M = d magnitude, the coefficient of n in
+// d mu and the sum that joins m M (1 / sigma + d2 / sigma^3) in d sigma.
+__device__ __forceinline__ void grad_row(const GradGauss &q, const LaneRay &ray, float mag, float M, float ncoef, float ssum, float (&d)[5])
+{
+    const float mM = mag * M;
+    const float alpha = -mM * q.inv_s2;
+    d[0] = __builtin_fmaf(alpha, q.px, ncoef * ray.nx);
+    d[1] = __builtin_fmaf(alpha, q.py, ncoef * ray.ny);
+    d[2] = __builtin_fmaf(alpha, q.pz, ncoef * ray.nz);
+    d[3] = mM * (q.inv_s + q.d2 * q.inv_s * q.inv_s2) + ssum;
+    d[4] = M;
+}
+// ... with the terms in W = the sum of all weights: -A C r e1 W onto the coefficient of n, A C r e1 m sqrt2 W onto d sigma, behind its other terms
+template <int EXP>
+__device__ __forceinline__ void grad_row_w(const GradGauss &q, const LaneRay &ray, float mag, float M, float ncoef, float ssum, float W, float (&d)[5])
+{
+    const float ArE = q.Ar * exp_neg_sq<EXP>(q.m);
+    grad_row(q, ray, mag, M, __builtin_fmaf(-ArE, W, ncoef), ssum, d);
+    d[3] = d[3] + ArE * q.m * SQRT_2 * W;
+}
+
+// ---- lane = ray (the short kernels) ----
+
+// s_acc: three running sums per list position and lane, [(c * RAY_PL + pos) * 64 + lane]: c = 0 M (d magnitude), 1 the coefficient of n,
+// 2 the sigma sum, the last two without their terms in W
+__device__ __forceinline__ float &grad_acc(float *s_acc, int c, uint32_t pos, uint32_t lane) { return s_acc[((uint32_t)c * RAY_PL + pos) * 64u + lane]; }
+
+// A lane's list: s_list[k*64 + lane], nl entries; loops over it run to nmax, the longest list of the wave's short rays
+struct LaneList {
+    const uint32_t *s_list;
+    uint32_t lane, nl, nmax;
+    __device__ __forceinline__ bool has(uint32_t j) const { return j < nl; }
+    __device__ __forceinline__ uint32_t at(uint32_t j) const { return j < nl ? s_list[j * 64 + lane] : 0u; } // past the end: row 0, never used
+};
+
+// One walk of a lane's list with the next entry's rows loaded one iteration ahead: grad_walk_begin loads the first entry's rows,
+// grad_walk_next hands out position j's grad_gauss (a harmless row with exact zero weights where the list has no position j) and loads
+// the rows of position j + 1.  The for (j < nmax) stays with the kernel (profiles/grad_bundle_refactor.md).
+struct ListWalk {
+    uint32_t lj;
+    float4 a, b;
+};
+__device__ __forceinline__ ListWalk grad_walk_begin(const SceneTables &S, const LaneList &L)
+{
+    ListWalk w;
+    w.lj = L.at(0);
+    w.a = S.mu_sig[w.lj]; w.b = S.gB[w.lj];
+    return w;
+}
+template <int EXP, int ERF>
+__device__ __forceinline__ GradGauss grad_walk_next(ListWalk &w, const SceneTables &S, const ErfEval<ERF> &erf, const LaneList &L, const LaneRay &ray, uint32_t j)
+{
+    const float4 ca = w.a, cb = w.b;
+    if (j + 1 < L.nmax) {
+        w.lj = L.at(j + 1);
+        w.a = S.mu_sig[w.lj]; w.b = S.gB[w.lj];
+    }
+    return grad_gauss<EXP, ERF>(erf, ca, cb, L.has(j), ray);
+}
+
+// Every list position to the table once, now that W is known.  The whole wave calls this.
+template <int EXP, int ERF>
+__device__ __forceinline__ void grad_flush_short(float *table, const SceneTables &S, const ErfEval<ERF> &erf, const LaneList &L, float *s_acc, const LaneRay &ray,
+                                                 float W)
+{
+    const uint32_t lane = L.lane;
+    for (uint32_t p = 0; p < L.nmax; ++p) {
+        const bool on = L.has(p); // nl is 0 in a lane without a ray of this kernel
+        const uint32_t idx = L.at(p);
+        const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], on, ray);
+        const float mag = on ? S.gD[idx].z : 0.f;
+        float d[5];
+        grad_row_w<EXP>(q, ray, mag, grad_acc(s_acc, 0, p, lane), grad_acc(s_acc, 1, p, lane), grad_acc(s_acc, 2, p, lane), W, d);
+        grad_deposit<5>(table, idx, on, d, 4u, lane);
+    }
+}
+
+// ---- the radiance gradient's pair loops: EC emitters against one absorber q (per lane in the short kernel, wave-uniform in the long) ----
+
+// where emitter (row ms) sits on the ray: the centre of its five sample points and their spacing; a lane without it gets a harmless one
+__device__ __forceinline__ void grad_emitter_place(bool on, float4 ms, const LaneRay &ray, float &mubar, float &sigma)
+{
+    const float cx = ms.x - ray.ox, cy = ms.y - ray.oy, cz = ms.z - ray.oz;
+    mubar = on ? dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz) : 0.f;
+    sigma = on ? ms.w : 1.f;
+}
+
+// pass 1: q's term of the exponents of T at the emitters' 5 EC sample points (the radiance kernel's pair loop)
+template <int ERF, int EC>
+__device__ __forceinline__ void grad_pass1(const ErfEval<ERF> &erf, const GradGauss &q, const float (&e_mubar)[EC], const float (&e_sigma)[EC], float (&acc)[EC][5])
+{
+#pragma unroll
+    for (int e = 0; e < EC; ++e) {
+        const float base = __builtin_fmaf(e_mubar[e], q.r, -q.m);
+        const float step = e_sigma[e] * q.r;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const float x = __builtin_fmaf((float)(k - 4), step, base);
+            acc[e][k] = __builtin_fmaf(q.A, q.E - erf(x), acc[e][k]);
+        }
+    }
+}
+
+// pass 2: the same pairs again; w_ik dealt to absorber q (P, Q, R) and through w e2 A C r back to the emitters (z, y)
+template <int EXP, int ERF, int EC>
+__device__ __forceinline__ void grad_pass2(const ErfEval<ERF> &erf, const GradGauss &q, const float (&e_mubar)[EC], const float (&e_sigma)[EC], const float (&w)[EC][5],
+                                           float (&z)[EC], float (&y)[EC], float &Pj, float &Qj, float &Rj)
+{
+#pragma unroll
+    for (int e = 0; e < EC; ++e) {
+        const float base = __builtin_fmaf(e_mubar[e], q.r, -q.m);
+        const float step = e_sigma[e] * q.r;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const float kf = (float)(k - 4);
+            const float t = q.Ar * grad_deal<EXP>(erf, w[e][k], __builtin_fmaf(kf, step, base), q.E, Pj, Qj, Rj);
+            z[e] += t;
+            y[e] = __builtin_fmaf(kf, t, y[e]);
+        }
     }
 }
 

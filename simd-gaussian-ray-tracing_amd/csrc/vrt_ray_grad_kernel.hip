@@ -16,19 +16,25 @@
 // Two passes over the pair loop per emitter chunk: the first is the radiance kernels' (the exponents of T, then w_ik); the second
 // evaluates D and e2 again and deals w_ik out to the absorbers (P, Q, R) and, through the same products, back to the emitter (Z, Y).
 // Nothing of size 5 n is stored: a chunk's w_ik live in registers between its two passes.
-//   ray_short_grad_kernel  lane = ray.  Three running sums per list position and lane in LDS (M, the n coefficient, the sigma sum:
-//                          24 KB next to the 8 KB of lists) take the chunks' shares; when all chunks are through, W is known and every
-//                          position is dealt to the caller's table once: 9 atomic adds per (ray, kept Gaussian) -- 4 (albedo) behind the
-//                          emitter's chunk, 5 at the end.  Where a position holds the same scene index in every lane that has one (a
-//                          coherent bundle), the values are summed over the wave (wave_sum) and ONE row segment is added.
-//   ray_long_grad_kernel   one wave per ray, lane = emitter, the absorber wave-uniform: P, Q, R are summed over the wave per (round of
-//                          128 emitters, absorber) and lanes 0..4 add one row segment; the emitter's own terms are per-lane adds (every
-//                          lane another row); the terms in W follow in a last walk of the list.
+//   ray_short_grad_kernel  lane = ray.  Three running sums per list position and lane in LDS (grad_acc: M, the n coefficient, the sigma
+//                          sum: 24 KB next to the 8 KB of lists) take the chunks' shares (ray_grad_chunk: two walks of the lane's list
+//                          through grad_walk_begin / grad_walk_next, their bodies grad_pass1 and grad_pass2); when all chunks are
+//                          through, W is known and every position is dealt to the caller's table once (grad_flush_short: grad_row_w,
+//                          then grad_deposit): 9 atomic adds per (ray, kept Gaussian) -- 4 (albedo) behind the emitter's chunk, 5 at the
+//                          end.  Where a position holds the same scene index in every lane that has one (a coherent bundle), the values
+//                          are summed over the wave (wave_sum) and ONE row segment is added.
+//   ray_long_grad_kernel   one wave per ray, lane = emitter, the absorber wave-uniform: the same grad_pass1 and grad_pass2; P, Q, R are
+//                          summed over the wave per (round of 128 emitters, absorber) and lanes 0..4 add one row segment (grad_row); the
+//                          emitter's own terms (grad_row again) are per-lane adds (every lane another row); the terms in W follow in a
+//                          last walk of the list.
 // Exp / Erf of the forward quantities are the selected pair's; e1 and e2 are exp_neg_sq<EXP>.  Only {vcl, libm} x {A&S, libm} are
 // instantiated: the piecewise approximations have jumps, and the entry point refuses them.
 // The sums in the caller's table depend on the arrival order of the atomic adds: not bitwise reproducible.
 // Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
-#include "vrt_ray_grad.hpp" // grad_gauss, grad_deposit, exact_diff: shared with vrt_ray_trans_grad_kernel.hip
+// What lives where: this file has the emitter's weights (grad_emitter), the chunk of the short kernel, the two kernels' own loops -- how
+// the absorber is loaded (per lane; readfirstlane + uload) and where a sum goes (LDS; the table) -- and the launch.  Every formula named
+// above is vrt_ray_grad.hpp's, shared with vrt_ray_trans_grad_kernel.hip.
+#include "vrt_ray_grad.hpp"
 
 namespace vrtk {
 
@@ -48,9 +54,6 @@ __device__ __forceinline__ float grad_emitter(bool on, float sigma, float d2, fl
     return on ? V : 0.f; // a lane without this emitter: exact zeros, whatever its exponents came to
 }
 
-// s_acc: three sums per list position and lane, [(c * RAY_PL + pos) * 64 + lane]: c = 0 M, 1 the coefficient of n, 2 the sigma sum
-__device__ __forceinline__ float &grad_acc(float *s_acc, int c, uint32_t pos, uint32_t lane) { return s_acc[((uint32_t)c * RAY_PL + pos) * 64u + lane]; }
-
 // One chunk of EC emitters (list positions i0 .. i0+EC-1 of every lane) against the lane's whole list, both passes.
 template <int EXP, int ERF, int EC>
 __device__ __forceinline__ void ray_grad_chunk(const RayArgs *Pp, const SceneTables *Sp, const uint32_t *s_list /*[k*64 + lane]*/, float *s_acc, uint32_t nl,
@@ -63,10 +66,7 @@ __device__ __forceinline__ void ray_grad_chunk(const RayArgs *Pp, const SceneTab
     for (int e = 0; e < EC; ++e) {
         const bool on = i0 + e < nl;
         const uint32_t idx = on ? s_list[(i0 + e) * 64 + lane] : 0u;
-        const float4 ms = S.mu_sig[idx];
-        const float cx = ms.x - ray.ox, cy = ms.y - ray.oy, cz = ms.z - ray.oz;
-        e_mubar[e] = on ? dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz) : 0.f;
-        e_sigma[e] = on ? ms.w : 1.f;
+        grad_emitter_place(on, S.mu_sig[idx], ray, e_mubar[e], e_sigma[e]);
     }
 
     // ---- pass 1: the exponents of T at the chunk's 5 EC sample points (the radiance kernel's pair loop) ----
@@ -75,27 +75,9 @@ __device__ __forceinline__ void ray_grad_chunk(const RayArgs *Pp, const SceneTab
     for (int e = 0; e < EC; ++e)
 #pragma unroll
         for (int k = 0; k < 5; ++k) acc[e][k] = 0.f;
-    uint32_t lj = nl ? s_list[lane] : 0u;
-    float4 a = S.mu_sig[lj], b = S.gB[lj];
-    for (uint32_t j = 0; j < nmax; ++j) {
-        const float4 ca = a, cb = b;
-        const bool vj = j < nl;
-        if (j + 1 < nmax) {
-            lj = (j + 1 < nl) ? s_list[(j + 1) * 64 + lane] : 0u;
-            a = S.mu_sig[lj]; b = S.gB[lj];
-        }
-        const GradGauss q = grad_gauss<EXP, ERF>(erf, ca, cb, vj, ray);
-#pragma unroll
-        for (int e = 0; e < EC; ++e) {
-            const float base = __builtin_fmaf(e_mubar[e], q.r, -q.m);
-            const float step = e_sigma[e] * q.r;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const float x = __builtin_fmaf((float)(k - 4), step, base);
-                acc[e][k] = __builtin_fmaf(q.A, q.E - erf(x), acc[e][k]);
-            }
-        }
-    }
+    const LaneList L = { s_list, lane, nl, nmax };
+    ListWalk lw = grad_walk_begin(S, L);
+    for (uint32_t j = 0; j < nmax; ++j) grad_pass1(erf, grad_walk_next<EXP, ERF>(lw, S, erf, L, ray, j), e_mubar, e_sigma, acc);
 
     // ---- the emitters: w_ik, V_i; the albedo rows leave here ----
     float w[EC][5], GV[EC];
@@ -119,34 +101,11 @@ __device__ __forceinline__ void ray_grad_chunk(const RayArgs *Pp, const SceneTab
     float z[EC], y[EC];
 #pragma unroll
     for (int e = 0; e < EC; ++e) z[e] = y[e] = 0.f;
-    lj = nl ? s_list[lane] : 0u;
-    a = S.mu_sig[lj]; b = S.gB[lj];
+    lw = grad_walk_begin(S, L);
     for (uint32_t j = 0; j < nmax; ++j) {
-        const float4 ca = a, cb = b;
-        const bool vj = j < nl;
-        if (j + 1 < nmax) {
-            lj = (j + 1 < nl) ? s_list[(j + 1) * 64 + lane] : 0u;
-            a = S.mu_sig[lj]; b = S.gB[lj];
-        }
-        const GradGauss q = grad_gauss<EXP, ERF>(erf, ca, cb, vj, ray);
+        const GradGauss q = grad_walk_next<EXP, ERF>(lw, S, erf, L, ray, j);
         float Pj = 0.f, Qj = 0.f, Rj = 0.f;
-#pragma unroll
-        for (int e = 0; e < EC; ++e) {
-            const float base = __builtin_fmaf(e_mubar[e], q.r, -q.m);
-            const float step = e_sigma[e] * q.r;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const float kf = (float)(k - 4);
-                const float x = __builtin_fmaf(kf, step, base);
-                const float we = w[e][k] * exp_neg_sq<EXP>(x);
-                Pj = __builtin_fmaf(w[e][k], q.E - erf(x), Pj);
-                Qj += we;
-                Rj = __builtin_fmaf(we, x, Rj);
-                const float t = q.Ar * we;
-                z[e] += t;
-                y[e] = __builtin_fmaf(kf, t, y[e]);
-            }
-        }
+        grad_pass2<EXP>(erf, q, e_mubar, e_sigma, w, z, y, Pj, Qj, Rj);
         grad_acc(s_acc, 0, j, lane) += q.Am * Pj;
         grad_acc(s_acc, 1, j, lane) += q.Ar * Qj;
         grad_acc(s_acc, 2, j, lane) += q.Ar * Rj * SQRT_2;
@@ -188,22 +147,7 @@ __global__ __launch_bounds__(64) void ray_short_grad_kernel(RayArgs) // read thr
         else ray_grad_chunk<EXP, ERF, 1>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
     }
 
-    // ---- every list position to the table once, now that W is known ----
-    const ErfEval<ERF> erf;
-    for (uint32_t p = 0; p < nmax; ++p) {
-        const bool on = p < nl; // nl is 0 in a lane without a ray of this kernel
-        const uint32_t idx = on ? s_list[p * 64 + lane] : 0u;
-        const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], on, ray);
-        const float mag = on ? S.gD[idx].z : 0.f;
-        const float M = grad_acc(s_acc, 0, p, lane), mM = mag * M;
-        const float ArE = q.Ar * exp_neg_sq<EXP>(q.m);
-        const float alpha = -mM * q.inv_s2;
-        const float beta = __builtin_fmaf(-ArE, W, grad_acc(s_acc, 1, p, lane));
-        const float dsig = mM * (q.inv_s + q.d2 * q.inv_s * q.inv_s2) + grad_acc(s_acc, 2, p, lane) + ArE * q.m * SQRT_2 * W;
-        const float d[5] = { __builtin_fmaf(alpha, q.px, beta * ray.nx), __builtin_fmaf(alpha, q.py, beta * ray.ny),
-                             __builtin_fmaf(alpha, q.pz, beta * ray.nz), dsig, M };
-        grad_deposit<5>(P.grad, idx, on, d, 4u, lane);
-    }
+    grad_flush_short<EXP, ERF>(P.grad, S, ErfEval<ERF>(), LaneList{ s_list, lane, nl, nmax }, s_acc, ray, W);
 }
 
 // One wave per long ray, lane = emitter (EC rounds of 64 at a time), the absorber wave-uniform.
@@ -232,10 +176,7 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
                 const uint32_t p = e0 + (uint32_t)e * 64u + lane;
                 e_on[e] = p < n;
                 e_idx[e] = long_list_entry(s_list, L.slot, e_on[e] ? p : 0u);
-                const float4 ms = S.mu_sig[e_idx[e]];
-                const float cx = ms.x - ray.ox, cy = ms.y - ray.oy, cz = ms.z - ray.oz;
-                e_mubar[e] = e_on[e] ? dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz) : 0.f;
-                e_sigma[e] = e_on[e] ? ms.w : 1.f;
+                grad_emitter_place(e_on[e], S.mu_sig[e_idx[e]], ray, e_mubar[e], e_sigma[e]);
             }
             // ---- pass 1 ----
             float acc[EC][5];
@@ -245,17 +186,7 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
                 for (int k = 0; k < 5; ++k) acc[e][k] = 0.f;
             for (uint32_t j = 0; j < n; ++j) {
                 const uint32_t idx = __builtin_amdgcn_readfirstlane(long_list_entry(s_list, L.slot, j));
-                const GradGauss q = grad_gauss<EXP, ERF>(erf, uload(S.mu_sig, idx), uload(S.gB, idx), true, ray);
-#pragma unroll
-                for (int e = 0; e < EC; ++e) {
-                    const float base = __builtin_fmaf(e_mubar[e], q.r, -q.m);
-                    const float step = e_sigma[e] * q.r;
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) {
-                        const float x = __builtin_fmaf((float)(k - 4), step, base);
-                        acc[e][k] = __builtin_fmaf(q.A, q.E - erf(x), acc[e][k]);
-                    }
-                }
+                grad_pass1(erf, grad_gauss<EXP, ERF>(erf, uload(S.mu_sig, idx), uload(S.gB, idx), true, ray), e_mubar, e_sigma, acc);
             }
             // ---- the emitters ----
             float w[EC][5], GV[EC], e_mag[EC];
@@ -282,30 +213,11 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
                 const uint32_t idx = __builtin_amdgcn_readfirstlane(long_list_entry(s_list, L.slot, j));
                 const GradGauss q = grad_gauss<EXP, ERF>(erf, uload(S.mu_sig, idx), uload(S.gB, idx), true, ray);
                 float Pj = 0.f, Qj = 0.f, Rj = 0.f;
-#pragma unroll
-                for (int e = 0; e < EC; ++e) {
-                    const float base = __builtin_fmaf(e_mubar[e], q.r, -q.m);
-                    const float step = e_sigma[e] * q.r;
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) {
-                        const float kf = (float)(k - 4);
-                        const float x = __builtin_fmaf(kf, step, base);
-                        const float we = w[e][k] * exp_neg_sq<EXP>(x);
-                        Pj = __builtin_fmaf(w[e][k], q.E - erf(x), Pj);
-                        Qj += we;
-                        Rj = __builtin_fmaf(we, x, Rj);
-                        const float t = q.Ar * we;
-                        z[e] += t;
-                        y[e] = __builtin_fmaf(kf, t, y[e]);
-                    }
-                }
+                grad_pass2<EXP>(erf, q, e_mubar, e_sigma, w, z, y, Pj, Qj, Rj);
                 Pj = wave_sum(Pj); Qj = wave_sum(Qj); Rj = wave_sum(Rj);
-                const float mag = uload(S.gD, idx).z;
-                const float M = q.Am * Pj, mM = mag * M, alpha = -mM * q.inv_s2, beta = q.Ar * Qj;
-                const float dsig = mM * (q.inv_s + q.d2 * q.inv_s * q.inv_s2) + q.Ar * Rj * SQRT_2;
-                const float dx = __builtin_fmaf(alpha, q.px, beta * ray.nx), dy = __builtin_fmaf(alpha, q.py, beta * ray.ny),
-                            dz = __builtin_fmaf(alpha, q.pz, beta * ray.nz);
-                const float mine = lane == 0 ? dx : lane == 1 ? dy : lane == 2 ? dz : lane == 3 ? dsig : M;
+                float d[5];
+                grad_row(q, ray, uload(S.gD, idx).z, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, d);
+                const float mine = lane == 0 ? d[0] : lane == 1 ? d[1] : lane == 2 ? d[2] : lane == 3 ? d[3] : d[4];
                 if (lane < 5u) atomicAdd(&P.grad[(size_t)idx * GRAD_STRIDE + 4u + lane], mine);
             }
             // ---- the emitters' own terms: every lane another row ----
@@ -313,13 +225,11 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
             for (int e = 0; e < EC; ++e) {
                 if (e_on[e]) {
                     const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[e_idx[e]], S.gB[e_idx[e]], true, ray);
-                    const float M = GV[e], mM = e_mag[e] * M, alpha = -mM * q.inv_s2, beta = -z[e];
+                    float d[5];
+                    grad_row(q, ray, e_mag[e], GV[e], -z[e], -y[e], d);
                     float *row = P.grad + (size_t)e_idx[e] * GRAD_STRIDE;
-                    atomicAdd(row + 4, __builtin_fmaf(alpha, q.px, beta * ray.nx));
-                    atomicAdd(row + 5, __builtin_fmaf(alpha, q.py, beta * ray.ny));
-                    atomicAdd(row + 6, __builtin_fmaf(alpha, q.pz, beta * ray.nz));
-                    atomicAdd(row + 7, mM * (q.inv_s + q.d2 * q.inv_s * q.inv_s2) - y[e]);
-                    atomicAdd(row + 8, M);
+#pragma unroll
+                    for (int c = 0; c < 5; ++c) atomicAdd(row + 4 + c, d[c]);
                 }
             }
         }
@@ -345,6 +255,7 @@ static void launch_ray_grad_bundle_t(const RayArgs &a, uint32_t long_grid, bool 
     if (indexed) launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, true>, ray_long_grad_kernel<EXP, ERF, true>, a, long_grid, st);
     else launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, false>, ray_long_grad_kernel<EXP, ERF, false>, a, long_grid, st);
 }
+// the four pairs of VRT_DISPATCH_GRAD_PAIR; out of line here because the entry points' check (vrt_hip_rays.cpp) asks too
 bool ray_grad_pair_supported(int exp_kind, int erf_kind)
 {
     return (exp_kind == VRT_EXP_VCL || exp_kind == VRT_EXP_LIBM) && (erf_kind == VRT_ERF_AS || erf_kind == VRT_ERF_LIBM);
@@ -352,12 +263,7 @@ bool ray_grad_pair_supported(int exp_kind, int erf_kind)
 void launch_ray_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
 {
     if (!a.nrays || !long_grid || !ray_grad_pair_supported(exp_kind, erf_kind)) return;
-    switch (exp_kind * 8 + erf_kind) {
-    case VRT_EXP_LIBM * 8 + VRT_ERF_LIBM: launch_ray_grad_bundle_t<VRT_EXP_LIBM, VRT_ERF_LIBM>(a, long_grid, indexed, st); break;
-    case VRT_EXP_LIBM * 8 + VRT_ERF_AS: launch_ray_grad_bundle_t<VRT_EXP_LIBM, VRT_ERF_AS>(a, long_grid, indexed, st); break;
-    case VRT_EXP_VCL * 8 + VRT_ERF_LIBM: launch_ray_grad_bundle_t<VRT_EXP_VCL, VRT_ERF_LIBM>(a, long_grid, indexed, st); break;
-    default: launch_ray_grad_bundle_t<VRT_EXP_VCL, VRT_ERF_AS>(a, long_grid, indexed, st); break;
-    }
+    VRT_DISPATCH_GRAD_PAIR(launch_ray_grad_bundle_t, a, long_grid, indexed, st);
 }
 
 } // namespace vrtk

@@ -17,23 +17,27 @@
 //   bracket a depth bundle returns.  A sample whose s_k is not finite or <= 0, or whose S_k == 0 (the depth bundle's +inf, 0 and NaN
 //   results) contributes exactly nothing, and its per-sample output is 0.
 // In both modes a sample with g_k == 0 is skipped exactly (its s_k is never used: no 0 * NaN), per-sample output 0.
-//   ray_short_trans_grad_kernel  lane = ray.  Per group of RAY_SG samples one walk of the lane's list forms E_k and S_k through grad_gauss
-//                                (the compensated c and mubar, not trans_entry's |c|^2 - mubar^2), then w_k, then a second walk deals w_k
-//                                out to P, Q, R of every list position.  Three running sums per list position and lane in LDS (A P / mag,
-//                                the coefficient of n without its W term, the sigma sum without its W term: 24 KB next to the 8 KB of
-//                                lists).  Only W is carried beside them: e1_j comes back from grad_gauss.  After the last group every
-//                                position goes to the table ONCE: 5 adds per (ray, kept Gaussian) whatever ns is, wave-summed where a
-//                                position holds one row in all lanes (grad_deposit).
+//   ray_short_trans_grad_kernel  lane = ray.  Per group of RAY_SG samples one walk of the lane's list (grad_walk_begin / grad_walk_next)
+//                                forms E_k and S_k through grad_gauss (the compensated c and mubar, not trans_entry's |c|^2 - mubar^2),
+//                                then w_k, then a second walk deals w_k out (grad_deal) to P, Q, R of every list position.  Three running
+//                                sums per list position and lane in LDS (grad_acc: A P / mag, the coefficient of n without its W term,
+//                                the sigma sum without its W term: 24 KB next to the 8 KB of lists).  Only W is carried beside them:
+//                                e1_j comes back from grad_gauss.  After the last group every position goes to the table ONCE
+//                                (grad_flush_short: grad_row_w, then grad_deposit): 5 adds per (ray, kept Gaussian) whatever ns is,
+//                                wave-summed where a position holds one row in all lanes.
 //   ray_long_trans_grad_kernel   one wave per queued ray, lane l takes entries l, l + 64, ...  The list has no bound, so no per-entry
 //                                sum waits in LDS: the samples are cut into chunks of NSC = 512.  E_k and S_k of a chunk's samples come
 //                                from wave_sum (w_k is wave-uniform) and go to LDS with their s_k; then every lane runs over its entries
-//                                with the chunk's samples in the inner loop, P, Q, R in registers, and adds its 5 values per entry and
-//                                chunk, the chunk's W terms included: 5 ceil(ns / NSC) adds per entry, every lane another row.
+//                                with the chunk's samples in the inner loop (grad_deal), P, Q, R in registers, and adds its 5 values per
+//                                entry and chunk (grad_row_w), the chunk's W terms included: 5 ceil(ns / NSC) adds per entry, every lane
+//                                another row.
 // The per-sample output is STORED (by the lane; by lane 0 of the long kernel), not added.
 // Exp / Erf of the forward quantities are the selected pair's; e1 and e2 are exp_neg_sq<EXP>.  Only {vcl, libm} x {A&S, libm} are
 // instantiated (ray_grad_pair_supported).  The sums in the caller's table depend on the arrival order of the atomic adds: not bitwise
 // reproducible.  Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
-#include "vrt_ray_grad.hpp"  // grad_gauss, grad_deposit: shared with vrt_ray_grad_kernel.hip
+// What lives where: this file has what a sample is (trans_grad_live, trans_grad_x, trans_grad_weight), the two kernels' loops over groups
+// and chunks of samples, and the launch.  The helpers named above are vrt_ray_grad.hpp's, shared with vrt_ray_grad_kernel.hip.
+#include "vrt_ray_grad.hpp"
 #include "vrt_ray_trans.hpp" // RAY_SG
 
 namespace vrtk {
@@ -69,9 +73,6 @@ __device__ __forceinline__ bool trans_grad_live(bool depth_mode, float s, float 
 // away), and e2 = exp(-x^2) passes an error dx on as 2 |x| dx -- 4e-5 of a far sample's addends on the grid scene, against 5e-6 this way.
 __device__ __forceinline__ float trans_grad_x(float s, const GradGauss &q) { return (s - q.mubar) * q.r; }
 
-// s_acc: three sums per list position and lane, [(c * RAY_PL + pos) * 64 + lane]: c = 0 A P / mag, 1 A C r Q, 2 A C R / sigma
-__device__ __forceinline__ float &tgrad_acc(float *s_acc, int c, uint32_t pos, uint32_t lane) { return s_acc[((uint32_t)c * RAY_PL + pos) * 64u + lane]; }
-
 template <int EXP, int ERF, bool INDEXED>
 __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
@@ -83,6 +84,7 @@ __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // re
     const ShortRay R = ray_short_begin<INDEXED>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
     const uint32_t nl = R.nl, nmax = R.nmax;
     const LaneRay &ray = R.ray;
+    const LaneList L = { s_list, lane, nl, nmax };
     const ErfEval<ERF> erf;
     const bool depth_mode = P.wrt == VRT_HIP_TGRAD_DEPTH;
     const uint64_t ns = P.ns;
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // re
 
     for (uint32_t p = 0; p < nmax; ++p)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) tgrad_acc(s_acc, c, p, lane) = 0.f;
+        for (int c = 0; c < 3; ++c) grad_acc(s_acc, c, p, lane) = 0.f; // here: A P / mag, A C r Q, A C R / sigma
 
     float W = 0.f;
     for (uint64_t k0 = 0; k0 < ns; k0 += RAY_SG) {
@@ -108,16 +110,10 @@ __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // re
         float accE[RAY_SG], accS[RAY_SG];
 #pragma unroll
         for (int g = 0; g < RAY_SG; ++g) accE[g] = accS[g] = 0.f;
-        uint32_t lj = nl ? s_list[lane] : 0u;
-        float4 a = S.mu_sig[lj], b = S.gB[lj];
+        ListWalk lw = grad_walk_begin(S, L);
         for (uint32_t j = 0; j < nmax; ++j) {
-            const float4 ca = a, cb = b;
-            const bool vj = j < nl;
-            if (j + 1 < nmax) { // the next entry's rows, one iteration ahead
-                lj = (j + 1 < nl) ? s_list[(j + 1) * 64 + lane] : 0u;
-                a = S.mu_sig[lj]; b = S.gB[lj];
-            }
-            const GradGauss q = grad_gauss<EXP, ERF>(erf, ca, cb, vj, ray);
+            const bool vj = L.has(j);
+            const GradGauss q = grad_walk_next<EXP, ERF>(lw, S, erf, L, ray, j);
 #pragma unroll
             for (int g = 0; g < RAY_SG; ++g) {
                 const float x = trans_grad_x(sv[g], q);
@@ -137,49 +133,20 @@ __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // re
         }
         if (!P.grad) continue;
         // ---- walk 2: the same entries again; w_k to P, Q, R of every position ----
-        lj = nl ? s_list[lane] : 0u;
-        a = S.mu_sig[lj]; b = S.gB[lj];
+        lw = grad_walk_begin(S, L);
         for (uint32_t j = 0; j < nmax; ++j) {
-            const float4 ca = a, cb = b;
-            const bool vj = j < nl;
-            if (j + 1 < nmax) {
-                lj = (j + 1 < nl) ? s_list[(j + 1) * 64 + lane] : 0u;
-                a = S.mu_sig[lj]; b = S.gB[lj];
-            }
-            const GradGauss q = grad_gauss<EXP, ERF>(erf, ca, cb, vj, ray);
+            const GradGauss q = grad_walk_next<EXP, ERF>(lw, S, erf, L, ray, j);
             float Pj = 0.f, Qj = 0.f, Rj = 0.f;
 #pragma unroll
-            for (int g = 0; g < RAY_SG; ++g) {
-                const float x = trans_grad_x(sv[g], q);
-                const float we = w[g] * exp_neg_sq<EXP>(x);
-                Pj = __builtin_fmaf(w[g], q.E - erf(x), Pj);
-                Qj += we;
-                Rj = __builtin_fmaf(we, x, Rj);
-            }
-            if (vj) {
-                tgrad_acc(s_acc, 0, j, lane) += q.Am * Pj;
-                tgrad_acc(s_acc, 1, j, lane) += q.Ar * Qj;
-                tgrad_acc(s_acc, 2, j, lane) += q.Ar * Rj * SQRT_2;
+            for (int g = 0; g < RAY_SG; ++g) grad_deal<EXP>(erf, w[g], trans_grad_x(sv[g], q), q.E, Pj, Qj, Rj);
+            if (L.has(j)) {
+                grad_acc(s_acc, 0, j, lane) += q.Am * Pj;
+                grad_acc(s_acc, 1, j, lane) += q.Ar * Qj;
+                grad_acc(s_acc, 2, j, lane) += q.Ar * Rj * SQRT_2;
             }
         }
     }
-    if (!P.grad) return;
-
-    // ---- every list position to the table once, now that W is known ----
-    for (uint32_t p = 0; p < nmax; ++p) {
-        const bool on = p < nl; // nl is 0 in a lane without a ray of this kernel
-        const uint32_t idx = on ? s_list[p * 64 + lane] : 0u;
-        const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], on, ray);
-        const float mag = on ? S.gD[idx].z : 0.f;
-        const float M = tgrad_acc(s_acc, 0, p, lane), mM = mag * M;
-        const float ArE = q.Ar * exp_neg_sq<EXP>(q.m);
-        const float alpha = -mM * q.inv_s2;
-        const float beta = __builtin_fmaf(-ArE, W, tgrad_acc(s_acc, 1, p, lane));
-        const float dsig = mM * (q.inv_s + q.d2 * q.inv_s * q.inv_s2) + tgrad_acc(s_acc, 2, p, lane) + ArE * q.m * SQRT_2 * W;
-        const float d[5] = { __builtin_fmaf(alpha, q.px, beta * ray.nx), __builtin_fmaf(alpha, q.py, beta * ray.ny),
-                             __builtin_fmaf(alpha, q.pz, beta * ray.nz), dsig, M };
-        grad_deposit<5>(P.grad, idx, on, d, 4u, lane);
-    }
+    if (P.grad) grad_flush_short<EXP, ERF>(P.grad, S, erf, L, s_acc, ray, W);
 }
 
 // One wave per long ray, lane l takes entries l, l + 64, ...; the samples in chunks of NSC.
@@ -251,26 +218,12 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
                     const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], true, ray);
                     float Pj = 0.f, Qj = 0.f, Rj = 0.f;
 #pragma unroll 4
-                    for (uint32_t k = 0; k < nc; ++k) {
-                        const float w = s_w[k];
-                        const float x = trans_grad_x(s_s[k], q);
-                        const float we = w * exp_neg_sq<EXP>(x);
-                        Pj = __builtin_fmaf(w, q.E - erf(x), Pj);
-                        Qj += we;
-                        Rj = __builtin_fmaf(we, x, Rj);
-                    }
-                    const float mag = S.gD[idx].z;
-                    const float M = q.Am * Pj, mM = mag * M;
-                    const float ArE = q.Ar * exp_neg_sq<EXP>(q.m);
-                    const float alpha = -mM * q.inv_s2;
-                    const float beta = __builtin_fmaf(-ArE, Wc, q.Ar * Qj);
-                    const float dsig = mM * (q.inv_s + q.d2 * q.inv_s * q.inv_s2) + q.Ar * Rj * SQRT_2 + ArE * q.m * SQRT_2 * Wc;
+                    for (uint32_t k = 0; k < nc; ++k) grad_deal<EXP>(erf, s_w[k], trans_grad_x(s_s[k], q), q.E, Pj, Qj, Rj);
+                    float d[5];
+                    grad_row_w<EXP>(q, ray, S.gD[idx].z, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, Wc, d);
                     float *row = P.grad + (size_t)idx * GRAD_STRIDE;
-                    atomicAdd(row + 4, __builtin_fmaf(alpha, q.px, beta * ray.nx));
-                    atomicAdd(row + 5, __builtin_fmaf(alpha, q.py, beta * ray.ny));
-                    atomicAdd(row + 6, __builtin_fmaf(alpha, q.pz, beta * ray.nz));
-                    atomicAdd(row + 7, dsig);
-                    atomicAdd(row + 8, M);
+#pragma unroll
+                    for (int c = 0; c < 5; ++c) atomicAdd(row + 4 + c, d[c]);
                 }
             }
             __syncthreads(); // the chunk's weights are read before the next chunk's are written
@@ -287,12 +240,7 @@ static void launch_ray_trans_grad_bundle_t(const RayArgs &a, uint32_t long_grid,
 void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
 {
     if (!a.nrays || !a.ns || !long_grid || !ray_grad_pair_supported(exp_kind, erf_kind)) return;
-    switch (exp_kind * 8 + erf_kind) {
-    case VRT_EXP_LIBM * 8 + VRT_ERF_LIBM: launch_ray_trans_grad_bundle_t<VRT_EXP_LIBM, VRT_ERF_LIBM>(a, long_grid, indexed, st); break;
-    case VRT_EXP_LIBM * 8 + VRT_ERF_AS: launch_ray_trans_grad_bundle_t<VRT_EXP_LIBM, VRT_ERF_AS>(a, long_grid, indexed, st); break;
-    case VRT_EXP_VCL * 8 + VRT_ERF_LIBM: launch_ray_trans_grad_bundle_t<VRT_EXP_VCL, VRT_ERF_LIBM>(a, long_grid, indexed, st); break;
-    default: launch_ray_trans_grad_bundle_t<VRT_EXP_VCL, VRT_ERF_AS>(a, long_grid, indexed, st); break;
-    }
+    VRT_DISPATCH_GRAD_PAIR(launch_ray_trans_grad_bundle_t, a, long_grid, indexed, st);
 }
 
 } // namespace vrtk

@@ -11,8 +11,21 @@ one over), wide_stack at RAY_LCAP and RAY_LCAP + 1 (one wave per ray: the list i
 scattered rays through `-g 16` (lists from a handful to far beyond RAY_PL in one wave).  Every bundle with one origin and with an origin
 per ray, the Morton index off and on, under every Exp / Erf pair the kernels are instantiated for; the tables of the transmittance and
 depth bundles shared and per ray, with 1, 4 and 7 values per ray (either side of the 4 that ride on one walk of a list).  The file
-holds the same bytes whenever the results do: the members are stored in name order with a fixed date."""
+holds the same bytes whenever the results do: the members are stored in name order with a fixed date.
+
+--grad adds (--grad-only: records alone) the two kinds of gradient bundle, under the four Exp / Erf pairs they have kernels for.  Their
+tables are sums of float atomics, so only bundles whose sums CAN come out the same twice are run: one ray (small 9 of
+tests/grad_bundle_scenes.py; the axial ray of the stack at RAY_PL and RAY_PL + 1 and of the wide stack at RAY_LCAP + 1, the one-wave-
+per-ray kernels' case with one entry in the scratch slot), and one wave of 64 near-axial rays that all keep the stack of RAY_PL (one row
+per list position in every lane: the wave-summed deposit).  The transmittance kind with 1, 4 and 5 samples -- the wide stack's ray
+also with NSC and NSC + 1, one and two chunks of the one-wave-per-ray kernel: two adds per address from one lane -- in both `wrt`
+modes, with and without the table and the per-sample output, which is stored, not added.  What is reproducible is for two runs of ONE build to say:
+
+    VRT_HIP_LIB=<build A> ... --grad-only --out a1.npz
+    VRT_HIP_LIB=<build A> ... --grad-only --out a2.npz --against a1.npz
+    VRT_HIP_LIB=<build B> ... --grad-only --out b.npz --against a1.npz --among a2.npz     (compares what a1 and a2 agree on)"""
 import argparse
+import hashlib
 import io
 import os
 import sys
@@ -24,6 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 import __graft_entry__ as ge  # noqa: E402
 import oracle  # noqa: E402  (its scene constructor alone: nothing of it is compiled or loaded)
+import grad_bundle_scenes as G  # noqa: E402
 import ray_bundle_scenes as S  # noqa: E402
 
 pkg = ge._load_pkg()
@@ -32,6 +46,10 @@ from sgrt_amd import scene  # noqa: E402
 NRAYS = 130
 PAIRS = [(0, 0), (0, 1), (1, 0), (1, 1), (2, 1), (3, 1), (1, 2), (1, 3), (1, 4)]   # VRT_DISPATCH_EXP_ERF (csrc/vrt_kernels_common.hpp)
 COUNTS = (1, 4, 7)
+GRAD_PAIRS = [(0, 0), (0, 1), (1, 0), (1, 1)]   # VRT_DISPATCH_GRAD_PAIR
+GRAD_COUNTS = (1, 4, 5)                         # either side of the 4 samples that ride on one walk of a list
+NSC = 512                                       # csrc/vrt_ray_trans_grad_kernel.hip: samples per chunk of the one-wave-per-ray kernel
+CHUNK_COUNTS = (NSC, NSC + 1)                   # one chunk exactly, and a second chunk of one sample: the wide stack's ray alone
 f32 = np.float32
 
 
@@ -89,6 +107,63 @@ def run():
     return {k: np.ascontiguousarray(v, f32).view(np.uint32) for k, v in res.items()}
 
 
+def grad_cases():
+    """(name, scene, origin [3], dirs [rays, 3], sample counts): bundles whose table sums can be reproducible"""
+    small = G.small(oracle, 9)
+    o, d = S.stack_rays(nmiss=0)
+    out = [("small9", small.g, small.o, small.d[:1], GRAD_COUNTS)]
+    out += [("stack%d" % k, S.stack_with_side(oracle, k), o, d[:1], GRAD_COUNTS) for k in (S.RAY_PL, S.RAY_PL + 1)]
+    out.append(("wide%d" % (S.RAY_LCAP + 1), S.wide_stack(oracle, S.RAY_LCAP, S.RAY_LCAP + 1).g, *(a[:1] if a.ndim == 2 else a for a in S.wide_rays()),
+                GRAD_COUNTS + CHUNK_COUNTS))
+    ang = np.arange(64) * (2 * np.pi / 64)
+    target = np.stack([0.02 * np.cos(ang) * (np.arange(64) % 4) / 3, 0.02 * np.sin(ang) * (np.arange(64) % 4) / 3, np.ones(64)], 1)
+    out.append(("stack%d_wave" % S.RAY_PL, S.stack_with_side(oracle, S.RAY_PL), o, S.normalise(target - o.astype(np.float64)), GRAD_COUNTS))
+    return out
+
+
+def table_of(cols):
+    """grad_columns undone: the table [N, GRAD_STRIDE]"""
+    return np.column_stack([cols["albedo"], cols["mu"], cols["sigma"], cols["magnitude"]])
+
+
+def run_grad():
+    res = {}
+    r = pkg.Renderer(0)
+    for name, g, o, d, counts in grad_cases():
+        nrays = len(d)
+        r.set_gaussians(g)
+        r.set_options(1, 1, S.CULL_EPS)
+        r.set_ray_index(0)
+        r.enable_stats(True)
+        r.radiance_rays(o, d)
+        st = r.ray_stats()
+        r.enable_stats(False)
+        print(f"grad {name}: {len(g)} Gaussians, {nrays} rays: {st['short_rays']} lane = ray ({st['lane_entries']} list entries), {st['long_rays']} one wave per ray, "
+              f"{st['scratch_rays']} of them past RAY_LCAP")
+        rng = np.random.default_rng(900 + len(g) + nrays)
+        gr = rng.uniform(-1.0, 1.0, size=(nrays, 4)).astype(f32)
+        for exp_kind, erf_kind in GRAD_PAIRS:
+            r.set_options(exp_kind, erf_kind, S.CULL_EPS)
+            for index in (0, 1):
+                r.set_ray_index(index)
+                key = f"grad/{name}/exp{exp_kind}_erf{erf_kind}/index{index}"
+                res[key + "/radiance/table"] = table_of(r.radiance_rays_grad(o, d, gr))
+                for ns in counts:
+                    s = np.tile(np.linspace(0.5, 6.0, ns).astype(f32), (nrays, 1))
+                    depth = r.depth_bundle(o, d, np.linspace(0.97, 0.35, ns).astype(f32))    # +inf where a level is never reached: contributes nothing
+                    gT = rng.uniform(-1.0, 1.0, size=(nrays, ns)).astype(f32)
+                    gT[0, ns - 1] = 0.0 if ns > 1 else gT[0, 0]                              # a sample that is skipped exactly
+                    for mode, wrt, at in (("T", pkg.TGRAD_T, s), ("depth", pkg.TGRAD_DEPTH, depth)):
+                        for what, table, per_sample in (("both", True, True), ("table", True, False), ("grad_s", False, True)):
+                            cols, gs = r.transmittance_bundle_grad(o, d, at, gT, wrt, True, table, per_sample)
+                            if table:
+                                res[f"{key}/{mode}/ns{ns}/{what}/table"] = table_of(cols)
+                            if per_sample:
+                                res[f"{key}/{mode}/ns{ns}/{what}/grad_s"] = gs
+    r.close()
+    return {k: np.ascontiguousarray(v, f32).view(np.uint32) for k, v in res.items()}
+
+
 def write(path, arrays):
     with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:
         for name in sorted(arrays):
@@ -101,17 +176,30 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     ap.add_argument("--against", help="an earlier --out file: name the results whose bits differ, exit 1 if any does")
+    ap.add_argument("--among", help="with --against: another --out file of the build that wrote --against; only the results on which the two agree are compared")
+    ap.add_argument("--grad", action="store_true", help="the gradient bundles as well")
+    ap.add_argument("--grad-only", action="store_true", help="the gradient bundles alone")
     a = ap.parse_args()
-    arrays = run()
+    arrays = {} if a.grad_only else run()
+    if a.grad or a.grad_only:
+        arrays.update(run_grad())
     write(a.out, arrays)
     finite = sum(int(np.isfinite(v.view(f32)).sum()) for v in arrays.values())
     print(f"{len(arrays)} results, {sum(v.size for v in arrays.values())} values ({finite} finite) from {pkg.LIB_PATH} -> {a.out}")
     if a.against:
         other = np.load(a.against)
-        bad = [k for k in sorted(set(arrays) | set(other.files)) if k not in arrays or k not in other.files or not np.array_equal(arrays[k], other[k])]
+        names = sorted(set(arrays) | set(other.files))
+        if a.among:
+            twin = np.load(a.among)
+            names = [k for k in names if k in other.files and k in twin.files and np.array_equal(other[k], twin[k])]
+            digest = hashlib.sha256()
+            for k in names:
+                digest.update(k.encode() + other[k].tobytes())
+            print(f"{len(names)} of {len(other.files)} results are the same in {a.against} and {a.among}: sha256 of their names and bits {digest.hexdigest()}")
+        bad = [k for k in names if k not in arrays or k not in other.files or not np.array_equal(arrays[k], other[k])]
         for k in bad:
             print("differs", k)
-        print(f"{len(bad)} of {len(arrays)} results differ from {a.against}")
+        print(f"{len(bad)} of {len(names)} results differ from {a.against}")
         sys.exit(1 if bad else 0)
 
 
