@@ -249,7 +249,19 @@ int vrt_hip_scatter_sparse_retained_device(vrt_hip_ctx *ctx, const uint32_t *con
 /* Several frames per assembly (the other end of vrt_hip_frame_batch_device): frame f is assembled into d_images[f] -- all
  * different buffers -- from shard s at d_shards[s] + f * frame_stride_words (what a gather of [rank][frame][prefix]
  * delivers), with one launch for all frames; retained != 0 as in the retained variant, per buffer (the context keeps a
- * history for up to 64 frame buffers). */
+ * history for up to 64 frame buffers; a call never drops the history of one of its own buffers to make room).
+ * Caller contract, for all three scatter calls:
+ *   - every shard starts on a 16-byte boundary (the pixels are read 16 bytes per lane), so frame_stride_words is a
+ *     multiple of 4;
+ *   - a shard whose header is not this job's ([1] != capacity or [2] != cells per tile), slots at and beyond [0], slots
+ *     beyond the capacity and keys whose tile is beyond the grid are ignored, whatever they hold;
+ *   - frame_stride_words may be a prefix P + 1024 k of the shard: slots at and beyond k are then not read, so a prefix
+ *     must hold every stored cell (k >= [0] of every shard of every frame) -- except that the caller who finds a fuller
+ *     shard afterwards gathers again and assembles again: the first assembly dropped the cells that did not travel;
+ *   - a stride of exactly P words (the header alone) keeps ALL slots: it is only valid when [0] == 0 in every shard of
+ *     every frame, slots below [0] would be read behind the prefix.
+ * A rejected call (VRT_HIP_ERR_INVALID: 0 or more than 64 frames, more than 64 shards, a stride that is no multiple of
+ * 4, two frames into one buffer, a tile size of 0 pixels) enqueues nothing and touches no frame buffer or history. */
 int vrt_hip_scatter_sparse_batch_device(vrt_hip_ctx *ctx, const uint32_t *const *d_shards, int nshards,
                                         size_t frame_stride_words, int nframes, int pack_flags, uint32_t *const *d_images,
                                         int retained, void *hip_stream);

@@ -156,10 +156,12 @@ int vrt_hip_scatter_sparse_batch_device(vrt_hip_ctx *c, const uint32_t *const *d
     }
     hipStream_t st = (hipStream_t)hip_stream;
     AssemblyFrames fr{};
-    for (int f = 0; f < nframes; ++f) {
+    for (int f = 0; f < nframes; ++f) { // every buffer is looked at before the first one is touched: a rejected call enqueues nothing
         if (!d_images[f]) return fail(c, VRT_HIP_ERR_INVALID, "scatter_sparse_batch: NULL image");
         for (int k = 0; k < f; ++k)
             if (d_images[k] == d_images[f]) return fail(c, VRT_HIP_ERR_INVALID, "scatter_sparse_batch: two frames of a batch into one buffer");
+    }
+    for (int f = 0; f < nframes; ++f) {
         bool incremental;
         if ((rc = assembly_background(c, g, d_images[f], retained != 0, st, &fr.stamp[f], &fr.seq[f], &incremental, d_images, nframes))) return rc;
         fr.image[f] = d_images[f];
