@@ -456,9 +456,12 @@ void radiance_rays_device(const f32 *d_origins, bool origin_per_ray, const f32 *
 // respect to the Gaussians (vrt_hip_radiance_rays_grad in include/vrt_hip.h has the function, the fixed kept lists and the supported
 // pairs: {vcl, libm} x {abramowitz_stegun, libm}; any other pair throws).  grad_out: gaussians.size() rows of VRT_HIP_GRAD_STRIDE
 // floats, OVERWRITTEN: [0..3] d albedo, [4..6] d mu, [7] d sigma, [8] d magnitude, [9..11] 0.  Summed with float atomics on the
-// device: not bitwise reproducible.  No gradient with respect to the rays.
+// device: not bitwise reproducible.  grad_rays_out (the overload with it; either output nullable, not both): nrays rows of
+// VRT_HIP_RAY_GRAD_STRIDE floats, [0..2] d(loss) / d(origin), [3] 0, [4..6] the tangential d(loss) / d(direction), [7] 0 -- summed without
+// atomics, bitwise reproducible ("ray gradients" in include/vrt_hip.h).  Each ray's kept list is held fixed.
 template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
-void radiance_rays_grad(const vec4f_t *o, const vec4f_t *n, size_t nrays, const gaussians_t &gaussians, const vec4f_t *grad_radiance, f32 *grad_out)
+void radiance_rays_grad(const vec4f_t *o, const vec4f_t *n, size_t nrays, const gaussians_t &gaussians, const vec4f_t *grad_radiance, f32 *grad_out,
+                        f32 *grad_rays_out)
 {
     static_assert(sizeof(vec4f_t) == 4 * sizeof(f32), "grad_radiance is handed to the library as 4 floats per ray");
     auto &d = detail::device_t::get();
@@ -469,19 +472,31 @@ void radiance_rays_grad(const vec4f_t *o, const vec4f_t *n, size_t nrays, const 
         oo[3 * r] = o[r].x; oo[3 * r + 1] = o[r].y; oo[3 * r + 2] = o[r].z;
         nn[3 * r] = n[r].x; nn[3 * r + 1] = n[r].y; nn[3 * r + 2] = n[r].z;
     }
-    d.check(vrt_hip_radiance_rays_grad(d.ctx, nrays, oo.data(), 1, nn.data(), grad_radiance ? &grad_radiance[0].x : nullptr, grad_out),
-            "vrt_hip_radiance_rays_grad");
+    d.check(vrt_hip_radiance_rays_grad_rays(d.ctx, nrays, oo.data(), 1, nn.data(), grad_radiance ? &grad_radiance[0].x : nullptr, grad_out, grad_rays_out),
+            "vrt_hip_radiance_rays_grad_rays");
 }
-// The same on the device: ADDS into d_grad (the caller clears it), enqueued on hip_stream, nothing waits.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void radiance_rays_grad(const vec4f_t *o, const vec4f_t *n, size_t nrays, const gaussians_t &gaussians, const vec4f_t *grad_radiance, f32 *grad_out)
+{
+    radiance_rays_grad<Exp, Erf>(o, n, nrays, gaussians, grad_radiance, grad_out, nullptr);
+}
+// The same on the device: ADDS into d_grad (the caller clears it), STORES d_grad_rays (16-byte aligned), enqueued on hip_stream, nothing
+// waits.  Without d_grad no atomic add is issued.
 template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
 void radiance_rays_grad_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const gaussians_t &gaussians,
-                               const f32 *d_grad_radiance, f32 *d_grad, void *hip_stream)
+                               const f32 *d_grad_radiance, f32 *d_grad, f32 *d_grad_rays, void *hip_stream)
 {
     auto &d = detail::device_t::get();
     d.upload_scene(gaussians.gaussians);
     d.options(Exp, Erf);
-    d.check(vrt_hip_radiance_rays_grad_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_grad_radiance, d_grad, hip_stream),
-            "vrt_hip_radiance_rays_grad_device");
+    d.check(vrt_hip_radiance_rays_grad_rays_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_grad_radiance, d_grad, d_grad_rays, hip_stream),
+            "vrt_hip_radiance_rays_grad_rays_device");
+}
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void radiance_rays_grad_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const gaussians_t &gaussians,
+                               const f32 *d_grad_radiance, f32 *d_grad, void *hip_stream)
+{
+    radiance_rays_grad_device<Exp, Erf>(d_origins, origin_per_ray, d_dirs, nrays, gaussians, d_grad_radiance, d_grad, nullptr, hip_stream);
 }
 // Transmittance bundles: broadcast_transmittance for ANY number of rays at ns depths each in ONE call, under the same per-ray cull
 // (vrt_hip_transmittance_bundle in include/vrt_hip.h: the exponent moves by less than 0.8 * cull_eps * min(N, 4096) = 3.3e-6 at the
@@ -548,10 +563,11 @@ void depth_bundle_device(const f32 *d_origins, bool origin_per_ray, const f32 *d
 // loss with respect to the Gaussians and to the samples or levels (vrt_hip_transmittance_bundle_grad in include/vrt_hip.h has the
 // function, the fixed kept lists and the supported pairs, those of radiance_rays_grad).  grad_out (nullable): gaussians.size() rows of
 // VRT_HIP_GRAD_STRIDE floats, OVERWRITTEN: [4..6] d mu, [7] d sigma, [8] d magnitude, everything else 0.  grad_s_out (nullable): nrays *
-// ns, d(loss) / d(s) or d(loss) / d(tau).  A sample with grad_T == 0 is skipped exactly.  Not bitwise reproducible.
+// ns, d(loss) / d(s) or d(loss) / d(tau).  A sample with grad_T == 0 is skipped exactly.  The table is not bitwise reproducible.
+// grad_rays_out (the overload with it; nullable): the ray rows, as radiance_rays_grad's, which are.
 template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
 void transmittance_bundle_grad(const vec4f_t *o, const vec4f_t *n, size_t nrays, const f32 *s, size_t ns, bool s_per_ray, const gaussians_t &gaussians,
-                               const f32 *grad_T, int wrt, f32 *grad_out, f32 *grad_s_out)
+                               const f32 *grad_T, int wrt, f32 *grad_out, f32 *grad_s_out, f32 *grad_rays_out)
 {
     auto &d = detail::device_t::get();
     d.upload_scene(gaussians.gaussians);
@@ -561,20 +577,35 @@ void transmittance_bundle_grad(const vec4f_t *o, const vec4f_t *n, size_t nrays,
         oo[3 * r] = o[r].x; oo[3 * r + 1] = o[r].y; oo[3 * r + 2] = o[r].z;
         nn[3 * r] = n[r].x; nn[3 * r + 1] = n[r].y; nn[3 * r + 2] = n[r].z;
     }
-    d.check(vrt_hip_transmittance_bundle_grad(d.ctx, nrays, oo.data(), 1, nn.data(), s, ns, s_per_ray ? 1 : 0, grad_T, wrt, grad_out, grad_s_out),
-            "vrt_hip_transmittance_bundle_grad");
+    d.check(vrt_hip_transmittance_bundle_grad_rays(d.ctx, nrays, oo.data(), 1, nn.data(), s, ns, s_per_ray ? 1 : 0, grad_T, wrt, grad_out, grad_s_out,
+                                                   grad_rays_out),
+            "vrt_hip_transmittance_bundle_grad_rays");
 }
-// The same on the device: ADDS into d_grad (the caller clears it), STORES d_grad_s, enqueued on hip_stream, nothing waits.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void transmittance_bundle_grad(const vec4f_t *o, const vec4f_t *n, size_t nrays, const f32 *s, size_t ns, bool s_per_ray, const gaussians_t &gaussians,
+                               const f32 *grad_T, int wrt, f32 *grad_out, f32 *grad_s_out)
+{
+    transmittance_bundle_grad<Exp, Erf>(o, n, nrays, s, ns, s_per_ray, gaussians, grad_T, wrt, grad_out, grad_s_out, nullptr);
+}
+// The same on the device: ADDS into d_grad (the caller clears it), STORES d_grad_s and d_grad_rays, enqueued on hip_stream, nothing waits.
 template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
 void transmittance_bundle_grad_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const f32 *d_s, size_t ns, bool s_per_ray,
-                                      const gaussians_t &gaussians, const f32 *d_grad_T, int wrt, f32 *d_grad, f32 *d_grad_s, void *hip_stream)
+                                      const gaussians_t &gaussians, const f32 *d_grad_T, int wrt, f32 *d_grad, f32 *d_grad_s, f32 *d_grad_rays,
+                                      void *hip_stream)
 {
     auto &d = detail::device_t::get();
     d.upload_scene(gaussians.gaussians);
     d.options(Exp, Erf);
-    d.check(vrt_hip_transmittance_bundle_grad_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_s, ns, s_per_ray ? 1 : 0, d_grad_T, wrt,
-                                                     d_grad, d_grad_s, hip_stream),
-            "vrt_hip_transmittance_bundle_grad_device");
+    d.check(vrt_hip_transmittance_bundle_grad_rays_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_s, ns, s_per_ray ? 1 : 0, d_grad_T, wrt,
+                                                          d_grad, d_grad_s, d_grad_rays, hip_stream),
+            "vrt_hip_transmittance_bundle_grad_rays_device");
+}
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void transmittance_bundle_grad_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const f32 *d_s, size_t ns, bool s_per_ray,
+                                      const gaussians_t &gaussians, const f32 *d_grad_T, int wrt, f32 *d_grad, f32 *d_grad_s, void *hip_stream)
+{
+    transmittance_bundle_grad_device<Exp, Erf>(d_origins, origin_per_ray, d_dirs, nrays, d_s, ns, s_per_ray, gaussians, d_grad_T, wrt, d_grad, d_grad_s, nullptr,
+                                               hip_stream);
 }
 // Ray bundles cull through the Morton index of the scene from the next call on (vrt_hip_set_ray_index in include/vrt_hip.h: off by
 // default, the same radiance and the same pixels bit for bit either way; the index is made once per scene).

@@ -416,7 +416,7 @@ int vrt_hip_depth_bundle(vrt_hip_ctx *ctx, size_t nrays, const float *origins, i
  * summed over the rays that keep j.  Exp and Erf in L and T are the selected pair's; their derivatives are the analytic ones
  * (Exp' = Exp, Erf'(x) = 2 / sqrt(pi) exp(-x^2)), also for the Abramowitz-Stegun Erf.  Supported pairs: {vcl_exp, expf} x
  * {A&S erf, erff}; under any other pair the call returns VRT_HIP_ERR_INVALID with a message and enqueues nothing (the piecewise
- * approximations have jumps).  Gradients with respect to the rays (origins, directions) are not computed.
+ * approximations have jumps).  The gradient with respect to the rays themselves is the _rays form's, below.
  * The _device form ADDS into d_grad (N rows of VRT_HIP_GRAD_STRIDE floats, N = Gaussians of the scene) with float atomics: the
  * caller clears the table, and may let several bundles add into it.  A row of a Gaussian that no ray keeps is not written at all.
  * The sums depend on the arrival order of the atomic adds: results are NOT bitwise reproducible from run to run.  d_grad_radiance
@@ -453,7 +453,7 @@ int vrt_hip_radiance_rays_grad(vrt_hip_ctx *ctx, size_t nrays, const float *orig
  * keeps: one table may collect a radiance gradient and a mask or depth gradient.  The _device form ADDS into d_grad with float
  * atomics (not bitwise reproducible) and STORES d_grad_s; either may be NULL, not both.  The host form overwrites grad_out (N rows,
  * untouched entries 0) and grad_s_out.  Exp and Erf of the forward quantities are the selected pair's, the derivatives the analytic
- * ones; supported pairs as above: {vcl_exp, expf} x {A&S erf, erff}.  No gradients with respect to the rays.
+ * ones; supported pairs as above: {vcl_exp, expf} x {A&S erf, erff}.  The gradient with respect to the rays is the _rays form's, below.
  * Everything else is the gradient bundle's contract: origins, origin_per_ray, dirs, the stream rules, the buffers that only grow, the
  * shared queue / counters / scratch slots / bitmap, the Morton index (the same kept lists either way), the statistics (for the same
  * rays every field a radiance bundle reports).  nrays == 0, ns == 0 or a scene of no Gaussians returns VRT_HIP_OK with nothing
@@ -467,6 +467,40 @@ int vrt_hip_transmittance_bundle_grad_device(vrt_hip_ctx *ctx, size_t nrays, con
 int vrt_hip_transmittance_bundle_grad(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
                                       const float *s, size_t ns, int s_per_ray, const float *grad_T, int wrt,
                                       float *grad_out /* N rows, OVERWRITTEN, or NULL */, float *grad_s_out /* nrays * ns, or NULL */);
+/* -------- ray gradients: d(loss) / d(origin, direction) of every ray, from either gradient bundle -----------------------------------
+ * The _rays forms are the two gradient bundles above with one more output: grad_rays, nrays rows of VRT_HIP_RAY_GRAD_STRIDE floats,
+ *   [0..2] d(loss) / d(origin of ray r)   [3] 0   [4..6] the tangential d(loss) / d(dir of ray r)   [7] 0
+ * of the same function under the same fixed kept lists.  Every observable depends on a ray (o, n) through c_j = mu_j - o and n alone;
+ * with ray r's share of row j's d mu written as a_j c_perp_j + b_j n (c_perp_j = c_j - mubar_j n, mubar_j = c_j . n),
+ *   d(loss) / d(o) = -sum_{j in K} (a_j c_perp_j + b_j n),      d(loss) / d(n) = sum_{j in K} (b_j - a_j mubar_j) c_perp_j.
+ * The tangential derivative is defined so: for a unit t perpendicular to dir, (row[4..6] . t) = d/d(eps) of the loss along the rays
+ * normalise(dir + eps t) at eps = 0.  The row is perpendicular to dir (to rounding): a caller who normalises a raw vector v gets
+ * d(loss) / d(v) = row[4..6] / |v|, which torch's normalize does by itself.  With a shared origin (origin_per_ray == 0) the rows are
+ * still per ray, and the caller sums columns 0..2 over the rays, as grad_s of shared samples.
+ * The rows are STORED, never added: every ray r < nrays gets a row, a ray that keeps nothing one of exact zeros, and nothing behind
+ * row nrays - 1 is written.  No atomic add takes part in them: a ray's row is summed in the order of its kept list (one wave per ray: in
+ * the fixed order of the wave's lanes), so the ray rows ARE bitwise reproducible -- from run to run, with the Morton index on or off,
+ * with or without the table, host or device form -- while the table is not.  d_grad_rays is 16-byte aligned.
+ * d_grad / grad_out may be NULL: then no atomic add is issued at all (a pose-only fit).  d_grad_rays / grad_rays_out may be NULL: then
+ * the call is the form above without _rays.  At least one output must be non-NULL: VRT_HIP_ERR_INVALID with the bundle kind's message
+ * otherwise.  In depth mode a sample that contributes nothing to the table contributes nothing to the ray's row.  Everything else --
+ * the checks and their messages, a bundle of nothing (nothing launched, nothing written), the supported pairs, the stream rules, the
+ * buffers that only grow, the statistics, the Morton index -- is the gradient bundle's contract. */
+enum { VRT_HIP_RAY_GRAD_STRIDE = 8 };  /* floats per ray row: [0..2] d origin, [3] 0, [4..6] tangential d direction, [7] 0 */
+int vrt_hip_radiance_rays_grad_rays_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                           const float *d_grad_radiance /* 4 per ray */, float *d_grad /* N rows, ADDED into; may be NULL */,
+                                           float *d_grad_rays /* nrays rows of VRT_HIP_RAY_GRAD_STRIDE, STORED; may be NULL */, void *hip_stream);
+int vrt_hip_radiance_rays_grad_rays(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                                    const float *grad_radiance, float *grad_out /* N rows, OVERWRITTEN, or NULL */,
+                                    float *grad_rays_out /* nrays rows, or NULL */);
+int vrt_hip_transmittance_bundle_grad_rays_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                                  const float *d_s, size_t ns, int s_per_ray, const float *d_grad_T /* nrays * ns */, int wrt,
+                                                  float *d_grad /* ADDED into; may be NULL */, float *d_grad_s /* stored; may be NULL */,
+                                                  float *d_grad_rays /* nrays rows of VRT_HIP_RAY_GRAD_STRIDE, STORED; may be NULL */, void *hip_stream);
+int vrt_hip_transmittance_bundle_grad_rays(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                                           const float *s, size_t ns, int s_per_ray, const float *grad_T, int wrt,
+                                           float *grad_out /* N rows, OVERWRITTEN, or NULL */, float *grad_s_out /* nrays * ns, or NULL */,
+                                           float *grad_rays_out /* nrays rows, or NULL */);
 typedef struct {
     uint64_t rays;           /* rays of the bundle                                                                  */
     uint64_t short_rays;     /* shaded lane = ray (list of at most 32)                                              */

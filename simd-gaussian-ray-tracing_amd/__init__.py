@@ -23,6 +23,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 EXP_LIBM, EXP_VCL, EXP_FAST, EXP_SPLINE = 0, 1, 2, 3
 ERF_LIBM, ERF_AS, ERF_SPLINE, ERF_SPLINE_MIRROR, ERF_TAYLOR = 0, 1, 2, 3, 4
 GRAD_STRIDE = 12            # VRT_HIP_GRAD_STRIDE: floats per row of a gradient bundle's table
+RAY_GRAD_STRIDE = 8         # VRT_HIP_RAY_GRAD_STRIDE: floats per ray row of a gradient bundle's ray output
 TGRAD_T, TGRAD_DEPTH = 0, 1 # VRT_HIP_TGRAD_*: what a transmittance gradient bundle's grad_T is the derivative with respect to
 TABLE_STEP_DEFAULT = 0.05   # vrt_hip_set_table_step: the library's default (0 = exact kernels only)
 PACK_TRUNC, PACK_ROUND, ALPHA_OPAQUE, ALPHA_COMPUTED = 0, 1, 0, 2
@@ -130,6 +131,12 @@ SYMBOLS = {
     "vrt_hip_radiance_rays_grad": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _f32p]),
     "vrt_hip_transmittance_bundle_grad_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "vrt_hip_transmittance_bundle_grad": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p, C.c_int, _f32p, _f32p]),
+    "vrt_hip_radiance_rays_grad_rays_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "vrt_hip_radiance_rays_grad_rays": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p]),
+    "vrt_hip_transmittance_bundle_grad_rays_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int, _vp, _vp, _vp,
+                                                                _vp]),
+    "vrt_hip_transmittance_bundle_grad_rays": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p, C.c_int, _f32p, _f32p,
+                                                         _f32p]),
     "vrt_hip_get_ray_stats": (C.c_int, [_vp, C.POINTER(RayStats)]),
     "vrt_hip_set_ray_index": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_ray_index_stats": (C.c_int, [_vp, C.POINTER(RayIndexStats)]),
@@ -213,6 +220,12 @@ def _table(v, nrays, per_ray):
 def grad_columns(table):
     """The columns of a gradient bundle's table [N, GRAD_STRIDE] (numpy array or torch tensor) by name: views, not copies."""
     return {"albedo": table[:, 0:4], "mu": table[:, 4:7], "sigma": table[:, 7], "magnitude": table[:, 8]}
+
+
+def ray_grad_columns(rows):
+    """The columns of a gradient bundle's ray rows [nrays, RAY_GRAD_STRIDE] (numpy array or torch tensor) by name: views, not copies.
+    "origin": d(loss) / d(origin) per ray (a bundle with one origin: sum them over the rays); "dir": the tangential d(loss) / d(dir)."""
+    return {"origin": rows[:, 0:3], "dir": rows[:, 4:7]}
 
 
 class Renderer:
@@ -578,18 +591,24 @@ class Renderer:
         self._device("depth_bundle_device", nrays, d_origins, origin_per_ray, d_dirs, d_tau or None, int(nt), int(bool(tau_per_ray)),
                      d_depth or None, stream or None)
 
-    def radiance_rays_grad(self, origins, dirs, grad_radiance):
-        """vrt_hip_radiance_rays_grad: the derivative of a loss with respect to the Gaussians, given its derivative grad_radiance
-        [nrays, 4] with respect to what radiance_rays returns for the same rays (the kept lists held fixed; no gradient for the rays).
+    def radiance_rays_grad(self, origins, dirs, grad_radiance, want_table=True, want_rays=False):
+        """vrt_hip_radiance_rays_grad_rays: the derivative of a loss with respect to the Gaussians and, with want_rays, to the rays,
+        given its derivative grad_radiance [nrays, 4] with respect to what radiance_rays returns for the same rays (each ray's kept
+        list is held fixed).
         Returns {"albedo": [N, 4], "mu": [N, 3], "sigma": [N], "magnitude": [N]}, float32.  The sums are float atomics on the device:
-        not bitwise reproducible."""
+        not bitwise reproducible.  With want_rays: (that dict, or None without want_table, {"origin": [nrays, 3], "dir": [nrays, 3]})
+        -- per ray d(loss) / d(origin) and the tangential d(loss) / d(dir), bitwise reproducible; without the table no atomic add is
+        issued at all."""
         origins, dirs, per_ray = _rays(origins, dirs)
         g = np.ascontiguousarray(grad_radiance, np.float32).reshape(-1, 4)
         assert len(g) == len(dirs)
-        out = np.zeros((self.n, GRAD_STRIDE), np.float32)
-        self._chk(self._L.vrt_hip_radiance_rays_grad(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(g), _fp(out)),
+        out = np.zeros((self.n, GRAD_STRIDE), np.float32) if want_table else None
+        rows = np.zeros((len(dirs), RAY_GRAD_STRIDE), np.float32) if want_rays else None
+        self._chk(self._L.vrt_hip_radiance_rays_grad_rays(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(g),
+                                                          _fp(out) if want_table else None, _fp(rows) if want_rays else None),
                   "radiance_rays_grad")
-        return grad_columns(out)
+        table = grad_columns(out) if want_table else None
+        return (table, ray_grad_columns(rows)) if want_rays else table
 
     def radiance_rays_grad_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_grad_radiance, d_grad, stream=0):
         """vrt_hip_radiance_rays_grad_device: device pointers, everything enqueued on `stream`; ADDS into d_grad ([N, GRAD_STRIDE]
@@ -597,24 +616,34 @@ class Renderer:
         self._device("radiance_rays_grad_device", nrays, d_origins, origin_per_ray, d_dirs, d_grad_radiance or None, d_grad or None,
                      stream or None)
 
-    def transmittance_bundle_grad(self, origins, dirs, s, grad_T, wrt=TGRAD_T, s_per_ray=None, want_table=True, want_grad_s=True):
-        """vrt_hip_transmittance_bundle_grad: the derivative of a loss with respect to the Gaussians and the samples, given its
+    def radiance_rays_grad_rays_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_grad_radiance, d_grad=0, d_grad_rays=0, stream=0):
+        """vrt_hip_radiance_rays_grad_rays_device: as radiance_rays_grad_device, and STORES d_grad_rays ([nrays, RAY_GRAD_STRIDE]
+        float32, 16-byte aligned: ray_grad_columns names its columns); either may be 0, not both."""
+        self._device("radiance_rays_grad_rays_device", nrays, d_origins, origin_per_ray, d_dirs, d_grad_radiance or None, d_grad or None,
+                     d_grad_rays or None, stream or None)
+
+    def transmittance_bundle_grad(self, origins, dirs, s, grad_T, wrt=TGRAD_T, s_per_ray=None, want_table=True, want_grad_s=True, want_rays=False):
+        """vrt_hip_transmittance_bundle_grad_rays: the derivative of a loss with respect to the Gaussians and the samples, given its
         derivative grad_T [nrays, ns] with respect to what transmittance_bundle returns for the same rays and samples s (wrt = TGRAD_T)
         -- or, with wrt = TGRAD_DEPTH, s [nrays, ns] the depths depth_bundle returned and grad_T the derivative with respect to them:
         the derivative with respect to the Gaussians and the levels tau (of the ideal crossing; a depth of +inf, 0 or NaN contributes
-        nothing).  A sample with grad_T == 0 is skipped exactly.  The kept lists are held fixed; no gradient for the rays.
+        nothing).  A sample with grad_T == 0 is skipped exactly.  Each ray's kept list is held fixed.
         Returns ({"albedo": zeros [N, 4], "mu": [N, 3], "sigma": [N], "magnitude": [N]} or None, grad_s [nrays, ns] or None), float32.
-        The table's sums are float atomics on the device: not bitwise reproducible."""
+        The table's sums are float atomics on the device: not bitwise reproducible.  With want_rays a third value follows:
+        {"origin": [nrays, 3], "dir": [nrays, 3]}, per ray d(loss) / d(origin) and the tangential d(loss) / d(dir), bitwise reproducible."""
         origins, dirs, per_ray = _rays(origins, dirs)
         s, ns, s_per_ray = _table(s, len(dirs), s_per_ray)
         g = np.ascontiguousarray(grad_T, np.float32)
         assert g.size == len(dirs) * ns
         out = np.zeros((self.n, GRAD_STRIDE), np.float32) if want_table else None
         gs = np.zeros((len(dirs), ns), np.float32) if want_grad_s else None
-        self._chk(self._L.vrt_hip_transmittance_bundle_grad(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(s), ns, int(s_per_ray), _fp(g),
-                                                            int(wrt), _fp(out) if want_table else None, _fp(gs) if want_grad_s else None),
+        rows = np.zeros((len(dirs), RAY_GRAD_STRIDE), np.float32) if want_rays else None
+        self._chk(self._L.vrt_hip_transmittance_bundle_grad_rays(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(s), ns, int(s_per_ray),
+                                                                 _fp(g), int(wrt), _fp(out) if want_table else None,
+                                                                 _fp(gs) if want_grad_s else None, _fp(rows) if want_rays else None),
                   "transmittance_bundle_grad")
-        return (grad_columns(out) if want_table else None), gs
+        res = ((grad_columns(out) if want_table else None), gs)
+        return res + (ray_grad_columns(rows),) if want_rays else res
 
     def transmittance_bundle_grad_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_s, ns, s_per_ray, d_grad_T, wrt, d_grad=0, d_grad_s=0,
                                          stream=0):
@@ -622,6 +651,13 @@ class Renderer:
         ([N, GRAD_STRIDE] float32: grad_columns names its columns) and STORES d_grad_s ([nrays, ns]); either may be 0, not both."""
         self._device("transmittance_bundle_grad_device", nrays, d_origins, origin_per_ray, d_dirs, d_s or None, int(ns), int(bool(s_per_ray)),
                      d_grad_T or None, int(wrt), d_grad or None, d_grad_s or None, stream or None)
+
+    def transmittance_bundle_grad_rays_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_s, ns, s_per_ray, d_grad_T, wrt, d_grad=0, d_grad_s=0,
+                                              d_grad_rays=0, stream=0):
+        """vrt_hip_transmittance_bundle_grad_rays_device: as transmittance_bundle_grad_device, and STORES d_grad_rays ([nrays,
+        RAY_GRAD_STRIDE] float32, 16-byte aligned); any of the three outputs may be 0, not all."""
+        self._device("transmittance_bundle_grad_rays_device", nrays, d_origins, origin_per_ray, d_dirs, d_s or None, int(ns), int(bool(s_per_ray)),
+                     d_grad_T or None, int(wrt), d_grad or None, d_grad_s or None, d_grad_rays or None, stream or None)
 
     def ray_stats(self):
         """Counts of the last bundle (enable_stats first): see vrt_hip_ray_stats in include/vrt_hip.h."""

@@ -1,17 +1,23 @@
 """torch.autograd face of the ray bundles: radiance, transmittance and depth of caller-given rays as differentiable functions of the
-Gaussians.
+Gaussians and of the rays.
 
     L = radiance_rays(renderer, mu, albedo, sigma, magnitude, origins, dirs)      # [nrays, 4], on cuda
     loss(L).backward()                                                            # mu.grad, albedo.grad, sigma.grad, magnitude.grad
     T = transmittance_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, s)      # [nrays, ns]: masks, shadow rays
     z = depth_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, tau)            # [nrays, nt]: depth maps, first hits
 
-Forward is Renderer.radiance_rays_device, backward Renderer.radiance_rays_grad_device (include/vrt_hip.h, "gradient bundles"): the
-derivative with each ray's kept list held fixed, under {vcl_exp, expf} x {A&S erf, erff} only, summed with float atomics (not bitwise
-reproducible).  No gradient is returned for the rays.  transmittance_bundle and depth_bundle run Renderer.transmittance_bundle_device /
-depth_bundle_device forward and Renderer.transmittance_bundle_grad_device backward ("transmittance gradient bundles"), under the same
-rules; they are differentiable in s and tau as well, never in albedo (T does not depend on it).  The depth's derivative is that of the
+Forward is Renderer.radiance_rays_device, backward Renderer.radiance_rays_grad_rays_device (include/vrt_hip.h, "gradient bundles" and
+"ray gradients"): the derivative with each ray's kept list held fixed, under {vcl_exp, expf} x {A&S erf, erff} only; the Gaussians'
+gradients are summed with float atomics (not bitwise reproducible).  transmittance_bundle and depth_bundle run
+Renderer.transmittance_bundle_device / depth_bundle_device forward and Renderer.transmittance_bundle_grad_rays_device backward
+("transmittance gradient bundles"), under the same rules; they are differentiable in s and tau as well, never in albedo (T does not depend on it).  The depth's derivative is that of the
 ideal crossing T(depth) = tau; a depth of +inf, 0 or NaN gets no gradient.
+
+Rays.  origins and dirs that require grad get one: origins [nrays, 3] d(loss) / d(origin) per ray, origins [3] its sum over the rays,
+dirs the TANGENTIAL derivative (perpendicular to each direction: dirs are unit vectors, and the chain rule through
+torch.nn.functional.normalize of a raw vector needs no more).  These rows come without atomic adds and are bitwise reproducible.
+ctx.needs_input_grad decides what backward asks of the library: with no Gaussian parameter requiring grad no table is passed (a
+pose-only fit pays for no atomic add), with no ray requiring grad the call is the one without ray rows.
 
 A Gaussian whose magnitude is exactly 0 is dropped by every ray's cull and therefore receives NO gradient, magnitude.grad included
 (although the true derivative is not 0): initialise magnitudes away from 0.
@@ -23,7 +29,7 @@ library yet; a fitting loop pays that upload once per step.
 import numpy as np
 import torch
 
-from . import GRAD_STRIDE, TGRAD_DEPTH, TGRAD_T, grad_columns
+from . import GRAD_STRIDE, RAY_GRAD_STRIDE, TGRAD_DEPTH, TGRAD_T, grad_columns, ray_grad_columns
 
 
 def _upload(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs):
@@ -36,15 +42,44 @@ def _upload(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs):
     d = dirs.detach().to(dev, torch.float32).contiguous().reshape(-1, 3)
     per_ray = o.numel() != 3
     ctx.renderer, ctx.rays, ctx.n = renderer, (o, d, per_ray), len(host[2])
+    ctx.ray_like = (origins, dirs)
     ctx.devices = [t.device for t in (mu, albedo, sigma, magnitude)]
     ctx.dtypes = [t.dtype for t in (mu, albedo, sigma, magnitude)]
     return dev, o, d, per_ray
 
 
 def _parameter_grads(ctx, table):
-    """The table's columns as the gradients of (mu, albedo, sigma, magnitude), each on its parameter's device and in its type."""
+    """The table's columns as the gradients of (mu, albedo, sigma, magnitude), each on its parameter's device and in its type; None
+    each where no table was asked for."""
+    if table is None:
+        return [None] * 4
     cols = grad_columns(table)
     return [cols[k].to(dev, dt) for k, dev, dt in zip(("mu", "albedo", "sigma", "magnitude"), ctx.devices, ctx.dtypes)]
+
+
+def _outputs(ctx, first_param):
+    """What a backward asks of the library, by ctx.needs_input_grad (the four parameters from index first_param, then origins, dirs):
+    the cleared table or None, the ray rows or None."""
+    o = ctx.rays[0]
+    need = ctx.needs_input_grad
+    table = torch.zeros((ctx.n, GRAD_STRIDE), dtype=torch.float32, device=o.device) if any(need[first_param:first_param + 4]) else None
+    rows = (torch.zeros((ctx.rays[1].shape[0], RAY_GRAD_STRIDE), dtype=torch.float32, device=o.device)
+            if any(need[first_param + 4:first_param + 6]) else None)
+    return table, rows
+
+
+def _ray_grads(ctx, rows):
+    """The ray rows as the gradients of (origins, dirs) in their shapes, devices and types: one origin for the bundle gets the sum."""
+    if rows is None:
+        return [None, None]
+    cols = ray_grad_columns(rows)
+    origins, dirs = ctx.ray_like
+    go = cols["origin"] if ctx.rays[2] else cols["origin"].sum(0)
+    return [go.reshape(origins.shape).to(origins.device, origins.dtype), cols["dir"].reshape(dirs.shape).to(dirs.device, dirs.dtype)]
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else 0
 
 
 class _RadianceRays(torch.autograd.Function):
@@ -61,17 +96,17 @@ class _RadianceRays(torch.autograd.Function):
     def backward(ctx, grad_out):
         o, d, per_ray = ctx.rays
         g = grad_out.to(o.device, torch.float32).contiguous()
-        table = torch.zeros((ctx.n, GRAD_STRIDE), dtype=torch.float32, device=o.device)
-        if d.shape[0] and ctx.n:
-            ctx.renderer.radiance_rays_grad_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), g.data_ptr(), table.data_ptr(),
-                                                   stream=torch.cuda.current_stream(o.device).cuda_stream)
-        return (None, *_parameter_grads(ctx, table), None, None)
+        table, rows = _outputs(ctx, 1)
+        if d.shape[0] and ctx.n and (table is not None or rows is not None):
+            ctx.renderer.radiance_rays_grad_rays_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), g.data_ptr(), d_grad=_ptr(table),
+                                                        d_grad_rays=_ptr(rows), stream=torch.cuda.current_stream(o.device).cuda_stream)
+        return (None, *_parameter_grads(ctx, table), *_ray_grads(ctx, rows))
 
 
 def radiance_rays(renderer, mu, albedo, sigma, magnitude, origins, dirs):
     """Radiance [nrays, 4] (a cuda tensor on torch's current device and stream) of the rays through the scene of the four parameter
-    tensors mu [N, 3], albedo [N, 4], sigma [N], magnitude [N], differentiable in those four.  origins: [3] or [nrays, 3]; dirs:
-    [nrays, 3], unit length.  The scene of `renderer` is REPLACED by the parameters, through the host (see the module's docstring);
+    tensors mu [N, 3], albedo [N, 4], sigma [N], magnitude [N], differentiable in those four and in the rays.  origins: [3] or
+    [nrays, 3]; dirs: [nrays, 3], unit length (its gradient is the tangential one: see the module's docstring).  The scene of `renderer` is REPLACED by the parameters, through the host (see the module's docstring);
     backward must run before the renderer's scene or options change again."""
     return _RadianceRays.apply(renderer, mu, albedo, sigma, magnitude, origins, dirs)
 
@@ -101,19 +136,19 @@ class _Profile(torch.autograd.Function):
         (out,) = ctx.saved_tensors
         nrays, n = out.shape
         g = grad_out.to(o.device, torch.float32).contiguous()
-        table = torch.zeros((ctx.n, GRAD_STRIDE), dtype=torch.float32, device=o.device)
+        table, rows = _outputs(ctx, 2)
         gv = torch.zeros((nrays, n), dtype=torch.float32, device=o.device)
         if nrays and n and ctx.n:
             # T mode: at the samples the forward took; depth mode: at the depths the forward returned, one row per ray
             s, s_per_ray = (ctx.values, ctx.v_per_ray) if ctx.wrt == TGRAD_T else (out, True)
-            ctx.renderer.transmittance_bundle_grad_device(nrays, o.data_ptr(), per_ray, d.data_ptr(), s.data_ptr(), n, s_per_ray, g.data_ptr(), ctx.wrt,
-                                                          d_grad=table.data_ptr(), d_grad_s=gv.data_ptr(),
-                                                          stream=torch.cuda.current_stream(o.device).cuda_stream)
+            ctx.renderer.transmittance_bundle_grad_rays_device(nrays, o.data_ptr(), per_ray, d.data_ptr(), s.data_ptr(), n, s_per_ray, g.data_ptr(),
+                                                               ctx.wrt, d_grad=_ptr(table), d_grad_s=gv.data_ptr(), d_grad_rays=_ptr(rows),
+                                                               stream=torch.cuda.current_stream(o.device).cuda_stream)
         if not ctx.v_per_ray:                       # values shared by the rays: their gradient is the sum over the rays
             gv = gv.sum(0).reshape(ctx.values.shape)
         grads = _parameter_grads(ctx, table)
         grads[1] = None                             # albedo
-        return (None, None, *grads, None, None, gv.to(ctx.v_like.device, ctx.v_like.dtype))
+        return (None, None, *grads, *_ray_grads(ctx, rows), gv.to(ctx.v_like.device, ctx.v_like.dtype))
 
 
 def transmittance_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, s):

@@ -1,5 +1,5 @@
 // vrt_hip_rays.cpp -- ray bundles of libvrt_hip.so (vrt_hip_radiance_rays*, vrt_hip_transmittance_bundle*, vrt_hip_depth_bundle*,
-// vrt_hip_radiance_rays_grad*, vrt_hip_transmittance_bundle_grad*): radiance of caller-given rays, transmittance at sample distances along
+// vrt_hip_radiance_rays_grad*, vrt_hip_transmittance_bundle_grad*, their _rays forms): radiance of caller-given rays, transmittance at sample distances along
 // them, the distance at which their transmittance falls to given levels, or the derivative of their radiance, transmittance or depth with
 // respect to the Gaussians, culled per ray (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip,
 // vrt_ray_grad_kernel.hip, vrt_ray_trans_grad_kernel.hip).  The scene tables and the
@@ -312,24 +312,73 @@ int vrt_hip_radiance_rays(vrt_hip_ctx *c, size_t nrays, const float *origins, in
                        });
 }
 
-int vrt_hip_radiance_rays_grad_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
-                                      const float *d_grad_radiance, float *d_grad, void *hip_stream)
+int vrt_hip_radiance_rays_grad_rays_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                           const float *d_grad_radiance, float *d_grad, float *d_grad_rays, void *hip_stream)
 {
-    return device_bundle(c, GRADIENT, { nrays, d_origins, origin_per_ray, d_dirs }, 1, d_grad_radiance && d_grad, 0, hip_stream, [&](RayArgs &a) {
-        a.grad_radiance = (const float4 *)d_grad_radiance; a.grad = d_grad;
-    });
+    return device_bundle(c, GRADIENT, { nrays, d_origins, origin_per_ray, d_dirs }, 1, d_grad_radiance && (d_grad || d_grad_rays), 0, hip_stream,
+                         [&](RayArgs &a) {
+                             a.grad_radiance = (const float4 *)d_grad_radiance; a.grad = d_grad; a.grad_rays = d_grad_rays;
+                         });
 }
 
-// grad_radiance in; a cleared table of the scene's size out
-int vrt_hip_radiance_rays_grad(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
-                               const float *grad_radiance, float *grad_out)
+// grad_radiance in; a cleared table of the scene's size and the ray rows out, either where asked for
+int vrt_hip_radiance_rays_grad_rays(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                                    const float *grad_radiance, float *grad_out, float *grad_rays_out)
 {
     const Rays r = { nrays, origins, origin_per_ray, dirs };
     int rc;
-    if (bundle_over(c, GRADIENT, r, 1, grad_radiance && grad_out, 0, rc)) return rc;
+    if (bundle_over(c, GRADIENT, r, 1, grad_radiance && (grad_out || grad_rays_out), 0, rc)) return rc;
     return host_bundle(c, r, { { c->rays_each_in, grad_radiance, nrays * 4 } },
-                       { { c->rays_table_out, grad_out, (size_t)c->n * VRT_HIP_GRAD_STRIDE, true } }, [&](const Rays &d) {
-                           return vrt_hip_radiance_rays_grad_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, c->rays_each_in.p, c->rays_table_out.p, c->stream);
+                       { { c->rays_table_out, grad_out, (size_t)c->n * VRT_HIP_GRAD_STRIDE, true },
+                         { c->rays_rows_out, grad_rays_out, nrays * VRT_HIP_RAY_GRAD_STRIDE } },
+                       [&](const Rays &d) {
+                           return vrt_hip_radiance_rays_grad_rays_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, c->rays_each_in.p,
+                                                                         wanted(grad_out, c->rays_table_out), wanted(grad_rays_out, c->rays_rows_out),
+                                                                         c->stream);
+                       });
+}
+
+// the table alone: the same calls without the ray rows
+int vrt_hip_radiance_rays_grad_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                      const float *d_grad_radiance, float *d_grad, void *hip_stream)
+{
+    return vrt_hip_radiance_rays_grad_rays_device(c, nrays, d_origins, origin_per_ray, d_dirs, d_grad_radiance, d_grad, nullptr, hip_stream);
+}
+
+int vrt_hip_radiance_rays_grad(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                               const float *grad_radiance, float *grad_out)
+{
+    return vrt_hip_radiance_rays_grad_rays(c, nrays, origins, origin_per_ray, dirs, grad_radiance, grad_out, nullptr);
+}
+
+int vrt_hip_transmittance_bundle_grad_rays_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                                  const float *d_s, size_t ns, int s_per_ray, const float *d_grad_T, int wrt, float *d_grad,
+                                                  float *d_grad_s, float *d_grad_rays, void *hip_stream)
+{
+    return device_bundle(c, TRANS_GRADIENT, { nrays, d_origins, origin_per_ray, d_dirs }, ns, d_s && d_grad_T && (d_grad || d_grad_s || d_grad_rays), wrt,
+                         hip_stream, [&](RayArgs &a) {
+                             a.s = d_s; a.ns = ns; a.s_per_ray = s_per_ray ? 1 : 0;
+                             a.grad_T = d_grad_T; a.wrt = wrt; a.grad = d_grad; a.grad_s = d_grad_s; a.grad_rays = d_grad_rays;
+                         });
+}
+
+// samples and grad_T in; a cleared table of the scene's size, the per-sample output and the ray rows out, each where asked for
+int vrt_hip_transmittance_bundle_grad_rays(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *s,
+                                           size_t ns, int s_per_ray, const float *grad_T, int wrt, float *grad_out, float *grad_s_out,
+                                           float *grad_rays_out)
+{
+    const Rays r = { nrays, origins, origin_per_ray, dirs };
+    int rc;
+    if (bundle_over(c, TRANS_GRADIENT, r, ns, s && grad_T && (grad_out || grad_s_out || grad_rays_out), wrt, rc)) return rc;
+    return host_bundle(c, r, { { c->rays_values_in, s, (s_per_ray ? nrays : 1) * ns }, { c->rays_each_in, grad_T, nrays * ns } },
+                       { { c->rays_table_out, grad_out, (size_t)c->n * VRT_HIP_GRAD_STRIDE, true },
+                         { c->rays_each_out, grad_s_out, nrays * ns },
+                         { c->rays_rows_out, grad_rays_out, nrays * VRT_HIP_RAY_GRAD_STRIDE } },
+                       [&](const Rays &d) {
+                           return vrt_hip_transmittance_bundle_grad_rays_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, c->rays_values_in.p, ns,
+                                                                                s_per_ray, c->rays_each_in.p, wrt, wanted(grad_out, c->rays_table_out),
+                                                                                wanted(grad_s_out, c->rays_each_out),
+                                                                                wanted(grad_rays_out, c->rays_rows_out), c->stream);
                        });
 }
 
@@ -337,28 +386,14 @@ int vrt_hip_transmittance_bundle_grad_device(vrt_hip_ctx *c, size_t nrays, const
                                              const float *d_s, size_t ns, int s_per_ray, const float *d_grad_T, int wrt, float *d_grad, float *d_grad_s,
                                              void *hip_stream)
 {
-    return device_bundle(c, TRANS_GRADIENT, { nrays, d_origins, origin_per_ray, d_dirs }, ns, d_s && d_grad_T && (d_grad || d_grad_s), wrt, hip_stream,
-                         [&](RayArgs &a) {
-                             a.s = d_s; a.ns = ns; a.s_per_ray = s_per_ray ? 1 : 0;
-                             a.grad_T = d_grad_T; a.wrt = wrt; a.grad = d_grad; a.grad_s = d_grad_s;
-                         });
+    return vrt_hip_transmittance_bundle_grad_rays_device(c, nrays, d_origins, origin_per_ray, d_dirs, d_s, ns, s_per_ray, d_grad_T, wrt, d_grad, d_grad_s,
+                                                         nullptr, hip_stream);
 }
 
-// samples and grad_T in; a cleared table of the scene's size and the per-sample output out, either where asked for
 int vrt_hip_transmittance_bundle_grad(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *s,
                                       size_t ns, int s_per_ray, const float *grad_T, int wrt, float *grad_out, float *grad_s_out)
 {
-    const Rays r = { nrays, origins, origin_per_ray, dirs };
-    int rc;
-    if (bundle_over(c, TRANS_GRADIENT, r, ns, s && grad_T && (grad_out || grad_s_out), wrt, rc)) return rc;
-    return host_bundle(c, r, { { c->rays_values_in, s, (s_per_ray ? nrays : 1) * ns }, { c->rays_each_in, grad_T, nrays * ns } },
-                       { { c->rays_table_out, grad_out, (size_t)c->n * VRT_HIP_GRAD_STRIDE, true },
-                         { c->rays_each_out, grad_s_out, nrays * ns } },
-                       [&](const Rays &d) {
-                           return vrt_hip_transmittance_bundle_grad_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, c->rays_values_in.p, ns, s_per_ray,
-                                                                           c->rays_each_in.p, wrt, wanted(grad_out, c->rays_table_out),
-                                                                           wanted(grad_s_out, c->rays_each_out), c->stream);
-                       });
+    return vrt_hip_transmittance_bundle_grad_rays(c, nrays, origins, origin_per_ray, dirs, s, ns, s_per_ray, grad_T, wrt, grad_out, grad_s_out, nullptr);
 }
 
 int vrt_hip_transmittance_bundle_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,

@@ -339,12 +339,14 @@ struct RayArgs {
     float *depth;                // [r * nt + k]
     // Gradient bundles (vrt_ray_grad_kernel.hip; behind everything the other kernels read)
     const float4 *grad_radiance; // [r] d(loss) / d(radiance of ray r)
-    float *grad;                 // [S.n * VRT_HIP_GRAD_STRIDE] the caller's table, added to with float atomics
+    float *grad;                 // nullable, [S.n * VRT_HIP_GRAD_STRIDE] the caller's table, added to with float atomics; nullptr: no add is issued
     // Transmittance gradient bundles (vrt_ray_trans_grad_kernel.hip; behind everything the other kernels read).  They reuse s, ns,
     // s_per_ray and grad (nullable here).
     const float *grad_T;         // [r * ns + k] d(loss) / d(T[r, k]) (wrt == VRT_HIP_TGRAD_T) or d(loss) / d(depth[r, k]) (VRT_HIP_TGRAD_DEPTH)
     float *grad_s;               // nullable, [r * ns + k], stored: d(loss) / d(s[r, k]) or d(loss) / d(tau[r, k])
     int wrt;
+    // Ray gradients (both gradient kernels; behind everything the other kernels read)
+    float *grad_rays;            // nullable, [r * VRT_HIP_RAY_GRAD_STRIDE], 16-byte aligned, stored: d(loss) / d(origin), 0, tangential d(loss) / d(dir), 0
 };
 constexpr int RAY_STATS_WORDS = 9, RAY_INDEX_STATS_WORDS = 5; // one device buffer: the index's words follow the nine
 void launch_ray_bundle(const RayArgs &a, uint32_t long_grid /* one-wave workgroups of the long kernel */, bool indexed, int exp_kind, int erf_kind,
@@ -353,12 +355,13 @@ void launch_ray_bundle(const RayArgs &a, uint32_t long_grid /* one-wave workgrou
 void launch_ray_trans_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
 // the same cull, then the distance at which T falls to each of a.nt levels per ray (vrt_ray_depth_kernel.hip)
 void launch_ray_depth_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
-// the same cull, then d(loss) / d(Gaussians) from a.grad_radiance, added into a.grad (vrt_ray_grad_kernel.hip).  Only the pairs
+// the same cull, then d(loss) / d(Gaussians) from a.grad_radiance, added into a.grad (where there), and d(loss) / d(rays) stored to
+// a.grad_rays (where there) (vrt_ray_grad_kernel.hip).  Only the pairs
 // ray_grad_pair_supported names have kernels; any other enqueues nothing.
 void launch_ray_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
 bool ray_grad_pair_supported(int exp_kind, int erf_kind);
 // the same cull, then d(loss) / d(Gaussians) from a.grad_T at the samples a.s, added into columns 4..8 of a.grad, and d(loss) /
-// d(samples or levels) stored to a.grad_s (vrt_ray_trans_grad_kernel.hip).  The pairs of ray_grad_pair_supported; any other enqueues nothing.
+// d(samples or levels) stored to a.grad_s, d(loss) / d(rays) to a.grad_rays (vrt_ray_trans_grad_kernel.hip).  The pairs of ray_grad_pair_supported; any other enqueues nothing.
 void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
 // group spheres of the Morton index: one per 64 consecutive leaf spheres, bounding them
 void launch_build_ray_groups(uint32_t nleaves, const float4 *leaves, float4 *groups, hipStream_t st);

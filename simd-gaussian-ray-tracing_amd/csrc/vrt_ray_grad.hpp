@@ -6,6 +6,7 @@
 //   grad_deal         one weight dealt to one absorber: P, Q, R
 //   grad_row, _w      the row segment (d mu xyz, d sigma, d magnitude) from M, the coefficient of n and the sigma sum; with the terms in W
 //   grad_deposit      a row segment into the caller's table, wave-summed where every lane names the same row
+//   grad_ray_add, _w, grad_ray_store   the same segment's share of the RAY's row (d origin, d direction), and the row's two stores
 //   LaneList, grad_acc, grad_walk_begin / _next, grad_flush_short   lane = ray: a lane's list, the three running sums per list position and lane in LDS, the walk of a
 //                     lane's list with the next entry's rows loaded one iteration ahead, and every position to the table once
 //   grad_emitter_place, grad_pass1, grad_pass2    the radiance gradient's emitter set-up and the bodies of its two pair loops
@@ -122,6 +123,40 @@ __device__ __forceinline__ void grad_row_w(const GradGauss &q, const LaneRay &ra
     d[3] = d[3] + ArE * q.m * SQRT_2 * W;
 }
 
+// ---- the ray's own row: d(loss) / d(origin, direction) ----
+// Every observable depends on the ray (o, n) through c_j = mu_j - o and n alone, and ray r's share of row j's d mu is a c_perp + b n with
+// a = -mag M / sigma^2 (grad_row's alpha) and b the whole coefficient of n.  Hence ("Ray gradients")
+//   d / d o = -sum_j (a_j c_perp_j + b_j n)                  (translation invariance)
+//   d / d n =  sum_j (b_j - a_j mubar_j) c_perp_j            (tangential: along normalise(n + eps t), t perpendicular to n)
+// Both are linear in (M, ncoef): grad_ray_add is called with the arguments of grad_row wherever a row segment is formed, and adds that
+// segment's share to six accumulators -- from a, b, mubar and c_perp themselves, not by projecting the finished row.  No atomic add: a
+// lane of the short kernels sums its ray's shares in list order, the long kernels finish with one wave_sum per component.
+constexpr int RAY_GRAD_STRIDE = VRT_HIP_RAY_GRAD_STRIDE; // floats per ray row: [0..2] d origin, [3] 0, [4..6] d direction, [7] 0
+__device__ __forceinline__ void grad_ray_add(const GradGauss &q, const LaneRay &ray, float mag, float M, float ncoef, float (&go)[3], float (&gn)[3])
+{
+    const float a = -(mag * M) * q.inv_s2;
+    const float t = __builtin_fmaf(-a, q.mubar, ncoef);
+    go[0] -= __builtin_fmaf(a, q.px, ncoef * ray.nx);
+    go[1] -= __builtin_fmaf(a, q.py, ncoef * ray.ny);
+    go[2] -= __builtin_fmaf(a, q.pz, ncoef * ray.nz);
+    gn[0] = __builtin_fmaf(t, q.px, gn[0]);
+    gn[1] = __builtin_fmaf(t, q.py, gn[1]);
+    gn[2] = __builtin_fmaf(t, q.pz, gn[2]);
+}
+// ... with the term in W on the coefficient of n, as grad_row_w
+template <int EXP>
+__device__ __forceinline__ void grad_ray_add_w(const GradGauss &q, const LaneRay &ray, float mag, float M, float ncoef, float W, float (&go)[3], float (&gn)[3])
+{
+    grad_ray_add(q, ray, mag, M, __builtin_fmaf(-(q.Ar * exp_neg_sq<EXP>(q.m)), W, ncoef), go, gn);
+}
+// ray r's row, STORED as two 16-byte stores
+__device__ __forceinline__ void grad_ray_store(float *grad_rays, uint64_t r, const float (&go)[3], const float (&gn)[3])
+{
+    float4 *row = (float4 *)(grad_rays + r * (uint64_t)RAY_GRAD_STRIDE);
+    row[0] = make_float4(go[0], go[1], go[2], 0.f);
+    row[1] = make_float4(gn[0], gn[1], gn[2], 0.f);
+}
+
 // ---- lane = ray (the short kernels) ----
 
 // s_acc: three running sums per list position and lane, [(c * RAY_PL + pos) * 64 + lane]: c = 0 M (d magnitude), 1 the coefficient of n,
@@ -161,20 +196,31 @@ __device__ __forceinline__ GradGauss grad_walk_next(ListWalk &w, const SceneTabl
     return grad_gauss<EXP, ERF>(erf, ca, cb, L.has(j), ray);
 }
 
-// Every list position to the table once, now that W is known.  The whole wave calls this.
-template <int EXP, int ERF>
-__device__ __forceinline__ void grad_flush_short(float *table, const SceneTables &S, const ErfEval<ERF> &erf, const LaneList &L, float *s_acc, const LaneRay &ray,
-                                                 float W)
+// Every list position to the table once, now that W is known, and -- RAYS -- the same segments to the lane's ray row in list order,
+// stored once where the lane `writes`.  With RAYS the table may be missing (table == nullptr, wave-uniform: no add is issued); without,
+// it is there, and this is the text the kernels ran before there were ray rows.  The whole wave calls this.
+template <int EXP, int ERF, bool RAYS>
+__device__ __forceinline__ void grad_flush_short(float *table, [[maybe_unused]] float *grad_rays, [[maybe_unused]] uint64_t r, [[maybe_unused]] bool writes,
+                                                 const SceneTables &S, const ErfEval<ERF> &erf, const LaneList &L, float *s_acc, const LaneRay &ray, float W)
 {
     const uint32_t lane = L.lane;
+    [[maybe_unused]] float go[3] = { 0.f, 0.f, 0.f }, gn[3] = { 0.f, 0.f, 0.f };
     for (uint32_t p = 0; p < L.nmax; ++p) {
         const bool on = L.has(p); // nl is 0 in a lane without a ray of this kernel
         const uint32_t idx = L.at(p);
         const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], on, ray);
         const float mag = on ? S.gD[idx].z : 0.f;
-        float d[5];
-        grad_row_w<EXP>(q, ray, mag, grad_acc(s_acc, 0, p, lane), grad_acc(s_acc, 1, p, lane), grad_acc(s_acc, 2, p, lane), W, d);
-        grad_deposit<5>(table, idx, on, d, 4u, lane);
+        if constexpr (RAYS) {
+            if (on) grad_ray_add_w<EXP>(q, ray, mag, grad_acc(s_acc, 0, p, lane), grad_acc(s_acc, 1, p, lane), W, go, gn);
+        }
+        if (!RAYS || table) {
+            float d[5];
+            grad_row_w<EXP>(q, ray, mag, grad_acc(s_acc, 0, p, lane), grad_acc(s_acc, 1, p, lane), grad_acc(s_acc, 2, p, lane), W, d);
+            grad_deposit<5>(table, idx, on, d, 4u, lane);
+        }
+    }
+    if constexpr (RAYS) {
+        if (writes) grad_ray_store(grad_rays, r, go, gn); // a ray that keeps nothing: exact zeros
     }
 }
 

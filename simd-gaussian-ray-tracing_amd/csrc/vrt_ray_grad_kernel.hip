@@ -30,6 +30,10 @@
 // Exp / Erf of the forward quantities are the selected pair's; e1 and e2 are exp_neg_sq<EXP>.  Only {vcl, libm} x {A&S, libm} are
 // instantiated: the piecewise approximations have jumps, and the entry point refuses them.
 // The sums in the caller's table depend on the arrival order of the atomic adds: not bitwise reproducible.
+// RAYS (vrt_hip_radiance_rays_grad_rays*): d(loss) / d(origin, direction) of every ray as well, one stored row per ray (grad_ray_add of
+// vrt_ray_grad.hpp beside every grad_row; DESIGN.md section 4, "Ray gradients"): summed per lane in list order (short) or per lane and then
+// over the wave in its fixed order (long), no atomic add, bitwise reproducible.  With RAYS the table may be missing (P.grad == nullptr): no
+// table add is issued.  RAYS is a template parameter: <.., false> is the kernel from before there were ray rows, register for register.
 // Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
 // What lives where: this file has the emitter's weights (grad_emitter), the chunk of the short kernel, the two kernels' own loops -- how
 // the absorber is loaded (per lane; readfirstlane + uload) and where a sum goes (LDS; the table) -- and the launch.  Every formula named
@@ -55,7 +59,7 @@ __device__ __forceinline__ float grad_emitter(bool on, float sigma, float d2, fl
 }
 
 // One chunk of EC emitters (list positions i0 .. i0+EC-1 of every lane) against the lane's whole list, both passes.
-template <int EXP, int ERF, int EC>
+template <int EXP, int ERF, int EC, bool RAYS>
 __device__ __forceinline__ void ray_grad_chunk(const RayArgs *Pp, const SceneTables *Sp, const uint32_t *s_list /*[k*64 + lane]*/, float *s_acc, uint32_t nl,
                                                uint32_t nmax, uint32_t lane, const LaneRay &ray, uint32_t i0, float4 g, float &W)
 {
@@ -94,7 +98,7 @@ __device__ __forceinline__ void ray_grad_chunk(const RayArgs *Pp, const SceneTab
         W = __builtin_fmaf(GV[e], mag, W);
         const float mV = mag * V;
         const float da[4] = { g.x * mV, g.y * mV, g.z * mV, g.w * mV };
-        grad_deposit<4>(Pp->grad, idx, on, da, 0u, lane);
+        if (!RAYS || Pp->grad) grad_deposit<4>(Pp->grad, idx, on, da, 0u, lane);
     }
 
     // ---- pass 2: the same pairs again; w_ik to the absorbers (P, Q, R) and through w e2 A C r back to the emitters (Z, Y) ----
@@ -120,7 +124,8 @@ __device__ __forceinline__ void ray_grad_chunk(const RayArgs *Pp, const SceneTab
     }
 }
 
-template <int EXP, int ERF, bool INDEXED>
+// RAYS: the ray rows are asked for (P.grad_rays != nullptr), and then the table may be missing; without, the table is there
+template <int EXP, int ERF, bool INDEXED, bool RAYS>
 __global__ __launch_bounds__(64) void ray_short_grad_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -141,17 +146,19 @@ __global__ __launch_bounds__(64) void ray_short_grad_kernel(RayArgs) // read thr
     constexpr int EC = 4;
     for (uint32_t i0 = 0; i0 < nmax; i0 += EC) {
         const uint32_t rem = nmax - i0;
-        if (rem >= (uint32_t)EC) ray_grad_chunk<EXP, ERF, EC>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
-        else if (rem == 3) ray_grad_chunk<EXP, ERF, 3>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
-        else if (rem == 2) ray_grad_chunk<EXP, ERF, 2>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
-        else ray_grad_chunk<EXP, ERF, 1>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
+        if (rem >= (uint32_t)EC) ray_grad_chunk<EXP, ERF, EC, RAYS>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
+        else if (rem == 3) ray_grad_chunk<EXP, ERF, 3, RAYS>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
+        else if (rem == 2) ray_grad_chunk<EXP, ERF, 2, RAYS>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
+        else ray_grad_chunk<EXP, ERF, 1, RAYS>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
     }
 
-    grad_flush_short<EXP, ERF>(P.grad, S, ErfEval<ERF>(), LaneList{ s_list, lane, nl, nmax }, s_acc, ray, W);
+    grad_flush_short<EXP, ERF, RAYS>(P.grad, P.grad_rays, R.rc, R.writes, S, ErfEval<ERF>(), LaneList{ s_list, lane, nl, nmax }, s_acc, ray, W);
 }
 
-// One wave per long ray, lane = emitter (EC rounds of 64 at a time), the absorber wave-uniform.
-template <int EXP, int ERF, bool INDEXED>
+// One wave per long ray, lane = emitter (EC rounds of 64 at a time), the absorber wave-uniform.  RAYS: as in the short kernel.  A template
+// parameter in all four gradient kernels: with a pointer test the six accumulators cost this one an occupancy step in five of its eight
+// instantiations, and the others a fraction of a percent of their time (profiles/ray_grad_rays.md); <.., false> is each kernel as it was.
+template <int EXP, int ERF, bool INDEXED, bool RAYS>
 __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -160,6 +167,7 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
     const uint32_t lane = threadIdx.x & 63u;
     const ErfEval<ERF> erf;
     constexpr int EC = 2;
+    const bool table = !RAYS || P.grad != nullptr; // wave-uniform
 
     LongRay L = ray_long_begin(&P);
     while (ray_long_next<INDEXED>(&P, &S, s_list, lane, L)) {
@@ -167,6 +175,7 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
         const uint32_t n = L.n;
         const float4 g = P.grad_radiance[L.r];
         float W = 0.f; // this lane's emitters; summed over the wave behind the rounds
+        [[maybe_unused]] float go[3] = { 0.f, 0.f, 0.f }, gn[3] = { 0.f, 0.f, 0.f }; // this lane's shares of the ray's row; summed over the wave behind the last walk
         for (uint32_t e0 = 0; e0 < n; e0 += 64u * EC) {
             float e_mubar[EC], e_sigma[EC];
             uint32_t e_idx[EC];
@@ -199,7 +208,7 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
                 const float V = grad_emitter<EXP>(e_on[e], e_sigma[e], q.d2, 0.5f * q.inv_s2, G * e_mag[e], acc[e], w[e]);
                 GV[e] = G * V;
                 W = __builtin_fmaf(GV[e], e_mag[e], W);
-                if (e_on[e]) {
+                if (table && e_on[e]) {
                     const float mV = e_mag[e] * V;
                     float *row = P.grad + (size_t)e_idx[e] * GRAD_STRIDE;
                     atomicAdd(row + 0, g.x * mV); atomicAdd(row + 1, g.y * mV); atomicAdd(row + 2, g.z * mV); atomicAdd(row + 3, g.w * mV);
@@ -215,21 +224,28 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
                 float Pj = 0.f, Qj = 0.f, Rj = 0.f;
                 grad_pass2<EXP>(erf, q, e_mubar, e_sigma, w, z, y, Pj, Qj, Rj);
                 Pj = wave_sum(Pj); Qj = wave_sum(Qj); Rj = wave_sum(Rj);
-                float d[5];
-                grad_row(q, ray, uload(S.gD, idx).z, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, d);
-                const float mine = lane == 0 ? d[0] : lane == 1 ? d[1] : lane == 2 ? d[2] : lane == 3 ? d[3] : d[4];
-                if (lane < 5u) atomicAdd(&P.grad[(size_t)idx * GRAD_STRIDE + 4u + lane], mine);
+                const float mag = uload(S.gD, idx).z;
+                if (RAYS && lane == 0) grad_ray_add(q, ray, mag, q.Am * Pj, q.Ar * Qj, go, gn); // wave-uniform: one lane takes it
+                if (table) {
+                    float d[5];
+                    grad_row(q, ray, mag, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, d);
+                    const float mine = lane == 0 ? d[0] : lane == 1 ? d[1] : lane == 2 ? d[2] : lane == 3 ? d[3] : d[4];
+                    if (lane < 5u) atomicAdd(&P.grad[(size_t)idx * GRAD_STRIDE + 4u + lane], mine);
+                }
             }
             // ---- the emitters' own terms: every lane another row ----
 #pragma unroll
             for (int e = 0; e < EC; ++e) {
                 if (e_on[e]) {
                     const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[e_idx[e]], S.gB[e_idx[e]], true, ray);
-                    float d[5];
-                    grad_row(q, ray, e_mag[e], GV[e], -z[e], -y[e], d);
-                    float *row = P.grad + (size_t)e_idx[e] * GRAD_STRIDE;
+                    if constexpr (RAYS) grad_ray_add(q, ray, e_mag[e], GV[e], -z[e], go, gn);
+                    if (table) {
+                        float d[5];
+                        grad_row(q, ray, e_mag[e], GV[e], -z[e], -y[e], d);
+                        float *row = P.grad + (size_t)e_idx[e] * GRAD_STRIDE;
 #pragma unroll
-                    for (int c = 0; c < 5; ++c) atomicAdd(row + 4 + c, d[c]);
+                        for (int c = 0; c < 5; ++c) atomicAdd(row + 4 + c, d[c]);
+                    }
                 }
             }
         }
@@ -241,10 +257,19 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
                 const uint32_t idx = long_list_entry(s_list, L.slot, p);
                 const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], true, ray);
                 const float ArEW = q.Ar * exp_neg_sq<EXP>(q.m) * W;
-                float *row = P.grad + (size_t)idx * GRAD_STRIDE;
-                atomicAdd(row + 4, -ArEW * ray.nx); atomicAdd(row + 5, -ArEW * ray.ny); atomicAdd(row + 6, -ArEW * ray.nz);
-                atomicAdd(row + 7, ArEW * q.m * SQRT_2);
+                if constexpr (RAYS) grad_ray_add(q, ray, 0.f, 0.f, -ArEW, go, gn);
+                if (table) {
+                    float *row = P.grad + (size_t)idx * GRAD_STRIDE;
+                    atomicAdd(row + 4, -ArEW * ray.nx); atomicAdd(row + 5, -ArEW * ray.ny); atomicAdd(row + 6, -ArEW * ray.nz);
+                    atomicAdd(row + 7, ArEW * q.m * SQRT_2);
+                }
             }
+        }
+        // ---- the ray's row: the lanes' shares in the wave's fixed order, one store ----
+        if constexpr (RAYS) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { go[c] = wave_sum(go[c]); gn[c] = wave_sum(gn[c]); }
+            if (lane == 0) grad_ray_store(P.grad_rays, L.r, go, gn);
         }
     }
 }
@@ -252,8 +277,11 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
 template <int EXP, int ERF>
 static void launch_ray_grad_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
 {
-    if (indexed) launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, true>, ray_long_grad_kernel<EXP, ERF, true>, a, long_grid, st);
-    else launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, false>, ray_long_grad_kernel<EXP, ERF, false>, a, long_grid, st);
+    if (a.grad_rays) {
+        if (indexed) launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, true, true>, ray_long_grad_kernel<EXP, ERF, true, true>, a, long_grid, st);
+        else launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, false, true>, ray_long_grad_kernel<EXP, ERF, false, true>, a, long_grid, st);
+    } else if (indexed) launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, true, false>, ray_long_grad_kernel<EXP, ERF, true, false>, a, long_grid, st);
+    else launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, false, false>, ray_long_grad_kernel<EXP, ERF, false, false>, a, long_grid, st);
 }
 // the four pairs of VRT_DISPATCH_GRAD_PAIR; out of line here because the entry points' check (vrt_hip_rays.cpp) asks too
 bool ray_grad_pair_supported(int exp_kind, int erf_kind)

@@ -32,6 +32,10 @@
 //                                entry and chunk (grad_row_w), the chunk's W terms included: 5 ceil(ns / NSC) adds per entry, every lane
 //                                another row.
 // The per-sample output is STORED (by the lane; by lane 0 of the long kernel), not added.
+// RAYS (vrt_hip_transmittance_bundle_grad_rays*): d(loss) / d(origin, direction) of every ray as well, one stored row per ray, in either
+// mode (the weights w_k are in the row segments already): grad_ray_add_w beside every grad_row_w, per lane in list order (short) or per
+// lane over its entries and all chunks and then one wave_sum per component (long).  No atomic add; bitwise reproducible.  A template
+// parameter: <.., false> is the kernel from before there were ray rows.
 // Exp / Erf of the forward quantities are the selected pair's; e1 and e2 are exp_neg_sq<EXP>.  Only {vcl, libm} x {A&S, libm} are
 // instantiated (ray_grad_pair_supported).  The sums in the caller's table depend on the arrival order of the atomic adds: not bitwise
 // reproducible.  Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
@@ -73,7 +77,8 @@ __device__ __forceinline__ bool trans_grad_live(bool depth_mode, float s, float 
 // away), and e2 = exp(-x^2) passes an error dx on as 2 |x| dx -- 4e-5 of a far sample's addends on the grid scene, against 5e-6 this way.
 __device__ __forceinline__ float trans_grad_x(float s, const GradGauss &q) { return (s - q.mubar) * q.r; }
 
-template <int EXP, int ERF, bool INDEXED>
+// RAYS: the ray rows are asked for (P.grad_rays != nullptr); without, each kernel is the text it was before there were ray rows
+template <int EXP, int ERF, bool INDEXED, bool RAYS>
 __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -131,7 +136,7 @@ __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // re
             W += w[g];
             if (gsp && R.writes && k0 + g < ns) gsp[k0 + g] = gs;
         }
-        if (!P.grad) continue;
+        if (!RAYS && !P.grad) continue;
         // ---- walk 2: the same entries again; w_k to P, Q, R of every position ----
         lw = grad_walk_begin(S, L);
         for (uint32_t j = 0; j < nmax; ++j) {
@@ -146,11 +151,11 @@ __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // re
             }
         }
     }
-    if (P.grad) grad_flush_short<EXP, ERF>(P.grad, S, erf, L, s_acc, ray, W);
+    if (RAYS || P.grad) grad_flush_short<EXP, ERF, RAYS>(P.grad, P.grad_rays, R.rc, R.writes, S, erf, L, s_acc, ray, W);
 }
 
 // One wave per long ray, lane l takes entries l, l + 64, ...; the samples in chunks of NSC.
-template <int EXP, int ERF, bool INDEXED>
+template <int EXP, int ERF, bool INDEXED, bool RAYS>
 __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -169,6 +174,7 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
         const float *sp = P.s + (P.s_per_ray ? L.r * ns : 0ull);
         const float *gp = P.grad_T + L.r * ns;
         float *gsp = P.grad_s ? P.grad_s + L.r * ns : nullptr;
+        [[maybe_unused]] float go[3] = { 0.f, 0.f, 0.f }, gn[3] = { 0.f, 0.f, 0.f }; // this lane's shares of the ray's row, over its entries and all chunks
         for (uint64_t c0 = 0; c0 < ns; c0 += NSC) {
             const uint32_t nc = (uint32_t)(ns - c0 < (uint64_t)NSC ? ns - c0 : (uint64_t)NSC);
             // ---- the chunk's samples to LDS, lane = sample (whole groups: what lies past the end is not live) ----
@@ -212,21 +218,31 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
             }
             __syncthreads(); // the chunk's weights are in LDS
             // ---- every lane its entries, the chunk's samples in the inner loop ----
-            if (P.grad) {
+            if (RAYS || P.grad) {
                 for (uint32_t p = lane; p < n; p += 64u) {
                     const uint32_t idx = long_list_entry(s_list, L.slot, p);
                     const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], true, ray);
                     float Pj = 0.f, Qj = 0.f, Rj = 0.f;
 #pragma unroll 4
                     for (uint32_t k = 0; k < nc; ++k) grad_deal<EXP>(erf, s_w[k], trans_grad_x(s_s[k], q), q.E, Pj, Qj, Rj);
-                    float d[5];
-                    grad_row_w<EXP>(q, ray, S.gD[idx].z, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, Wc, d);
-                    float *row = P.grad + (size_t)idx * GRAD_STRIDE;
+                    const float mag = S.gD[idx].z;
+                    if constexpr (RAYS) grad_ray_add_w<EXP>(q, ray, mag, q.Am * Pj, q.Ar * Qj, Wc, go, gn);
+                    if (P.grad) {
+                        float d[5];
+                        grad_row_w<EXP>(q, ray, mag, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, Wc, d);
+                        float *row = P.grad + (size_t)idx * GRAD_STRIDE;
 #pragma unroll
-                    for (int c = 0; c < 5; ++c) atomicAdd(row + 4 + c, d[c]);
+                        for (int c = 0; c < 5; ++c) atomicAdd(row + 4 + c, d[c]);
+                    }
                 }
             }
             __syncthreads(); // the chunk's weights are read before the next chunk's are written
+        }
+        // ---- the ray's row: the lanes' shares in the wave's fixed order, one store ----
+        if constexpr (RAYS) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { go[c] = wave_sum(go[c]); gn[c] = wave_sum(gn[c]); }
+            if (lane == 0) grad_ray_store(P.grad_rays, L.r, go, gn);
         }
     }
 }
@@ -234,8 +250,11 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
 template <int EXP, int ERF>
 static void launch_ray_trans_grad_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
 {
-    if (indexed) launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, true>, ray_long_trans_grad_kernel<EXP, ERF, true>, a, long_grid, st);
-    else launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, false>, ray_long_trans_grad_kernel<EXP, ERF, false>, a, long_grid, st);
+    if (a.grad_rays) {
+        if (indexed) launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, true, true>, ray_long_trans_grad_kernel<EXP, ERF, true, true>, a, long_grid, st);
+        else launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, false, true>, ray_long_trans_grad_kernel<EXP, ERF, false, true>, a, long_grid, st);
+    } else if (indexed) launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, true, false>, ray_long_trans_grad_kernel<EXP, ERF, true, false>, a, long_grid, st);
+    else launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, false, false>, ray_long_trans_grad_kernel<EXP, ERF, false, false>, a, long_grid, st);
 }
 void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
 {

@@ -46,6 +46,16 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
       reported as measured.  `--tgrad-only` runs this part alone, prints its JSON line and writes ray_trans_grad.json and
       ray_trans_grad.md (and nothing else) to --out-dir; the .md ends with the text of <out-dir>/ray_trans_grad_resources.txt when that
       file is there (the output of `tools/kernel_resources.sh raytgrad`).
+  (rg) ray gradients (vrt_hip_radiance_rays_grad_rays_device, vrt_hip_transmittance_bundle_grad_rays_device): the 2^20 scattered and the
+      4096 zoomed (coherent) rays of (g) and the 4096 x 64 samples of (tg), device pointers, index off, four paths alternating in the same
+      run: the forward bundle, the gradient call with the table alone (what (g) and (tg) time), with table and ray rows, and with the ray
+      rows alone (no table, so no atomic add); each gradient time also as a ratio to the forward bundle.  The ray rows alone issue the
+      same passes as the table call and no atomic add: the run fails if their median exceeds the table call's by more than the spread
+      (max - min) of that run's own repeats of either.  `--rgrad-only` runs this part alone, prints its JSON line and writes
+      ray_grad_rays.json and ray_grad_rays.md (and nothing else) to --out-dir; the .md takes in, where they are there,
+      <out-dir>/ray_grad_rays_existing.json ({"parent": {"grad": .., "tgrad": ..}, "new": {..}, optionally "parent_again": {..}}: the
+      results of `--grad-only` and `--tgrad-only` on the commit before the ray rows and on this one, same machine, same session), <out-dir>/ray_grad_rays_pose_fit.json
+      (the line of tools/pose_fit.py) and <out-dir>/ray_grad_rays_resources.txt (tools/kernel_resources.sh raygrad and raytgrad on both).
 """
 import argparse
 import json
@@ -444,6 +454,131 @@ rocprofv3, the host-pointer form, any scene but `-g 64`, the max-ilp scheduler o
     return "\n".join(lines)
 
 
+def part_rgrad(g, calls=3, repeats=7):
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    cam, _ = scene.cli_camera(64, 64)
+    centre = g["mu"][len(g) // 2 + int(round(len(g) ** 0.5)) // 2, :3].astype(np.float64)
+    u = (np.arange(64) - 31.5) / 64 * 0.03
+    target = centre[None, :] + np.stack([np.tile(u, 64), np.repeat(u, 64), np.zeros(4096)], 1)
+    dz = target - np.asarray(cam.position, np.float64)[:3]
+    zoom = (np.asarray(cam.position, f32)[:3], np.ascontiguousarray((dz / np.linalg.norm(dz, axis=1, keepdims=True)).astype(f32)))
+    cases = (("scattered_2^20", scattered(g, 1 << 20), 1, None), ("zoom_64x64", zoom, 0, None),
+             ("profiles_4096_ns64", aimed_rays(g), 0, np.linspace(0.5, 8.0, 64).astype(f32)))
+    rows = {}
+    for label, (o, d), per, s in cases:
+        nrays = len(d)
+        t_o, t_d = torch.from_numpy(np.ascontiguousarray(o, f32)).cuda(), torch.from_numpy(np.ascontiguousarray(d, f32)).cuda()
+        r = pkg.Renderer(0)
+        r.set_gaussians(g)
+        table = torch.zeros((len(g), pkg.GRAD_STRIDE), dtype=torch.float32, device="cuda")
+        rays = [torch.zeros((nrays, pkg.RAY_GRAD_STRIDE), dtype=torch.float32, device="cuda") for _ in range(2)]
+        if s is None:
+            t_g = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, size=(nrays, 4)).astype(f32)).cuda()
+            out = torch.zeros((nrays, 4), dtype=torch.float32, device="cuda")
+
+            def grad(d_grad, d_rays):
+                r.radiance_rays_grad_rays_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_g.data_ptr(), d_grad, d_rays, st)
+            fns = [lambda: r.radiance_rays_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), out.data_ptr(), 0, PACK, st)]
+        else:
+            ns = len(s)
+            t_s = torch.from_numpy(s).cuda()
+            t_g = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, size=(nrays, ns)).astype(f32)).cuda()
+            out, gs = (torch.zeros((nrays, ns), dtype=torch.float32, device="cuda") for _ in range(2))
+
+            def grad(d_grad, d_rays):      # the per-sample output in every path, as (tg) times it
+                r.transmittance_bundle_grad_rays_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_s.data_ptr(), ns, 0, t_g.data_ptr(), pkg.TGRAD_T,
+                                                        d_grad, gs.data_ptr(), d_rays, st)
+            fns = [lambda: r.transmittance_bundle_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_s.data_ptr(), ns, 0, out.data_ptr(), st)]
+        fns += [lambda: grad(table.data_ptr(), 0), lambda: grad(table.data_ptr(), rays[0].data_ptr()), lambda: grad(0, rays[1].data_ptr())]
+        torch.cuda.synchronize()
+        t = windows(fns, calls, repeats, warm=2)
+        torch.cuda.synchronize()
+        same = bool((rays[0].view(torch.int32) == rays[1].view(torch.int32)).all().item())
+        finite = bool(torch.isfinite(rays[1]).all().item())
+        r.close()
+        fwd = t[0]["median"]
+        rows[label] = {"rays": nrays, "ns": 0 if s is None else len(s), "forward_ms": t[0], "table_ms": t[1], "table_and_rays_ms": t[2], "rays_only_ms": t[3],
+                       "table_over_forward": round(t[1]["median"] / fwd, 2), "table_and_rays_over_forward": round(t[2]["median"] / fwd, 2),
+                       "rays_only_over_forward": round(t[3]["median"] / fwd, 2), "ray_rows_same_bits_with_and_without_table": same, "finite": finite}
+    return {"gaussians": len(g), "calls": calls, "repeats": repeats, "rows": rows}
+
+
+def check_rgrad(z):
+    for label, r in z["rows"].items():
+        assert r["finite"] and r["ray_rows_same_bits_with_and_without_table"], label
+        slack = max(r["table_ms"]["max"] - r["table_ms"]["min"], r["rays_only_ms"]["max"] - r["rays_only_ms"]["min"])
+        assert r["rays_only_ms"]["median"] <= r["table_ms"]["median"] + slack, \
+            f"{label}: the ray rows alone (the same passes, no atomic add) are slower than the table call by more than the spread of this run's repeats"
+
+
+def existing_rows(z):
+    """(label, index, forward, gradient) of a --grad-only or --tgrad-only result"""
+    fwd, grad = ("radiance", "grad") if "grad_off_ms" in next(iter(z["rows"].values())) else ("trans", "tgrad")
+    return [(label, key, r[f"{fwd}_{key}_ms"], r[f"{grad}_{key}_ms"]) for label, r in z["rows"].items() for key in ("off", "on")]
+
+
+def markdown_rgrad(z, existing=None, pose=None, resources=""):
+    lines = [f"""# Ray gradients (tools/ray_bundles.py --rgrad-only, tools/pose_fit.py)
+
+## The new outputs
+
+`vrt_hip_radiance_rays_grad_rays_device` / `vrt_hip_transmittance_bundle_grad_rays_device` on `-g 64` (N = {z['gaussians']}), device pointers,
+Morton index off, stream events around {z['calls']} back-to-back calls, {z['repeats']} windows per path after warm-up, the four paths of a
+bundle alternating; ms per call, median (min .. max), and the median as a ratio to the forward bundle of the same rays in the same run.
+"table" is the call the existing entry points make.  The run fails if the ray rows alone are slower than the table call by more than
+the spread of its own repeats.
+
+| bundle | rays | ns | forward | table | table + ray rows | ray rows only | / forward: table | table + rows | rows only | same ray bits with / without table |
+|---|---|---|---|---|---|---|---|---|---|---|"""]
+    for label, r in z["rows"].items():
+        lines.append(f"| {label} | {r['rays']} | {r['ns'] or ''} | {ms(r['forward_ms'])} | {ms(r['table_ms'])} | {ms(r['table_and_rays_ms'])} | {ms(r['rays_only_ms'])} | "
+                     f"{r['table_over_forward']} | {r['table_and_rays_over_forward']} | {r['rays_only_over_forward']} | {r['ray_rows_same_bits_with_and_without_table']} |")
+    lines.append("")
+    if existing:
+        again = existing.get("parent_again")
+        lines.append("""## The existing path, parent against new
+
+`--grad-only` and `--tgrad-only` (the table alone, through the entry points without ray rows) on the commit before the ray rows and on
+this one: same machine, same session, one run (process) each""" + (", and the parent's a second time: what one run of the same code differs from another by" if again else "") + """.
+Gradient ms per call, median (min .. max).  Worse: the new median exceeds the parent's by more than the parent's own spread (max - min)
+over its repeats.
+
+| part | bundle | index | parent | new | new - parent | parent spread | worse |""" + (" parent again - parent |" if again else "") + """
+|---|---|---|---|---|---|---|---|""" + ("---|" if again else ""))
+        for part in ("grad", "tgrad"):
+            rows_again = existing_rows(again[part]) if again else None
+            for k, ((label, key, _, pg), (_, _, _, ng)) in enumerate(zip(existing_rows(existing["parent"][part]), existing_rows(existing["new"][part]))):
+                diff, sp = ng["median"] - pg["median"], pg["max"] - pg["min"]
+                lines.append(f"| {part} | {label} | {key} | {ms(pg)} | {ms(ng)} | {diff:+.5f} | {sp:.5f} | {diff > sp} |"
+                             + (f" {rows_again[k][3]['median'] - pg['median']:+.5f} |" if again else ""))
+        lines.append("")
+    else:
+        lines.append("## The existing path, parent against new\n\nNOT RUN: no ray_grad_rays_existing.json was given.\n")
+    if pose:
+        k = max(1, len(pose["loss"]) // 10)
+        lines.append(f"""## Pose fit (tools/pose_fit.py)
+
+`{pose['scene']}`, {pose['rays']} rays of a pinhole camera, {pose['steps']} steps of Adam (lr {pose['lr_t']} on the translation, {pose['lr_w']} on the
+rotation vector, both times {pose['decay']} per step) through `autograd.radiance_rays`, no table.  Offset {pose['offset_start']:.4f} -> {pose['offset_end']:.5f} units, angle
+{pose['angle_deg_start']:.3f} -> {pose['angle_deg_end']:.4f} degrees.  Step (forward, backward, update; the scene goes through the host every
+step): median {pose['step_ms_median']} ms, fastest {pose['step_ms_min']} ms.  Loss at every {k}th step:
+
+```
+{'  '.join(f'{v:.4e}' for v in pose['loss'][::k])}
+final {pose['loss'][-1]:.4e}
+```
+""")
+    else:
+        lines.append("## Pose fit (tools/pose_fit.py)\n\nNOT RUN: no ray_grad_rays_pose_fit.json was given.\n")
+    if resources:
+        lines.append("## Resources\n\n" + resources.rstrip() + "\n")
+    lines.append("""Not taken: a profile under rocprofv3, the Morton index on for the new outputs, the host-pointer forms, depth mode and the shadow rays
+(ns = 1) with ray rows, any scene but `-g 64` (pose fit: `-g 16`), more than one run of any figure.
+""")
+    return "\n".join(lines)
+
+
 def windows(fns, calls, repeats, warm=3):
     """ms per call of each fn: `repeats` windows of `calls` back-to-back calls between two stream events, the fns alternating."""
     import torch
@@ -636,6 +771,7 @@ def main():
     ap.add_argument("--depth-only", action="store_true")
     ap.add_argument("--grad-only", action="store_true")
     ap.add_argument("--tgrad-only", action="store_true")
+    ap.add_argument("--rgrad-only", action="store_true")
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
     if a.transmittance_only:
@@ -663,6 +799,21 @@ def main():
             f.write(markdown_tgrad(z, open(res).read() if os.path.exists(res) else ""))
         print(json.dumps({"tgrad": z}))
         check_tgrad(z)
+        return
+    if a.rgrad_only:
+        z = part_rgrad(g)
+        os.makedirs(a.out_dir, exist_ok=True)
+        with open(os.path.join(a.out_dir, "ray_grad_rays.json"), "w") as f:
+            f.write(json.dumps({"what": "ray gradients against the table call and the forward bundle of the same rays; see tools/ray_bundles.py (rg)", "rgrad": z}) + "\n")
+
+        def side(name, load):
+            path = os.path.join(a.out_dir, name)
+            return load(open(path).read()) if os.path.exists(path) else None
+        with open(os.path.join(a.out_dir, "ray_grad_rays.md"), "w") as f:
+            f.write(markdown_rgrad(z, side("ray_grad_rays_existing.json", json.loads), side("ray_grad_rays_pose_fit.json", json.loads),
+                                   side("ray_grad_rays_resources.txt", str) or ""))
+        print(json.dumps({"rgrad": z}))
+        check_rgrad(z)
         return
     if a.depth_only:
         z = part_depth(g)
