@@ -257,8 +257,11 @@ struct device_t {
         for (size_t i = 0; i < g.size() * sizeof(gaussian_t); ++i) { h ^= p[i]; h *= 1099511628211ull; }
         return h;
     }
+    bool device_scene = false; // the scene came from device memory (vrt::set_gaussians_device): an EMPTY vector stands for it
     void upload_scene(const std::vector<gaussian_t> &g)
     {
+        if (device_scene && g.empty()) return;
+        device_scene = false;
         const u64 h = hash(g);
         if (scene_n == g.size() && scene_hash == h && scene_key) return;
         check(vrt_hip_set_gaussians_aos(ctx, g.size(), g.data()), "vrt_hip_set_gaussians_aos");
@@ -613,6 +616,18 @@ inline void set_ray_index(bool on)
 {
     auto &d = detail::device_t::get();
     d.check(vrt_hip_set_ray_index(d.ctx, on ? 1 : 0), "vrt_hip_set_ray_index");
+}
+// The scene from DEVICE memory (vrt_hip_set_gaussians_device in include/vrt_hip.h): d_mu [n, 3], d_albedo [n, 4] with alpha in column 3,
+// d_sigma [n], d_magnitude [n], float32; everything enqueued on hip_stream, nothing waited for (but where a buffer has to grow), the same
+// scene bit for bit as the same values uploaded from the host.  It stays the scene of every later call that is given an EMPTY
+// gaussians_t; a call with Gaussians of its own uploads those, as always.  Tile sets of the scene before are gone.
+inline void set_gaussians_device(size_t n, const f32 *d_mu, const f32 *d_albedo, const f32 *d_sigma, const f32 *d_magnitude, void *hip_stream)
+{
+    auto &d = detail::device_t::get();
+    d.check(vrt_hip_set_gaussians_device(d.ctx, n, d_mu, d_albedo, d_sigma, d_magnitude, hip_stream), "vrt_hip_set_gaussians_device");
+    d.device_scene = true;
+    d.scene_key = nullptr;
+    ++d.generation;
 }
 // ======== end of the extension ==========================================================================================
 

@@ -79,6 +79,24 @@ int vrt_hip_set_gaussians(vrt_hip_ctx *ctx, size_t n, const float *mu_x, const f
                           const float *albedo_a, const float *sigma, const float *magnitude);
 /* AoS upload == std::vector<gaussian_t> (types.h:195-200: albedo[4], mu[4], sigma, magnitude; 40 B). */
 int vrt_hip_set_gaussians_aos(vrt_hip_ctx *ctx, size_t n, const void *gaussians);
+/* The scene from DEVICE memory, for loops that keep their parameters on the GPU (an optimiser step, an animation): d_mu [n, 3],
+ * d_albedo [n, 4] with alpha in column 3, d_sigma [n], d_magnitude [n], float32, packed -- the layout of a gradient bundle's columns.
+ * The scene becomes exactly what vrt_hip_set_gaussians makes of the same values with albedo_a given: every later frame, query, bundle,
+ * gradient row, statistic and the Morton index are the same bit for bit.  Everything is enqueued on `hip_stream` -- the read of the
+ * caller's arrays, the scene tables, and the Morton index when vrt_hip_set_ray_index is on, which for such a scene is built by kernels
+ * (also by the first bundle after it is switched on) -- and the call returns without waiting for it: the caller may overwrite its
+ * arrays with later work on that stream.  Against work in flight the call is ordered like a bundle: on the stream of the last *_device
+ * call nothing waits, a change of stream waits for the other stream.  Work on the context's own stream is ordered by events.
+ * The two waits that remain:
+ *   - a buffer that has to grow is freed first, which waits for the device: a larger n than before, the first call, more temporary
+ *     storage for the index's sort.  With n unchanged no call waits;
+ *   - the host keeps one value derived from the scene, the largest finite |albedo|, which scales the frame kernels' prune budget.  After
+ *     a device update it is pending: the first frame afterwards (and vrt_hip_copy_state from this context) waits once for that update
+ *     and reads one word back.  Bundles never need it: a loop of device updates and bundles never waits.
+ * Host state changes as vrt_hip_set_gaussians changes it (caller-made tile lists are dropped, vrt_hip_state_generation advances by
+ * one).  n == 0 is legal with NULL pointers; a NULL array with n > 0, or n > 0xFFFFFFF0, is VRT_HIP_ERR_INVALID and changes nothing. */
+int vrt_hip_set_gaussians_device(vrt_hip_ctx *ctx, size_t n, const float *d_mu, const float *d_albedo, const float *d_sigma,
+                                 const float *d_magnitude, void *hip_stream);
 
 /* -------- tiling: replaces tile_gaussians + tiles_t (rt.cpp:29-69, types.h:272-287) - */
 /* On-device binning with the reference's exact inclusion test, from the camera's view
@@ -524,7 +542,8 @@ int vrt_hip_get_ray_stats(vrt_hip_ctx *ctx, vrt_hip_ray_stats *out);   /* of the
  * kernel, and rays / short_rays / long_rays / lane_entries / lane_pairs / scratch_rays of vrt_hip_ray_stats are the same numbers
  * (its chunk fields are 0 for an indexed bundle: vrt_hip_ray_index_stats below has their counterparts).
  * The index depends on the scene and cull_eps alone: it is made with the scene tables (or by the first bundle after it was switched
- * on), on the host from the centres read back, and never per bundle.  Costs 36 B per Gaussian of device memory plus one bit per
+ * on), on the host from the centres read back -- for a scene of vrt_hip_set_gaussians_device on the device, the same index -- and never
+ * per bundle.  Costs 36 B per Gaussian of device memory plus one bit per
  * Gaussian and workgroup of the one-wave-per-ray kernel.  The call waits for bundles in flight, counts as a state change
  * (vrt_hip_state_generation) and is carried over by vrt_hip_copy_state, whose mirror builds the same index. */
 int vrt_hip_set_ray_index(vrt_hip_ctx *ctx, int on);
@@ -539,6 +558,9 @@ typedef struct {
     uint64_t members_tested; /* sum over rays of the Gaussians tested one by one (members of leaves its WAVE kept)       */
 } vrt_hip_ray_index_stats;
 int vrt_hip_get_ray_index_stats(vrt_hip_ctx *ctx, vrt_hip_ray_index_stats *out); /* of the last bundle, when vrt_hip_enable_stats is on (waits for it) */
+/* Diagnostic: out[Morton position] = scene index, N words (cap = room in out).  Brings the scene tables up to date and waits for work in
+ * flight; VRT_HIP_ERR_INVALID when the index is off or not built yet (switched on after the tables: the next bundle builds it). */
+int vrt_hip_get_ray_index_perm(vrt_hip_ctx *ctx, uint32_t *out, size_t cap);
 
 /* Numeric cross-checks of rt.cpp:8-27 (transmittance_step uses fast_exp like the reference).
  * vrt_hip_transmittance_step runs the reference's float32 loop `for (t = 0; t <= s; t += delta)` per sample point, and refuses with

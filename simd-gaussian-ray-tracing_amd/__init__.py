@@ -71,6 +71,7 @@ SYMBOLS = {
     "vrt_hip_version": (C.c_char_p, []),
     "vrt_hip_set_gaussians": (C.c_int, [_vp, C.c_size_t] + [_f32p] * 9),
     "vrt_hip_set_gaussians_aos": (C.c_int, [_vp, C.c_size_t, _vp]),
+    "vrt_hip_set_gaussians_device": (C.c_int, [_vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp]),
     "vrt_hip_tile_gaussians": (C.c_int, [_vp, C.c_float, C.c_float, _f32p]),
     "vrt_hip_tile_gaussians_device": (C.c_int, [_vp, C.c_float, C.c_float, _f32p, _vp]),
     "vrt_hip_set_tiles": (C.c_int, [_vp, C.c_float, C.c_float, C.c_uint64, C.c_uint64, _u32p, _u32p]),
@@ -140,6 +141,7 @@ SYMBOLS = {
     "vrt_hip_get_ray_stats": (C.c_int, [_vp, C.POINTER(RayStats)]),
     "vrt_hip_set_ray_index": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_ray_index_stats": (C.c_int, [_vp, C.POINTER(RayIndexStats)]),
+    "vrt_hip_get_ray_index_perm": (C.c_int, [_vp, _u32p, C.c_size_t]),
     "vrt_hip_transmittance_step": (C.c_int, [_vp, _f32p, _f32p, _f32p, C.c_size_t, C.c_float, _f32p]),
     "vrt_hip_density": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p]),
     "vrt_hip_eval_erf": (C.c_int, [_vp, C.c_int, _f32p, C.c_size_t, _f32p]),
@@ -241,6 +243,7 @@ class Renderer:
                 raise VrtHipError(f"vrt_hip_create({device}) failed ({rc}): {self._L.vrt_hip_last_error(None).decode()}")
             _handle = h
         self._h = _handle
+        self.device = device if self._owned else None   # the HIP device of a context made here (a group's members: not known)
         self._host = {}   # registered host buffers by address: kept alive while the GPU may write them
         self.n = 0
         self.w = self.h = 0
@@ -289,6 +292,14 @@ class Renderer:
         self.n = len(s)
         self._chk(self._L.vrt_hip_set_gaussians(self._h, len(s), *[_fp(c) for c in cols], None if a is None else _fp(a),
                                                 _fp(s), _fp(m)), "set_gaussians")
+
+    def set_gaussians_device(self, n, d_mu, d_albedo, d_sigma, d_magnitude, stream=0):
+        """vrt_hip_set_gaussians_device: the scene from device pointers (mu [n, 3], albedo [n, 4] with alpha in column 3, sigma [n],
+        magnitude [n], float32, packed), everything enqueued on `stream` and nothing waited for: the same scene, bit for bit, as
+        set_gaussians_soa(..., alpha=...) of the same values."""
+        self._chk(self._L.vrt_hip_set_gaussians_device(self._h, int(n), d_mu or None, d_albedo or None, d_sigma or None, d_magnitude or None,
+                                                       stream or None), "set_gaussians_device")
+        self.n = int(n)
 
     # ---- tiles ----
     def tile_gaussians(self, tw, th, view):
@@ -675,6 +686,13 @@ class Renderer:
         s = RayIndexStats()
         self._chk(self._L.vrt_hip_get_ray_index_stats(self._h, C.byref(s)), "get_ray_index_stats")
         return {k: getattr(s, k) for k, _ in RayIndexStats._fields_}
+
+    def ray_index_perm(self):
+        """Diagnostic: the Morton index as perm[Morton position] = scene index, u32 [N] (waits; raises while the index is off or not
+        built): see vrt_hip_get_ray_index_perm in include/vrt_hip.h."""
+        out = np.zeros(max(self.n, 1), np.uint32)
+        self._chk(self._L.vrt_hip_get_ray_index_perm(self._h, out.ctypes.data_as(_u32p), out.size), "get_ray_index_perm")
+        return out[:self.n]
 
     def eval_erf(self, kind, x):
         x = np.ascontiguousarray(x, np.float32)

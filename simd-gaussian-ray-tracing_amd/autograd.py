@@ -22,9 +22,13 @@ pose-only fit pays for no atomic add), with no ray requiring grad the call is th
 A Gaussian whose magnitude is exactly 0 is dropped by every ray's cull and therefore receives NO gradient, magnitude.grad included
 (although the true derivative is not 0): initialise magnitudes away from 0.
 
-Known limit: the scene reaches the renderer through the HOST -- forward copies the four parameter tensors to the CPU and calls
-set_gaussians_soa, which waits for the device and rebuilds the scene tables.  A device-side scene update is not part of this
-library yet; a fitting loop pays that upload once per step.
+The scene.  Every forward REPLACES the renderer's scene by the parameters.  With all four parameter tensors on the renderer's cuda device
+it does so on the device (Renderer.set_gaussians_device): the tensors are converted with .to(float32).contiguous() there and the scene
+tables -- and the Morton index, when it is on -- are rebuilt by kernels on torch's current stream, with nothing copied to the host and
+nothing waited for (but where a buffer of the renderer has to grow: a larger scene, the first call).  A fitting loop of bundles with
+cuda parameters never blocks the host.  With any parameter tensor elsewhere (the CPU, another device) the scene goes through the host
+as before: the four tensors are copied to the CPU and set_gaussians_soa waits for the device and rebuilds the tables.  Both ways make
+the same scene, bit for bit.
 """
 import numpy as np
 import torch
@@ -33,15 +37,25 @@ from . import GRAD_STRIDE, RAY_GRAD_STRIDE, TGRAD_DEPTH, TGRAD_T, grad_columns, 
 
 
 def _upload(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs):
-    """What every forward begins with: the scene of `renderer` replaced by the parameters (through the host: the module's known limit),
-    the rays on torch's current device, and in ctx what backward needs of them.  Returns (device, origins, dirs, origin per ray)."""
+    """What every forward begins with: the scene of `renderer` replaced by the parameters (on the device when all four are on the
+    renderer's cuda device, through the host otherwise: the module's docstring), the rays on torch's current device, and in ctx what
+    backward needs of them.  Returns (device, origins, dirs, origin per ray)."""
     dev = torch.device("cuda", torch.cuda.current_device())
-    host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in (mu, albedo, sigma, magnitude)]
-    renderer.set_gaussians_soa(host[0], host[1][:, :3], host[2], host[3], alpha=np.ascontiguousarray(host[1][:, 3]))
+    params = (mu, albedo, sigma, magnitude)
+    if getattr(renderer, "device", None) == dev.index and all(t.device == dev for t in params):
+        # (the converted tensors may be temporaries: torch hands their memory on in stream order, behind the kernels that read them)
+        m, a, s, g = (t.detach().to(torch.float32).contiguous() for t in params)
+        n = s.numel()
+        assert m.numel() == 3 * n and a.numel() == 4 * n and g.numel() == n
+        renderer.set_gaussians_device(n, m.data_ptr(), a.data_ptr(), s.data_ptr(), g.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+    else:
+        host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in params]
+        renderer.set_gaussians_soa(host[0], host[1][:, :3], host[2], host[3], alpha=np.ascontiguousarray(host[1][:, 3]))
+        n = len(host[2])
     o = origins.detach().to(dev, torch.float32).contiguous()
     d = dirs.detach().to(dev, torch.float32).contiguous().reshape(-1, 3)
     per_ray = o.numel() != 3
-    ctx.renderer, ctx.rays, ctx.n = renderer, (o, d, per_ray), len(host[2])
+    ctx.renderer, ctx.rays, ctx.n = renderer, (o, d, per_ray), n
     ctx.ray_like = (origins, dirs)
     ctx.devices = [t.device for t in (mu, albedo, sigma, magnitude)]
     ctx.dtypes = [t.dtype for t in (mu, albedo, sigma, magnitude)]
@@ -106,7 +120,7 @@ class _RadianceRays(torch.autograd.Function):
 def radiance_rays(renderer, mu, albedo, sigma, magnitude, origins, dirs):
     """Radiance [nrays, 4] (a cuda tensor on torch's current device and stream) of the rays through the scene of the four parameter
     tensors mu [N, 3], albedo [N, 4], sigma [N], magnitude [N], differentiable in those four and in the rays.  origins: [3] or
-    [nrays, 3]; dirs: [nrays, 3], unit length (its gradient is the tangential one: see the module's docstring).  The scene of `renderer` is REPLACED by the parameters, through the host (see the module's docstring);
+    [nrays, 3]; dirs: [nrays, 3], unit length (its gradient is the tangential one: see the module's docstring).  The scene of `renderer` is REPLACED by the parameters (see the module's docstring);
     backward must run before the renderer's scene or options change again."""
     return _RadianceRays.apply(renderer, mu, albedo, sigma, magnitude, origins, dirs)
 

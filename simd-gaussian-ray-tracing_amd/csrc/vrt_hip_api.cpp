@@ -87,6 +87,20 @@ int rebuild_tables(vrt_hip_ctx *c)
     return VRT_HIP_OK;
 }
 
+// albedo_scale of a scene set from device memory: one word, read once behind the event recorded at that update
+int resolve_albedo_scale(vrt_hip_ctx *c)
+{
+    if (!c->albedo_pending) return VRT_HIP_OK;
+    HIPCHK(c, hipEventSynchronize(c->scene_done));
+    uint32_t bits = 0;
+    HIPCHK(c, hipMemcpy(&bits, c->scene_words.p + 6, sizeof bits, hipMemcpyDeviceToHost));
+    float v;
+    memcpy(&v, &bits, sizeof v);
+    c->albedo_scale = std::max(1.f, v);
+    c->albedo_pending = false;
+    return VRT_HIP_OK;
+}
+
 SceneTables tables(const vrt_hip_ctx *c)
 {
     SceneTables s;
@@ -328,6 +342,8 @@ int vrt_hip_create(int device, vrt_hip_ctx **out)
     c->ray_index = c->tune.ray_index;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
+        hipEventCreateWithFlags(&c->scene_order, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->scene_done, hipEventDisableTiming) != hipSuccess ||
         c->d_stats.reserve(STAT_WORDS) != hipSuccess) {
         vrt_hip_destroy(c);
         return fail(nullptr, VRT_HIP_ERR_HIP, "create: stream/event creation failed");
@@ -346,6 +362,8 @@ void vrt_hip_destroy(vrt_hip_ctx *c)
     for (auto &e : c->tev) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->scene_order) (void)hipEventDestroy(c->scene_order);
+    if (c->scene_done) (void)hipEventDestroy(c->scene_done);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c; // the buffers free themselves
 }
@@ -370,6 +388,7 @@ int vrt_hip_set_gaussians(vrt_hip_ctx *c, size_t n, const float *mu_x, const flo
     c->has_alpha = aa != nullptr;
     // the cull bounds count a dropped Gaussian's emission at albedo <= 1 (the reference's range): brighter scenes shrink the prune's budget
     c->albedo_scale = 1.f;
+    c->albedo_pending = false; c->scene_on_device = false;
     for (int ch = 3; ch <= 6; ++ch)
         if (src[ch])
             for (size_t i = 0; i < n; ++i) { const float v = fabsf(src[ch][i]); if (v > c->albedo_scale && v < INFINITY) c->albedo_scale = v; }
@@ -401,6 +420,54 @@ int vrt_hip_set_gaussians_aos(vrt_hip_ctx *c, size_t n, const void *gaussians)
                                  soa[5].data(), soa[6].data(), soa[7].data(), soa[8].data());
 }
 
+// The scene from device memory: what vrt_hip_set_gaussians and the table build of rebuild_tables do, as kernels on the caller's stream
+// and with no wait (include/vrt_hip.h has the contract).  Work of the context's own stream is ordered by two events, never by the host.
+int vrt_hip_set_gaussians_device(vrt_hip_ctx *c, size_t n, const float *d_mu, const float *d_albedo, const float *d_sigma,
+                                 const float *d_magnitude, void *hip_stream)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    if (n > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "set_gaussians_device: too many Gaussians");
+    if (n && (!d_mu || !d_albedo || !d_sigma || !d_magnitude)) return fail(c, VRT_HIP_ERR_INVALID, "set_gaussians_device: NULL array");
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    wait_for_last_stream(c, st); // frames and bundles in flight on another stream read what this rewrites
+    c->last_stream = st;
+    HIPCHK(c, hipEventRecord(c->scene_order, c->stream)); // ... and so may work on the context's own stream
+    HIPCHK(c, hipStreamWaitEvent(st, c->scene_order, 0));
+    // (a buffer that grows is freed first, which waits for the device: nothing in flight loses its memory)
+    SceneColumns cols;
+    for (int i = 0; i < 9; ++i) { HIPCHK(c, c->soa[i].reserve(n)); cols.c[i] = c->soa[i].p; }
+    HIPCHK(c, c->mu_sig.reserve(n)); HIPCHK(c, c->gA.reserve(n)); HIPCHK(c, c->gB.reserve(n));
+    HIPCHK(c, c->gC.reserve(n)); HIPCHK(c, c->gD.reserve(n)); HIPCHK(c, c->iota.reserve(n));
+    HIPCHK(c, c->gChunk.reserve((n + 63u) / 64u));
+    HIPCHK(c, c->scene_words.reserve(8));
+    HIPCHK(c, hipMemsetAsync(c->scene_words.p + 6, 0, sizeof(uint32_t), st));
+    const uint32_t un = (uint32_t)n;
+    launch_ingest_scene(un, d_mu, d_albedo, d_sigma, d_magnitude, cols, c->scene_words.p + 6, st);
+    const float eps_eff = c->cull_eps * std::min(1.f, 4096.f / (float)std::max(un, 1u)); // as rebuild_tables
+    launch_build_static(un, c->soa[0].p, c->soa[1].p, c->soa[2].p, c->soa[3].p, c->soa[4].p, c->soa[5].p, c->soa[6].p, c->soa[7].p,
+                        c->soa[8].p, eps_eff, exp_floor_x(c->exp_kind), c->mu_sig.p, c->gB.p, c->gC.p, c->gD.p, st);
+    launch_build_chunks(un, c->mu_sig.p, c->gB.p, c->gChunk.p, st);
+    launch_iota(c->iota.p, un, st);
+    HIPCHK(c, hipGetLastError());
+    c->has_alpha = true;
+    c->n = un;
+    c->scene_on_device = true;
+    ++c->state_gen;
+    c->reset_seq = c->frame_seq;
+    c->tables_dirty = false; // built eagerly; a later change of cull_eps or the Exp kind rebuilds them from soa, as after any setter
+    c->ray_index_dirty = true;
+    c->gA_valid = false;
+    c->lists_dirty = true;
+    if (c->tile_mode == TILES_HOST) { untile(c); c->shard_dirty = true; }
+    c->ref_valid = false;
+    if (c->ray_index) { int rc = build_ray_index_device(c, st); if (rc) return rc; }
+    c->albedo_pending = true; // the word is read by the first call that needs albedo_scale (resolve_albedo_scale)
+    HIPCHK(c, hipEventRecord(c->scene_done, st));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->scene_done, 0)); // queries and frames on the context's stream see this scene
+    return VRT_HIP_OK;
+}
+
 uint64_t vrt_hip_state_generation(const vrt_hip_ctx *c) { return c ? c->state_gen : 0; }
 
 int vrt_hip_get_image_size(const vrt_hip_ctx *c, uint32_t *w, uint32_t *h)
@@ -418,11 +485,14 @@ int vrt_hip_copy_state(vrt_hip_ctx *dst, const vrt_hip_ctx *src)
     HIPCHK(dst, hipSetDevice(dst->device));
     { int rc = quiesce(dst); if (rc) return rc; }
     HIPCHK(dst, hipStreamSynchronize(src->stream)); // uploads of the source are synchronous, its table build runs on its stream
+    // a source set from device memory: its columns are there once its update is done, and so is the word albedo_scale is read from
+    if (resolve_albedo_scale(const_cast<vrt_hip_ctx *>(src))) return fail(dst, VRT_HIP_ERR_HIP, "copy_state: " + src->err);
     for (int i = 0; i < 9; ++i) {
         HIPCHK(dst, dst->soa[i].reserve(src->n));
         if (src->n && src->soa[i].p) HIPCHK(dst, hipMemcpy(dst->soa[i].p, src->soa[i].p, (size_t)src->n * sizeof(float), hipMemcpyDeviceToDevice));
     }
     dst->has_alpha = src->has_alpha; dst->n = src->n; dst->albedo_scale = src->albedo_scale;
+    dst->albedo_pending = false; dst->scene_on_device = false;
     dst->exp_kind = src->exp_kind; dst->erf_kind = src->erf_kind; dst->cull_eps = src->cull_eps; dst->cull_prune = src->cull_prune;
     dst->table_hx = src->table_hx; dst->table_budget = src->table_budget; dst->tune.table_adapt = src->tune.table_adapt; dst->tune.table_room = src->tune.table_room;
     dst->rank = src->rank; dst->world = src->world;

@@ -95,6 +95,13 @@ struct vrt_hip_ctx {
     DevBuf<uint32_t> iota;
     bool tables_dirty = true;
     bool gA_valid = false;
+    // A scene set from device memory (vrt_hip_set_gaussians_device): everything above was filled by kernels on the caller's stream.
+    // scene_words: [0..5] the Morton box of the index build, [6] the bits of the scene's largest finite |albedo| above 1 (0: none), which
+    // the host has not read while albedo_pending; scene_done is recorded behind the update, scene_order ahead of it on the context's stream.
+    bool scene_on_device = false; // the index of this scene is built on the device
+    DevBuf<uint32_t> scene_words;
+    bool albedo_pending = false;
+    hipEvent_t scene_order = nullptr, scene_done = nullptr;
     float gA_origin[3] = { 0, 0, 0 };
 
     // tiles.  "ref" lists carry the reference semantics (tiles_t): uploaded by the caller (TILES_HOST), one
@@ -254,6 +261,10 @@ struct vrt_hip_ctx {
     DevBuf<uint32_t> ri_perm;     // Morton position -> scene index
     DevBuf<float4> ri_mu_sig, ri_gB, ri_leaves, ri_groups; // permuted rows, spheres over 64 positions, spheres over 64 leaves
     DevBuf<uint32_t> ri_bitmap;   // the long kernel's bitmaps, ceil(n / 32) words per workgroup: zeroed when it grows, left all zero by every bundle
+    DevBuf<uint32_t> ri_keys;     // the device build's keys, unsorted and sorted (2 n)
+    DevBuf<unsigned char> ri_sort_tmp; // ... and its sort's temporary storage, ri_sort_bytes for a scene of ri_sort_n: grows only
+    uint32_t ri_sort_n = 0xFFFFFFFFu;
+    size_t ri_sort_bytes = 0;
     bool ray_indexed_last = false; // the last bundle went through the index
     uint32_t ri_last_leaves = 0, ri_last_groups = 0; // ... over this many leaves and groups
     DevBuf<unsigned long long> d_stats, d_timeline; // d_timeline: VRT_HIP_TIMELINE diagnostics
@@ -285,6 +296,8 @@ void wait_for_last_stream(vrt_hip_ctx *c, hipStream_t st); // before work on `st
 int check_ready(vrt_hip_ctx *c);
 int rebuild_tables(vrt_hip_ctx *c);
 int build_ray_index(vrt_hip_ctx *c); // vrt_hip_rays.cpp: the tables are built and nothing is in flight
+int build_ray_index_device(vrt_hip_ctx *c, hipStream_t st); // vrt_hip_rays.cpp: the same index behind the table build on `st`, nothing waited for
+int resolve_albedo_scale(vrt_hip_ctx *c); // albedo_scale of a scene set from device memory, read back once (waits for that update)
 int rebuild_shard(vrt_hip_ctx *c);
 vrtk::SceneTables tables(const vrt_hip_ctx *c);
 vrtk::TileLists tile_geometry(const vrt_hip_ctx *c);

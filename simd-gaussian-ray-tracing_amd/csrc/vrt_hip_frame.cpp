@@ -293,6 +293,7 @@ int plan_frame(vrt_hip_ctx *c, const float origin[3], int pack_flags, uint32_t *
     if (geo.tile_w == 0 || geo.tile_h == 0) return fail(c, VRT_HIP_ERR_INVALID, "render: tile size is 0 pixels");
     const bool use_shard = c->world > 1 || out_mode != OUT_RASTER; // compact and sparse targets hold this rank's tiles only
     if ((rc = rebuild_tables(c))) return rc; // (waits for everything in flight itself, and forgets the last stream: before the hand-over)
+    if ((rc = resolve_albedo_scale(c))) return rc; // the first frame of a scene set from device memory waits for one word: the prune budget needs it
     wait_for_last_stream(c, st);
     c->last_stream = st;
     if (t0) HIPCHK(c, hipEventRecord(t0, st));

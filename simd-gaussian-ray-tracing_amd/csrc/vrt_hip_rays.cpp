@@ -81,7 +81,10 @@ int enqueue_bundle(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int ori
     const bool indexed = c->ray_index;
     if (indexed && c->ray_index_dirty) { // switched on after the tables were made
         { int rc = quiesce(c); if (rc) return rc; }
-        { int rc = build_ray_index(c); if (rc) return rc; }
+        if (c->scene_on_device) { // its tables were made on the device: so is its index, on the context's stream like the host's build
+            { int rc = build_ray_index_device(c, c->stream); if (rc) return rc; }
+            HIPCHK(c, hipStreamSynchronize(c->stream)); // bundles may use a caller's stream
+        } else { int rc = build_ray_index(c); if (rc) return rc; }
     }
     wait_for_last_stream(c, st); // a bundle in flight on another stream uses the queue and the scratch slots
     c->last_stream = st;
@@ -160,6 +163,31 @@ int build_ray_index(vrt_hip_ctx *c)
     launch_build_ray_groups(nleaves, c->ri_leaves.p, c->ri_groups.p, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream)); // bundles may use a caller's stream
+    c->ray_index_dirty = false;
+    return VRT_HIP_OK;
+}
+
+// The same index built on the device, behind the table build on `st` and with nothing waited for (vrt_scene_kernel.hip): serves a scene
+// set from device memory.  A buffer that grows is freed first, which waits for the device -- a larger scene, the first build, more
+// temporary storage for the sort; with the scene's size unchanged nothing waits.
+int build_ray_index_device(vrt_hip_ctx *c, hipStream_t st)
+{
+    const uint32_t n = c->n, nleaves = (n + 63u) / 64u, ngroups = (nleaves + 63u) / 64u;
+    if (c->ri_sort_n != n) {
+        c->ri_sort_bytes = morton_sort_bytes(n);
+        if (!c->ri_sort_bytes) return fail(c, VRT_HIP_ERR_HIP, "ray index: the sort's storage query failed");
+        c->ri_sort_n = n;
+    }
+    HIPCHK(c, c->ri_perm.reserve(n)); HIPCHK(c, c->ri_mu_sig.reserve(n)); HIPCHK(c, c->ri_gB.reserve(n));
+    HIPCHK(c, c->ri_leaves.reserve(nleaves)); HIPCHK(c, c->ri_groups.reserve(ngroups));
+    HIPCHK(c, c->ri_keys.reserve((size_t)n * 2)); HIPCHK(c, c->ri_sort_tmp.reserve(c->ri_sort_bytes));
+    HIPCHK(c, c->scene_words.reserve(8));
+    HIPCHK(c, launch_morton_index(n, c->mu_sig.p, c->gB.p, c->iota.p, c->scene_words.p, c->ri_keys.p, c->ri_sort_tmp.p, c->ri_sort_bytes,
+                                  c->ri_perm.p, c->ri_mu_sig.p, c->ri_gB.p, st));
+    launch_build_chunks(n, c->ri_mu_sig.p, c->ri_gB.p, c->ri_leaves.p, st);
+    launch_morton_open_leaves(n, c->ri_mu_sig.p, c->ri_gB.p, c->ri_leaves.p, st);
+    launch_build_ray_groups(nleaves, c->ri_leaves.p, c->ri_groups.p, st);
+    HIPCHK(c, hipGetLastError());
     c->ray_index_dirty = false;
     return VRT_HIP_OK;
 }
@@ -465,6 +493,18 @@ int vrt_hip_get_ray_index_stats(vrt_hip_ctx *c, vrt_hip_ray_index_stats *out)
     HIPCHK(c, hipMemcpy(w, c->ray_stats.p + RAY_STATS_WORDS, sizeof(w), hipMemcpyDeviceToHost));
     out->indexed = 1; out->groups = c->ri_last_groups; out->leaves = c->ri_last_leaves;
     out->groups_tested = w[0]; out->groups_kept = w[1]; out->leaves_tested = w[2]; out->leaves_kept = w[3]; out->members_tested = w[4];
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_get_ray_index_perm(vrt_hip_ctx *c, uint32_t *out, size_t cap)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = rebuild_tables(c); if (rc) return rc; }
+    if (!c->ray_index || c->ray_index_dirty) return fail(c, VRT_HIP_ERR_INVALID, "get_ray_index_perm: the index is off or not built yet");
+    if (c->n && (!out || cap < c->n)) return fail(c, VRT_HIP_ERR_INVALID, "get_ray_index_perm: buffer too small");
+    { int rc = quiesce(c); if (rc) return rc; } // waits for the build
+    if (c->n) HIPCHK(c, hipMemcpy(out, c->ri_perm.p, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return VRT_HIP_OK;
 }
 

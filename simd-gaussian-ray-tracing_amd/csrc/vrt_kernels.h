@@ -366,6 +366,20 @@ void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool ind
 // group spheres of the Morton index: one per 64 consecutive leaf spheres, bounding them
 void launch_build_ray_groups(uint32_t nleaves, const float4 *leaves, float4 *groups, hipStream_t st);
 
+// a scene set from device memory (vrt_scene_kernel.hip)
+struct SceneColumns { float *c[9]; }; // mu_x mu_y mu_z ar ag ab aa sigma mag
+// the caller's packed rows (mu [n, 3], albedo [n, 4] with alpha in column 3, sigma [n], mag [n]) into the nine columns; *albedo_bits
+// (cleared on the stream before) = max(itself, bits of the largest finite |albedo| above 1)
+void launch_ingest_scene(uint32_t n, const float *mu, const float *albedo, const float *sigma, const float *mag, const SceneColumns &out,
+                         uint32_t *albedo_bits, hipStream_t st);
+// The Morton index on the device, morton_order's permutation exactly: perm[Morton position] = scene index and the rows of mu_sig / gB in
+// that order.  box: 6 words of scratch; keys: 2 n words; sort_tmp: morton_sort_bytes(n) bytes (0: the query failed); iota: 0 .. n - 1.
+size_t morton_sort_bytes(uint32_t n);
+hipError_t launch_morton_index(uint32_t n, const float4 *mu_sig, const float4 *gB, const uint32_t *iota, uint32_t *box, uint32_t *keys,
+                               void *sort_tmp, size_t sort_bytes, uint32_t *perm, float4 *mu_sig_m, float4 *gB_m, hipStream_t st);
+// after launch_build_chunks over the permuted rows: a NaN radius for every leaf with a member that is not finite (build_ray_index's rule)
+void launch_morton_open_leaves(uint32_t n, const float4 *mu_sig_m, const float4 *gB_m, float4 *leaves, hipStream_t st);
+
 // point queries
 void launch_transmittance(const SceneTables &s, const float o[3], const float n[3], const float *d_s, size_t ns,
                           float *d_T, int exp_kind, int erf_kind, hipStream_t st);

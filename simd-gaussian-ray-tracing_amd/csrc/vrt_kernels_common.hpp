@@ -7,6 +7,7 @@
 //   vrt_ray_grad_kernel.hip   gradient bundles: d(radiance) / d(Gaussians) along such rays
 //   vrt_ray_trans_grad_kernel.hip  transmittance gradient bundles: d(T) / d(Gaussians, samples) and d(depth) / d(Gaussians, levels) (all five over vrt_ray_cull.hpp)
 //   vrt_kernels.hip        the frame's set-up: scene tables, tile cones, list kernels
+//   vrt_scene_kernel.hip   a scene set from device memory: the ingest kernel, the Morton index built on the device
 //   vrt_assembly_kernel.hip, vrt_query_kernel.hip, vrt_host_frame.hip   frame assembly, point queries, host delivery (tile_pixel)
 // Hand-written for gfx950 (CDNA4, wave64).  No MFMA: the path is VALU + quarter-rate transcendental bound (one v_rcp_f32 per
 // Abramowitz-Stegun erf term); Gaussian parameters reach the inner loops through LDS rows or wave-uniform scalar loads.

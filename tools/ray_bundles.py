@@ -56,6 +56,14 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
       <out-dir>/ray_grad_rays_existing.json ({"parent": {"grad": .., "tgrad": ..}, "new": {..}, optionally "parent_again": {..}}: the
       results of `--grad-only` and `--tgrad-only` on the commit before the ray rows and on this one, same machine, same session), <out-dir>/ray_grad_rays_pose_fit.json
       (the line of tools/pose_fit.py) and <out-dir>/ray_grad_rays_resources.txt (tools/kernel_resources.sh raygrad and raytgrad on both).
+  (su) scene updates (vrt_hip_set_gaussians_device): one fitting step -- forward and backward of autograd.radiance_rays on `-g 64` -- with
+      the four parameter tensors on the CPU (the scene goes through the host: the path before the device setter, measured alongside) and
+      with them on the GPU (the scene is set from device memory), on 4096 aimed rays and on 2^20 scattered rays, Morton index off and on;
+      host clock around windows of steps that end in a synchronise, the two kinds alternating, after warm-up.  Also the setter alone
+      (stream events around calls enqueued back to back) and the host time one call of it takes (enqueue only; the window is
+      synchronised afterwards).  The step with cuda parameters has to be faster than the step with CPU parameters in every row; the
+      ratio and the setter's times are recorded, not asserted.  `--scene-update-only` runs this part alone, prints its JSON line and
+      writes scene_update.json and scene_update.md (and nothing else) to --out-dir.
 """
 import argparse
 import json
@@ -579,6 +587,90 @@ final {pose['loss'][-1]:.4e}
     return "\n".join(lines)
 
 
+def part_scene(g, repeats=7, warm=2):
+    import torch
+    from sgrt_amd import autograd
+    st = torch.cuda.current_stream().cuda_stream
+    p = {"mu": g["mu"][:, :3], "albedo": g["albedo"], "sigma": g["sigma"], "magnitude": g["magnitude"]}
+    order = ("mu", "albedo", "sigma", "magnitude")
+    rows = {}
+    for label, (o, d), steps in (("aimed_4096", aimed_rays(g), 20), ("scattered_2^20", scattered(g, 1 << 20), 3)):
+        nrays = len(d)
+        t_o, t_d = torch.from_numpy(np.ascontiguousarray(o, f32)).cuda(), torch.from_numpy(np.ascontiguousarray(d, f32)).cuda()
+        t_w = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, size=(nrays, 4)).astype(f32)).cuda()
+        for on in (0, 1):
+            r = pkg.Renderer(0)
+            r.set_ray_index(on)
+            params = {where: [torch.tensor(np.ascontiguousarray(p[k], f32), device=where, requires_grad=True) for k in order] for where in ("cpu", "cuda")}
+
+            def step(where):
+                ps = params[where]
+                for t in ps:
+                    t.grad = None
+                (autograd.radiance_rays(r, *ps, t_o, t_d) * t_w).sum().backward()
+
+            def window(where):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    step(where)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3 / steps
+            for _ in range(warm):
+                window("cpu"), window("cuda")
+            ms_step = {"cpu": [], "cuda": []}
+            for _ in range(repeats):
+                for where in ("cpu", "cuda"):
+                    ms_step[where].append(window(where))
+            grads = {where: [t.grad.detach().cpu().numpy().astype(np.float64) for t in params[where]] for where in params}
+            scale = max(float(np.abs(a).max()) for a in grads["cpu"])
+            diff = max(float(np.abs(a - b).max()) for a, b in zip(grads["cpu"], grads["cuda"]))
+            dev = [t.detach().contiguous() for t in params["cuda"]]
+            ptrs = [t.data_ptr() for t in dev]
+            setter = windows([lambda: r.set_gaussians_device(len(g), *ptrs, stream=st)], 20, repeats, warm=3)[0]
+            enqueue = []
+            for _ in range(repeats):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(20):
+                    r.set_gaussians_device(len(g), *ptrs, stream=st)
+                enqueue.append((time.perf_counter() - t0) * 1e3 / 20)
+                torch.cuda.synchronize()
+            r.close()
+            host, device = spread(ms_step["cpu"]), spread(ms_step["cuda"])
+            rows[f"{label} index {'on' if on else 'off'}"] = {
+                "rays": nrays, "index": on, "steps_per_window": steps, "step_cpu_parameters_ms": host, "step_cuda_parameters_ms": device,
+                "host_over_device": round(host["median"] / device["median"], 2), "setter_ms": setter, "setter_enqueue_host_ms": spread(enqueue),
+                "largest_gradient": scale, "largest_gradient_difference_between_the_paths": diff}
+    return {"gaussians": len(g), "rows": rows}
+
+
+def check_scene(z):
+    for label, r in z["rows"].items():
+        assert r["step_cuda_parameters_ms"]["median"] < r["step_cpu_parameters_ms"]["median"], \
+            f"{label}: the fitting step with cuda parameters has to be faster than the step with CPU parameters of the same run"
+
+
+def markdown_scene(z):
+    lines = [f"""# Scene updates from device memory (tools/ray_bundles.py --scene-update-only)
+
+`-g 64` ({z['gaussians']} Gaussians).  One fitting step = forward + backward of `autograd.radiance_rays`.  With the four parameter
+tensors on the CPU the scene reaches the renderer through the host (`set_gaussians_soa`: the path before
+`vrt_hip_set_gaussians_device`, measured alongside); with them on the GPU it is set from device memory.  Host clock around windows of
+steps that end in a synchronise, the two kinds alternating in the same process, after warm-up; ms per step, median (min .. max).  The
+setter alone: stream events around 20 calls enqueued back to back; its enqueue: host clock around 20 calls, nothing waited for.  The
+only condition: the step with cuda parameters is faster in every row.  The parameter gradients of the two paths differ by float
+atomic order only (last column: largest difference / largest gradient).
+
+| bundle | rays | step, CPU parameters | step, cuda parameters | CPU / cuda | setter alone | setter, host time per call | gradient difference |
+|---|---|---|---|---|---|---|---|"""]
+    for label, r in z["rows"].items():
+        lines.append(f"| {label} | {r['rays']} | {ms(r['step_cpu_parameters_ms'])} | {ms(r['step_cuda_parameters_ms'])} | {r['host_over_device']} | "
+                     f"{ms(r['setter_ms'])} | {ms(r['setter_enqueue_host_ms'])} | "
+                     f"{r['largest_gradient_difference_between_the_paths']:.3g} / {r['largest_gradient']:.3g} |")
+    return "\n".join(lines) + "\n"
+
+
 def windows(fns, calls, repeats, warm=3):
     """ms per call of each fn: `repeats` windows of `calls` back-to-back calls between two stream events, the fns alternating."""
     import torch
@@ -772,8 +864,20 @@ def main():
     ap.add_argument("--grad-only", action="store_true")
     ap.add_argument("--tgrad-only", action="store_true")
     ap.add_argument("--rgrad-only", action="store_true")
+    ap.add_argument("--scene-update-only", action="store_true")
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
+    if a.scene_update_only:
+        z = part_scene(g)
+        print(json.dumps({"scene_update": z}))
+        os.makedirs(a.out_dir, exist_ok=True)
+        with open(os.path.join(a.out_dir, "scene_update.json"), "w") as f:
+            f.write(json.dumps({"what": "a fitting step with CPU-resident and with cuda-resident parameters, and the device setter alone; see tools/ray_bundles.py (su)",
+                                "scene_update": z}) + "\n")
+        with open(os.path.join(a.out_dir, "scene_update.md"), "w") as f:
+            f.write(markdown_scene(z))
+        check_scene(z)
+        return
     if a.transmittance_only:
         t = part_t(g)
         print(json.dumps({"t": t}))
