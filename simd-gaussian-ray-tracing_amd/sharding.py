@@ -302,7 +302,10 @@ class SparseFrameGatherer:
         import torch
         frames = self.shard[b].view(self.F, self.words)[:nf]
         prefix = self.P + int(cells) * CELL * CELL
-        send = frames[:, :prefix].contiguous()
+        # a copy of its own, always: a prefix that is the whole buffer, or any prefix of a batch of one frame, is contiguous as it lies, and
+        # .contiguous() would hand the collective the shard buffer itself -- which a render stream that waits for sent[b] alone overwrites
+        # while the collective still reads it
+        send = frames[:, :prefix].clone(memory_format=torch.contiguous_format)
         if send.is_cuda:                                               # the shard buffer may be rendered into again after this
             self.sent[b] = torch.cuda.Event()
             self.sent[b].record()
