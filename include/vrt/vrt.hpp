@@ -617,6 +617,30 @@ inline void set_ray_index(bool on)
     auto &d = detail::device_t::get();
     d.check(vrt_hip_set_ray_index(d.ctx, on ? 1 : 0), "vrt_hip_set_ray_index");
 }
+// Gradient bundles build their table without float atomics from the next call on: bit for bit reproducible, summed in a documented
+// order (vrt_hip_set_grad_ordered in include/vrt_hip.h: off by default; an ordered call waits once for its stream).
+inline void set_grad_ordered(bool on)
+{
+    auto &d = detail::device_t::get();
+    d.check(vrt_hip_set_grad_ordered(d.ctx, on ? 1 : 0), "vrt_hip_set_grad_ordered");
+}
+// The records the last ordered gradient bundle reduced its table from, in consumed order (vrt_hip_get_grad_records): record i is
+// rows[9 * i .. 9 * i + 8] = columns 0..8 of the table, the share of ray[i] in the row of Gaussian gauss[i].  Waits for the call.
+struct grad_records_t {
+    std::vector<u32> gauss, ray;
+    std::vector<f32> rows;
+};
+inline grad_records_t grad_records()
+{
+    auto &d = detail::device_t::get();
+    grad_records_t out;
+    size_t n = 0;
+    const int rc = vrt_hip_get_grad_records(d.ctx, nullptr, nullptr, nullptr, 0, &n);
+    if (n == 0) { d.check(rc, "vrt_hip_get_grad_records"); return out; }
+    out.gauss.resize(n); out.ray.resize(n); out.rows.resize(n * 9);
+    d.check(vrt_hip_get_grad_records(d.ctx, out.gauss.data(), out.ray.data(), out.rows.data(), n, &n), "vrt_hip_get_grad_records");
+    return out;
+}
 // The scene from DEVICE memory (vrt_hip_set_gaussians_device in include/vrt_hip.h): d_mu [n, 3], d_albedo [n, 4] with alpha in column 3,
 // d_sigma [n], d_magnitude [n], float32; everything enqueued on hip_stream, nothing waited for (but where a buffer has to grow), the same
 // scene bit for bit as the same values uploaded from the host.  It stays the scene of every later call that is given an EMPTY

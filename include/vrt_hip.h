@@ -437,7 +437,8 @@ int vrt_hip_depth_bundle(vrt_hip_ctx *ctx, size_t nrays, const float *origins, i
  * approximations have jumps).  The gradient with respect to the rays themselves is the _rays form's, below.
  * The _device form ADDS into d_grad (N rows of VRT_HIP_GRAD_STRIDE floats, N = Gaussians of the scene) with float atomics: the
  * caller clears the table, and may let several bundles add into it.  A row of a Gaussian that no ray keeps is not written at all.
- * The sums depend on the arrival order of the atomic adds: results are NOT bitwise reproducible from run to run.  d_grad_radiance
+ * The sums depend on the arrival order of the atomic adds: results are NOT bitwise reproducible from run to run, unless
+ * vrt_hip_set_grad_ordered (below) is on.  d_grad_radiance
  * is 16-byte aligned, as d_radiance of vrt_hip_radiance_rays_device.  The host form overwrites grad_out (columns 9..11 with 0).
  * Everything else is the radiance bundle's: origins, origin_per_ray, dirs, the stream rules, the buffers that only grow, the shared
  * queue / counters / scratch slots / bitmap, the Morton index (the same kept lists either way), "counts as a frame in flight";
@@ -469,7 +470,7 @@ int vrt_hip_radiance_rays_grad(vrt_hip_ctx *ctx, size_t nrays, const float *orig
  * samples with zeros.  Other values that are not finite propagate as the arithmetic makes them.
  * Columns 0..3 (albedo: T does not depend on it) and 9..11 of the table are never touched, nor the rows of Gaussians that no ray
  * keeps: one table may collect a radiance gradient and a mask or depth gradient.  The _device form ADDS into d_grad with float
- * atomics (not bitwise reproducible) and STORES d_grad_s; either may be NULL, not both.  The host form overwrites grad_out (N rows,
+ * atomics (not bitwise reproducible unless vrt_hip_set_grad_ordered, below, is on) and STORES d_grad_s; either may be NULL, not both.  The host form overwrites grad_out (N rows,
  * untouched entries 0) and grad_s_out.  Exp and Erf of the forward quantities are the selected pair's, the derivatives the analytic
  * ones; supported pairs as above: {vcl_exp, expf} x {A&S erf, erff}.  The gradient with respect to the rays is the _rays form's, below.
  * Everything else is the gradient bundle's contract: origins, origin_per_ray, dirs, the stream rules, the buffers that only grow, the
@@ -498,7 +499,8 @@ int vrt_hip_transmittance_bundle_grad(vrt_hip_ctx *ctx, size_t nrays, const floa
  * The rows are STORED, never added: every ray r < nrays gets a row, a ray that keeps nothing one of exact zeros, and nothing behind
  * row nrays - 1 is written.  No atomic add takes part in them: a ray's row is summed in the order of its kept list (one wave per ray: in
  * the fixed order of the wave's lanes), so the ray rows ARE bitwise reproducible -- from run to run, with the Morton index on or off,
- * with or without the table, host or device form -- while the table is not.  d_grad_rays is 16-byte aligned.
+ * with or without the table, host or device form -- while the table is not, unless vrt_hip_set_grad_ordered (below) is on.
+ * d_grad_rays is 16-byte aligned.
  * d_grad / grad_out may be NULL: then no atomic add is issued at all (a pose-only fit).  d_grad_rays / grad_rays_out may be NULL: then
  * the call is the form above without _rays.  At least one output must be non-NULL: VRT_HIP_ERR_INVALID with the bundle kind's message
  * otherwise.  In depth mode a sample that contributes nothing to the table contributes nothing to the ray's row.  Everything else --
@@ -519,6 +521,50 @@ int vrt_hip_transmittance_bundle_grad_rays(vrt_hip_ctx *ctx, size_t nrays, const
                                            const float *s, size_t ns, int s_per_ray, const float *grad_T, int wrt,
                                            float *grad_out /* N rows, OVERWRITTEN, or NULL */, float *grad_s_out /* nrays * ns, or NULL */,
                                            float *grad_rays_out /* nrays rows, or NULL */);
+/* -------- ordered gradient tables: reproducible bits, no float atomics --------------------------------------------------------------
+ * Off by default (first value from VRT_HIP_GRAD_ORDERED=0|1 at vrt_hip_create).  With on != 0 all eight gradient entry points above
+ * that are given a table (d_grad / grad_out) build it without a single float atomic add, into the table or into any staging memory,
+ * and the table is a function of (rays, their order, inputs, scene, options, the table's contents before) alone: bit for bit the same
+ * from run to run, with the Morton index on or off, host or device form, with or without ray rows or statistics, on any stream.  No
+ * signature changes; ray rows, grad_s and every statistic of vrt_hip_get_ray_stats / vrt_hip_get_ray_index_stats are what the same
+ * call gives with the switch off, bit for bit and field for field.  A call without a table (ray rows or grad_s alone) is the call above.
+ * What an ordered call enqueues on the caller's stream:
+ *   1. count   the cull alone: the length of every ray's kept list;
+ *   2. place   every ray gets a range of records -- one per kept Gaussian, two for a ray of the radiance gradient that keeps more than
+ *              32 -- by an exclusive scan in ray order.  The total goes to the host: AN ORDERED CALL WAITS ONCE HERE for its stream (the
+ *              sort takes its size on the host and the record buffers may have to grow), also in the _device forms, which therefore
+ *              cannot be captured into a graph; with the switch off no _device form ever waits.  A total above 2^32 - 1 records is
+ *              refused with VRT_HIP_ERR_INVALID, an allocation that fails with VRT_HIP_ERR_HIP: the table is untouched and nothing
+ *              further is enqueued.  A total of 0 (no ray keeps anything) runs the kernels of the switch off, which then add nothing;
+ *   3. record  the gradient kernels, storing what they add with the switch off as records (Gaussian index, ray id, 9 floats = columns
+ *              0..8 of the table, columns nobody computes 0): one per list position of a ray that keeps at most 32; per kept Gaussian
+ *              of a longer ray an emitter record and an absorber record (radiance gradient) or one record (transmittance gradient).
+ *              A long ray whose second cull does not give the counted length files nothing, and counts as a mismatch (never seen; the
+ *              host forms return VRT_HIP_ERR_HIP with a message on one, vrt_hip_get_grad_ordered_stats reports them);
+ *   4. sort    a stable radix sort by Gaussian index: the CONSUMED ORDER is (Gaussian, ray id, the record's place in its ray);
+ *   5. reduce  NORMATIVE.  For Gaussian j with records rho_0 .. rho_{m-1} in consumed order and each column c: a_l = (((+0.0f +
+ *              rho_l[c]) + rho_{l+64}[c]) + rho_{l+128}[c]) + ... for l = 0..63 (+0.0f where there is no record); then six steps s = 1,
+ *              2, 4, 8, 16, 32 in this order, each a_l <- a_l + a_{l xor s} from the values before the step; then table[j, c] <-
+ *              table[j, c] + a_0.  Plain float32 adds.  Columns 0..8 for a radiance gradient, 4..8 for a transmittance gradient; rows of
+ *              Gaussians without records, columns 9..11 and (transmittance gradient) 0..3 are not written at all.
+ * The ordered table agrees with the atomic one within the rounding of either.  A segment of m records is summed ceil(m / 64) + 6 adds
+ * deep, so its rounding grows like that depth times 2^-24 times the sum of the absolute addends: harmless at thousands of rays per
+ * Gaussian, not at millions.  Memory: 56 B per record (key, ray id, 9 floats, and the sort's three words) plus the sort's temporary
+ * storage and 20 B per ray, in buffers of the context that only grow.  The call waits for bundles in flight, counts as a state change
+ * (vrt_hip_state_generation) and is carried over by vrt_hip_copy_state. */
+int vrt_hip_set_grad_ordered(vrt_hip_ctx *ctx, int on);
+/* The records of the last ordered call in consumed order, sentinel rows of mismatched rays left out: gauss[i], ray[i] and rows[9 * i ..
+ * 9 * i + 8] for i < *count; what the table was reduced from (per-ray gradient rows for Gauss-Newton or per-ray clipping).  Waits for the
+ * call.  Before any ordered call, or after one that kept nothing or was refused: *count = 0.  cap (the room in each array, in records)
+ * smaller than the count: VRT_HIP_ERR_INVALID with *count set, nothing copied; with cap == 0 the arrays may be NULL. */
+int vrt_hip_get_grad_records(vrt_hip_ctx *ctx, uint32_t *gauss, uint32_t *ray, float *rows /* [cap * 9] */, size_t cap, size_t *count);
+typedef struct {
+    uint64_t records;        /* records reduced into the table (sentinel rows not counted)                          */
+    uint64_t gaussians;      /* Gaussians with at least one record: the rows of the table that were written         */
+    uint64_t longest;        /* records of the longest segment                                                      */
+    uint64_t mismatches;     /* rays whose second cull missed the counted length (0, or the call's table is short)  */
+} vrt_hip_grad_ordered_stats;
+int vrt_hip_get_grad_ordered_stats(vrt_hip_ctx *ctx, vrt_hip_grad_ordered_stats *out); /* of the last ordered call (waits for it); zeros before any */
 typedef struct {
     uint64_t rays;           /* rays of the bundle                                                                  */
     uint64_t short_rays;     /* shaded lane = ray (list of at most 32)                                              */

@@ -55,6 +55,13 @@ class RayIndexStats(C.Structure):
                                           "members_tested")]
 
 
+class GradOrderedStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("records", "gaussians", "longest", "mismatches")]
+
+
+GRAD_RECORD_COLS = 9        # floats per record of an ordered gradient table: the table's columns 0..8
+
+
 def build(verbose=False):
     """Compile csrc/ for gfx950 with hipcc (cross-compiles without a GPU)."""
     out = None if verbose else subprocess.DEVNULL
@@ -142,6 +149,9 @@ SYMBOLS = {
     "vrt_hip_set_ray_index": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_ray_index_stats": (C.c_int, [_vp, C.POINTER(RayIndexStats)]),
     "vrt_hip_get_ray_index_perm": (C.c_int, [_vp, _u32p, C.c_size_t]),
+    "vrt_hip_set_grad_ordered": (C.c_int, [_vp, C.c_int]),
+    "vrt_hip_get_grad_records": (C.c_int, [_vp, _u32p, _u32p, _f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vrt_hip_get_grad_ordered_stats": (C.c_int, [_vp, C.POINTER(GradOrderedStats)]),
     "vrt_hip_transmittance_step": (C.c_int, [_vp, _f32p, _f32p, _f32p, C.c_size_t, C.c_float, _f32p]),
     "vrt_hip_density": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p]),
     "vrt_hip_eval_erf": (C.c_int, [_vp, C.c_int, _f32p, C.c_size_t, _f32p]),
@@ -607,7 +617,7 @@ class Renderer:
         given its derivative grad_radiance [nrays, 4] with respect to what radiance_rays returns for the same rays (each ray's kept
         list is held fixed).
         Returns {"albedo": [N, 4], "mu": [N, 3], "sigma": [N], "magnitude": [N]}, float32.  The sums are float atomics on the device:
-        not bitwise reproducible.  With want_rays: (that dict, or None without want_table, {"origin": [nrays, 3], "dir": [nrays, 3]})
+        not bitwise reproducible, unless set_grad_ordered is on.  With want_rays: (that dict, or None without want_table, {"origin": [nrays, 3], "dir": [nrays, 3]})
         -- per ray d(loss) / d(origin) and the tangential d(loss) / d(dir), bitwise reproducible; without the table no atomic add is
         issued at all."""
         origins, dirs, per_ray = _rays(origins, dirs)
@@ -640,7 +650,7 @@ class Renderer:
         the derivative with respect to the Gaussians and the levels tau (of the ideal crossing; a depth of +inf, 0 or NaN contributes
         nothing).  A sample with grad_T == 0 is skipped exactly.  Each ray's kept list is held fixed.
         Returns ({"albedo": zeros [N, 4], "mu": [N, 3], "sigma": [N], "magnitude": [N]} or None, grad_s [nrays, ns] or None), float32.
-        The table's sums are float atomics on the device: not bitwise reproducible.  With want_rays a third value follows:
+        The table's sums are float atomics on the device: not bitwise reproducible, unless set_grad_ordered is on.  With want_rays a third value follows:
         {"origin": [nrays, 3], "dir": [nrays, 3]}, per ray d(loss) / d(origin) and the tangential d(loss) / d(dir), bitwise reproducible."""
         origins, dirs, per_ray = _rays(origins, dirs)
         s, ns, s_per_ray = _table(s, len(dirs), s_per_ray)
@@ -693,6 +703,33 @@ class Renderer:
         out = np.zeros(max(self.n, 1), np.uint32)
         self._chk(self._L.vrt_hip_get_ray_index_perm(self._h, out.ctypes.data_as(_u32p), out.size), "get_ray_index_perm")
         return out[:self.n]
+
+    def set_grad_ordered(self, on):
+        """Gradient bundles build their table without float atomics, bit for bit reproducible and summed in a documented order (off by
+        default; an ordered call waits once for its stream): see vrt_hip_set_grad_ordered in include/vrt_hip.h."""
+        self._chk(self._L.vrt_hip_set_grad_ordered(self._h, int(bool(on))), "set_grad_ordered")
+
+    def grad_records(self):
+        """The records the last ordered gradient bundle reduced its table from, in consumed order (Gaussian, ray, place in the ray):
+        (gauss u32 [m], ray u32 [m], rows f32 [m, 9] = the table's columns 0..8).  Waits; m = 0 before any ordered call.  See
+        vrt_hip_get_grad_records in include/vrt_hip.h."""
+        n = C.c_size_t()
+        rc = self._L.vrt_hip_get_grad_records(self._h, None, None, None, 0, C.byref(n))
+        m = n.value
+        gauss, ray, rows = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros((m, GRAD_RECORD_COLS), np.float32)
+        if m == 0:
+            self._chk(rc, "get_grad_records")
+            return gauss, ray, rows
+        self._chk(self._L.vrt_hip_get_grad_records(self._h, gauss.ctypes.data_as(_u32p), ray.ctypes.data_as(_u32p), _fp(rows), m, C.byref(n)),
+                  "get_grad_records")
+        return gauss, ray, rows
+
+    def grad_ordered_stats(self):
+        """Counts of the last ordered gradient bundle (records, Gaussians with records, longest segment, mismatches): see
+        vrt_hip_grad_ordered_stats in include/vrt_hip.h."""
+        s = GradOrderedStats()
+        self._chk(self._L.vrt_hip_get_grad_ordered_stats(self._h, C.byref(s)), "get_grad_ordered_stats")
+        return {k: getattr(s, k) for k, _ in GradOrderedStats._fields_}
 
     def eval_erf(self, kind, x):
         x = np.ascontiguousarray(x, np.float32)

@@ -8,7 +8,9 @@ Gaussians and of the rays.
 
 Forward is Renderer.radiance_rays_device, backward Renderer.radiance_rays_grad_rays_device (include/vrt_hip.h, "gradient bundles" and
 "ray gradients"): the derivative with each ray's kept list held fixed, under {vcl_exp, expf} x {A&S erf, erff} only; the Gaussians'
-gradients are summed with float atomics (not bitwise reproducible).  transmittance_bundle and depth_bundle run
+gradients are summed with float atomics (not bitwise reproducible) -- unless the renderer's switch is on (Renderer.set_grad_ordered:
+nothing changes here, backward calls the same entry points): then they are summed in a documented order, two backward passes give
+bit-equal .grad, and every backward that asks for a table waits once for its stream.  transmittance_bundle and depth_bundle run
 Renderer.transmittance_bundle_device / depth_bundle_device forward and Renderer.transmittance_bundle_grad_rays_device backward
 ("transmittance gradient bundles"), under the same rules; they are differentiable in s and tau as well, never in albedo (T does not depend on it).  The depth's derivative is that of the
 ideal crossing T(depth) = tau; a depth of +inf, 0 or NaN gets no gradient.

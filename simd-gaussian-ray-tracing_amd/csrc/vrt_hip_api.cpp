@@ -307,6 +307,7 @@ Tuning read_tuning()
     t.table_diag = getenv("VRT_HIP_TABLE_DIAG") != nullptr;
     if (const char *e = getenv("VRT_HIP_RETAIN_FRAME")) t.retain_frame = atoi(e) != 0;
     if (const char *e = getenv("VRT_HIP_RAY_INDEX")) t.ray_index = atoi(e) != 0;
+    if (const char *e = getenv("VRT_HIP_GRAD_ORDERED")) t.grad_ordered = atoi(e) != 0;
     return t;
 }
 
@@ -340,6 +341,7 @@ int vrt_hip_create(int device, vrt_hip_ctx **out)
     c->tune = read_tuning();
     c->cull_prune = c->tune.cull_prune; c->table_hx = c->tune.table_step; c->table_budget = c->tune.table_budget;
     c->ray_index = c->tune.ray_index;
+    c->grad_ordered = c->tune.grad_ordered;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreateWithFlags(&c->scene_order, hipEventDisableTiming) != hipSuccess ||
@@ -496,6 +498,7 @@ int vrt_hip_copy_state(vrt_hip_ctx *dst, const vrt_hip_ctx *src)
     dst->exp_kind = src->exp_kind; dst->erf_kind = src->erf_kind; dst->cull_eps = src->cull_eps; dst->cull_prune = src->cull_prune;
     dst->table_hx = src->table_hx; dst->table_budget = src->table_budget; dst->tune.table_adapt = src->tune.table_adapt; dst->tune.table_room = src->tune.table_room;
     dst->rank = src->rank; dst->world = src->world;
+    dst->grad_ordered = src->grad_ordered;
     dst->ray_index = src->ray_index; // the mirror builds the same index with its tables: the order is a function of the scene alone
     dst->tables_dirty = true; dst->lists_dirty = true; dst->shard_dirty = true; dst->ref_valid = false;
     dst->reset_seq = dst->frame_seq;
@@ -545,6 +548,16 @@ int vrt_hip_set_cull_prune(vrt_hip_ctx *c, float kappa)
     if (!(kappa >= 0.f)) return fail(c, VRT_HIP_ERR_INVALID, "set_cull_prune: the factor must be >= 0 (0 = off)");
     if (kappa != c->cull_prune) c->reset_seq = c->frame_seq;
     c->cull_prune = kappa;
+    ++c->state_gen;
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_set_grad_ordered(vrt_hip_ctx *c, int on)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // bundles in flight keep the path they were enqueued with
+    c->grad_ordered = on != 0;
     ++c->state_gen;
     return VRT_HIP_OK;
 }

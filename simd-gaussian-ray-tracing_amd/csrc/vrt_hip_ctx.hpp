@@ -69,6 +69,7 @@ struct Tuning {
     bool table_diag = false;     // VRT_HIP_TABLE_DIAG set: vrt_hip_render with stats on prints the table phase split
     bool retain_frame = true;    // VRT_HIP_RETAIN_FRAME=0: every vrt_hip_frame clears its whole image (no retained history)
     bool ray_index = false;      // VRT_HIP_RAY_INDEX=1: the context's first vrt_hip_ctx::ray_index
+    bool grad_ordered = false;   // VRT_HIP_GRAD_ORDERED=1: the context's first vrt_hip_ctx::grad_ordered
 };
 
 enum TileMode { TILES_NONE = 0, TILES_HOST = 1, TILES_DEVICE = 2 };
@@ -267,6 +268,19 @@ struct vrt_hip_ctx {
     size_t ri_sort_bytes = 0;
     bool ray_indexed_last = false; // the last bundle went through the index
     uint32_t ri_last_leaves = 0, ri_last_groups = 0; // ... over this many leaves and groups
+    // Ordered gradient tables (vrt_hip_set_grad_ordered; ordered_bundle in vrt_hip_rays.cpp).  Buffers of the context that only grow, used
+    // on the stream of the call like the long-ray queue (wait_for_last_stream covers them): per ray the counted length, its records and
+    // their first; per record its Gaussian, its ray, its 9 floats, the sorted keys, the consumed order and an identity; per Gaussian where
+    // its segment begins and ends; the words of the call; temporary storage of the scan and the sort.
+    bool grad_ordered = false;    // gradient bundles with a table take the ordered path
+    DevBuf<uint32_t> ord_len, ord_gauss, ord_ray, ord_keys_sorted, ord_order, ord_iota, ord_seg;
+    DevBuf<unsigned long long> ord_count, ord_base, ord_words;
+    DevBuf<float> ord_rows;
+    DevBuf<unsigned char> ord_scan_tmp, ord_sort_tmp;
+    size_t ord_iota_filled = 0;   // ord_iota holds 0 .. this - 1
+    bool ord_valid = false;       // an ordered call has cleared ord_words: they are that call's
+    uint64_t ord_total = 0;       // rows the last ordered call recorded, sentinel rows included (0: it kept nothing, or was refused)
+    bool ord_ran = false;         // set by an ordered call that recorded: the host forms look at its mismatch word once they have waited
     DevBuf<unsigned long long> d_stats, d_timeline; // d_timeline: VRT_HIP_TIMELINE diagnostics
     size_t timeline_items = 0, timeline_tiles = 0;
     DevBuf<unsigned long long> d_timeline_lists;

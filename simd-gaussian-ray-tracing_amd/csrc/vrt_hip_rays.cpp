@@ -4,7 +4,7 @@
 // respect to the Gaussians, culled per ray (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip,
 // vrt_ray_grad_kernel.hip, vrt_ray_trans_grad_kernel.hip).  The scene tables and the
 // chunk spheres are the frame pipeline's; the long-ray queue, its counters and the long kernel's scratch slots belong to the context
-// and only grow.
+// and only grow.  So do the buffers of the ordered gradient tables (vrt_hip_set_grad_ordered: ordered_bundle, and the two read-outs).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -201,13 +201,19 @@ struct BundleKind {
     bool gradient; // a derivative: a scene of no Gaussians is a bundle of nothing, and the Exp / Erf pair must have kernels
     bool modes;    // ... of what `wrt` names
     void (*launch)(const RayArgs &, uint32_t, bool, int, int, hipStream_t);
+    // a gradient with the ordered switch on and a table (ordered_bundle): the kernels that record, whether a long ray files two records
+    // per kept Gaussian, and the first column of the table its reduction writes
+    void (*launch_ordered)(const RayArgs &, uint32_t, bool, int, int, hipStream_t) = nullptr;
+    bool ord_two = false;
+    int ord_first_col = 0;
 };
 const BundleKind RADIANCE = { "radiance_rays", "no output buffer", "", false, false, launch_ray_bundle };
 const BundleKind TRANSMITTANCE = { "transmittance_bundle", "NULL samples or result", "ns", false, false, launch_ray_trans_bundle };
 const BundleKind DEPTH = { "depth_bundle", "NULL levels or result", "nt", false, false, launch_ray_depth_bundle };
-const BundleKind GRADIENT = { "radiance_rays_grad", "NULL grad_radiance or gradient table", "", true, false, launch_ray_grad_bundle };
+const BundleKind GRADIENT = { "radiance_rays_grad", "NULL grad_radiance or gradient table", "", true, false, launch_ray_grad_bundle,
+                              launch_ray_grad_bundle_ordered, true, 0 };
 const BundleKind TRANS_GRADIENT = { "transmittance_bundle_grad", "NULL samples or grad_T, or neither a gradient table nor grad_s", "ns", true, true,
-                                    launch_ray_trans_grad_bundle };
+                                    launch_ray_trans_grad_bundle, launch_ray_trans_grad_bundle_ordered, false, 4 };
 
 // The rays of a call, device or host pointers alike
 struct Rays {
@@ -237,6 +243,55 @@ bool bundle_over(vrt_hip_ctx *c, const BundleKind &k, const Rays &r, size_t n, b
     return true;
 }
 
+// A gradient bundle with a table while vrt_hip_set_grad_ordered is on (include/vrt_hip.h has the contract, vrt_grad_ordered_kernel.hip
+// the pipeline): count and place, ONE wait for the total, then the record kernels, the sort and the reduction -- or, where no ray keeps
+// anything, the kernels of the switch off, which then add nothing.  Refused before anything touches the table: a total beyond 2^32 - 1,
+// a buffer that cannot grow.
+int ordered_bundle(vrt_hip_ctx *c, const BundleKind &k, Bundle &b, hipStream_t st)
+{
+    RayArgs &a = b.a;
+    const size_t nrays = (size_t)a.nrays;
+    const size_t scan_bytes = grad_ordered_scan_bytes(nrays);
+    if (!scan_bytes) return fail(c, VRT_HIP_ERR_HIP, std::string(k.name) + ": ordered table: the scan's storage query failed");
+    HIPCHK(c, c->ord_len.reserve(nrays)); HIPCHK(c, c->ord_count.reserve(nrays)); HIPCHK(c, c->ord_base.reserve(nrays));
+    HIPCHK(c, c->ord_words.reserve(GRAD_ORD_WORDS)); HIPCHK(c, c->ord_scan_tmp.reserve(scan_bytes));
+    a.ord_len = c->ord_len.p; a.ord_count = c->ord_count.p; a.ord_two = k.ord_two ? 1 : 0; a.ord_base = c->ord_base.p;
+    a.ord_words = c->ord_words.p;
+    c->ord_valid = true; c->ord_total = 0;
+    HIPCHK(c, launch_grad_ordered_count(a, b.indexed, c->ord_base.p, c->ord_scan_tmp.p, scan_bytes, st));
+    unsigned long long total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, c->ord_words.p + GRAD_ORD_TOTAL, sizeof(total), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st)); // the one wait of an ordered call: the sort takes its size on the host, and the buffers may have to grow
+    if (total > 0xFFFFFFFFull) return fail(c, VRT_HIP_ERR_INVALID, std::string(k.name) + ": ordered table: more than 2^32 - 1 records in one bundle");
+    if (total == 0) { // no ray keeps anything: nothing to record, sort or reduce; ray rows, grad_s and statistics by the kernels of the switch off
+        k.launch(a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
+        HIPCHK(c, hipGetLastError());
+        return VRT_HIP_OK;
+    }
+    const size_t rows = (size_t)total;
+    const size_t sort_bytes = grad_ordered_sort_bytes(total, c->n);
+    if (!sort_bytes) return fail(c, VRT_HIP_ERR_HIP, std::string(k.name) + ": ordered table: the sort's storage query failed");
+    HIPCHK(c, c->ord_gauss.reserve(rows)); HIPCHK(c, c->ord_ray.reserve(rows)); HIPCHK(c, c->ord_rows.reserve(rows * GRAD_ORD_COLS));
+    HIPCHK(c, c->ord_keys_sorted.reserve(rows)); HIPCHK(c, c->ord_order.reserve(rows)); HIPCHK(c, c->ord_seg.reserve((size_t)c->n * 2));
+    HIPCHK(c, c->ord_sort_tmp.reserve(sort_bytes));
+    if (c->ord_iota.cap < rows) { c->ord_iota_filled = 0; HIPCHK(c, c->ord_iota.reserve(rows)); }
+    if (c->ord_iota_filled < rows) {
+        launch_grad_ordered_iota(c->ord_iota.p, c->ord_iota_filled, rows, st);
+        c->ord_iota_filled = rows;
+    }
+    a.ord_gauss = c->ord_gauss.p; a.ord_ray = c->ord_ray.p; a.ord_rows = c->ord_rows.p;
+    k.launch_ordered(a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
+    HIPCHK(c, hipGetLastError());
+    GradOrderedSort o{};
+    o.total = total; o.n = c->n;
+    o.keys = c->ord_gauss.p; o.iota = c->ord_iota.p; o.keys_sorted = c->ord_keys_sorted.p; o.order = c->ord_order.p; o.seg = c->ord_seg.p;
+    o.sort_tmp = c->ord_sort_tmp.p; o.sort_bytes = sort_bytes;
+    o.rows = c->ord_rows.p; o.table = a.grad; o.first_col = k.ord_first_col; o.words = c->ord_words.p;
+    HIPCHK(c, launch_grad_ordered_reduce(o, st));
+    c->ord_total = total; c->ord_ran = true;
+    return VRT_HIP_OK;
+}
+
 // The device form of every kind: the check, what every bundle enqueues, the kind's own fields of RayArgs (fill), its two kernels
 template <class Fill>
 int device_bundle(vrt_hip_ctx *c, const BundleKind &k, const Rays &r, size_t n, bool io_ok, int wrt, void *hip_stream, Fill &&fill)
@@ -248,6 +303,7 @@ int device_bundle(vrt_hip_ctx *c, const BundleKind &k, const Rays &r, size_t n, 
     rc = enqueue_bundle(c, r.nrays, r.origins, r.origin_per_ray, r.dirs, st, b);
     if (rc) return rc;
     fill(b.a);
+    if (c->grad_ordered && k.launch_ordered && b.a.grad) return ordered_bundle(c, k, b, st);
     k.launch(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
     HIPCHK(c, hipGetLastError());
     return VRT_HIP_OK;
@@ -303,11 +359,17 @@ int host_bundle(vrt_hip_ctx *c, const Rays &r, std::initializer_list<CopiedIn> i
     for (const CopiedIn &s : in) HIPCHK(c, hipMemcpyAsync(s.buf.data(), s.host, s.count * s.buf.size, hipMemcpyHostToDevice, c->stream));
     for (const BroughtBack &s : out)
         if (s.host && s.clear) HIPCHK(c, hipMemsetAsync(s.buf.data(), 0, s.count * s.buf.size, c->stream));
+    c->ord_ran = false;
     rc = device(Rays{ r.nrays, c->rays_in[0].p, r.origin_per_ray, c->rays_in[1].p });
     if (rc) return rc;
     for (const BroughtBack &s : out)
         if (s.host) HIPCHK(c, hipMemcpyAsync(s.host, s.buf.data(), s.count * s.buf.size, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->ord_ran) { // an ordered table: a ray that missed its counted length filed nothing, and the table is short of it
+        unsigned long long missed = 0;
+        HIPCHK(c, hipMemcpy(&missed, c->ord_words.p + GRAD_ORD_MISMATCH, sizeof(missed), hipMemcpyDeviceToHost));
+        if (missed) return fail(c, VRT_HIP_ERR_HIP, "ordered table: " + std::to_string(missed) + " rays missed the list length the count pass found");
+    }
     return VRT_HIP_OK;
 }
 
@@ -479,6 +541,47 @@ int vrt_hip_get_ray_stats(vrt_hip_ctx *c, vrt_hip_ray_stats *out)
     HIPCHK(c, hipMemcpy(w, c->ray_stats.p, sizeof(w), hipMemcpyDeviceToHost));
     out->rays = w[0]; out->short_rays = w[1]; out->long_rays = w[2]; out->lane_entries = w[3]; out->lane_pairs = w[4];
     out->chunks_tested = w[5]; out->chunks_kept = w[6]; out->members_tested = w[7]; out->scratch_rays = w[8];
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_get_grad_ordered_stats(vrt_hip_ctx *c, vrt_hip_grad_ordered_stats *out)
+{
+    if (!c || !out) return VRT_HIP_ERR_INVALID;
+    *out = vrt_hip_grad_ordered_stats{};
+    if (!c->ord_valid) return VRT_HIP_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // waits for the call
+    unsigned long long w[GRAD_ORD_WORDS];
+    HIPCHK(c, hipMemcpy(w, c->ord_words.p, sizeof(w), hipMemcpyDeviceToHost));
+    out->records = w[GRAD_ORD_RECORDS]; out->gaussians = w[GRAD_ORD_TOUCHED]; out->longest = w[GRAD_ORD_LONGEST]; out->mismatches = w[GRAD_ORD_MISMATCH];
+    return VRT_HIP_OK;
+}
+
+// The records as the reduction consumed them: the sorted keys and the order are the sort's; sentinel rows sort last, so the first
+// `records` places of the order are the records.  Gathered on the host: a read-out, not a hot path.
+int vrt_hip_get_grad_records(vrt_hip_ctx *c, uint32_t *gauss, uint32_t *ray, float *rows, size_t cap, size_t *count)
+{
+    if (!c || !count) return VRT_HIP_ERR_INVALID;
+    *count = 0;
+    if (!c->ord_valid || !c->ord_total) return VRT_HIP_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // waits for the call
+    unsigned long long w[GRAD_ORD_WORDS];
+    HIPCHK(c, hipMemcpy(w, c->ord_words.p, sizeof(w), hipMemcpyDeviceToHost));
+    const size_t n = (size_t)w[GRAD_ORD_RECORDS], total = (size_t)c->ord_total;
+    *count = n;
+    if (n > cap || (n && (!gauss || !ray || !rows))) return fail(c, VRT_HIP_ERR_INVALID, "get_grad_records: buffer too small");
+    if (!n) return VRT_HIP_OK;
+    std::vector<uint32_t> order(n), rays(total);
+    std::vector<float> all(total * GRAD_ORD_COLS);
+    HIPCHK(c, hipMemcpy(gauss, c->ord_keys_sorted.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(order.data(), c->ord_order.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(rays.data(), c->ord_ray.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(all.data(), c->ord_rows.p, total * GRAD_ORD_COLS * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        ray[i] = rays[order[i]];
+        std::memcpy(rows + i * GRAD_ORD_COLS, all.data() + (size_t)order[i] * GRAD_ORD_COLS, GRAD_ORD_COLS * sizeof(float));
+    }
     return VRT_HIP_OK;
 }
 

@@ -347,7 +347,20 @@ struct RayArgs {
     int wrt;
     // Ray gradients (both gradient kernels; behind everything the other kernels read)
     float *grad_rays;            // nullable, [r * VRT_HIP_RAY_GRAD_STRIDE], 16-byte aligned, stored: d(loss) / d(origin), 0, tangential d(loss) / d(dir), 0
+    // Ordered gradient tables (vrt_hip_set_grad_ordered; read by the count kernel and the ORDERED instantiations of the gradient kernels
+    // only, which never touch `grad`; behind everything the other kernels read)
+    uint32_t *ord_len;              // [r] the count pass's list length of ray r, long rays too
+    unsigned long long *ord_count;  // [r] the records of ray r: its length, twice that for a long ray when ord_two
+    int ord_two;                    // the radiance gradient: a long ray files an emitter and an absorber record per kept Gaussian
+    const unsigned long long *ord_base; // [r] the first record of ray r: the exclusive scan of ord_count
+    uint32_t *ord_gauss, *ord_ray;  // [record] the Gaussian (S.n: a sentinel row of a ray whose re-cull missed its length) and the ray
+    float *ord_rows;                // [record * GRAD_ORD_COLS] the table's columns 0..8
+    unsigned long long *ord_words;  // [GRAD_ORD_WORDS]
 };
+constexpr int GRAD_ORD_COLS = 9;    // floats per record
+// the words of an ordered call, cleared on the stream ahead of its count pass: rays whose re-cull missed the counted length; records
+// reduced, Gaussians with records and the longest segment (by the reduction); rows placed, sentinel rows included (by the scan)
+enum { GRAD_ORD_MISMATCH = 0, GRAD_ORD_RECORDS = 1, GRAD_ORD_TOUCHED = 2, GRAD_ORD_LONGEST = 3, GRAD_ORD_TOTAL = 4, GRAD_ORD_WORDS = 5 };
 constexpr int RAY_STATS_WORDS = 9, RAY_INDEX_STATS_WORDS = 5; // one device buffer: the index's words follow the nine
 void launch_ray_bundle(const RayArgs &a, uint32_t long_grid /* one-wave workgroups of the long kernel */, bool indexed, int exp_kind, int erf_kind,
                        hipStream_t st);
@@ -363,6 +376,32 @@ bool ray_grad_pair_supported(int exp_kind, int erf_kind);
 // the same cull, then d(loss) / d(Gaussians) from a.grad_T at the samples a.s, added into columns 4..8 of a.grad, and d(loss) /
 // d(samples or levels) stored to a.grad_s, d(loss) / d(rays) to a.grad_rays (vrt_ray_trans_grad_kernel.hip).  The pairs of ray_grad_pair_supported; any other enqueues nothing.
 void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+// Ordered gradient tables (vrt_hip_set_grad_ordered; vrt_grad_ordered_kernel.hip has the pipeline).  The same two bundles with every
+// add into a.grad replaced by a store into the records at a.ord_base[r] (the ORDERED instantiations, in translation units of their own:
+// vrt_ray_grad_ordered_kernel.hip, vrt_ray_trans_grad_ordered_kernel.hip); a.grad is not touched.
+void launch_ray_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+void launch_ray_trans_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+// count and place: a.ord_words cleared, a.ord_len / a.ord_count by the cull alone, base = the exclusive scan of a.ord_count (tmp:
+// grad_ordered_scan_bytes(nrays) bytes; 0: the query failed), a.ord_words[GRAD_ORD_TOTAL] = the rows of the call.  a.nrays > 0.
+size_t grad_ordered_scan_bytes(size_t nrays);
+hipError_t launch_grad_ordered_count(const RayArgs &a, bool indexed, unsigned long long *base, void *tmp, size_t tmp_bytes, hipStream_t st);
+// sort and reduce: `total` records (keys: Gaussian index, n for a sentinel row) into the consumed order, then table[j, first_col..8] +=
+// the ordered sum of Gaussian j's records.  sort_tmp: grad_ordered_sort_bytes(total, n) bytes; iota: 0 .. total - 1; seg: 2 n words.
+struct GradOrderedSort {
+    uint64_t total;
+    uint32_t n;
+    const uint32_t *keys, *iota;
+    uint32_t *keys_sorted, *order, *seg;
+    void *sort_tmp;
+    size_t sort_bytes;
+    const float *rows;
+    float *table;
+    int first_col; // 0: the radiance gradient, 4: the transmittance gradient (columns 0..3 are not written)
+    unsigned long long *words;
+};
+size_t grad_ordered_sort_bytes(uint64_t total, uint32_t n);
+void launch_grad_ordered_iota(uint32_t *p, uint64_t from, uint64_t to, hipStream_t st); // p[i] = i for from <= i < to
+hipError_t launch_grad_ordered_reduce(const GradOrderedSort &o, hipStream_t st);
 // group spheres of the Morton index: one per 64 consecutive leaf spheres, bounding them
 void launch_build_ray_groups(uint32_t nleaves, const float4 *leaves, float4 *groups, hipStream_t st);
 

@@ -6,6 +6,7 @@
 //   grad_deal         one weight dealt to one absorber: P, Q, R
 //   grad_row, _w      the row segment (d mu xyz, d sigma, d magnitude) from M, the coefficient of n and the sigma sum; with the terms in W
 //   grad_deposit      a row segment into the caller's table, wave-summed where every lane names the same row
+//   grad_record_*, grad_records_short   ORDERED: the same segments stored as records instead, and the guard of a ray's range
 //   grad_ray_add, _w, grad_ray_store   the same segment's share of the RAY's row (d origin, d direction), and the row's two stores
 //   LaneList, grad_acc, grad_walk_begin / _next, grad_flush_short   lane = ray: a lane's list, the three running sums per list position and lane in LDS, the walk of a
 //                     lane's list with the next entry's rows loaded one iteration ahead, and every position to the table once
@@ -89,6 +90,58 @@ __device__ __forceinline__ void grad_deposit(float *table, uint32_t idx, bool on
 #pragma unroll
         for (int c = 0; c < NV; ++c) atomicAdd(&table[(size_t)idx * GRAD_STRIDE + col0 + c], v[c]);
     }
+}
+
+// ---- ordered gradient tables (vrt_hip_set_grad_ordered): the ORDERED instantiations store what the others add ----
+// A record is (Gaussian index, ray id, GRAD_ORD_COLS floats = the table's columns 0..8) at a place of its ray's own range
+// [ord_base[r], ord_base[r] + ord_count[r]).  Every cell of a record is written by ONE thread, which may read back its own earlier
+// store; a record's first write is a store; columns nobody computes are stored as 0.  vrt_grad_ordered_kernel.hip sums them.
+template <int NV>
+__device__ __forceinline__ void grad_record_store(const RayArgs *Pp, uint64_t rec, uint32_t col0, const float (&v)[NV])
+{
+    float *row = Pp->ord_rows + rec * (uint64_t)GRAD_ORD_COLS + col0;
+#pragma unroll
+    for (int c = 0; c < NV; ++c) row[c] = v[c];
+}
+// ... NV values onto columns col0.. of a record this thread stored before
+template <int NV>
+__device__ __forceinline__ void grad_record_add(const RayArgs *Pp, uint64_t rec, uint32_t col0, const float (&v)[NV])
+{
+    float *row = Pp->ord_rows + rec * (uint64_t)GRAD_ORD_COLS + col0;
+#pragma unroll
+    for (int c = 0; c < NV; ++c) row[c] = row[c] + v[c];
+}
+__device__ __forceinline__ void grad_record_zero_albedo(const RayArgs *Pp, uint64_t rec)
+{
+    const float zero[4] = { 0.f, 0.f, 0.f, 0.f };
+    grad_record_store<4>(Pp, rec, 0u, zero);
+}
+__device__ __forceinline__ void grad_record_name(const RayArgs *Pp, uint64_t rec, uint32_t idx, uint64_t r)
+{
+    Pp->ord_gauss[rec] = idx;
+    Pp->ord_ray[rec] = (uint32_t)r;
+}
+// The guard: a ray whose list is not as long as the count pass found it names every row of its range a sentinel (key = N: sorted
+// last, read by no segment), touches nothing outside the range and counts one mismatch.  Called by the lanes `lanes` apart that share
+// the ray (1: a lane of the short kernels, 64: the wave of the long ones, `first` = the lane's place among them).
+__device__ __forceinline__ void grad_record_mismatch(const RayArgs *Pp, uint64_t r, uint32_t first, uint32_t lanes)
+{
+    const uint64_t base = Pp->ord_base[r], rows = Pp->ord_count[r];
+    for (uint64_t k = first; k < rows; k += lanes) grad_record_name(Pp, base + k, Pp->S.n, r);
+    if (first == 0) atomicAdd(&Pp->ord_words[GRAD_ORD_MISMATCH], 1ull);
+}
+// A lane of the short kernels behind ray_short_begin: its ray's first record, and whether its records may be stored (the guard)
+struct ShortRecords {
+    uint64_t base;
+    bool on;
+};
+__device__ __forceinline__ ShortRecords grad_records_short(const RayArgs *Pp, const ShortRay &R)
+{
+    ShortRecords o;
+    o.base = Pp->ord_base[R.rc];
+    o.on = R.writes && R.nl == Pp->ord_len[R.rc];
+    if (R.writes && !o.on) grad_record_mismatch(Pp, R.rc, 0u, 1u);
+    return o;
 }
 
 // One weight w dealt to one absorber at x = x_ikj (or x_kj), E = Erf(-mubar_j r_j): P += w D, Q += w e2, R += w e2 x.  Returns w e2.
@@ -199,9 +252,13 @@ __device__ __forceinline__ GradGauss grad_walk_next(ListWalk &w, const SceneTabl
 // Every list position to the table once, now that W is known, and -- RAYS -- the same segments to the lane's ray row in list order,
 // stored once where the lane `writes`.  With RAYS the table may be missing (table == nullptr, wave-uniform: no add is issued); without,
 // it is there, and this is the text the kernels ran before there were ray rows.  The whole wave calls this.
-template <int EXP, int ERF, bool RAYS>
+// ORDERED: position p's segment is STORED to record base + p of the lane's ray (rec_on: the lane's list is as long as the count pass found
+// it), with its name; zero_albedo: and zeros to its columns 0..3, which nobody else writes (the transmittance gradient).
+template <int EXP, int ERF, bool RAYS, bool ORDERED = false>
 __device__ __forceinline__ void grad_flush_short(float *table, [[maybe_unused]] float *grad_rays, [[maybe_unused]] uint64_t r, [[maybe_unused]] bool writes,
-                                                 const SceneTables &S, const ErfEval<ERF> &erf, const LaneList &L, float *s_acc, const LaneRay &ray, float W)
+                                                 const SceneTables &S, const ErfEval<ERF> &erf, const LaneList &L, float *s_acc, const LaneRay &ray, float W,
+                                                 [[maybe_unused]] const RayArgs *Pp = nullptr, [[maybe_unused]] uint64_t base = 0,
+                                                 [[maybe_unused]] bool rec_on = false, [[maybe_unused]] bool zero_albedo = false)
 {
     const uint32_t lane = L.lane;
     [[maybe_unused]] float go[3] = { 0.f, 0.f, 0.f }, gn[3] = { 0.f, 0.f, 0.f };
@@ -216,6 +273,13 @@ __device__ __forceinline__ void grad_flush_short(float *table, [[maybe_unused]] 
         if (!RAYS || table) {
             float d[5];
             grad_row_w<EXP>(q, ray, mag, grad_acc(s_acc, 0, p, lane), grad_acc(s_acc, 1, p, lane), grad_acc(s_acc, 2, p, lane), W, d);
+            if constexpr (ORDERED) {
+                if (on && rec_on) {
+                    if (zero_albedo) grad_record_zero_albedo(Pp, base + p);
+                    grad_record_store<5>(Pp, base + p, 4u, d);
+                    grad_record_name(Pp, base + p, idx, r);
+                }
+            } else
             grad_deposit<5>(table, idx, on, d, 4u, lane);
         }
     }

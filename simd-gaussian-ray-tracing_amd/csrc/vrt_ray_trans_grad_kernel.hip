@@ -38,7 +38,10 @@
 // parameter: <.., false> is the kernel from before there were ray rows.
 // Exp / Erf of the forward quantities are the selected pair's; e1 and e2 are exp_neg_sq<EXP>.  Only {vcl, libm} x {A&S, libm} are
 // instantiated (ray_grad_pair_supported).  The sums in the caller's table depend on the arrival order of the atomic adds: not bitwise
-// reproducible.  Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
+// reproducible -- unless ORDERED (vrt_hip_set_grad_ordered): a template parameter of both kernels, instantiated in
+// vrt_ray_trans_grad_ordered_kernel.hip, with which every add into the table becomes a store into a record of the ray's own range
+// (vrt_ray_grad.hpp has the record rules, vrt_grad_ordered_kernel.hip what runs before and behind).
+// Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
 // What lives where: this file has what a sample is (trans_grad_live, trans_grad_x, trans_grad_weight), the two kernels' loops over groups
 // and chunks of samples, and the launch.  The helpers named above are vrt_ray_grad.hpp's, shared with vrt_ray_grad_kernel.hip.
 #include "vrt_ray_grad.hpp"
@@ -77,8 +80,10 @@ __device__ __forceinline__ bool trans_grad_live(bool depth_mode, float s, float 
 // away), and e2 = exp(-x^2) passes an error dx on as 2 |x| dx -- 4e-5 of a far sample's addends on the grid scene, against 5e-6 this way.
 __device__ __forceinline__ float trans_grad_x(float s, const GradGauss &q) { return (s - q.mubar) * q.r; }
 
-// RAYS: the ray rows are asked for (P.grad_rays != nullptr); without, each kernel is the text it was before there were ray rows
-template <int EXP, int ERF, bool INDEXED, bool RAYS>
+// RAYS: the ray rows are asked for (P.grad_rays != nullptr); without, each kernel is the text it was before there were ray rows.
+// ORDERED (vrt_hip_set_grad_ordered, the table is there): one record per list position at ord_base[r] + position, stored whole at the
+// flush -- zeros in columns 0..3, no sum across lanes.  <.., false> is the kernel as it is without.
+template <int EXP, int ERF, bool INDEXED, bool RAYS, bool ORDERED = false>
 __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -151,11 +156,17 @@ __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // re
             }
         }
     }
+    if constexpr (ORDERED) {
+        const ShortRecords rec = grad_records_short(&P, R);
+        grad_flush_short<EXP, ERF, RAYS, true>(P.grad, P.grad_rays, R.rc, R.writes, S, erf, L, s_acc, ray, W, &P, rec.base, rec.on, true);
+    } else
     if (RAYS || P.grad) grad_flush_short<EXP, ERF, RAYS>(P.grad, P.grad_rays, R.rc, R.writes, S, erf, L, s_acc, ray, W);
 }
 
 // One wave per long ray, lane l takes entries l, l + 64, ...; the samples in chunks of NSC.
-template <int EXP, int ERF, bool INDEXED, bool RAYS>
+// ORDERED: one record per entry at ord_base[r] + p, owned by the lane that takes entry p: stored whole (zeros in columns 0..3, the name)
+// with the first chunk of samples, the later chunks' segments added onto the lane's own stores.
+template <int EXP, int ERF, bool INDEXED, bool RAYS, bool ORDERED = false>
 __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -174,6 +185,12 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
         const float *sp = P.s + (P.s_per_ray ? L.r * ns : 0ull);
         const float *gp = P.grad_T + L.r * ns;
         float *gsp = P.grad_s ? P.grad_s + L.r * ns : nullptr;
+        [[maybe_unused]] uint64_t base = 0;
+        if constexpr (ORDERED) {
+            // the guard: the re-cull gives the counted length, and the ray's range is a long ray's
+            if (n != P.ord_len[L.r] || P.ord_count[L.r] != 1ull * n) { grad_record_mismatch(&P, L.r, lane, 64u); continue; }
+            base = P.ord_base[L.r];
+        }
         [[maybe_unused]] float go[3] = { 0.f, 0.f, 0.f }, gn[3] = { 0.f, 0.f, 0.f }; // this lane's shares of the ray's row, over its entries and all chunks
         for (uint64_t c0 = 0; c0 < ns; c0 += NSC) {
             const uint32_t nc = (uint32_t)(ns - c0 < (uint64_t)NSC ? ns - c0 : (uint64_t)NSC);
@@ -227,6 +244,15 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
                     for (uint32_t k = 0; k < nc; ++k) grad_deal<EXP>(erf, s_w[k], trans_grad_x(s_s[k], q), q.E, Pj, Qj, Rj);
                     const float mag = S.gD[idx].z;
                     if constexpr (RAYS) grad_ray_add_w<EXP>(q, ray, mag, q.Am * Pj, q.Ar * Qj, Wc, go, gn);
+                    if constexpr (ORDERED) {
+                        float d[5];
+                        grad_row_w<EXP>(q, ray, mag, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, Wc, d);
+                        if (c0 == 0) {
+                            grad_record_zero_albedo(&P, base + p);
+                            grad_record_store<5>(&P, base + p, 4u, d);
+                            grad_record_name(&P, base + p, idx, L.r);
+                        } else grad_record_add<5>(&P, base + p, 4u, d);
+                    } else
                     if (P.grad) {
                         float d[5];
                         grad_row_w<EXP>(q, ray, mag, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, Wc, d);
@@ -247,6 +273,7 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
     }
 }
 
+#ifndef VRT_GRAD_ORDERED_UNIT
 template <int EXP, int ERF>
 static void launch_ray_trans_grad_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
 {
@@ -261,5 +288,21 @@ void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool ind
     if (!a.nrays || !a.ns || !long_grid || !ray_grad_pair_supported(exp_kind, erf_kind)) return;
     VRT_DISPATCH_GRAD_PAIR(launch_ray_trans_grad_bundle_t, a, long_grid, indexed, st);
 }
+#else // vrt_ray_trans_grad_ordered_kernel.hip: the ORDERED instantiations alone, so that the build stays parallel
+template <int EXP, int ERF>
+static void launch_ray_trans_grad_bundle_ordered_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
+{
+    if (a.grad_rays) {
+        if (indexed) launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, true, true, true>, ray_long_trans_grad_kernel<EXP, ERF, true, true, true>, a, long_grid, st);
+        else launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, false, true, true>, ray_long_trans_grad_kernel<EXP, ERF, false, true, true>, a, long_grid, st);
+    } else if (indexed) launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, true, false, true>, ray_long_trans_grad_kernel<EXP, ERF, true, false, true>, a, long_grid, st);
+    else launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, false, false, true>, ray_long_trans_grad_kernel<EXP, ERF, false, false, true>, a, long_grid, st);
+}
+void launch_ray_trans_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
+{
+    if (!a.nrays || !a.ns || !long_grid || !a.grad || !ray_grad_pair_supported(exp_kind, erf_kind)) return;
+    VRT_DISPATCH_GRAD_PAIR(launch_ray_trans_grad_bundle_ordered_t, a, long_grid, indexed, st);
+}
+#endif
 
 } // namespace vrtk

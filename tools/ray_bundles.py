@@ -38,6 +38,13 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
       `--grad-only` runs this part alone, prints its JSON line and writes ray_grad.json and ray_grad.md (and nothing else) to --out-dir;
       the .md ends with the text of <out-dir>/ray_grad_resources.txt when that file is there (the output of
       `tools/kernel_resources.sh raygrad`, which needs the compiler and no GPU).
+  (go) ordered gradient tables (vrt_hip_set_grad_ordered): the three bundles of (g), index off and on, vrt_hip_radiance_rays_grad_device
+      with the switch on against the same call with it off (float atomics) in the same run, four contexts, windows alternating.  With it
+      the records, the Gaussians with records and the longest segment of one call, and in the same run: the ordered table twice (equal
+      bits), with the index on and off (equal bits), and its largest difference from the atomic table.  There is no pass / fail ratio.
+      `--ordered-only` runs this part alone, prints its JSON line and writes ray_grad_ordered.json and ray_grad_ordered.md (and nothing
+      else) to --out-dir; the .md ends with the text of <out-dir>/ray_grad_ordered_resources.txt when that file is there (the output of
+      `tools/kernel_resources.sh raygrad`, `raytgrad` and `gradord`).
   (tg) transmittance gradient bundles (vrt_hip_transmittance_bundle_grad_device, table and per-sample output): the 2^20 scattered rays of
       (d) with ns = 1 (shadow rays, s = 8), the 4096 aimed rays of (t) with ns = 64 (profiles), and the 4096 aimed rays of (depth) in depth
       mode at the depths of level 0.5 (and, beside it, of level 0.99, which these rays do reach), device pointers, index off and on, each
@@ -309,10 +316,8 @@ def write_depth(z, out_dir):
 ATOMIC_RATE = 1.3e12   # bytes of float atomic adds per second, chip-wide
 
 
-def part_grad(g, calls=3, repeats=5):
-    import torch
-    st = torch.cuda.current_stream().cuda_stream
-    rows = {}
+def grad_bundles(g):
+    """The three bundles of (g) and (go): (label, (origins, dirs), origin per ray)"""
     cam, _ = scene.cli_camera(64, 64)
     pinhole = (np.asarray(cam.position, f32)[:3], directions(cam.plane(), cam.position))
     centre = g["mu"][len(g) // 2 + int(round(len(g) ** 0.5)) // 2, :3].astype(np.float64)
@@ -320,7 +325,14 @@ def part_grad(g, calls=3, repeats=5):
     target = centre[None, :] + np.stack([np.tile(u, 64), np.repeat(u, 64), np.zeros(4096)], 1)
     dz = target - np.asarray(cam.position, np.float64)[:3]
     zoom = (pinhole[0], np.ascontiguousarray((dz / np.linalg.norm(dz, axis=1, keepdims=True)).astype(f32)))
-    for label, (o, d), per in (("pinhole_64x64", pinhole, 0), ("zoom_64x64", zoom, 0), ("scattered_2^20", scattered(g, 1 << 20), 1)):
+    return (("pinhole_64x64", pinhole, 0), ("zoom_64x64", zoom, 0), ("scattered_2^20", scattered(g, 1 << 20), 1))
+
+
+def part_grad(g, calls=3, repeats=5):
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    rows = {}
+    for label, (o, d), per in grad_bundles(g):
         nrays = len(d)
         t_o, t_d = torch.from_numpy(np.ascontiguousarray(o, f32)).cuda(), torch.from_numpy(np.ascontiguousarray(d, f32)).cuda()
         t_g = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, size=(nrays, 4)).astype(f32)).cuda()
@@ -372,6 +384,86 @@ scheduler on this unit, variants of the LDS layout.
 """)
     if resources:
         lines.append("Resources (`tools/kernel_resources.sh raygrad`; template arguments: Exp (0 libm, 1 vcl), Erf (0 libm, 1 A&S), INDEXED):\n\n```\n" + resources.rstrip() + "\n```\n")
+    return "\n".join(lines)
+
+
+def part_ordered(g, calls=3, repeats=5):
+    """(go) ordered against atomic gradient tables, in the same run: the bundles of (g), Morton index off and on, four contexts"""
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    rows = {}
+    for label, (o, d), per in grad_bundles(g):
+        nrays = len(d)
+        t_o, t_d = torch.from_numpy(np.ascontiguousarray(o, f32)).cuda(), torch.from_numpy(np.ascontiguousarray(d, f32)).cuda()
+        t_g = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, size=(nrays, 4)).astype(f32)).cuda()
+        ctx = {}
+        for index in (0, 1):
+            for ordered in (0, 1):
+                r = pkg.Renderer(0)
+                r.set_gaussians(g)
+                r.set_ray_index(index)
+                r.set_grad_ordered(ordered)
+                ctx[index, ordered] = r
+        table = {k: torch.zeros((len(g), pkg.GRAD_STRIDE), dtype=torch.float32, device="cuda") for k in ctx}
+        torch.cuda.synchronize()
+        keys = sorted(ctx)
+        fns = [lambda k=k: ctx[k].radiance_rays_grad_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_g.data_ptr(), table[k].data_ptr(), st)
+               for k in keys]
+        t = dict(zip(keys, windows(fns, calls, repeats, warm=2)))
+        for k in keys:
+            table[k].zero_()
+        torch.cuda.synchronize()
+        for fn in fns:
+            fn()
+        torch.cuda.synchronize()
+        ost = ctx[0, 1].grad_ordered_stats()
+        again = table[0, 1].clone()
+        table[0, 1].zero_()
+        fns[keys.index((0, 1))]()
+        torch.cuda.synchronize()
+        scale = float(table[0, 0].abs().max().item())
+        row = {"rays": nrays, "records": ost["records"], "gaussians_with_records": ost["gaussians"], "longest_segment": ost["longest"],
+               "mismatches": ost["mismatches"], "record_bytes": 56 * ost["records"],
+               "ordered_bits_repeat": bool(torch.equal(again, table[0, 1])), "ordered_bits_index_on_equal_off": bool(torch.equal(table[0, 1], table[1, 1])),
+               "max_abs_ordered_minus_atomic_over_max_abs": float((table[0, 1] - table[0, 0]).abs().max().item()) / max(scale, 1e-30)}
+        for index, name in ((0, "off"), (1, "on")):
+            row[f"atomic_{name}_ms"], row[f"ordered_{name}_ms"] = t[index, 0], t[index, 1]
+            row[f"ordered_over_atomic_{name}"] = round(t[index, 1]["median"] / t[index, 0]["median"], 2)
+        for r in ctx.values():
+            r.close()
+        rows[label] = row
+    return {"gaussians": len(g), "rows": rows}
+
+
+def markdown_ordered(z, resources=""):
+    lines = [f"""# Ordered gradient tables (tools/ray_bundles.py --ordered-only)
+
+`vrt_hip_radiance_rays_grad_device` with `vrt_hip_set_grad_ordered` on against the same call with it off (float atomics), in the same
+run: `-g 64` (N = {z['gaussians']}), the three bundles of profiles/ray_grad.md, device pointers, stream events around back-to-back calls,
+the four paths (atomic / ordered, Morton index off / on: four contexts) alternating; ms per call, median (min .. max).  An ordered call
+holds a count pass, a scan, ONE host wait, the record kernels, a radix sort and the reduction.  There is no pass / fail ratio.
+
+| bundle | rays | index | atomic | ordered | ordered / atomic | records | Gaussians with records | longest segment | record memory (56 B each) |
+|---|---|---|---|---|---|---|---|---|---|"""]
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            lines.append(f"| {label} | {r['rays']} | {key} | {ms(r[f'atomic_{key}_ms'])} | {ms(r[f'ordered_{key}_ms'])} | {r[f'ordered_over_atomic_{key}']} | "
+                         f"{r['records']} | {r['gaussians_with_records']} | {r['longest_segment']} | {r['record_bytes']} |")
+    lines.append("""
+Checked in the same run, per bundle: the ordered table of a second call equals the first bit for bit, the ordered table with the index on
+equals the one with it off bit for bit, no mismatch; the largest |ordered - atomic| over the largest |atomic| entry:
+""")
+    for label, r in z["rows"].items():
+        lines.append(f"- {label}: repeat equal {r['ordered_bits_repeat']}, index on = off {r['ordered_bits_index_on_equal_off']}, mismatches {r['mismatches']}, "
+                     f"difference {r['max_abs_ordered_minus_atomic_over_max_abs']:.2e}")
+    lines.append("""
+Not taken: the transmittance gradient, the host-pointer forms, a profile under rocprofv3 (which of count, sort and reduction the time goes
+to), any scene but `-g 64`.
+""")
+    if resources:
+        lines.append("Resources (`tools/kernel_resources.sh raygrad`, `raytgrad` and `gradord`; template arguments: Exp (0 libm, 1 vcl), Erf (0 libm, 1 A&S), "
+                     "INDEXED, RAYS, ORDERED).  The thirty-two instantiations without ORDERED have the figures they had before the parameter was "
+                     "added, line for line; no ORDERED instantiation spills or uses scratch:\n\n```\n" + resources.rstrip() + "\n```\n")
     return "\n".join(lines)
 
 
@@ -862,6 +954,7 @@ def main():
     ap.add_argument("--transmittance-only", action="store_true")
     ap.add_argument("--depth-only", action="store_true")
     ap.add_argument("--grad-only", action="store_true")
+    ap.add_argument("--ordered-only", action="store_true")
     ap.add_argument("--tgrad-only", action="store_true")
     ap.add_argument("--rgrad-only", action="store_true")
     ap.add_argument("--scene-update-only", action="store_true")
@@ -892,6 +985,16 @@ def main():
         with open(os.path.join(a.out_dir, "ray_grad.md"), "w") as f:
             f.write(markdown_grad(z, open(res).read() if os.path.exists(res) else ""))
         print(json.dumps({"grad": z}))
+        return
+    if a.ordered_only:
+        z = part_ordered(g)
+        os.makedirs(a.out_dir, exist_ok=True)
+        with open(os.path.join(a.out_dir, "ray_grad_ordered.json"), "w") as f:
+            f.write(json.dumps({"what": "ordered against atomic gradient tables of the same rays; see tools/ray_bundles.py (go)", "ordered": z}) + "\n")
+        res = os.path.join(a.out_dir, "ray_grad_ordered_resources.txt")
+        with open(os.path.join(a.out_dir, "ray_grad_ordered.md"), "w") as f:
+            f.write(markdown_ordered(z, open(res).read() if os.path.exists(res) else ""))
+        print(json.dumps({"ordered": z}))
         return
     if a.tgrad_only:
         z = part_tgrad(g)
