@@ -6,10 +6,10 @@
 //   grad_deal         one weight dealt to one absorber: P, Q, R
 //   grad_row, _w      the row segment (d mu xyz, d sigma, d magnitude) from M, the coefficient of n and the sigma sum; with the terms in W
 //   grad_deposit      a row segment into the caller's table, wave-summed where every lane names the same row
-//   grad_record_*, grad_records_short   ORDERED: the same segments stored as records instead, and the guard of a ray's range
+//   GradSink          where a row segment goes: added to the table, or -- ORDERED -- stored in a record; the record rules and the guard of a ray's range
 //   grad_ray_add, _w, grad_ray_store   the same segment's share of the RAY's row (d origin, d direction), and the row's two stores
 //   LaneList, grad_acc, grad_walk_begin / _next, grad_flush_short   lane = ray: a lane's list, the three running sums per list position and lane in LDS, the walk of a
-//                     lane's list with the next entry's rows loaded one iteration ahead, and every position to the table once
+//                     lane's list with the next entry's rows loaded one iteration ahead, and every position to the sink once
 //   grad_emitter_place, grad_pass1, grad_pass2    the radiance gradient's emitter set-up and the bodies of its two pair loops
 #pragma once
 #include "vrt_ray_cull.hpp"
@@ -92,57 +92,115 @@ __device__ __forceinline__ void grad_deposit(float *table, uint32_t idx, bool on
     }
 }
 
-// ---- ordered gradient tables (vrt_hip_set_grad_ordered): the ORDERED instantiations store what the others add ----
+// ---- the table sink: where a row segment goes when it leaves a kernel ----
+// The only text that knows whether a segment is ADDED to the caller's table P.grad (float atomics: the sums depend on their arrival
+// order) or -- ORDERED (vrt_hip_set_grad_ordered) -- STORED in a record that vrt_grad_ordered_kernel.hip sums behind the kernel.  A kernel
+// builds one sink, tells it the ray (short_ray, long_ray: ORDERED, the guard of the ray's range) and hands it every segment once.
 // A record is (Gaussian index, ray id, GRAD_ORD_COLS floats = the table's columns 0..8) at a place of its ray's own range
-// [ord_base[r], ord_base[r] + ord_count[r]).  Every cell of a record is written by ONE thread, which may read back its own earlier
-// store; a record's first write is a store; columns nobody computes are stored as 0.  vrt_grad_ordered_kernel.hip sums them.
-template <int NV>
-__device__ __forceinline__ void grad_record_store(const RayArgs *Pp, uint64_t rec, uint32_t col0, const float (&v)[NV])
-{
-    float *row = Pp->ord_rows + rec * (uint64_t)GRAD_ORD_COLS + col0;
+// [ord_base[r], ord_base[r] + ord_count[r]); the kernels name it by that place.  The record rules, kept here and nowhere else:
+//   - every cell of a record is written by ONE thread, which may read back its own earlier store;
+//   - a thread's first write to a cell is a store, every later one (`first` = false) an add onto it;
+//   - the first write that OPENS a record (GRAD_OPEN, not GRAD_STORE) stores its name behind the segment, and zeros to the albedo columns
+//     where no segment of the kernel writes them (zero_albedo: the transmittance gradient): columns nobody computes are stored as 0.
+// Which thread owns which record, and when a write is its first, is the kernel's to say.
+enum GradFirst { GRAD_STORE, GRAD_OPEN };
+template <bool ORDERED>
+struct GradSink {
+    const RayArgs *Pp;
+    bool zero_albedo; // ORDERED: GRAD_OPEN stores zeros to columns 0..3
+    uint64_t r, base; // ORDERED, set by short_ray / long_ray: the ray and the first record of its range,
+    bool admits;      // and whether the guard lets this lane's records be stored (a lane of the short kernels)
+    __device__ __forceinline__ GradSink(const RayArgs *args, bool zeros) : Pp(args), zero_albedo(zeros) {}
+
+    // is there a table at all?  Wave-uniform.  ORDERED: always (the launch refuses a call without one).
+    __device__ __forceinline__ bool table() const { return ORDERED || Pp->grad != nullptr; }
+    // is a segment to be formed?  Without RAYS no test: the radiance gradient has its table by contract, and the transmittance gradient,
+    // which may be asked for grad_s alone, gets here only behind table().
+    template <bool RAYS>
+    __device__ __forceinline__ bool wanted() const { return !RAYS || table(); }
+
+    // A lane of the short kernels behind ray_short_begin: its ray's range, and the guard.
+    __device__ __forceinline__ void short_ray(const ShortRay &R)
+    {
+        if constexpr (ORDERED) {
+            r = R.rc;
+            base = Pp->ord_base[R.rc];
+            admits = R.writes && R.nl == Pp->ord_len[R.rc];
+            if (R.writes && !admits) mismatch(R.rc, 0u, 1u);
+        }
+    }
+    // The wave of a long kernel behind ray_long_next, `per_gauss` records per kept Gaussian: the ray's range, and the guard -- the re-cull
+    // gives the counted length, and the range is a long ray's.  false: the mismatch is filed, skip the ray.
+    __device__ __forceinline__ bool long_ray(uint64_t ray_id, uint32_t n, uint32_t per_gauss, uint32_t lane)
+    {
+        if constexpr (ORDERED) {
+            if (n != Pp->ord_len[ray_id] || Pp->ord_count[ray_id] != (uint64_t)per_gauss * n) { mismatch(ray_id, lane, 64u); return false; }
+            r = ray_id;
+            base = Pp->ord_base[ray_id];
+        }
+        return true;
+    }
+
+    // One thread's segment: NV values for columns col0.. of Gaussian idx -- added to its row, or written to record `rec` of the ray's range
+    template <int NV>
+    __device__ __forceinline__ void put(uint64_t rec, uint32_t idx, uint32_t col0, const float (&v)[NV], GradFirst how, bool first = true) const
+    {
+        if constexpr (ORDERED) {
+            float *row = Pp->ord_rows + (base + rec) * (uint64_t)GRAD_ORD_COLS;
+            if (first) {
+                if (how == GRAD_OPEN && zero_albedo) { row[0] = 0.f; row[1] = 0.f; row[2] = 0.f; row[3] = 0.f; }
 #pragma unroll
-    for (int c = 0; c < NV; ++c) row[c] = v[c];
-}
-// ... NV values onto columns col0.. of a record this thread stored before
-template <int NV>
-__device__ __forceinline__ void grad_record_add(const RayArgs *Pp, uint64_t rec, uint32_t col0, const float (&v)[NV])
-{
-    float *row = Pp->ord_rows + rec * (uint64_t)GRAD_ORD_COLS + col0;
+                for (int c = 0; c < NV; ++c) row[col0 + c] = v[c];
+                if (how == GRAD_OPEN) name(base + rec, idx);
+            } else {
 #pragma unroll
-    for (int c = 0; c < NV; ++c) row[c] = row[c] + v[c];
-}
-__device__ __forceinline__ void grad_record_zero_albedo(const RayArgs *Pp, uint64_t rec)
-{
-    const float zero[4] = { 0.f, 0.f, 0.f, 0.f };
-    grad_record_store<4>(Pp, rec, 0u, zero);
-}
-__device__ __forceinline__ void grad_record_name(const RayArgs *Pp, uint64_t rec, uint32_t idx, uint64_t r)
-{
-    Pp->ord_gauss[rec] = idx;
-    Pp->ord_ray[rec] = (uint32_t)r;
-}
-// The guard: a ray whose list is not as long as the count pass found it names every row of its range a sentinel (key = N: sorted
-// last, read by no segment), touches nothing outside the range and counts one mismatch.  Called by the lanes `lanes` apart that share
-// the ray (1: a lane of the short kernels, 64: the wave of the long ones, `first` = the lane's place among them).
-__device__ __forceinline__ void grad_record_mismatch(const RayArgs *Pp, uint64_t r, uint32_t first, uint32_t lanes)
-{
-    const uint64_t base = Pp->ord_base[r], rows = Pp->ord_count[r];
-    for (uint64_t k = first; k < rows; k += lanes) grad_record_name(Pp, base + k, Pp->S.n, r);
-    if (first == 0) atomicAdd(&Pp->ord_words[GRAD_ORD_MISMATCH], 1ull);
-}
-// A lane of the short kernels behind ray_short_begin: its ray's first record, and whether its records may be stored (the guard)
-struct ShortRecords {
-    uint64_t base;
-    bool on;
+                for (int c = 0; c < NV; ++c) row[col0 + c] = row[col0 + c] + v[c];
+            }
+        } else {
+            float *row = Pp->grad + (size_t)idx * GRAD_STRIDE + col0;
+#pragma unroll
+            for (int c = 0; c < NV; ++c) atomicAdd(row + c, v[c]);
+        }
+    }
+    // The short kernels' deposit, called by the whole wave; `on`: this lane has something.  Added through grad_deposit, wave-summed where
+    // every lane names one row -- or one record per lane, a first write, no sum across lanes: a record holds its own ray's share.
+    template <int NV>
+    __device__ __forceinline__ void deposit(uint64_t rec, uint32_t idx, bool on, const float (&v)[NV], uint32_t col0, uint32_t lane, GradFirst how) const
+    {
+        if constexpr (ORDERED) {
+            if (on && admits) put<NV>(rec, idx, col0, v, how);
+        } else
+            grad_deposit<NV>(Pp->grad, idx, on, v, col0, lane);
+    }
+    // The long radiance kernel's absorber segment, called by the whole wave: lanes 0..4 hold one column each in `mine` and add it -- or own
+    // columns 4..8 of record `rec` across the rounds, where lanes 5..8 store the zeros of columns 0..3 and lane 9 the name in the first.
+    __device__ __forceinline__ void absorber(uint64_t rec, uint32_t idx, float mine, uint32_t lane, bool first) const
+    {
+        if constexpr (ORDERED) {
+            float *row = Pp->ord_rows + (base + rec) * (uint64_t)GRAD_ORD_COLS;
+            if (lane < 5u) row[4u + lane] = first ? mine : row[4u + lane] + mine;
+            else if (first && lane < 9u) row[lane - 5u] = 0.f;
+            else if (first && lane == 9u) name(base + rec, idx);
+        } else if (lane < 5u) atomicAdd(&Pp->grad[(size_t)idx * GRAD_STRIDE + 4u + lane], mine);
+    }
+
+private:
+    __device__ __forceinline__ void name(uint64_t at, uint32_t idx) const { name_as(at, idx, r); }
+    __device__ __forceinline__ void name_as(uint64_t at, uint32_t idx, uint64_t ray_id) const
+    {
+        Pp->ord_gauss[at] = idx;
+        Pp->ord_ray[at] = (uint32_t)ray_id;
+    }
+    // A ray whose list is not as long as the count pass found it names every row of its range a sentinel (key = N: sorted last, read by no
+    // segment), touches nothing outside the range and counts one mismatch.  Called by the lanes `lanes` apart that share the ray (1: a lane
+    // of the short kernels, 64: the wave of the long ones, `first` = the lane's place among them).
+    __device__ __forceinline__ void mismatch(uint64_t ray_id, uint32_t first, uint32_t lanes) const
+    {
+        const uint64_t range = Pp->ord_base[ray_id], rows = Pp->ord_count[ray_id];
+        for (uint64_t k = first; k < rows; k += lanes) name_as(range + k, Pp->S.n, ray_id);
+        if (first == 0) atomicAdd(&Pp->ord_words[GRAD_ORD_MISMATCH], 1ull);
+    }
 };
-__device__ __forceinline__ ShortRecords grad_records_short(const RayArgs *Pp, const ShortRay &R)
-{
-    ShortRecords o;
-    o.base = Pp->ord_base[R.rc];
-    o.on = R.writes && R.nl == Pp->ord_len[R.rc];
-    if (R.writes && !o.on) grad_record_mismatch(Pp, R.rc, 0u, 1u);
-    return o;
-}
 
 // One weight w dealt to one absorber at x = x_ikj (or x_kj), E = Erf(-mubar_j r_j): P += w D, Q += w e2, R += w e2 x.  Returns w e2.
 template <int EXP, int ERF>
@@ -249,16 +307,13 @@ __device__ __forceinline__ GradGauss grad_walk_next(ListWalk &w, const SceneTabl
     return grad_gauss<EXP, ERF>(erf, ca, cb, L.has(j), ray);
 }
 
-// Every list position to the table once, now that W is known, and -- RAYS -- the same segments to the lane's ray row in list order,
-// stored once where the lane `writes`.  With RAYS the table may be missing (table == nullptr, wave-uniform: no add is issued); without,
-// it is there, and this is the text the kernels ran before there were ray rows.  The whole wave calls this.
-// ORDERED: position p's segment is STORED to record base + p of the lane's ray (rec_on: the lane's list is as long as the count pass found
-// it), with its name; zero_albedo: and zeros to its columns 0..3, which nobody else writes (the transmittance gradient).
-template <int EXP, int ERF, bool RAYS, bool ORDERED = false>
-__device__ __forceinline__ void grad_flush_short(float *table, [[maybe_unused]] float *grad_rays, [[maybe_unused]] uint64_t r, [[maybe_unused]] bool writes,
-                                                 const SceneTables &S, const ErfEval<ERF> &erf, const LaneList &L, float *s_acc, const LaneRay &ray, float W,
-                                                 [[maybe_unused]] const RayArgs *Pp = nullptr, [[maybe_unused]] uint64_t base = 0,
-                                                 [[maybe_unused]] bool rec_on = false, [[maybe_unused]] bool zero_albedo = false)
+// Every list position to the sink once, now that W is known (position p: record p of the lane's ray, opened here), and -- RAYS -- the same
+// segments to the lane's ray row in list order, stored once where the lane `writes`.  With RAYS the table may be missing (wave-uniform:
+// no segment is formed); without, it is there, and this is the text the kernels ran before there were ray rows.  The whole wave calls this.
+template <int EXP, int ERF, bool RAYS, bool ORDERED>
+__device__ __forceinline__ void grad_flush_short(const GradSink<ORDERED> &sink, [[maybe_unused]] float *grad_rays, [[maybe_unused]] uint64_t r,
+                                                 [[maybe_unused]] bool writes, const SceneTables &S, const ErfEval<ERF> &erf, const LaneList &L, float *s_acc,
+                                                 const LaneRay &ray, float W)
 {
     const uint32_t lane = L.lane;
     [[maybe_unused]] float go[3] = { 0.f, 0.f, 0.f }, gn[3] = { 0.f, 0.f, 0.f };
@@ -270,17 +325,10 @@ __device__ __forceinline__ void grad_flush_short(float *table, [[maybe_unused]] 
         if constexpr (RAYS) {
             if (on) grad_ray_add_w<EXP>(q, ray, mag, grad_acc(s_acc, 0, p, lane), grad_acc(s_acc, 1, p, lane), W, go, gn);
         }
-        if (!RAYS || table) {
+        if (sink.template wanted<RAYS>()) {
             float d[5];
             grad_row_w<EXP>(q, ray, mag, grad_acc(s_acc, 0, p, lane), grad_acc(s_acc, 1, p, lane), grad_acc(s_acc, 2, p, lane), W, d);
-            if constexpr (ORDERED) {
-                if (on && rec_on) {
-                    if (zero_albedo) grad_record_zero_albedo(Pp, base + p);
-                    grad_record_store<5>(Pp, base + p, 4u, d);
-                    grad_record_name(Pp, base + p, idx, r);
-                }
-            } else
-            grad_deposit<5>(table, idx, on, d, 4u, lane);
+            sink.template deposit<5>(p, idx, on, d, 4u, lane, GRAD_OPEN);
         }
     }
     if constexpr (RAYS) {
@@ -331,6 +379,17 @@ __device__ __forceinline__ void grad_pass2(const ErfEval<ERF> &erf, const GradGa
             y[e] = __builtin_fmaf(kf, t, y[e]);
         }
     }
+}
+
+// ---- the launch: a bundle's run-time switches INDEXED and RAYS as the constants I.value, R.value of a generic callable f(I, R) ----
+template <class F>
+inline void grad_dispatch_indexed_rays(bool indexed, bool rays, F &&f)
+{
+    if (rays) {
+        if (indexed) f(std::true_type(), std::true_type());
+        else f(std::false_type(), std::true_type());
+    } else if (indexed) f(std::true_type(), std::false_type());
+    else f(std::false_type(), std::false_type());
 }
 
 } // namespace vrtk

@@ -20,7 +20,7 @@
 //                          sum: 24 KB next to the 8 KB of lists) take the chunks' shares (ray_grad_chunk: two walks of the lane's list
 //                          through grad_walk_begin / grad_walk_next, their bodies grad_pass1 and grad_pass2); when all chunks are
 //                          through, W is known and every position is dealt to the caller's table once (grad_flush_short: grad_row_w,
-//                          then grad_deposit): 9 atomic adds per (ray, kept Gaussian) -- 4 (albedo) behind the emitter's chunk, 5 at the
+//                          then the sink's deposit): 9 atomic adds per (ray, kept Gaussian) -- 4 (albedo) behind the emitter's chunk, 5 at the
 //                          end.  Where a position holds the same scene index in every lane that has one (a coherent bundle), the values
 //                          are summed over the wave (wave_sum) and ONE row segment is added.
 //   ray_long_grad_kernel   one wave per ray, lane = emitter, the absorber wave-uniform: the same grad_pass1 and grad_pass2; P, Q, R are
@@ -30,16 +30,15 @@
 // Exp / Erf of the forward quantities are the selected pair's; e1 and e2 are exp_neg_sq<EXP>.  Only {vcl, libm} x {A&S, libm} are
 // instantiated: the piecewise approximations have jumps, and the entry point refuses them.
 // The sums in the caller's table depend on the arrival order of the atomic adds: not bitwise reproducible -- unless ORDERED
-// (vrt_hip_set_grad_ordered): a template parameter of both kernels, instantiated in vrt_ray_grad_ordered_kernel.hip, with which every add
-// into the table becomes a store into a record of the ray's own range and the table is not touched (vrt_ray_grad.hpp has the record
-// rules, vrt_grad_ordered_kernel.hip the count pass before and the sort and the reduction behind).  <.., false> is each kernel as it is.
+// (vrt_hip_set_grad_ordered): a template parameter of both kernels, instantiated in vrt_ray_grad_ordered_kernel.hip.  Where a segment
+// goes is GradSink's (vrt_ray_grad.hpp, with the record rules); the kernels say which lane owns which record and when a write is the first.
 // RAYS (vrt_hip_radiance_rays_grad_rays*): d(loss) / d(origin, direction) of every ray as well, one stored row per ray (grad_ray_add of
 // vrt_ray_grad.hpp beside every grad_row; DESIGN.md section 4, "Ray gradients"): summed per lane in list order (short) or per lane and then
 // over the wave in its fixed order (long), no atomic add, bitwise reproducible.  With RAYS the table may be missing (P.grad == nullptr): no
 // table add is issued.  RAYS is a template parameter: <.., false> is the kernel from before there were ray rows, register for register.
 // Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
 // What lives where: this file has the emitter's weights (grad_emitter), the chunk of the short kernel, the two kernels' own loops -- how
-// the absorber is loaded (per lane; readfirstlane + uload) and where a sum goes (LDS; the table) -- and the launch.  Every formula named
+// the absorber is loaded (per lane; readfirstlane + uload) and where a sum goes (LDS; the sink) -- and the launch.  Every formula named
 // above is vrt_ray_grad.hpp's, shared with vrt_ray_trans_grad_kernel.hip.
 #include "vrt_ray_grad.hpp"
 
@@ -61,12 +60,11 @@ __device__ __forceinline__ float grad_emitter(bool on, float sigma, float d2, fl
     return on ? V : 0.f; // a lane without this emitter: exact zeros, whatever its exponents came to
 }
 
-// One chunk of EC emitters (list positions i0 .. i0+EC-1 of every lane) against the lane's whole list, both passes.
-// ORDERED: the albedo columns are stored to the records rec.base + position (rec.on: the guard admits this lane's records)
+// One chunk of EC emitters (list positions i0 .. i0+EC-1 of every lane) against the lane's whole list, both passes.  The albedo
+// columns of position p leave here, for record p of the lane's ray: its first write to them (the flush opens the record).
 template <int EXP, int ERF, int EC, bool RAYS, bool ORDERED>
-__device__ __forceinline__ void ray_grad_chunk(const RayArgs *Pp, const SceneTables *Sp, const uint32_t *s_list /*[k*64 + lane]*/, float *s_acc, uint32_t nl,
-                                               uint32_t nmax, uint32_t lane, const LaneRay &ray, uint32_t i0, float4 g, float &W,
-                                               [[maybe_unused]] const ShortRecords &rec)
+__device__ __forceinline__ void ray_grad_chunk(const GradSink<ORDERED> &sink, const SceneTables *Sp, const uint32_t *s_list /*[k*64 + lane]*/, float *s_acc,
+                                               uint32_t nl, uint32_t nmax, uint32_t lane, const LaneRay &ray, uint32_t i0, float4 g, float &W)
 {
     const SceneTables &S = *Sp;
     const ErfEval<ERF> erf;
@@ -103,10 +101,7 @@ __device__ __forceinline__ void ray_grad_chunk(const RayArgs *Pp, const SceneTab
         W = __builtin_fmaf(GV[e], mag, W);
         const float mV = mag * V;
         const float da[4] = { g.x * mV, g.y * mV, g.z * mV, g.w * mV };
-        if constexpr (ORDERED) {
-            if (on && rec.on) grad_record_store<4>(Pp, rec.base + i0 + e, 0u, da);
-        } else
-        if (!RAYS || Pp->grad) grad_deposit<4>(Pp->grad, idx, on, da, 0u, lane);
+        if (sink.template wanted<RAYS>()) sink.template deposit<4>((uint64_t)i0 + e, idx, on, da, 0u, lane, GRAD_STORE);
     }
 
     // ---- pass 2: the same pairs again; w_ik to the absorbers (P, Q, R) and through w e2 A C r back to the emitters (Z, Y) ----
@@ -133,9 +128,8 @@ __device__ __forceinline__ void ray_grad_chunk(const RayArgs *Pp, const SceneTab
 }
 
 // RAYS: the ray rows are asked for (P.grad_rays != nullptr), and then the table may be missing; without, the table is there.
-// ORDERED (vrt_hip_set_grad_ordered, the table is there): one record per list position at ord_base[r] + position -- the albedo columns at
-// the emitter's chunk, columns 4..8 and the name at the flush, no sum across lanes: a record holds its own ray's share.  <.., false> is the
-// kernel as it is without.
+// ORDERED: one record per list position, the lane's own -- the albedo columns at the emitter's chunk, columns 4..8 and the name at the
+// flush.  <.., false> is the kernel as it is without.
 template <int EXP, int ERF, bool INDEXED, bool RAYS, bool ORDERED = false>
 __global__ __launch_bounds__(64) void ray_short_grad_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
@@ -148,8 +142,8 @@ __global__ __launch_bounds__(64) void ray_short_grad_kernel(RayArgs) // read thr
     const uint32_t nl = R.nl, nmax = R.nmax;
     const LaneRay &ray = R.ray;
     const float4 g = P.grad_radiance[R.rc];
-    [[maybe_unused]] ShortRecords rec = { 0, false };
-    if constexpr (ORDERED) rec = grad_records_short(&P, R);
+    GradSink<ORDERED> sink(&P, false);
+    sink.short_ray(R);
 
     for (uint32_t p = 0; p < nmax; ++p)
 #pragma unroll
@@ -159,23 +153,22 @@ __global__ __launch_bounds__(64) void ray_short_grad_kernel(RayArgs) // read thr
     constexpr int EC = 4;
     for (uint32_t i0 = 0; i0 < nmax; i0 += EC) {
         const uint32_t rem = nmax - i0;
-        if (rem >= (uint32_t)EC) ray_grad_chunk<EXP, ERF, EC, RAYS, ORDERED>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W, rec);
-        else if (rem == 3) ray_grad_chunk<EXP, ERF, 3, RAYS, ORDERED>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W, rec);
-        else if (rem == 2) ray_grad_chunk<EXP, ERF, 2, RAYS, ORDERED>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W, rec);
-        else ray_grad_chunk<EXP, ERF, 1, RAYS, ORDERED>(&P, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W, rec);
+        if (rem >= (uint32_t)EC) ray_grad_chunk<EXP, ERF, EC, RAYS>(sink, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
+        else if (rem == 3) ray_grad_chunk<EXP, ERF, 3, RAYS>(sink, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
+        else if (rem == 2) ray_grad_chunk<EXP, ERF, 2, RAYS>(sink, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
+        else ray_grad_chunk<EXP, ERF, 1, RAYS>(sink, &S, s_list, s_acc, nl, nmax, lane, ray, i0, g, W);
     }
 
-    grad_flush_short<EXP, ERF, RAYS, ORDERED>(P.grad, P.grad_rays, R.rc, R.writes, S, ErfEval<ERF>(), LaneList{ s_list, lane, nl, nmax }, s_acc, ray, W, &P,
-                                              rec.base, rec.on, false);
+    grad_flush_short<EXP, ERF, RAYS>(sink, P.grad_rays, R.rc, R.writes, S, ErfEval<ERF>(), LaneList{ s_list, lane, nl, nmax }, s_acc, ray, W);
 }
 
 // One wave per long ray, lane = emitter (EC rounds of 64 at a time), the absorber wave-uniform.  RAYS: as in the short kernel.  A template
 // parameter in all four gradient kernels: with a pointer test the six accumulators cost this one an occupancy step in five of its eight
 // instantiations, and the others a fraction of a percent of their time (profiles/ray_grad_rays.md); <.., false> is each kernel as it was.
-// ORDERED: two records per kept Gaussian in the ray's range.  The EMITTER record of position p (ord_base[r] + p) belongs to the lane that
-// holds p as an emitter, lane p mod 64, in its round and again in the last walk: the albedo columns, the emitter's own terms, then the W
-// terms onto its own stores.  The ABSORBER record of position j (ord_base[r] + n + j): lanes 0..4 own columns 4..8 and accumulate grad_row of
-// the wave-summed P, Q, R over the rounds, lanes 5..8 store the zeros of columns 0..3 and lane 9 the name in the first round.
+// ORDERED: two records per kept Gaussian in the ray's range.  The EMITTER record of position p (record p) belongs to the lane that holds p
+// as an emitter, lane p mod 64, in its round and again in the last walk: it opens it with the albedo columns, stores the emitter's own
+// terms, then adds the W terms onto its own stores.  The ABSORBER record of position j (record n + j) is the wave's (GradSink::absorber),
+// its first write in the first round.
 template <int EXP, int ERF, bool INDEXED, bool RAYS, bool ORDERED = false>
 __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
 {
@@ -185,19 +178,15 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
     const uint32_t lane = threadIdx.x & 63u;
     const ErfEval<ERF> erf;
     constexpr int EC = 2;
-    const bool table = !RAYS || P.grad != nullptr; // wave-uniform
+    GradSink<ORDERED> sink(&P, false);
+    const bool table = sink.template wanted<RAYS>(); // wave-uniform
 
     LongRay L = ray_long_begin(&P);
     while (ray_long_next<INDEXED>(&P, &S, s_list, lane, L)) {
         const LaneRay ray = L.ray;
         const uint32_t n = L.n;
         const float4 g = P.grad_radiance[L.r];
-        [[maybe_unused]] uint64_t base = 0;
-        if constexpr (ORDERED) {
-            // the guard: the re-cull gives the counted length, and the ray's range is a long ray's
-            if (n != P.ord_len[L.r] || P.ord_count[L.r] != 2ull * n) { grad_record_mismatch(&P, L.r, lane, 64u); continue; }
-            base = P.ord_base[L.r];
-        }
+        if (!sink.long_ray(L.r, n, 2u, lane)) continue;
         float W = 0.f; // this lane's emitters; summed over the wave behind the rounds
         [[maybe_unused]] float go[3] = { 0.f, 0.f, 0.f }, gn[3] = { 0.f, 0.f, 0.f }; // this lane's shares of the ray's row; summed over the wave behind the last walk
         for (uint32_t e0 = 0; e0 < n; e0 += 64u * EC) {
@@ -232,19 +221,10 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
                 const float V = grad_emitter<EXP>(e_on[e], e_sigma[e], q.d2, 0.5f * q.inv_s2, G * e_mag[e], acc[e], w[e]);
                 GV[e] = G * V;
                 W = __builtin_fmaf(GV[e], e_mag[e], W);
-                if constexpr (ORDERED) {
-                    if (e_on[e]) {
-                        const float mV = e_mag[e] * V;
-                        const float da[4] = { g.x * mV, g.y * mV, g.z * mV, g.w * mV };
-                        const uint64_t rec = base + e0 + (uint32_t)e * 64u + lane;
-                        grad_record_store<4>(&P, rec, 0u, da);
-                        grad_record_name(&P, rec, e_idx[e], L.r);
-                    }
-                } else
                 if (table && e_on[e]) {
                     const float mV = e_mag[e] * V;
-                    float *row = P.grad + (size_t)e_idx[e] * GRAD_STRIDE;
-                    atomicAdd(row + 0, g.x * mV); atomicAdd(row + 1, g.y * mV); atomicAdd(row + 2, g.z * mV); atomicAdd(row + 3, g.w * mV);
+                    const float da[4] = { g.x * mV, g.y * mV, g.z * mV, g.w * mV };
+                    sink.template put<4>((uint64_t)e0 + (uint32_t)e * 64u + lane, e_idx[e], 0u, da, GRAD_OPEN);
                 }
             }
             // ---- pass 2: per absorber P, Q, R over the wave, one row segment by lanes 0..4 ----
@@ -259,21 +239,10 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
                 Pj = wave_sum(Pj); Qj = wave_sum(Qj); Rj = wave_sum(Rj);
                 const float mag = uload(S.gD, idx).z;
                 if (RAYS && lane == 0) grad_ray_add(q, ray, mag, q.Am * Pj, q.Ar * Qj, go, gn); // wave-uniform: one lane takes it
-                if constexpr (ORDERED) {
-                    float d[5];
-                    grad_row(q, ray, mag, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, d);
-                    const float mine = lane == 0 ? d[0] : lane == 1 ? d[1] : lane == 2 ? d[2] : lane == 3 ? d[3] : d[4];
-                    const uint64_t rec = base + n + j;
-                    float *row = P.ord_rows + rec * (uint64_t)GRAD_ORD_COLS;
-                    if (lane < 5u) row[4u + lane] = e0 == 0u ? mine : row[4u + lane] + mine;
-                    else if (e0 == 0u && lane < 9u) row[lane - 5u] = 0.f;
-                    else if (e0 == 0u && lane == 9u) grad_record_name(&P, rec, idx, L.r);
-                } else
                 if (table) {
                     float d[5];
                     grad_row(q, ray, mag, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, d);
-                    const float mine = lane == 0 ? d[0] : lane == 1 ? d[1] : lane == 2 ? d[2] : lane == 3 ? d[3] : d[4];
-                    if (lane < 5u) atomicAdd(&P.grad[(size_t)idx * GRAD_STRIDE + 4u + lane], mine);
+                    sink.absorber((uint64_t)n + j, idx, lane == 0 ? d[0] : lane == 1 ? d[1] : lane == 2 ? d[2] : lane == 3 ? d[3] : d[4], lane, e0 == 0u);
                 }
             }
             // ---- the emitters' own terms: every lane another row ----
@@ -282,17 +251,10 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
                 if (e_on[e]) {
                     const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[e_idx[e]], S.gB[e_idx[e]], true, ray);
                     if constexpr (RAYS) grad_ray_add(q, ray, e_mag[e], GV[e], -z[e], go, gn);
-                    if constexpr (ORDERED) {
-                        float d[5];
-                        grad_row(q, ray, e_mag[e], GV[e], -z[e], -y[e], d);
-                        grad_record_store<5>(&P, base + e0 + (uint32_t)e * 64u + lane, 4u, d);
-                    } else
                     if (table) {
                         float d[5];
                         grad_row(q, ray, e_mag[e], GV[e], -z[e], -y[e], d);
-                        float *row = P.grad + (size_t)e_idx[e] * GRAD_STRIDE;
-#pragma unroll
-                        for (int c = 0; c < 5; ++c) atomicAdd(row + 4 + c, d[c]);
+                        sink.template put<5>((uint64_t)e0 + (uint32_t)e * 64u + lane, e_idx[e], 4u, d, GRAD_STORE);
                     }
                 }
             }
@@ -306,14 +268,9 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
                 const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], true, ray);
                 const float ArEW = q.Ar * exp_neg_sq<EXP>(q.m) * W;
                 if constexpr (RAYS) grad_ray_add(q, ray, 0.f, 0.f, -ArEW, go, gn);
-                if constexpr (ORDERED) {
-                    const float dw[4] = { -ArEW * ray.nx, -ArEW * ray.ny, -ArEW * ray.nz, ArEW * q.m * SQRT_2 };
-                    grad_record_add<4>(&P, base + p, 4u, dw); // onto this lane's own stores: p mod 64 is its lane in every round
-                } else
                 if (table) {
-                    float *row = P.grad + (size_t)idx * GRAD_STRIDE;
-                    atomicAdd(row + 4, -ArEW * ray.nx); atomicAdd(row + 5, -ArEW * ray.ny); atomicAdd(row + 6, -ArEW * ray.nz);
-                    atomicAdd(row + 7, ArEW * q.m * SQRT_2);
+                    const float dw[4] = { -ArEW * ray.nx, -ArEW * ray.ny, -ArEW * ray.nz, ArEW * q.m * SQRT_2 };
+                    sink.template put<4>(p, idx, 4u, dw, GRAD_STORE, false); // onto this lane's own stores: p mod 64 is its lane in every round
                 }
             }
         }
@@ -330,11 +287,9 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
 template <int EXP, int ERF>
 static void launch_ray_grad_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
 {
-    if (a.grad_rays) {
-        if (indexed) launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, true, true>, ray_long_grad_kernel<EXP, ERF, true, true>, a, long_grid, st);
-        else launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, false, true>, ray_long_grad_kernel<EXP, ERF, false, true>, a, long_grid, st);
-    } else if (indexed) launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, true, false>, ray_long_grad_kernel<EXP, ERF, true, false>, a, long_grid, st);
-    else launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, false, false>, ray_long_grad_kernel<EXP, ERF, false, false>, a, long_grid, st);
+    grad_dispatch_indexed_rays(indexed, a.grad_rays != nullptr, [&](auto I, auto R) {
+        launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, I.value, R.value, false>, ray_long_grad_kernel<EXP, ERF, I.value, R.value, false>, a, long_grid, st);
+    });
 }
 // the four pairs of VRT_DISPATCH_GRAD_PAIR; out of line here because the entry points' check (vrt_hip_rays.cpp) asks too
 bool ray_grad_pair_supported(int exp_kind, int erf_kind)
@@ -351,11 +306,9 @@ void launch_ray_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, 
 template <int EXP, int ERF>
 static void launch_ray_grad_bundle_ordered_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
 {
-    if (a.grad_rays) {
-        if (indexed) launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, true, true, true>, ray_long_grad_kernel<EXP, ERF, true, true, true>, a, long_grid, st);
-        else launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, false, true, true>, ray_long_grad_kernel<EXP, ERF, false, true, true>, a, long_grid, st);
-    } else if (indexed) launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, true, false, true>, ray_long_grad_kernel<EXP, ERF, true, false, true>, a, long_grid, st);
-    else launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, false, false, true>, ray_long_grad_kernel<EXP, ERF, false, false, true>, a, long_grid, st);
+    grad_dispatch_indexed_rays(indexed, a.grad_rays != nullptr, [&](auto I, auto R) {
+        launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, I.value, R.value, true>, ray_long_grad_kernel<EXP, ERF, I.value, R.value, true>, a, long_grid, st);
+    });
 }
 void launch_ray_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
 {

@@ -23,7 +23,7 @@
 //                                sums per list position and lane in LDS (grad_acc: A P / mag, the coefficient of n without its W term,
 //                                the sigma sum without its W term: 24 KB next to the 8 KB of lists).  Only W is carried beside them:
 //                                e1_j comes back from grad_gauss.  After the last group every position goes to the table ONCE
-//                                (grad_flush_short: grad_row_w, then grad_deposit): 5 adds per (ray, kept Gaussian) whatever ns is,
+//                                (grad_flush_short: grad_row_w, then the sink's deposit): 5 adds per (ray, kept Gaussian) whatever ns is,
 //                                wave-summed where a position holds one row in all lanes.
 //   ray_long_trans_grad_kernel   one wave per queued ray, lane l takes entries l, l + 64, ...  The list has no bound, so no per-entry
 //                                sum waits in LDS: the samples are cut into chunks of NSC = 512.  E_k and S_k of a chunk's samples come
@@ -39,8 +39,7 @@
 // Exp / Erf of the forward quantities are the selected pair's; e1 and e2 are exp_neg_sq<EXP>.  Only {vcl, libm} x {A&S, libm} are
 // instantiated (ray_grad_pair_supported).  The sums in the caller's table depend on the arrival order of the atomic adds: not bitwise
 // reproducible -- unless ORDERED (vrt_hip_set_grad_ordered): a template parameter of both kernels, instantiated in
-// vrt_ray_trans_grad_ordered_kernel.hip, with which every add into the table becomes a store into a record of the ray's own range
-// (vrt_ray_grad.hpp has the record rules, vrt_grad_ordered_kernel.hip what runs before and behind).
+// vrt_ray_trans_grad_ordered_kernel.hip.  Where a segment goes is GradSink's (vrt_ray_grad.hpp, with the record rules).
 // Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
 // What lives where: this file has what a sample is (trans_grad_live, trans_grad_x, trans_grad_weight), the two kernels' loops over groups
 // and chunks of samples, and the launch.  The helpers named above are vrt_ray_grad.hpp's, shared with vrt_ray_grad_kernel.hip.
@@ -81,8 +80,7 @@ __device__ __forceinline__ bool trans_grad_live(bool depth_mode, float s, float 
 __device__ __forceinline__ float trans_grad_x(float s, const GradGauss &q) { return (s - q.mubar) * q.r; }
 
 // RAYS: the ray rows are asked for (P.grad_rays != nullptr); without, each kernel is the text it was before there were ray rows.
-// ORDERED (vrt_hip_set_grad_ordered, the table is there): one record per list position at ord_base[r] + position, stored whole at the
-// flush -- zeros in columns 0..3, no sum across lanes.  <.., false> is the kernel as it is without.
+// ORDERED: one record per list position, the lane's own, opened and stored whole at the flush.  <.., false> is the kernel as it is without.
 template <int EXP, int ERF, bool INDEXED, bool RAYS, bool ORDERED = false>
 __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
@@ -156,16 +154,14 @@ __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // re
             }
         }
     }
-    if constexpr (ORDERED) {
-        const ShortRecords rec = grad_records_short(&P, R);
-        grad_flush_short<EXP, ERF, RAYS, true>(P.grad, P.grad_rays, R.rc, R.writes, S, erf, L, s_acc, ray, W, &P, rec.base, rec.on, true);
-    } else
-    if (RAYS || P.grad) grad_flush_short<EXP, ERF, RAYS>(P.grad, P.grad_rays, R.rc, R.writes, S, erf, L, s_acc, ray, W);
+    GradSink<ORDERED> sink(&P, true);
+    sink.short_ray(R);
+    if (RAYS || sink.table()) grad_flush_short<EXP, ERF, RAYS>(sink, P.grad_rays, R.rc, R.writes, S, erf, L, s_acc, ray, W);
 }
 
 // One wave per long ray, lane l takes entries l, l + 64, ...; the samples in chunks of NSC.
-// ORDERED: one record per entry at ord_base[r] + p, owned by the lane that takes entry p: stored whole (zeros in columns 0..3, the name)
-// with the first chunk of samples, the later chunks' segments added onto the lane's own stores.
+// ORDERED: one record per entry, record p owned by the lane that takes entry p: opened with the first chunk of samples, the later chunks'
+// segments added onto the lane's own stores.
 template <int EXP, int ERF, bool INDEXED, bool RAYS, bool ORDERED = false>
 __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
 {
@@ -185,12 +181,8 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
         const float *sp = P.s + (P.s_per_ray ? L.r * ns : 0ull);
         const float *gp = P.grad_T + L.r * ns;
         float *gsp = P.grad_s ? P.grad_s + L.r * ns : nullptr;
-        [[maybe_unused]] uint64_t base = 0;
-        if constexpr (ORDERED) {
-            // the guard: the re-cull gives the counted length, and the ray's range is a long ray's
-            if (n != P.ord_len[L.r] || P.ord_count[L.r] != 1ull * n) { grad_record_mismatch(&P, L.r, lane, 64u); continue; }
-            base = P.ord_base[L.r];
-        }
+        GradSink<ORDERED> sink(&P, true); // per ray: built outside, the range's base is carried round this loop (profiles/grad_sink_refactor.md)
+        if (!sink.long_ray(L.r, n, 1u, lane)) continue;
         [[maybe_unused]] float go[3] = { 0.f, 0.f, 0.f }, gn[3] = { 0.f, 0.f, 0.f }; // this lane's shares of the ray's row, over its entries and all chunks
         for (uint64_t c0 = 0; c0 < ns; c0 += NSC) {
             const uint32_t nc = (uint32_t)(ns - c0 < (uint64_t)NSC ? ns - c0 : (uint64_t)NSC);
@@ -235,7 +227,7 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
             }
             __syncthreads(); // the chunk's weights are in LDS
             // ---- every lane its entries, the chunk's samples in the inner loop ----
-            if (RAYS || P.grad) {
+            if (RAYS || sink.table()) {
                 for (uint32_t p = lane; p < n; p += 64u) {
                     const uint32_t idx = long_list_entry(s_list, L.slot, p);
                     const GradGauss q = grad_gauss<EXP, ERF>(erf, S.mu_sig[idx], S.gB[idx], true, ray);
@@ -244,21 +236,10 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
                     for (uint32_t k = 0; k < nc; ++k) grad_deal<EXP>(erf, s_w[k], trans_grad_x(s_s[k], q), q.E, Pj, Qj, Rj);
                     const float mag = S.gD[idx].z;
                     if constexpr (RAYS) grad_ray_add_w<EXP>(q, ray, mag, q.Am * Pj, q.Ar * Qj, Wc, go, gn);
-                    if constexpr (ORDERED) {
+                    if (sink.table()) {
                         float d[5];
                         grad_row_w<EXP>(q, ray, mag, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, Wc, d);
-                        if (c0 == 0) {
-                            grad_record_zero_albedo(&P, base + p);
-                            grad_record_store<5>(&P, base + p, 4u, d);
-                            grad_record_name(&P, base + p, idx, L.r);
-                        } else grad_record_add<5>(&P, base + p, 4u, d);
-                    } else
-                    if (P.grad) {
-                        float d[5];
-                        grad_row_w<EXP>(q, ray, mag, q.Am * Pj, q.Ar * Qj, q.Ar * Rj * SQRT_2, Wc, d);
-                        float *row = P.grad + (size_t)idx * GRAD_STRIDE;
-#pragma unroll
-                        for (int c = 0; c < 5; ++c) atomicAdd(row + 4 + c, d[c]);
+                        sink.template put<5>(p, idx, 4u, d, GRAD_OPEN, c0 == 0);
                     }
                 }
             }
@@ -277,11 +258,9 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
 template <int EXP, int ERF>
 static void launch_ray_trans_grad_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
 {
-    if (a.grad_rays) {
-        if (indexed) launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, true, true>, ray_long_trans_grad_kernel<EXP, ERF, true, true>, a, long_grid, st);
-        else launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, false, true>, ray_long_trans_grad_kernel<EXP, ERF, false, true>, a, long_grid, st);
-    } else if (indexed) launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, true, false>, ray_long_trans_grad_kernel<EXP, ERF, true, false>, a, long_grid, st);
-    else launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, false, false>, ray_long_trans_grad_kernel<EXP, ERF, false, false>, a, long_grid, st);
+    grad_dispatch_indexed_rays(indexed, a.grad_rays != nullptr, [&](auto I, auto R) {
+        launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, I.value, R.value, false>, ray_long_trans_grad_kernel<EXP, ERF, I.value, R.value, false>, a, long_grid, st);
+    });
 }
 void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
 {
@@ -292,11 +271,9 @@ void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool ind
 template <int EXP, int ERF>
 static void launch_ray_trans_grad_bundle_ordered_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
 {
-    if (a.grad_rays) {
-        if (indexed) launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, true, true, true>, ray_long_trans_grad_kernel<EXP, ERF, true, true, true>, a, long_grid, st);
-        else launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, false, true, true>, ray_long_trans_grad_kernel<EXP, ERF, false, true, true>, a, long_grid, st);
-    } else if (indexed) launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, true, false, true>, ray_long_trans_grad_kernel<EXP, ERF, true, false, true>, a, long_grid, st);
-    else launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, false, false, true>, ray_long_trans_grad_kernel<EXP, ERF, false, false, true>, a, long_grid, st);
+    grad_dispatch_indexed_rays(indexed, a.grad_rays != nullptr, [&](auto I, auto R) {
+        launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, I.value, R.value, true>, ray_long_trans_grad_kernel<EXP, ERF, I.value, R.value, true>, a, long_grid, st);
+    });
 }
 void launch_ray_trans_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
 {

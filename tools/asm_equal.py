@@ -17,7 +17,7 @@ LABEL_NUMBERS = [(re.compile(r"\.LBB\d+_"), ".LBB_"), (re.compile(r"\.Ltmp\d+"),
 
 
 def kernels(directory):
-    """{symbol: (code lines, {resource: value})} of every kernel in the directory's listings; a symbol seen twice is an error"""
+    """{symbol: (code lines, {resource: value})} of every kernel in the directory's listings; a symbol seen twice with two texts is an error"""
     out = {}
     for path in sorted(glob.glob(os.path.join(directory, "*.s"))):
         name, code, res = None, [], {}
@@ -28,8 +28,8 @@ def kernels(directory):
                 name, code, res = m.group(1), [], {}
             elif name and line.startswith(".Lfunc_end"):
                 if res:  # only kernels have a descriptor; device functions that were not inlined do not
-                    if name in out:
-                        sys.exit(f"{directory}: kernel {name} is defined twice")
+                    if name in out and out[name] != (code, res):  # the same text twice: a header-only library's kernel in two units
+                        sys.exit(f"{directory}: kernel {name} is defined twice, differently")
                     out[name] = (code, res)
                 name = None
             elif name and line.startswith(".amdhsa_"):

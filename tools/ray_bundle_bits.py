@@ -19,7 +19,13 @@ tests/grad_bundle_scenes.py; the axial ray of the stack at RAY_PL and RAY_PL + 1
 per-ray kernels' case with one entry in the scratch slot), and one wave of 64 near-axial rays that all keep the stack of RAY_PL (one row
 per list position in every lane: the wave-summed deposit).  The transmittance kind with 1, 4 and 5 samples -- the wide stack's ray
 also with NSC and NSC + 1, one and two chunks of the one-wave-per-ray kernel: two adds per address from one lane -- in both `wrt`
-modes, with and without the table and the per-sample output, which is stored, not added.  What is reproducible is for two runs of ONE build to say:
+modes, with and without the table and the per-sample output, which is stored, not added.  Every one of these calls again with the
+ray rows (want_rays: the RAYS kernels), rows alone and rows with the table -- rows alone for the wave of 64; the rows are stored, not
+added, and compare on every bundle.  Then the ORDERED kernels (set_grad_ordered: reproducible by contract): the same bundles and three
+of the 130-ray bundles above (the stack at RAY_PL + 1, the wide stack at RAY_LCAP + 1 and the scattered rays: long and short rays in
+one wave, whole waves and a ragged last one, the scratch slot), both kinds of gradient without and with the ray rows, the wide stacks
+also with NSC + 1 samples -- the table, the ray rows, and the count and sha256 of grad_records() (130 rays x 1025 kept x 2 records are
+12 MB a call).  What is reproducible without the contract is for two runs of ONE build to say:
 
     VRT_HIP_LIB=<build A> ... --grad-only --out a1.npz
     VRT_HIP_LIB=<build A> ... --grad-only --out a2.npz --against a1.npz
@@ -126,6 +132,53 @@ def table_of(cols):
     return np.column_stack([cols["albedo"], cols["mu"], cols["sigma"], cols["magnitude"]])
 
 
+def rows_of(rows):
+    """ray_grad_columns undone: [nrays, 6]"""
+    return np.column_stack([rows["origin"], rows["dir"]])
+
+
+def records_of(r):
+    """the count and the sha256 of grad_records() of the last ordered call, as 9 words"""
+    gauss, ray, rows = r.grad_records()
+    digest = hashlib.sha256(gauss.tobytes() + ray.tobytes() + rows.tobytes()).digest()
+    return np.concatenate([[len(gauss)], np.frombuffer(digest, np.uint32)]).astype(np.uint32).view(f32)
+
+
+def run_grad_ordered(r, res):
+    """The ORDERED kernels, without and with the ray rows; the switch is off again behind them."""
+    bundles = [(name, g, o, d, GRAD_COUNTS + ((NSC + 1,) if name.startswith("wide") else ())) for name, g, o, d, _ in grad_cases()]
+    bundles += [(f"{name}_{NRAYS}rays", g, on, d, GRAD_COUNTS + ((NSC + 1,) if name.startswith("wide") else ()))
+                for name, g, _, on, d in cases() if name in ("stack%d" % (S.RAY_PL + 1), "wide%d" % (S.RAY_LCAP + 1), "scattered")]
+    r.set_grad_ordered(True)
+    for name, g, o, d, counts in bundles:
+        nrays = len(d)
+        r.set_gaussians(g)
+        rng = np.random.default_rng(7000 + len(g) + nrays)
+        gr = rng.uniform(-1.0, 1.0, size=(nrays, 4)).astype(f32)
+        gTs = {ns: rng.uniform(-1.0, 1.0, size=(nrays, ns)).astype(f32) for ns in counts}
+        for exp_kind, erf_kind in GRAD_PAIRS:
+            r.set_options(exp_kind, erf_kind, S.CULL_EPS)
+            for index in (0, 1):
+                r.set_ray_index(index)
+                key = f"gradord/{name}/exp{exp_kind}_erf{erf_kind}/index{index}"
+                res[key + "/radiance/table"] = table_of(r.radiance_rays_grad(o, d, gr))
+                res[key + "/radiance/records"] = records_of(r)
+                cols, rows = r.radiance_rays_grad(o, d, gr, True, True)
+                res[key + "/radiance/rays/table"], res[key + "/radiance/rays/rows"], res[key + "/radiance/rays/records"] = table_of(cols), rows_of(rows), records_of(r)
+                for ns in counts:
+                    s = np.tile(np.linspace(0.5, 6.0, ns).astype(f32), (nrays, 1))
+                    depth = r.depth_bundle(o, d, np.linspace(0.97, 0.35, ns).astype(f32))
+                    for mode, wrt, at in (("T", pkg.TGRAD_T, s), ("depth", pkg.TGRAD_DEPTH, depth)):
+                        at_key = f"{key}/{mode}/ns{ns}"
+                        res[at_key + "/table"] = table_of(r.transmittance_bundle_grad(o, d, at, gTs[ns], wrt, True, True, True)[0])
+                        res[at_key + "/records"] = records_of(r)
+                        cols, _, rows = r.transmittance_bundle_grad(o, d, at, gTs[ns], wrt, True, True, False, True)
+                        res[at_key + "/rays/table"], res[at_key + "/rays/rows"], res[at_key + "/rays/records"] = table_of(cols), rows_of(rows), records_of(r)
+        st = r.grad_ordered_stats()
+        print(f"ordered {name}: {nrays} rays, the last call: " + ", ".join(f"{k} {v}" for k, v in st.items()))
+    r.set_grad_ordered(False)
+
+
 def run_grad():
     res = {}
     r = pkg.Renderer(0)
@@ -148,6 +201,10 @@ def run_grad():
                 r.set_ray_index(index)
                 key = f"grad/{name}/exp{exp_kind}_erf{erf_kind}/index{index}"
                 res[key + "/radiance/table"] = table_of(r.radiance_rays_grad(o, d, gr))
+                res[key + "/radiance/rays_alone/rows"] = rows_of(r.radiance_rays_grad(o, d, gr, False, True)[1])
+                if nrays == 1:
+                    cols, rows = r.radiance_rays_grad(o, d, gr, True, True)
+                    res[key + "/radiance/rays_table/table"], res[key + "/radiance/rays_table/rows"] = table_of(cols), rows_of(rows)
                 for ns in counts:
                     s = np.tile(np.linspace(0.5, 6.0, ns).astype(f32), (nrays, 1))
                     depth = r.depth_bundle(o, d, np.linspace(0.97, 0.35, ns).astype(f32))    # +inf where a level is never reached: contributes nothing
@@ -160,6 +217,12 @@ def run_grad():
                                 res[f"{key}/{mode}/ns{ns}/{what}/table"] = table_of(cols)
                             if per_sample:
                                 res[f"{key}/{mode}/ns{ns}/{what}/grad_s"] = gs
+                        res[f"{key}/{mode}/ns{ns}/rays_alone/rows"] = rows_of(r.transmittance_bundle_grad(o, d, at, gT, wrt, True, False, False, True)[2])
+                        if nrays == 1:
+                            cols, gs, rows = r.transmittance_bundle_grad(o, d, at, gT, wrt, True, True, True, True)
+                            res[f"{key}/{mode}/ns{ns}/rays_table/table"], res[f"{key}/{mode}/ns{ns}/rays_table/rows"] = table_of(cols), rows_of(rows)
+                            res[f"{key}/{mode}/ns{ns}/rays_table/grad_s"] = gs
+    run_grad_ordered(r, res)
     r.close()
     return {k: np.ascontiguousarray(v, f32).view(np.uint32) for k, v in res.items()}
 
