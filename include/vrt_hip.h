@@ -210,8 +210,14 @@ int vrt_hip_sync(vrt_hip_ctx *ctx);
  * a buffer once; then each vrt_hip_frame_host enqueues the frame and its delivery into the buffer on the context's stream
  * and returns, and vrt_hip_sync waits.  A delivery writes only the 32x32-pixel cells that changed in that buffer since its
  * last delivery (cells lit now, and cells lit then that are dark now); the first delivery, another image size, tile grid or
- * background, and frames whose per-cell stamps were not kept (VRT_HIP_RETAIN_FRAME=0) copy the whole frame.  Up to 16
- * buffers per context (a ring of frames in flight), each with its own history. */
+ * background, and frames whose per-cell stamps were not kept (VRT_HIP_RETAIN_FRAME=0, a tile of more than 64 cells, a sharded
+ * context) copy the whole frame: its w*h pixels, nothing beyond them in a larger buffer.  A frame without stamps records
+ * nothing, so the delivery after it is a whole copy too.  A repeated pose is an ordinary frame: its lists are built anew, its
+ * stamps kept, its delivery writes the lit cells again.  Dense frames: a buffer whose deliveries counted more than 3/4 of the
+ * frame's cells (cells lit, or lit before and dark now) gets whole copies until they count less; the count a delivery reads
+ * is that of the delivery before the previous one into that buffer (older while frames are in flight), so the switch lags by
+ * two deliveries either way -- speed only, the pixels are the same.  Up to 16 buffers per context (a ring of frames in
+ * flight), each with its own history and count. */
 /* Page-locks and maps a caller-owned host buffer of `pixels` u32s for this context (hipHostRegister, mapped).  `image` must
  * be 64-byte aligned (what simd::aligned_malloc gives, main.cpp:245).  Refused (VRT_HIP_ERR_INVALID): NULL or misaligned
  * pointer, 0 pixels, a buffer already registered, with this or any context.  The buffer's history starts empty: its

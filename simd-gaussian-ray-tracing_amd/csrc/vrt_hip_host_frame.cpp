@@ -14,7 +14,10 @@
 // launch on the buffer publishes that count in a host-mapped word per buffer, and a delivery whose buffer's word says more
 // than three quarters of the frame's cells is a full copy.  Measured on the cfg5 orbit (monkey 4096^2): a delta whose count
 // was above one half took 750 us, the full copy 1186 us, so the two break even above 0.5 * 1186 / 750 = 79 % of the cells.
-// The choice lags by a delivery or two: speed only, the pixels are the same either way.
+// The choice lags by two deliveries: launch k publishes the count of launch k - 1, and the host reads the word before it
+// enqueues launch k + 1 (with frames in flight it reads an older one still).  Speed only, the pixels are the same either
+// way.  A delivery without stamps launches nothing: the two tally words keep their turn.  tests/host_frame_scenes.py models
+// all of this word by word.
 #include <algorithm>
 #include <mutex>
 #include <utility>

@@ -1,6 +1,7 @@
 """Host frames (vrt_hip_host_register / vrt_hip_frame_host / vrt_hip_host_unregister): frames delivered into a caller's
 registered host buffer, only the cells that changed in that buffer since its last delivery.  Every frame must equal a fresh
-render of its pose, whatever the buffer received before."""
+render of its pose, whatever the buffer received before.  These are the workload's frames; which words each delivery writes and
+leaves alone is checked cell by cell, on crafted cases against a model, in tests/test_gpu_host_frame_cells.py."""
 import os
 import subprocess
 
