@@ -617,6 +617,14 @@ inline void set_ray_index(bool on)
     auto &d = detail::device_t::get();
     d.check(vrt_hip_set_ray_index(d.ctx, on ? 1 : 0), "vrt_hip_set_ray_index");
 }
+// Ray bundles of more than 64 rays are shaded in an order that puts rays which keep the same bounding spheres into the same wave, from
+// the next call on (vrt_hip_set_ray_sort in include/vrt_hip.h: off by default; every result stays at the caller's ray index, the same
+// bits either way; for probes, second bounces, shuffled batches -- a camera's own order gains nothing).
+inline void set_ray_sort(bool on)
+{
+    auto &d = detail::device_t::get();
+    d.check(vrt_hip_set_ray_sort(d.ctx, on ? 1 : 0), "vrt_hip_set_ray_sort");
+}
 // Gradient bundles build their table without float atomics from the next call on: bit for bit reproducible, summed in a documented
 // order (vrt_hip_set_grad_ordered in include/vrt_hip.h: off by default; an ordered call waits once for its stream).
 inline void set_grad_ordered(bool on)

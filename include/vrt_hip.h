@@ -613,6 +613,39 @@ int vrt_hip_get_ray_index_stats(vrt_hip_ctx *ctx, vrt_hip_ray_index_stats *out);
 /* Diagnostic: out[Morton position] = scene index, N words (cap = room in out).  Brings the scene tables up to date and waits for work in
  * flight; VRT_HIP_ERR_INVALID when the index is off or not built yet (switched on after the tables: the next bundle builds it). */
 int vrt_hip_get_ray_index_perm(vrt_hip_ctx *ctx, uint32_t *out, size_t cap);
+/* Sorted bundles (off by default, first value from VRT_HIP_RAY_SORT=0|1 at vrt_hip_create).  A wave of the lane = ray kernels tests the
+ * members of every sphere that SOME of its 64 rays keeps, so rays that are neighbours in the bundle but not in space (probes, second
+ * bounces, a shuffled batch of pixels) pay for each other's spheres, with or without the index.  With on != 0 every bundle of more than
+ * 64 rays -- radiance, transmittance, depth, both gradients, host and device forms, ordered tables included -- is shaded in an order
+ * that puts rays which keep the same spheres into the same wave.  Every output word stays at the caller's ray index and every bit stays
+ * the same: a ray's bits are a function of (ray, scene, options), whatever its wave-mates are (only a gradient table summed with float
+ * atomics differs as it does between any two runs).
+ *   Key of ray r, 32 bits: (min(first, 0xFFFF) << 16) | min(last, 0xFFFF), where first and last are the lowest and the highest sphere
+ *   that the ray's OWN sphere tests keep -- leaf spheres in Morton position (own group test && own leaf test) with the index on, chunk
+ *   spheres with it off; 0xFFFFFFFF for a ray that keeps no sphere.  A function of (ray, scene, options) alone; no member test.
+ *   Order: ascending key, equal keys in ascending ray id (a stable sort) -- a function of (rays, scene, options).
+ *   Cost: one kernel lane = ray over the bundle's own order (the sphere tests of the cull and nothing below them; with the index its
+ *   waves visit the leaf spheres of every group some lane keeps) and one radix sort of nrays (key, id) pairs (over the bits the scene's
+ *   sphere count needs: the keys are filed packed, in the same order, and vrt_hip_get_ray_order unpacks them), both on the call's stream
+ *   ahead of the bundle's kernels; 16 B per ray of device memory plus the sort's temporary storage, owned by the context, growing only.
+ *   A sorted call whose buffers need not grow waits for nothing and allocates nothing.  A bundle that arrives in a coherent order
+ *   (a camera's rows) pays the two steps for nothing.
+ * A bundle of at most 64 rays is one wave: it is not sorted, and `sorted` says so.  With vrt_hip_enable_stats on, the per-WAVE fields
+ * (members_tested and leaves_tested of vrt_hip_ray_stats / vrt_hip_ray_index_stats) count the waves of the sorted order; all per-ray
+ * fields (rays, short_rays, long_rays, lane_entries, lane_pairs, scratch_rays, chunks_tested, chunks_kept, groups_tested, groups_kept,
+ * leaves_kept) are unchanged.  The call waits for bundles in flight, counts as a state change (vrt_hip_state_generation) and is carried
+ * over by vrt_hip_copy_state. */
+int vrt_hip_set_ray_sort(vrt_hip_ctx *ctx, int on);
+typedef struct {
+    uint64_t sorted;              /* 1: the last bundle was shaded in the sorted order (0: switch off, or at most 64 rays)      */
+    uint64_t rays;                /* rays of the last bundle                                                                    */
+    uint64_t rays_without_sphere; /* of a sorted bundle: rays whose own tests keep no sphere (key 0xFFFFFFFF, sorted last)       */
+} vrt_hip_ray_sort_stats;
+int vrt_hip_get_ray_sort_stats(vrt_hip_ctx *ctx, vrt_hip_ray_sort_stats *out); /* of the last bundle (waits for a sorted one); needs no vrt_hip_enable_stats */
+/* Diagnostic: the last bundle's order[slot] = ray id (lane l of wave w took ray order[64 w + l]) and, where keys != NULL, keys[ray id];
+ * *count = its rays, cap = room in each array.  Waits for the bundle.  VRT_HIP_ERR_INVALID when the switch is off or the last bundle
+ * was not sorted. */
+int vrt_hip_get_ray_order(vrt_hip_ctx *ctx, uint32_t *order, uint32_t *keys, size_t cap, size_t *count);
 
 /* Numeric cross-checks of rt.cpp:8-27 (transmittance_step uses fast_exp like the reference).
  * vrt_hip_transmittance_step runs the reference's float32 loop `for (t = 0; t <= s; t += delta)` per sample point, and refuses with

@@ -55,6 +55,10 @@ class RayIndexStats(C.Structure):
                                           "members_tested")]
 
 
+class RaySortStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("sorted", "rays", "rays_without_sphere")]
+
+
 class GradOrderedStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("records", "gaussians", "longest", "mismatches")]
 
@@ -149,6 +153,9 @@ SYMBOLS = {
     "vrt_hip_set_ray_index": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_ray_index_stats": (C.c_int, [_vp, C.POINTER(RayIndexStats)]),
     "vrt_hip_get_ray_index_perm": (C.c_int, [_vp, _u32p, C.c_size_t]),
+    "vrt_hip_set_ray_sort": (C.c_int, [_vp, C.c_int]),
+    "vrt_hip_get_ray_sort_stats": (C.c_int, [_vp, C.POINTER(RaySortStats)]),
+    "vrt_hip_get_ray_order": (C.c_int, [_vp, _u32p, _u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vrt_hip_set_grad_ordered": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_grad_records": (C.c_int, [_vp, _u32p, _u32p, _f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vrt_hip_get_grad_ordered_stats": (C.c_int, [_vp, C.POINTER(GradOrderedStats)]),
@@ -703,6 +710,27 @@ class Renderer:
         out = np.zeros(max(self.n, 1), np.uint32)
         self._chk(self._L.vrt_hip_get_ray_index_perm(self._h, out.ctypes.data_as(_u32p), out.size), "get_ray_index_perm")
         return out[:self.n]
+
+    def set_ray_sort(self, on):
+        """Ray bundles of more than 64 rays are shaded in an order that puts rays which keep the same bounding spheres into the same wave
+        (off by default; every output stays at the caller's ray index, the same bits either way): see vrt_hip_set_ray_sort in
+        include/vrt_hip.h."""
+        self._chk(self._L.vrt_hip_set_ray_sort(self._h, int(bool(on))), "set_ray_sort")
+
+    def ray_sort_stats(self):
+        """Whether the last bundle was sorted, its rays and those that keep no sphere: see vrt_hip_ray_sort_stats in include/vrt_hip.h."""
+        s = RaySortStats()
+        self._chk(self._L.vrt_hip_get_ray_sort_stats(self._h, C.byref(s)), "get_ray_sort_stats")
+        return {k: getattr(s, k) for k, _ in RaySortStats._fields_}
+
+    def ray_order(self):
+        """Diagnostic: (order u32 [nrays], keys u32 [nrays]) of the last sorted bundle -- order[slot] = ray id, keys[ray id] (waits; raises
+        while the sort is off or the last bundle was not sorted): see vrt_hip_get_ray_order in include/vrt_hip.h."""
+        n = self.ray_sort_stats()["rays"]
+        order, keys, count = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32), C.c_size_t()
+        self._chk(self._L.vrt_hip_get_ray_order(self._h, order.ctypes.data_as(_u32p), keys.ctypes.data_as(_u32p), order.size, C.byref(count)),
+                  "get_ray_order")
+        return order[:count.value], keys[:count.value]
 
     def set_grad_ordered(self, on):
         """Gradient bundles build their table without float atomics, bit for bit reproducible and summed in a documented order (off by

@@ -29,9 +29,10 @@ __global__ __launch_bounds__(64) void ray_count_kernel(RayArgs) // read through 
     const SceneTables &S = P.S;
     __shared__ uint32_t s_list[RAY_PL * 64]; // the cull files a short list here; nobody reads it
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t r = (uint64_t)blockIdx.x * 64u + lane;
-    const bool valid = r < P.nrays; // the grid has no wave without a valid ray
-    const LaneRay ray = load_ray(P, valid ? r : P.nrays - 1);
+    const ShortSlot slot = ray_short_slot(&P, lane); // the waves of the record kernels behind this one: a sorted bundle is counted in its sorted order
+    const uint64_t r = slot.r;
+    const bool valid = slot.valid;
+    const LaneRay ray = load_ray(P, slot.rc);
     const uint32_t N = S.n, nch = (N + 63u) / 64u;
     RayCullCounts cnt;
     const uint32_t nl = ray_short_cull<INDEXED>(&P, &S, N, nch, s_list, lane, valid, ray, cnt);

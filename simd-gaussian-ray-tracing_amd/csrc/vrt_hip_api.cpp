@@ -308,6 +308,7 @@ Tuning read_tuning()
     if (const char *e = getenv("VRT_HIP_RETAIN_FRAME")) t.retain_frame = atoi(e) != 0;
     if (const char *e = getenv("VRT_HIP_RAY_INDEX")) t.ray_index = atoi(e) != 0;
     if (const char *e = getenv("VRT_HIP_GRAD_ORDERED")) t.grad_ordered = atoi(e) != 0;
+    if (const char *e = getenv("VRT_HIP_RAY_SORT")) t.ray_sort = atoi(e) != 0;
     return t;
 }
 
@@ -342,6 +343,7 @@ int vrt_hip_create(int device, vrt_hip_ctx **out)
     c->cull_prune = c->tune.cull_prune; c->table_hx = c->tune.table_step; c->table_budget = c->tune.table_budget;
     c->ray_index = c->tune.ray_index;
     c->grad_ordered = c->tune.grad_ordered;
+    c->ray_sort = c->tune.ray_sort;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreateWithFlags(&c->scene_order, hipEventDisableTiming) != hipSuccess ||
@@ -499,6 +501,7 @@ int vrt_hip_copy_state(vrt_hip_ctx *dst, const vrt_hip_ctx *src)
     dst->table_hx = src->table_hx; dst->table_budget = src->table_budget; dst->tune.table_adapt = src->tune.table_adapt; dst->tune.table_room = src->tune.table_room;
     dst->rank = src->rank; dst->world = src->world;
     dst->grad_ordered = src->grad_ordered;
+    dst->ray_sort = src->ray_sort;
     dst->ray_index = src->ray_index; // the mirror builds the same index with its tables: the order is a function of the scene alone
     dst->tables_dirty = true; dst->lists_dirty = true; dst->shard_dirty = true; dst->ref_valid = false;
     dst->reset_seq = dst->frame_seq;
@@ -558,6 +561,16 @@ int vrt_hip_set_grad_ordered(vrt_hip_ctx *c, int on)
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = quiesce(c); if (rc) return rc; } // bundles in flight keep the path they were enqueued with
     c->grad_ordered = on != 0;
+    ++c->state_gen;
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_set_ray_sort(vrt_hip_ctx *c, int on)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // bundles in flight keep the order they were enqueued with
+    c->ray_sort = on != 0;
     ++c->state_gen;
     return VRT_HIP_OK;
 }

@@ -70,6 +70,7 @@ struct Tuning {
     bool retain_frame = true;    // VRT_HIP_RETAIN_FRAME=0: every vrt_hip_frame clears its whole image (no retained history)
     bool ray_index = false;      // VRT_HIP_RAY_INDEX=1: the context's first vrt_hip_ctx::ray_index
     bool grad_ordered = false;   // VRT_HIP_GRAD_ORDERED=1: the context's first vrt_hip_ctx::grad_ordered
+    bool ray_sort = false;       // VRT_HIP_RAY_SORT=1: the context's first vrt_hip_ctx::ray_sort
 };
 
 enum TileMode { TILES_NONE = 0, TILES_HOST = 1, TILES_DEVICE = 2 };
@@ -281,6 +282,19 @@ struct vrt_hip_ctx {
     bool ord_valid = false;       // an ordered call has cleared ord_words: they are that call's
     uint64_t ord_total = 0;       // rows the last ordered call recorded, sentinel rows included (0: it kept nothing, or was refused)
     bool ord_ran = false;         // set by an ordered call that recorded: the host forms look at its mismatch word once they have waited
+    // Sorted bundles (vrt_hip_set_ray_sort; sort_bundle in vrt_hip_rays.cpp).  Buffers of the context that only grow, used on the stream of
+    // the call like the long-ray queue (wait_for_last_stream covers them): per ray its key, the identity, the sorted keys and the order
+    // (slot -> ray id); one word, the rays that keep no sphere; temporary storage of the sort, rs_sort_bytes for a bundle of rs_sort_n rays.
+    bool ray_sort = false;        // bundles of more than one wave are shaded in the sorted order
+    DevBuf<uint32_t> rs_keys, rs_ids, rs_keys_sorted, rs_order;
+    DevBuf<unsigned long long> rs_none;
+    DevBuf<unsigned char> rs_sort_tmp;
+    size_t rs_sort_n = 0, rs_sort_bytes = 0;
+    uint32_t rs_sort_bits = 0;    // ... and keys of this many bits per field (ray_sort_field_bits)
+    bool rs_last_valid = false;   // a bundle has run: the two below are its
+    bool rs_last_sorted = false;  // it was sorted: rs_keys, rs_order and rs_none are its
+    size_t rs_last_rays = 0;
+    uint32_t rs_last_spheres = 0; // what its keys were packed for (ray_sort_unpack)
     DevBuf<unsigned long long> d_stats, d_timeline; // d_timeline: VRT_HIP_TIMELINE diagnostics
     size_t timeline_items = 0, timeline_tiles = 0;
     DevBuf<unsigned long long> d_timeline_lists;

@@ -4,7 +4,8 @@
 // respect to the Gaussians, culled per ray (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip,
 // vrt_ray_grad_kernel.hip, vrt_ray_trans_grad_kernel.hip).  The scene tables and the
 // chunk spheres are the frame pipeline's; the long-ray queue, its counters and the long kernel's scratch slots belong to the context
-// and only grow.  So do the buffers of the ordered gradient tables (vrt_hip_set_grad_ordered: ordered_bundle, and the two read-outs).
+// and only grow.  So do the buffers of the ordered gradient tables (vrt_hip_set_grad_ordered: ordered_bundle, and the two read-outs)
+// and of the sorted bundles (vrt_hip_set_ray_sort: sort_bundle, and the two read-outs).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -74,6 +75,32 @@ struct Bundle {
     uint32_t grid = 0;
     bool indexed = false;
 };
+// A bundle while vrt_hip_set_ray_sort is on (include/vrt_hip.h has the contract, vrt_ray_sort_kernel.hip the two steps): the keys by the
+// sphere tests of the cull the bundle will run, the stable sort, and a.order for the lane = ray kernels behind them -- all on the call's
+// stream.  A bundle of one wave has nothing to regroup and is not sorted.  The storage query is the host's, from nrays; a buffer that
+// grows is freed first, which waits for the device, and a call whose buffers are large enough waits for nothing.
+int sort_bundle(vrt_hip_ctx *c, RayArgs &a, bool indexed, hipStream_t st)
+{
+    const size_t nrays = (size_t)a.nrays;
+    c->rs_last_valid = true; c->rs_last_sorted = false; c->rs_last_rays = nrays;
+    if (!c->ray_sort || nrays <= 64) return VRT_HIP_OK;
+    const uint32_t spheres = (c->n + 63u) / 64u, bits = ray_sort_field_bits(spheres);
+    if (c->rs_sort_n != nrays || c->rs_sort_bits != bits) {
+        c->rs_sort_bytes = ray_sort_bytes(nrays, spheres);
+        if (!c->rs_sort_bytes) return fail(c, VRT_HIP_ERR_HIP, "ray sort: the sort's storage query failed");
+        c->rs_sort_n = nrays; c->rs_sort_bits = bits;
+    }
+    HIPCHK(c, c->rs_keys.reserve(nrays)); HIPCHK(c, c->rs_ids.reserve(nrays)); HIPCHK(c, c->rs_keys_sorted.reserve(nrays));
+    HIPCHK(c, c->rs_order.reserve(nrays)); HIPCHK(c, c->rs_none.reserve(1)); HIPCHK(c, c->rs_sort_tmp.reserve(c->rs_sort_bytes));
+    RaySort o{};
+    o.keys = c->rs_keys.p; o.ids = c->rs_ids.p; o.keys_sorted = c->rs_keys_sorted.p; o.order = c->rs_order.p; o.none = c->rs_none.p;
+    o.spheres = spheres; o.sort_tmp = c->rs_sort_tmp.p; o.sort_bytes = c->rs_sort_bytes;
+    HIPCHK(c, launch_ray_sort(a, indexed, o, st));
+    a.order = c->rs_order.p;
+    c->rs_last_sorted = true; c->rs_last_spheres = spheres;
+    return VRT_HIP_OK;
+}
+
 int enqueue_bundle(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs, hipStream_t st, Bundle &b)
 {
     HIPCHK(c, hipSetDevice(c->device));
@@ -119,7 +146,7 @@ int enqueue_bundle(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int ori
         a.index_stats = c->stats_on ? c->ray_stats.p + RAY_STATS_WORDS : nullptr;
     }
     b.grid = grid; b.indexed = indexed;
-    return VRT_HIP_OK;
+    return sort_bundle(c, a, indexed, st);
 }
 
 } // namespace
@@ -596,6 +623,40 @@ int vrt_hip_get_ray_index_stats(vrt_hip_ctx *c, vrt_hip_ray_index_stats *out)
     HIPCHK(c, hipMemcpy(w, c->ray_stats.p + RAY_STATS_WORDS, sizeof(w), hipMemcpyDeviceToHost));
     out->indexed = 1; out->groups = c->ri_last_groups; out->leaves = c->ri_last_leaves;
     out->groups_tested = w[0]; out->groups_kept = w[1]; out->leaves_tested = w[2]; out->leaves_kept = w[3]; out->members_tested = w[4];
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_get_ray_sort_stats(vrt_hip_ctx *c, vrt_hip_ray_sort_stats *out)
+{
+    if (!c || !out) return VRT_HIP_ERR_INVALID;
+    *out = vrt_hip_ray_sort_stats{};
+    if (!c->rs_last_valid) return VRT_HIP_OK;
+    out->rays = c->rs_last_rays;
+    if (!c->rs_last_sorted) return VRT_HIP_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // waits for the bundle
+    unsigned long long none = 0;
+    HIPCHK(c, hipMemcpy(&none, c->rs_none.p, sizeof(none), hipMemcpyDeviceToHost));
+    out->sorted = 1; out->rays_without_sphere = none;
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_get_ray_order(vrt_hip_ctx *c, uint32_t *order, uint32_t *keys, size_t cap, size_t *count)
+{
+    if (!c || !count) return VRT_HIP_ERR_INVALID;
+    *count = 0;
+    if (!c->ray_sort || !c->rs_last_valid || !c->rs_last_sorted)
+        return fail(c, VRT_HIP_ERR_INVALID, "get_ray_order: the sort is off, or the last bundle was not sorted");
+    const size_t n = c->rs_last_rays;
+    *count = n;
+    if (!order || cap < n) return fail(c, VRT_HIP_ERR_INVALID, "get_ray_order: buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // waits for the bundle
+    HIPCHK(c, hipMemcpy(order, c->rs_order.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (keys) { // filed packed: the documented key back
+        HIPCHK(c, hipMemcpy(keys, c->rs_keys.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < n; ++r) keys[r] = ray_sort_unpack(keys[r], c->rs_last_spheres);
+    }
     return VRT_HIP_OK;
 }
 

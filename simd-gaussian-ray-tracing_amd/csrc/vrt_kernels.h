@@ -356,6 +356,9 @@ struct RayArgs {
     uint32_t *ord_gauss, *ord_ray;  // [record] the Gaussian (S.n: a sentinel row of a ray whose re-cull missed its length) and the ray
     float *ord_rows;                // [record * GRAD_ORD_COLS] the table's columns 0..8
     unsigned long long *ord_words;  // [GRAD_ORD_WORDS]
+    // Sorted bundles (vrt_hip_set_ray_sort; behind everything the other kernels read)
+    const uint32_t *order;          // nullable, [nrays] slot -> ray id: lane l of workgroup b of a lane = ray kernel takes ray order[64 b + l];
+                                    // nullptr: ray 64 b + l, the bundle's own order
 };
 constexpr int GRAD_ORD_COLS = 9;    // floats per record
 // the words of an ordered call, cleared on the stream ahead of its count pass: rays whose re-cull missed the counted length; records
@@ -402,6 +405,23 @@ struct GradOrderedSort {
 size_t grad_ordered_sort_bytes(uint64_t total, uint32_t n);
 void launch_grad_ordered_iota(uint32_t *p, uint64_t from, uint64_t to, hipStream_t st); // p[i] = i for from <= i < to
 hipError_t launch_grad_ordered_reduce(const GradOrderedSort &o, hipStream_t st);
+// Sorted bundles (vrt_hip_set_ray_sort; vrt_ray_sort_kernel.hip): keys[r] = the key of ray r by the sphere tests of the cull the bundle
+// will run (a.leaves / a.groups with `indexed`, a.chunks without; include/vrt_hip.h states the key), order = the ray ids sorted by
+// key, ties in ray order (rocPRIM's stable radix_sort_pairs), *none (cleared on the stream before) = the rays that keep no sphere.
+// keys are filed PACKED to the bits the scene's `spheres` (leaves, or chunks: ceil(n / 64)) need -- the same order in fewer radix digits;
+// ray_sort_unpack gives the documented key back.  ids: nrays words of scratch (the identity); sort_tmp: ray_sort_bytes(nrays, spheres)
+// bytes (0: the query failed).  a.nrays > 0; nothing waits.
+struct RaySort {
+    uint32_t *keys, *ids, *keys_sorted, *order;
+    unsigned long long *none;
+    uint32_t spheres;
+    void *sort_tmp;
+    size_t sort_bytes;
+};
+size_t ray_sort_bytes(size_t nrays, uint32_t spheres);
+uint32_t ray_sort_field_bits(uint32_t spheres);
+uint32_t ray_sort_unpack(uint32_t packed, uint32_t spheres);
+hipError_t launch_ray_sort(const RayArgs &a, bool indexed, const RaySort &o, hipStream_t st);
 // group spheres of the Morton index: one per 64 consecutive leaf spheres, bounding them
 void launch_build_ray_groups(uint32_t nleaves, const float4 *leaves, float4 *groups, hipStream_t st);
 

@@ -168,8 +168,8 @@ __device__ __forceinline__ void ray_short_file(const RayArgs *Pp, uint32_t nch, 
     }
 }
 
-// A lane's ray behind its cull, as every lane = ray kernel begins: the ray (a lane past the end of the bundle works on the last ray
-// and writes nothing), its list in s_list[k*64 + lane], filed to the long-ray queue and counted.
+// A lane's ray behind its cull, as every lane = ray kernel begins: the ray (a lane past the end of the bundle works on the ray of the
+// last slot and writes nothing), its list in s_list[k*64 + lane], filed to the long-ray queue and counted.
 struct ShortRay {
     uint64_t r, rc;  // the lane's ray id, and the same clamped to the bundle
     bool valid, is_long, writes /* valid && !is_long: this lane's result is this kernel's to store */;
@@ -177,14 +177,27 @@ struct ShortRay {
     uint32_t nmax;   // the longest nl of the wave: its loops run that far, so that the wave stays together
     LaneRay ray;
 };
+// Which ray a lane of a lane = ray kernel works on: slot 64 * workgroup + lane of the bundle's own order, or of the sorted order
+// (P.order: vrt_hip_set_ray_sort).  Everything behind this addresses rays, results, the queue and the records by the ray id.
+struct ShortSlot { uint64_t r, rc; bool valid; }; // ShortRay's fields of these names
+__device__ __forceinline__ ShortSlot ray_short_slot(const RayArgs *Pp, uint32_t lane)
+{
+    const RayArgs &P = *Pp;
+    ShortSlot s;
+    const uint64_t slot = (uint64_t)blockIdx.x * 64u + lane;
+    s.valid = slot < P.nrays; // the grid has no wave without a valid ray
+    s.rc = s.valid ? slot : P.nrays - 1;
+    if (P.order) s.rc = P.order[s.rc];
+    s.r = s.valid ? s.rc : slot;
+    return s;
+}
 template <bool INDEXED>
 __device__ __forceinline__ ShortRay ray_short_begin(const RayArgs *Pp, const SceneTables *Sp, uint32_t *s_list /*[RAY_PL * 64]*/, uint32_t lane)
 {
     const RayArgs &P = *Pp;
     ShortRay R;
-    R.r = (uint64_t)blockIdx.x * 64u + lane;
-    R.valid = R.r < P.nrays; // the grid has no wave without a valid ray
-    R.rc = R.valid ? R.r : P.nrays - 1;
+    const ShortSlot s = ray_short_slot(Pp, lane);
+    R.r = s.r; R.rc = s.rc; R.valid = s.valid;
     R.ray = load_ray(P, R.rc);
     const uint32_t N = Sp->n, nch = (N + 63u) / 64u;
     RayCullCounts cnt;

@@ -71,6 +71,15 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
       synchronised afterwards).  The step with cuda parameters has to be faster than the step with CPU parameters in every row; the
       ratio and the setter's times are recorded, not asserted.  `--scene-update-only` runs this part alone, prints its JSON line and
       writes scene_update.json and scene_update.md (and nothing else) to --out-dir.
+  (so) sorted bundles (vrt_hip_set_ray_sort): the `-g 64 -w 2048` frame's rays in the camera's order (where sorting can only cost: reported,
+      no gate), the same rays under a seeded permutation, 2^20 rays aimed at random Gaussians (vrt_hip_radiance_rays_device, packed pixels
+      out) and 4096 aimed rays through the radiance gradient (vrt_hip_radiance_rays_grad_device); four contexts per bundle -- Morton index
+      off and on, sort off and on -- their windows alternating in the same run, stream events around back-to-back calls.  Each row carries
+      members_tested of one call (vrt_hip_ray_stats / vrt_hip_ray_index_stats) and whether the sorted result equals the unsorted one bit for
+      bit (the gradient's atomic table: its largest difference).  The run fails unless the permuted pinhole bundle with index and sort on is
+      faster than with the index on and the sort off.  `--sort-only` runs this part alone, prints its JSON line and writes ray_sort.json
+      and ray_sort.md (and nothing else) to --out-dir; the .md ends with the text of <out-dir>/ray_sort_resources.txt when that file is
+      there (the output of `tools/kernel_resources.sh raysort`).
 """
 import argparse
 import json
@@ -763,6 +772,97 @@ atomic order only (last column: largest difference / largest gradient).
     return "\n".join(lines) + "\n"
 
 
+def part_sort(g, w, calls=3, repeats=5):
+    """(so) sort off against on, Morton index off and on, in the same run"""
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    cam, _ = scene.cli_camera(w, w)
+    pin = directions(cam.plane(), cam.position)
+    perm = np.random.default_rng(17).permutation(len(pin))
+    bundles = [(f"-g 64 -w {w} pinhole, camera order", (cam.position, pin), False),
+               (f"-g 64 -w {w} pinhole, seeded permutation", (cam.position, np.ascontiguousarray(pin[perm])), False),
+               ("2^20 rays aimed at random Gaussians", aimed_rays(g, 1 << 20), False),
+               ("4096 aimed rays, radiance gradient", aimed_rays(g, 4096), True)]
+    rows = {}
+    for label, (o, d), grad in bundles:
+        nrays = len(d)
+        t_o, t_d = torch.from_numpy(np.ascontiguousarray(o, f32)).cuda(), torch.from_numpy(np.ascontiguousarray(d, f32)).cuda()
+        t_g = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, size=(nrays, 4)).astype(f32)).cuda() if grad else None
+        keys = [(index, sort) for index in (0, 1) for sort in (0, 1)]
+        ctx = {}
+        for index, sort in keys:
+            r = pkg.Renderer(0)
+            r.set_gaussians(g)
+            r.set_ray_index(index)
+            r.set_ray_sort(sort)
+            ctx[index, sort] = r
+        out = {k: (torch.zeros((len(g), pkg.GRAD_STRIDE), dtype=torch.float32, device="cuda") if grad else torch.zeros(nrays, dtype=torch.int32, device="cuda"))
+               for k in keys}
+        torch.cuda.synchronize()
+        if grad:
+            fns = [lambda k=k: ctx[k].radiance_rays_grad_device(nrays, t_o.data_ptr(), 0, t_d.data_ptr(), t_g.data_ptr(), out[k].data_ptr(), st) for k in keys]
+        else:
+            fns = [lambda k=k: ctx[k].radiance_rays_device(nrays, t_o.data_ptr(), 0, t_d.data_ptr(), 0, out[k].data_ptr(), PACK, st) for k in keys]
+        t = dict(zip(keys, windows(fns, calls, repeats, warm=2)))
+        members, sorted_flag = {}, {}
+        for k, fn in zip(keys, fns):
+            out[k].zero_()
+            ctx[k].enable_stats(True)
+            fn()
+            members[k] = (ctx[k].ray_index_stats() if k[0] else ctx[k].ray_stats())["members_tested"]
+            sorted_flag[k] = ctx[k].ray_sort_stats()["sorted"]
+        torch.cuda.synchronize()
+        row = {"rays": nrays, "gradient": grad}
+        for index, name in ((0, "off"), (1, "on")):
+            row[f"index_{name}"] = {"sort_off_ms": t[index, 0], "sort_on_ms": t[index, 1], "off_over_on": round(t[index, 0]["median"] / t[index, 1]["median"], 2),
+                                    "members_tested_sort_off": members[index, 0], "members_tested_sort_on": members[index, 1],
+                                    "sorted": [sorted_flag[index, 0], sorted_flag[index, 1]]}
+            if grad:
+                scale = float(out[index, 0].abs().max().item())
+                row[f"index_{name}"]["max_abs_sorted_minus_unsorted_over_max_abs"] = float((out[index, 1] - out[index, 0]).abs().max().item()) / max(scale, 1e-30)
+            else:
+                row[f"index_{name}"]["identical"] = bool(torch.equal(out[index, 0], out[index, 1]))
+        for r in ctx.values():
+            r.close()
+        rows[label] = row
+    return {"gaussians": len(g), "rows": rows}
+
+
+def check_sort(z):
+    for label, r in z["rows"].items():
+        for name in ("index_off", "index_on"):
+            assert r[name]["sorted"] == [0, 1], (label, name)
+            assert r["gradient"] or r[name]["identical"], (label, name, "the sorted bundle's pixels differ from the unsorted bundle's")
+    p = next(r for label, r in z["rows"].items() if "permutation" in label)["index_on"]
+    assert p["sort_on_ms"]["median"] < p["sort_off_ms"]["median"], "the permuted pinhole bundle with index and sort on has to be faster than with the sort off"
+
+
+def markdown_sort(z, resources=""):
+    lines = [f"""# Sorted bundles (tools/ray_bundles.py --sort-only)
+
+`vrt_hip_set_ray_sort` on against off, in the same run: `-g 64` (N = {z['gaussians']}), device pointers, stream events around back-to-back calls,
+the four paths (Morton index off / on, sort off / on: four contexts) alternating; ms per call, median (min .. max).  A sorted call holds
+the key kernel and a radix sort of (key, ray id) ahead of the bundle's own two kernels, on the same stream, with no wait.  members tested:
+`members_tested` of one call (`vrt_hip_ray_stats` with the index off, `vrt_hip_ray_index_stats` with it on).  The camera-order row is
+where sorting can only cost; the run fails unless the permuted pinhole bundle with index and sort on is faster than with the sort off.
+
+| bundle | rays | index | sort off | sort on | off / on | members tested, sort off | sort on | same bits |
+|---|---|---|---|---|---|---|---|---|"""]
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            x = r[f"index_{key}"]
+            same = f"table differs by {x['max_abs_sorted_minus_unsorted_over_max_abs']:.1e} of its largest entry (float atomics)" if r["gradient"] else str(x["identical"])
+            lines.append(f"| {label} | {r['rays']} | {key} | {ms(x['sort_off_ms'])} | {ms(x['sort_on_ms'])} | {x['off_over_on']} | "
+                         f"{x['members_tested_sort_off']} | {x['members_tested_sort_on']} | {same} |")
+    lines.append("""
+Not taken: the transmittance, depth and transmittance gradient bundles, the ordered tables, the host-pointer forms, per-ray origins, a
+profile under rocprofv3 (the key kernel's and the sort's own share), any scene but `-g 64`.
+""")
+    if resources:
+        lines.append("Resources of the key kernel (`tools/kernel_resources.sh raysort`; template argument: INDEXED):\n\n```\n" + resources.rstrip() + "\n```\n")
+    return "\n".join(lines)
+
+
 def windows(fns, calls, repeats, warm=3):
     """ms per call of each fn: `repeats` windows of `calls` back-to-back calls between two stream events, the fns alternating."""
     import torch
@@ -958,6 +1058,7 @@ def main():
     ap.add_argument("--tgrad-only", action="store_true")
     ap.add_argument("--rgrad-only", action="store_true")
     ap.add_argument("--scene-update-only", action="store_true")
+    ap.add_argument("--sort-only", action="store_true")
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
     if a.scene_update_only:
@@ -970,6 +1071,17 @@ def main():
         with open(os.path.join(a.out_dir, "scene_update.md"), "w") as f:
             f.write(markdown_scene(z))
         check_scene(z)
+        return
+    if a.sort_only:
+        z = part_sort(g, a.width)
+        print(json.dumps({"sort": z}))
+        os.makedirs(a.out_dir, exist_ok=True)
+        with open(os.path.join(a.out_dir, "ray_sort.json"), "w") as f:
+            f.write(json.dumps({"what": "sorted against unsorted bundles of the same rays, Morton index off and on; see tools/ray_bundles.py (so)", "sort": z}) + "\n")
+        res = os.path.join(a.out_dir, "ray_sort_resources.txt")
+        with open(os.path.join(a.out_dir, "ray_sort.md"), "w") as f:
+            f.write(markdown_sort(z, open(res).read() if os.path.exists(res) else ""))
+        check_sort(z)
         return
     if a.transmittance_only:
         t = part_t(g)
