@@ -501,6 +501,39 @@ void radiance_rays_grad_device(const f32 *d_origins, bool origin_per_ray, const 
 {
     radiance_rays_grad_device<Exp, Erf>(d_origins, origin_per_ray, d_dirs, nrays, gaussians, d_grad_radiance, d_grad, nullptr, hip_stream);
 }
+// Tangent bundles: forward mode, J . v.  Given a direction in parameter space -- tangent (nullable): gaussians.size() rows of
+// VRT_HIP_GRAD_STRIDE floats in radiance_rays_grad's layout, [0..3] d albedo, [4..6] d mu, [7] d sigma, [8] d magnitude, [9..11] never read;
+// ray_tangent (nullable, not both): nrays rows of VRT_HIP_RAY_GRAD_STRIDE floats, [0..2] d origin, [4..6] d direction (only its part
+// perpendicular to the direction counts), [3] and [7] never read -- out[r] is how out[r] of radiance_rays moves along it, each ray's kept
+// list held fixed (vrt_hip_radiance_rays_tangent in include/vrt_hip.h; the pairs of radiance_rays_grad, any other throws).  Stored, no
+// atomic add: bitwise reproducible.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void radiance_rays_tangent(const vec4f_t *o, const vec4f_t *n, size_t nrays, const gaussians_t &gaussians, const f32 *tangent, const f32 *ray_tangent,
+                           vec4f_t *out)
+{
+    static_assert(sizeof(vec4f_t) == 4 * sizeof(f32), "out is handed to the library as 4 floats per ray");
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    std::vector<f32> oo(3 * nrays), nn(3 * nrays);
+    for (size_t r = 0; r < nrays; ++r) {
+        oo[3 * r] = o[r].x; oo[3 * r + 1] = o[r].y; oo[3 * r + 2] = o[r].z;
+        nn[3 * r] = n[r].x; nn[3 * r + 1] = n[r].y; nn[3 * r + 2] = n[r].z;
+    }
+    d.check(vrt_hip_radiance_rays_tangent(d.ctx, nrays, oo.data(), 1, nn.data(), tangent, ray_tangent, out ? &out[0].x : nullptr),
+            "vrt_hip_radiance_rays_tangent");
+}
+// The same on the device (all three 16-byte aligned): STORES d_out, enqueued on hip_stream, nothing waits.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void radiance_rays_tangent_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const gaussians_t &gaussians,
+                                  const f32 *d_tangent, const f32 *d_ray_tangent, f32 *d_out, void *hip_stream)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    d.check(vrt_hip_radiance_rays_tangent_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_tangent, d_ray_tangent, d_out, hip_stream),
+            "vrt_hip_radiance_rays_tangent_device");
+}
 // Transmittance bundles: broadcast_transmittance for ANY number of rays at ns depths each in ONE call, under the same per-ray cull
 // (vrt_hip_transmittance_bundle in include/vrt_hip.h: the exponent moves by less than 0.8 * cull_eps * min(N, 4096) = 3.3e-6 at the
 // defaults).  s: ns sample distances shared by all rays (s_per_ray = false) or nrays * ns, [r * ns + k]; T_out[r * ns + k].  Shadow

@@ -527,6 +527,50 @@ int vrt_hip_transmittance_bundle_grad_rays(vrt_hip_ctx *ctx, size_t nrays, const
                                            const float *s, size_t ns, int s_per_ray, const float *grad_T, int wrt,
                                            float *grad_out /* N rows, OVERWRITTEN, or NULL */, float *grad_s_out /* nrays * ns, or NULL */,
                                            float *grad_rays_out /* nrays rows, or NULL */);
+/* -------- tangent bundles: J . v of the radiance of ANY rays, forward mode -----------------------------------------------------------
+ * The other half of the gradient bundles: they give J^T . u, from d(loss) / d(radiance) to d(loss) / d(Gaussians, rays); this gives
+ * J . v, how the radiance of every ray moves when the Gaussians and the rays move along a given direction v (a Gauss-Newton step by
+ * conjugate gradients needs J^T (J v); a sensitivity image is J v for a one-hot v).  The function is the one the gradient bundles
+ * differentiate (the formula at "gradient bundles" above): L(r) over the list K that ray r keeps under the bundles' cull rule, HELD
+ * FIXED, Exp and Erf the selected pair's, their derivatives the analytic ones, also for the Abramowitz-Stegun Erf.  Supported pairs:
+ * {vcl_exp, expf} x {A&S erf, erff}; under any other pair the call returns VRT_HIP_ERR_INVALID with a message and enqueues nothing.
+ * The direction:
+ *   tangent      N rows of VRT_HIP_GRAD_STRIDE floats, the gradient table's layout (J and J^T share one layout):
+ *                [0..3] d albedo rgba   [4..6] d mu xyz   [7] d sigma   [8] d magnitude   [9..11] never read
+ *   ray_tangent  nrays rows of VRT_HIP_RAY_GRAD_STRIDE floats, the ray rows' layout, per ray also when origin_per_ray == 0:
+ *                [0..2] d origin   [3] never read   [4..6] d direction   [7] never read
+ *                Of d direction only the part perpendicular to dir counts: the derivative is taken along normalise(dir + eps t).  (It
+ *                enters through c_perp_j . t alone, which drops the part along dir to rounding, as the ray rows are perpendicular
+ *                to dir to rounding: J . v is the transpose of the _rays forms' rows term for term.)
+ * Either may be NULL, which means zero; both NULL: VRT_HIP_ERR_INVALID.  The result:
+ *   out[4 r ..] = sum_{j in K(r)} dL(r) / d(theta_j) . tangent_j  +  dL(r) / d(o, n) . ray_tangent_r          4 floats per ray, STORED
+ * A Gaussian that a ray drops contributes nothing to that ray, whatever its row holds (its row is not read for it) -- one of magnitude
+ * 0 is such a case for every ray; a ray that keeps nothing gets zeros; nothing behind ray nrays - 1 is written.
+ * With c = mu - o, mubar = c . n, c_perp = c - mubar n, d2 = |c_perp|^2, r = 1 / (sqrt2 sigma), C = 2 / sqrt(pi), dn the tangential part
+ * of the ray's direction tangent, x_ikj = (mubar_i + k sigma_i - mubar_j) r_j, D_ikj = Erf(-mubar_j r_j) - Erf(x_ikj), e1_j =
+ * exp(-(mubar_j r_j)^2), e2_ikj = exp(-x_ikj^2) and t_ik the ik term of L without its albedo, the chain rule gives
+ *   dc_j = dmu_j - do,   dmubar_j = dc_j . n + c_perp_j . dn,   dd2_j = 2 c_perp_j . dc_j - 2 mubar_j (c_perp_j . dn),
+ *   dA_j = A_j (dsigma_j / sigma_j - dd2_j / (2 sigma_j^2) + d2_j dsigma_j / sigma_j^3) + (A_j / m_j) dm_j        (A_j / m_j formed without dividing)
+ *   dx_ikj = (dmubar_i + k dsigma_i - dmubar_j) r_j - x_ikj dsigma_j / sigma_j,
+ *   dD_ikj = C [e1_j (-dmubar_j r_j + mubar_j r_j dsigma_j / sigma_j) - e2_ikj dx_ikj],     dE_ik = sum_j (dA_j D_ikj + A_j dD_ikj),
+ *   dL = sum_ik [da_i t_ik + a_i t_ik (dsigma_i / sigma_i + dm_i / m_i - dd2_i / (2 sigma_i^2) + d2_i dsigma_i / sigma_i^3 + dE_ik)]   (no division by m_i either)
+ * ONE pass over the (emitter, sample, absorber) pairs; every result is a store; no atomic add takes part and there is no table, so a
+ * result is a function of (ray, its ray tangent, the tangent rows of the Gaussians it keeps, scene, options) alone: bitwise
+ * reproducible from run to run, host or device form, whatever the other rays of the bundle are, with vrt_hip_set_ray_index and
+ * vrt_hip_set_ray_sort on or off (the same bits at the same ray index).  vrt_hip_set_grad_ordered has no effect here.
+ * d_tangent, d_ray_tangent and d_out are 16-byte aligned.  Everything else is the gradient bundle's contract: origins, origin_per_ray,
+ * dirs, the stream rules (everything enqueued on hip_stream, no host wait, no allocation once a bundle of this size has been seen), the
+ * buffers that only grow, the shared queue / counters / scratch slots / bitmap, "counts as a frame in flight";
+ * vrt_hip_get_ray_stats / vrt_hip_get_ray_index_stats report for the same rays every field a radiance bundle reports, and the same rays
+ * go to the same kind of kernel.  nrays == 0 or a scene of no Gaussians returns VRT_HIP_OK with nothing launched and nothing written;
+ * NULL origins, dirs or out with work to do, both inputs NULL, more than 2^32 - 16 rays, or an unsupported pair: VRT_HIP_ERR_INVALID
+ * with a message, nothing enqueued.  The host form stages tangent, ray_tangent and out in context buffers that only grow and waits once. */
+int vrt_hip_radiance_rays_tangent_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                         const float *d_tangent      /* N rows of VRT_HIP_GRAD_STRIDE, or NULL */,
+                                         const float *d_ray_tangent  /* nrays rows of VRT_HIP_RAY_GRAD_STRIDE, or NULL */,
+                                         float *d_out                /* 4 per ray, STORED */, void *hip_stream);
+int vrt_hip_radiance_rays_tangent(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                                  const float *tangent, const float *ray_tangent, float *out);   /* host pointers, waits */
 /* -------- ordered gradient tables: reproducible bits, no float atomics --------------------------------------------------------------
  * Off by default (first value from VRT_HIP_GRAD_ORDERED=0|1 at vrt_hip_create).  With on != 0 all eight gradient entry points above
  * that are given a table (d_grad / grad_out) build it without a single float atomic add, into the table or into any staging memory,

@@ -145,6 +145,8 @@ SYMBOLS = {
     "vrt_hip_transmittance_bundle_grad": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p, C.c_int, _f32p, _f32p]),
     "vrt_hip_radiance_rays_grad_rays_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "vrt_hip_radiance_rays_grad_rays": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p]),
+    "vrt_hip_radiance_rays_tangent_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "vrt_hip_radiance_rays_tangent": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p]),
     "vrt_hip_transmittance_bundle_grad_rays_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int, _vp, _vp, _vp,
                                                                 _vp]),
     "vrt_hip_transmittance_bundle_grad_rays": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p, C.c_int, _f32p, _f32p,
@@ -245,6 +247,35 @@ def ray_grad_columns(rows):
     """The columns of a gradient bundle's ray rows [nrays, RAY_GRAD_STRIDE] (numpy array or torch tensor) by name: views, not copies.
     "origin": d(loss) / d(origin) per ray (a bundle with one origin: sum them over the rays); "dir": the tangential d(loss) / d(dir)."""
     return {"origin": rows[:, 0:3], "dir": rows[:, 4:7]}
+
+
+def _pack_tangent(tangent, n):
+    """A tangent bundle's direction in the Gaussians as the library takes it, f32 [n, GRAD_STRIDE]: from the dict grad_columns makes (a
+    missing key: zeros) or from a packed array."""
+    if not isinstance(tangent, dict):
+        t = np.ascontiguousarray(tangent, np.float32)
+        assert t.shape == (n, GRAD_STRIDE), t.shape
+        return t
+    t = np.zeros((n, GRAD_STRIDE), np.float32)
+    cols = grad_columns(t)
+    for k, v in tangent.items():
+        cols[k][...] = np.asarray(v, np.float32).reshape(cols[k].shape)
+    return t
+
+
+def _pack_ray_tangent(ray_tangent, nrays):
+    """... and in the rays, f32 [nrays, RAY_GRAD_STRIDE]: from the dict ray_grad_columns makes (a missing key: zeros; an "origin" of
+    [3] moves every ray's origin alike) or from a packed array."""
+    if not isinstance(ray_tangent, dict):
+        t = np.ascontiguousarray(ray_tangent, np.float32)
+        assert t.shape == (nrays, RAY_GRAD_STRIDE), t.shape
+        return t
+    t = np.zeros((nrays, RAY_GRAD_STRIDE), np.float32)
+    cols = ray_grad_columns(t)
+    for k, v in ray_tangent.items():
+        v = np.asarray(v, np.float32)
+        cols[k][...] = v.reshape(1, 3) if v.size == 3 else v.reshape(nrays, 3)
+    return t
 
 
 class Renderer:
@@ -649,6 +680,29 @@ class Renderer:
         float32, 16-byte aligned: ray_grad_columns names its columns); either may be 0, not both."""
         self._device("radiance_rays_grad_rays_device", nrays, d_origins, origin_per_ray, d_dirs, d_grad_radiance or None, d_grad or None,
                      d_grad_rays or None, stream or None)
+
+    def radiance_rays_tangent(self, origins, dirs, tangent=None, ray_tangent=None):
+        """vrt_hip_radiance_rays_tangent: forward mode, J . v -- how what radiance_rays returns for the same rays moves along a direction
+        in parameter space (each ray's kept list is held fixed).  tangent: the direction's part in the Gaussians, the dict grad_columns
+        makes ({"albedo": [N, 4], "mu": [N, 3], "sigma": [N], "magnitude": [N]}, a missing key: zeros) or a packed [N, GRAD_STRIDE] array
+        (columns 9..11 are never read); ray_tangent: its part in the rays, the dict ray_grad_columns makes ({"origin": [nrays, 3] or [3]
+        for every ray, "dir": [nrays, 3]}, a missing key: zeros) or a packed [nrays, RAY_GRAD_STRIDE] array; of "dir" only the part
+        perpendicular to the ray's direction counts.  Either may be None (zero), not both.  Returns float32 [nrays, 4], stored without
+        atomic adds: bitwise reproducible."""
+        origins, dirs, per_ray = _rays(origins, dirs)
+        t = None if tangent is None else _pack_tangent(tangent, self.n)
+        rt = None if ray_tangent is None else _pack_ray_tangent(ray_tangent, len(dirs))
+        out = np.zeros((len(dirs), 4), np.float32)
+        self._chk(self._L.vrt_hip_radiance_rays_tangent(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), None if t is None else _fp(t),
+                                                        None if rt is None else _fp(rt), _fp(out)), "radiance_rays_tangent")
+        return out
+
+    def radiance_rays_tangent_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_tangent=0, d_ray_tangent=0, d_out=0, stream=0):
+        """vrt_hip_radiance_rays_tangent_device: device pointers, everything enqueued on `stream`; reads d_tangent ([N, GRAD_STRIDE]
+        float32) and d_ray_tangent ([nrays, RAY_GRAD_STRIDE] float32), either may be 0, not both, and STORES d_out ([nrays, 4] float32);
+        all three 16-byte aligned."""
+        self._device("radiance_rays_tangent_device", nrays, d_origins, origin_per_ray, d_dirs, d_tangent or None, d_ray_tangent or None,
+                     d_out or None, stream or None)
 
     def transmittance_bundle_grad(self, origins, dirs, s, grad_T, wrt=TGRAD_T, s_per_ray=None, want_table=True, want_grad_s=True, want_rays=False):
         """vrt_hip_transmittance_bundle_grad_rays: the derivative of a loss with respect to the Gaussians and the samples, given its

@@ -21,6 +21,13 @@ torch.nn.functional.normalize of a raw vector needs no more).  These rows come w
 ctx.needs_input_grad decides what backward asks of the library: with no Gaussian parameter requiring grad no table is passed (a
 pose-only fit pays for no atomic add), with no ray requiring grad the call is the one without ray rows.
 
+Forward mode.  radiance_rays also works under torch.autograd.forward_ad and torch.func.jvp: its jvp is
+Renderer.radiance_rays_tangent_device (include/vrt_hip.h, "tangent bundles"), J . v under the same fixed kept lists and the same pairs,
+one pass, stored without atomic adds and bitwise reproducible.  The tangent table is built from the tangents of mu, albedo, sigma and
+magnitude, the ray rows from those of origins ([3]: the same row for every ray) and dirs (only the part perpendicular to each direction
+counts); a group without any tangent is not passed, and with no tangent at all nothing is issued.  transmittance_bundle and depth_bundle
+are reverse mode only.
+
 A Gaussian whose magnitude is exactly 0 is dropped by every ray's cull and therefore receives NO gradient, magnitude.grad included
 (although the true derivative is not 0): initialise magnitudes away from 0.
 
@@ -39,9 +46,14 @@ from . import GRAD_STRIDE, RAY_GRAD_STRIDE, TGRAD_DEPTH, TGRAD_T, grad_columns, 
 
 
 def _upload(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs):
-    """What every forward begins with: the scene of `renderer` replaced by the parameters (on the device when all four are on the
-    renderer's cuda device, through the host otherwise: the module's docstring), the rays on torch's current device, and in ctx what
-    backward needs of them.  Returns (device, origins, dirs, origin per ray)."""
+    """What a forward with a ctx begins with: _set_scene, then _remember.  Returns (device, origins, dirs, origin per ray)."""
+    _set_scene(renderer, mu, albedo, sigma, magnitude)
+    return _remember(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs)
+
+
+def _set_scene(renderer, mu, albedo, sigma, magnitude):
+    """The scene of `renderer` replaced by the parameters: on the device when all four are on the renderer's cuda device, through the
+    host otherwise (the module's docstring)."""
     dev = torch.device("cuda", torch.cuda.current_device())
     params = (mu, albedo, sigma, magnitude)
     if getattr(renderer, "device", None) == dev.index and all(t.device == dev for t in params):
@@ -53,11 +65,22 @@ def _upload(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs):
     else:
         host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in params]
         renderer.set_gaussians_soa(host[0], host[1][:, :3], host[2], host[3], alpha=np.ascontiguousarray(host[1][:, 3]))
-        n = len(host[2])
+
+
+def _rays(origins, dirs):
+    """The rays as the library takes them, on torch's current device: (device, origins, dirs [nrays, 3], origin per ray).  Rays that are
+    float32, contiguous and on that device already are taken as they are, not copied."""
+    dev = torch.device("cuda", torch.cuda.current_device())
     o = origins.detach().to(dev, torch.float32).contiguous()
     d = dirs.detach().to(dev, torch.float32).contiguous().reshape(-1, 3)
-    per_ray = o.numel() != 3
-    ctx.renderer, ctx.rays, ctx.n = renderer, (o, d, per_ray), n
+    return dev, o, d, o.numel() != 3
+
+
+def _remember(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs):
+    """In ctx what backward (and jvp) need of the call: the renderer, the rays (_rays), the scene's size, and where and of what type the
+    inputs are.  Returns what _rays returns."""
+    dev, o, d, per_ray = _rays(origins, dirs)
+    ctx.renderer, ctx.rays, ctx.n = renderer, (o, d, per_ray), sigma.numel()
     ctx.ray_like = (origins, dirs)
     ctx.devices = [t.device for t in (mu, albedo, sigma, magnitude)]
     ctx.dtypes = [t.dtype for t in (mu, albedo, sigma, magnitude)]
@@ -98,10 +121,30 @@ def _ptr(t):
     return t.data_ptr() if t is not None else 0
 
 
-class _RadianceRays(torch.autograd.Function):
+class _TangentBundle(torch.autograd.Function):
+    """The library call of _RadianceRays.jvp as a Function of its own: under torch.func's transforms the tensors a jvp sees are wrapped,
+    and a Function's forward is where torch hands over plain ones, whose memory can be named.  Not differentiable itself."""
+
     @staticmethod
-    def forward(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs):
-        dev, o, d, per_ray = _upload(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs)
+    def forward(renderer, o, d, per_ray, table, rows):
+        out = torch.zeros((d.shape[0], 4), dtype=torch.float32, device=o.device)
+        renderer.radiance_rays_tangent_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), d_tangent=_ptr(table), d_ray_tangent=_ptr(rows),
+                                              d_out=out.data_ptr(), stream=torch.cuda.current_stream(o.device).cuda_stream)
+        return out
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+
+class _RadianceRays(torch.autograd.Function):
+    """forward and setup_context apart, as torch.func's transforms (jvp among them) ask of a Function: forward sets the scene and shades,
+    setup_context remembers (from the inputs alone, which is all torch gives it: rays that forward had to convert are converted again)"""
+
+    @staticmethod
+    def forward(renderer, mu, albedo, sigma, magnitude, origins, dirs):
+        _set_scene(renderer, mu, albedo, sigma, magnitude)
+        dev, o, d, per_ray = _rays(origins, dirs)
         out = torch.empty((d.shape[0], 4), dtype=torch.float32, device=dev)
         if d.shape[0]:
             renderer.radiance_rays_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), d_radiance=out.data_ptr(),
@@ -109,7 +152,38 @@ class _RadianceRays(torch.autograd.Function):
         return out
 
     @staticmethod
+    def setup_context(ctx, inputs, output):
+        _remember(ctx, *inputs)
+        # jvp sees None for an input without a tangent, not zeros, and passes no table for them.  The switch holds for backward too: it
+        # sees None where the output's gradient is undefined, and then returns no gradients instead of those of a zero grad_out.
+        ctx.set_materialize_grads(False)
+
+    @staticmethod
+    def jvp(ctx, _, t_mu, t_albedo, t_sigma, t_magnitude, t_origins, t_dirs):
+        """Forward mode (torch.autograd.forward_ad, torch.func.jvp): Renderer.radiance_rays_tangent_device over the scene and the rays
+        of the forward, on torch's current stream.  The tangent table is built from the tangents of the four parameters, the ray rows
+        from those of origins (one origin for the bundle: the same row for every ray) and dirs; a group none of whose inputs has a
+        tangent is not passed at all, and with no tangent anywhere nothing is issued."""
+        o, d, per_ray = ctx.rays
+        nrays, n = d.shape[0], ctx.n
+
+        def cols(shapes, tangents):
+            return [torch.zeros(shape, dtype=torch.float32, device=o.device) if t is None else t.detach().to(o.device, torch.float32).reshape(shape)
+                    for shape, t in zip(shapes, tangents)]
+        table = rows = None
+        if any(t is not None for t in (t_mu, t_albedo, t_sigma, t_magnitude)):          # grad_columns' layout
+            table = torch.cat(cols(((n, 4), (n, 3), (n, 1), (n, 1), (n, GRAD_STRIDE - 9)), (t_albedo, t_mu, t_sigma, t_magnitude, None)), 1)
+        if t_origins is not None or t_dirs is not None:                                 # ray_grad_columns' layout
+            t_o = None if t_origins is None else t_origins.detach().reshape(-1, 3).expand(nrays, 3)      # [1, 3]: the same row for every ray
+            rows = torch.cat(cols(((nrays, 3), (nrays, 1), (nrays, 3), (nrays, 1)), (t_o, None, t_dirs, None)), 1)
+        if not (nrays and n) or (table is None and rows is None):
+            return torch.zeros((nrays, 4), dtype=torch.float32, device=o.device)
+        return _TangentBundle.apply(ctx.renderer, o, d, per_ray, table, rows)
+
+    @staticmethod
     def backward(ctx, grad_out):
+        if grad_out is None:                 # (set_materialize_grads above) nothing flows back through the radiance
+            return (None,) * 7
         o, d, per_ray = ctx.rays
         g = grad_out.to(o.device, torch.float32).contiguous()
         table, rows = _outputs(ctx, 1)
@@ -123,7 +197,7 @@ def radiance_rays(renderer, mu, albedo, sigma, magnitude, origins, dirs):
     """Radiance [nrays, 4] (a cuda tensor on torch's current device and stream) of the rays through the scene of the four parameter
     tensors mu [N, 3], albedo [N, 4], sigma [N], magnitude [N], differentiable in those four and in the rays.  origins: [3] or
     [nrays, 3]; dirs: [nrays, 3], unit length (its gradient is the tangential one: see the module's docstring).  The scene of `renderer` is REPLACED by the parameters (see the module's docstring);
-    backward must run before the renderer's scene or options change again."""
+    backward must run before the renderer's scene or options change again.  Forward mode too: the module's docstring."""
     return _RadianceRays.apply(renderer, mu, albedo, sigma, magnitude, origins, dirs)
 
 
@@ -170,12 +244,14 @@ class _Profile(torch.autograd.Function):
 def transmittance_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, s):
     """Transmittance [nrays, ns] (a cuda tensor on torch's current device and stream) at the sample distances s ([ns], shared by the
     rays, or [nrays, ns]) along the rays through the scene of the four parameter tensors, differentiable in mu, sigma, magnitude and
-    s; albedo gets no gradient (None).  Rays, the replaced scene and the order of backward: as radiance_rays."""
+    s; albedo gets no gradient (None).  Reverse mode only: forward-mode AD (forward_ad, torch.func.jvp) raises.  Rays, the replaced scene
+    and the order of backward: as radiance_rays."""
     return _Profile.apply(renderer, TGRAD_T, mu, albedo, sigma, magnitude, origins, dirs, s)
 
 
 def depth_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, tau):
     """The distance [nrays, nt] along each ray at which its transmittance falls to the levels tau ([nt], shared by the rays, or
     [nrays, nt]), differentiable in mu, sigma, magnitude and tau (the derivative of the ideal crossing; a result of +inf, 0 or NaN
-    gets and gives no gradient); albedo gets no gradient (None).  Rays, the replaced scene and the order of backward: as radiance_rays."""
+    gets and gives no gradient); albedo gets no gradient (None).  Reverse mode only: forward-mode AD raises.  Rays, the replaced scene and
+    the order of backward: as radiance_rays."""
     return _Profile.apply(renderer, TGRAD_DEPTH, mu, albedo, sigma, magnitude, origins, dirs, tau)

@@ -253,6 +253,8 @@ struct vrt_hip_ctx {
     DevBuf<float> rays_each_out;  // something per ray and value, out: T, depths, d loss / d samples (or levels)
     DevBuf<float> rays_table_out; // the gradient table [n, VRT_HIP_GRAD_STRIDE], cleared ahead of every bundle that adds to it
     DevBuf<float> rays_rows_out;  // the ray rows of a gradient bundle [nrays, VRT_HIP_RAY_GRAD_STRIDE], out
+    DevBuf<float> rays_table_in;  // the tangent table of a tangent bundle [n, VRT_HIP_GRAD_STRIDE], in
+    DevBuf<float> rays_rows_in;   // the ray tangents of a tangent bundle [nrays, VRT_HIP_RAY_GRAD_STRIDE], in
     DevBuf<float4> rays_rad;      // radiance per ray, out
     DevBuf<uint32_t> rays_img;    // packed pixels per ray, out
     bool ray_stats_valid = false; // ray_stats holds the counts of the last bundle (stats were on for it)

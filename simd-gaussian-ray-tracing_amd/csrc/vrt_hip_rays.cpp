@@ -1,8 +1,8 @@
 // vrt_hip_rays.cpp -- ray bundles of libvrt_hip.so (vrt_hip_radiance_rays*, vrt_hip_transmittance_bundle*, vrt_hip_depth_bundle*,
-// vrt_hip_radiance_rays_grad*, vrt_hip_transmittance_bundle_grad*, their _rays forms): radiance of caller-given rays, transmittance at sample distances along
+// vrt_hip_radiance_rays_grad*, vrt_hip_transmittance_bundle_grad*, their _rays forms, vrt_hip_radiance_rays_tangent*): radiance of caller-given rays, transmittance at sample distances along
 // them, the distance at which their transmittance falls to given levels, or the derivative of their radiance, transmittance or depth with
-// respect to the Gaussians, culled per ray (vrt_ray_kernel.hip, vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip,
-// vrt_ray_grad_kernel.hip, vrt_ray_trans_grad_kernel.hip).  The scene tables and the
+// respect to the Gaussians, or how their radiance moves along a direction (forward mode), culled per ray (vrt_ray_kernel.hip,
+// vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip, vrt_ray_grad_kernel.hip, vrt_ray_trans_grad_kernel.hip, vrt_ray_tangent_kernel.hip).  The scene tables and the
 // chunk spheres are the frame pipeline's; the long-ray queue, its counters and the long kernel's scratch slots belong to the context
 // and only grow.  So do the buffers of the ordered gradient tables (vrt_hip_set_grad_ordered: ordered_bundle, and the two read-outs)
 // and of the sorted bundles (vrt_hip_set_ray_sort: sort_bundle, and the two read-outs).
@@ -241,6 +241,8 @@ const BundleKind GRADIENT = { "radiance_rays_grad", "NULL grad_radiance or gradi
                               launch_ray_grad_bundle_ordered, true, 0 };
 const BundleKind TRANS_GRADIENT = { "transmittance_bundle_grad", "NULL samples or grad_T, or neither a gradient table nor grad_s", "ns", true, true,
                                     launch_ray_trans_grad_bundle, launch_ray_trans_grad_bundle_ordered, false, 4 };
+// forward mode: a derivative (the scene of no Gaussians, the pairs), but no table: nothing for the ordered switch to order
+const BundleKind TANGENT = { "radiance_rays_tangent", "NULL output, or neither a tangent table nor ray tangents", "", true, false, launch_ray_tangent_bundle };
 
 // The rays of a call, device or host pointers alike
 struct Rays {
@@ -376,14 +378,16 @@ int host_bundle(vrt_hip_ctx *c, const Rays &r, std::initializer_list<CopiedIn> i
     int rc = quiesce(c);
     if (rc) return rc;
     const size_t no = (r.origin_per_ray ? r.nrays : 1) * 3;
-    for (const CopiedIn &s : in) HIPCHK(c, s.buf.reserve(s.count));
+    for (const CopiedIn &s : in)
+        if (s.host) HIPCHK(c, s.buf.reserve(s.count)); // (an input the kind lets the caller leave out: host == nullptr)
     for (const BroughtBack &s : out)
         if (s.host) HIPCHK(c, s.buf.reserve(s.count));
     HIPCHK(c, c->rays_in[0].reserve(no));
     HIPCHK(c, c->rays_in[1].reserve(r.nrays * 3));
     HIPCHK(c, hipMemcpyAsync(c->rays_in[0].p, r.origins, no * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->rays_in[1].p, r.dirs, r.nrays * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    for (const CopiedIn &s : in) HIPCHK(c, hipMemcpyAsync(s.buf.data(), s.host, s.count * s.buf.size, hipMemcpyHostToDevice, c->stream));
+    for (const CopiedIn &s : in)
+        if (s.host) HIPCHK(c, hipMemcpyAsync(s.buf.data(), s.host, s.count * s.buf.size, hipMemcpyHostToDevice, c->stream));
     for (const BroughtBack &s : out)
         if (s.host && s.clear) HIPCHK(c, hipMemsetAsync(s.buf.data(), 0, s.count * s.buf.size, c->stream));
     c->ord_ran = false;
@@ -466,6 +470,31 @@ int vrt_hip_radiance_rays_grad(vrt_hip_ctx *c, size_t nrays, const float *origin
                                const float *grad_radiance, float *grad_out)
 {
     return vrt_hip_radiance_rays_grad_rays(c, nrays, origins, origin_per_ray, dirs, grad_radiance, grad_out, nullptr);
+}
+
+// forward mode: the direction in, J . v of the radiance out
+int vrt_hip_radiance_rays_tangent_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                         const float *d_tangent, const float *d_ray_tangent, float *d_out, void *hip_stream)
+{
+    return device_bundle(c, TANGENT, { nrays, d_origins, origin_per_ray, d_dirs }, 1, d_out && (d_tangent || d_ray_tangent), 0, hip_stream,
+                         [&](RayArgs &a) {
+                             a.tangent = d_tangent; a.ray_tangent = d_ray_tangent; a.tangent_out = (float4 *)d_out;
+                         });
+}
+
+// the tangent table of the scene's size and the ray tangents in, either where given; 4 floats per ray out
+int vrt_hip_radiance_rays_tangent(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *tangent,
+                                  const float *ray_tangent, float *out)
+{
+    const Rays r = { nrays, origins, origin_per_ray, dirs };
+    int rc;
+    if (bundle_over(c, TANGENT, r, 1, out && (tangent || ray_tangent), 0, rc)) return rc;
+    return host_bundle(c, r, { { c->rays_table_in, tangent, (size_t)c->n * VRT_HIP_GRAD_STRIDE },
+                               { c->rays_rows_in, ray_tangent, nrays * VRT_HIP_RAY_GRAD_STRIDE } },
+                       { { c->rays_rad, out, nrays } }, [&](const Rays &d) {
+                           return vrt_hip_radiance_rays_tangent_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, wanted(tangent, c->rays_table_in),
+                                                                       wanted(ray_tangent, c->rays_rows_in), (float *)c->rays_rad.p, c->stream);
+                       });
 }
 
 int vrt_hip_transmittance_bundle_grad_rays_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,

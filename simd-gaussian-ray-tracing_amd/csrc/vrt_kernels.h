@@ -359,6 +359,10 @@ struct RayArgs {
     // Sorted bundles (vrt_hip_set_ray_sort; behind everything the other kernels read)
     const uint32_t *order;          // nullable, [nrays] slot -> ray id: lane l of workgroup b of a lane = ray kernel takes ray order[64 b + l];
                                     // nullptr: ray 64 b + l, the bundle's own order
+    // Tangent bundles (vrt_ray_tangent_kernel.hip; behind everything the other kernels read)
+    const float *tangent;           // nullable, [S.n * VRT_HIP_GRAD_STRIDE], 16-byte aligned: the direction's row per Gaussian, columns 9..11 never used
+    const float *ray_tangent;       // nullable, [r * VRT_HIP_RAY_GRAD_STRIDE], 16-byte aligned: d origin, -, d direction, - per ray
+    float4 *tangent_out;            // [r] stored: how the radiance of ray r moves along the direction
 };
 constexpr int GRAD_ORD_COLS = 9;    // floats per record
 // the words of an ordered call, cleared on the stream ahead of its count pass: rays whose re-cull missed the counted length; records
@@ -379,6 +383,9 @@ bool ray_grad_pair_supported(int exp_kind, int erf_kind);
 // the same cull, then d(loss) / d(Gaussians) from a.grad_T at the samples a.s, added into columns 4..8 of a.grad, and d(loss) /
 // d(samples or levels) stored to a.grad_s, d(loss) / d(rays) to a.grad_rays (vrt_ray_trans_grad_kernel.hip).  The pairs of ray_grad_pair_supported; any other enqueues nothing.
 void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+// the same cull, then J . v: how the radiance of every ray moves along the direction (a.tangent per Gaussian, a.ray_tangent per ray, either
+// nullable), stored to a.tangent_out (vrt_ray_tangent_kernel.hip).  The pairs of ray_grad_pair_supported; any other enqueues nothing.
+void launch_ray_tangent_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
 // Ordered gradient tables (vrt_hip_set_grad_ordered; vrt_grad_ordered_kernel.hip has the pipeline).  The same two bundles with every
 // add into a.grad replaced by a store into the records at a.ord_base[r] (the ORDERED instantiations, in translation units of their own:
 // vrt_ray_grad_ordered_kernel.hip, vrt_ray_trans_grad_ordered_kernel.hip); a.grad is not touched.

@@ -1,6 +1,7 @@
 // vrt_ray_grad.hpp -- what the derivative kernels of the ray bundles share: vrt_ray_grad_kernel.hip (d radiance / d Gaussians) and
-// vrt_ray_trans_grad_kernel.hip (d transmittance / d Gaussians and samples, d depth / d Gaussians and levels).  One text each, for both
-// translation units and for the short and the long kernel of either:
+// vrt_ray_trans_grad_kernel.hip (d transmittance / d Gaussians and samples, d depth / d Gaussians and levels) -- and, of grad_gauss, the
+// list walk and grad_acc's layout, vrt_ray_tangent_kernel.hip (forward mode: J . v of the radiance).  One text each, for these
+// translation units and for the short and the long kernel of each:
 //   grad_gauss        one Gaussian against one ray with the compensated c = mu - o and mubar = c . n that keep d / d mu accurate: the same
 //                     (ray, Gaussian) gives the same A, c_perp, d2 and Erf(-mubar r) in either kind of gradient
 //   grad_deal         one weight dealt to one absorber: P, Q, R

@@ -80,6 +80,16 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
       faster than with the index on and the sort off.  `--sort-only` runs this part alone, prints its JSON line and writes ray_sort.json
       and ray_sort.md (and nothing else) to --out-dir; the .md ends with the text of <out-dir>/ray_sort_resources.txt when that file is
       there (the output of `tools/kernel_resources.sh raysort`).
+  (tn) tangent bundles (vrt_hip_radiance_rays_tangent_device, a dense tangent table and dense ray tangents in, 4 floats per ray out): the
+      2^20 scattered rays of (d) and 4096 rays from one origin aimed at the same dozen Gaussians of `-g 64` (every wave's lanes keep the
+      same few), device pointers, Morton index off and on (two contexts), five paths alternating in the same run: the tangent bundle, the
+      radiance bundle, the gradient bundle with a table and atomic adds (vrt_hip_radiance_rays_grad_device), and two radiance bundles back
+      to back (what a one-sided finite difference costs); stream events around back-to-back calls, after warm-up.  The yardstick is the
+      gradient bundle in the same run: one pass instead of two and stores instead of atomic adds, so the run fails if the tangent
+      bundle's median exceeds the gradient bundle's in any row.  The ratios to one and to two radiance bundles are written down, not
+      judged.  `--tangent-only` runs this part alone, prints its JSON line and writes ray_tangent.json and ray_tangent.md (and nothing
+      else) to --out-dir; the .md ends with the text of <out-dir>/ray_tangent_resources.txt when that file is there (the output of
+      `tools/kernel_resources.sh raytangent`).
 """
 import argparse
 import json
@@ -688,6 +698,108 @@ final {pose['loss'][-1]:.4e}
     return "\n".join(lines)
 
 
+def dozen_rays(g, count=4096, seed=13, origin=(0.0, 0.0, -4.0)):
+    """`count` rays from one origin, each aimed at one of the same twelve neighbouring Gaussians of the grid's middle with a jitter of
+    about sigma"""
+    rng = np.random.default_rng(seed)
+    mu = g["mu"][:, :3].astype(np.float64)
+    near = np.argsort(((mu - mu.mean(0)) ** 2).sum(1), kind="stable")[:12]
+    pick = near[rng.integers(0, 12, size=count)]
+    target = mu[pick] + rng.normal(size=(count, 3)) * g["sigma"][pick, None]
+    o = np.asarray(origin, f32)
+    d = target - o.astype(np.float64)
+    return o, np.ascontiguousarray((d / np.linalg.norm(d, axis=1, keepdims=True)).astype(f32))
+
+
+def part_tangent(g, calls=3, repeats=7):
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(17)
+    t_v = torch.from_numpy(rng.uniform(-1, 1, size=(len(g), pkg.GRAD_STRIDE)).astype(f32)).cuda()
+    rows = {}
+    for label, (o, d), per in (("scattered_2^20", scattered(g, 1 << 20), 1), ("dozen_4096", dozen_rays(g), 0)):
+        nrays = len(d)
+        t_o, t_d = torch.from_numpy(np.ascontiguousarray(o, f32)).cuda(), torch.from_numpy(np.ascontiguousarray(d, f32)).cuda()
+        t_g = torch.from_numpy(rng.uniform(-1, 1, size=(nrays, 4)).astype(f32)).cuda()
+        t_rv = torch.from_numpy(rng.uniform(-1, 1, size=(nrays, pkg.RAY_GRAD_STRIDE)).astype(f32)).cuda()
+        ctx = [pkg.Renderer(0), pkg.Renderer(0)]
+        for on, r in enumerate(ctx):
+            r.set_gaussians(g)
+            r.set_ray_index(on)
+        rad = [torch.zeros((nrays, 4), dtype=torch.float32, device="cuda") for _ in ctx]
+        out = [torch.zeros((nrays, 4), dtype=torch.float32, device="cuda") for _ in ctx]
+        # (the gradient call ADDS into its table, and the table is not cleared between the calls of a window: what a clear would cost is
+        # left out of the yardstick's time, which only makes the comparison harder for the tangent bundle; the sums' values are not used)
+        table = [torch.zeros((len(g), pkg.GRAD_STRIDE), dtype=torch.float32, device="cuda") for _ in ctx]
+        torch.cuda.synchronize()
+
+        def radiance(k):
+            ctx[k].radiance_rays_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), rad[k].data_ptr(), 0, PACK, st)
+
+        def twice(k):
+            radiance(k)
+            radiance(k)
+        fns = []
+        for k in (0, 1):
+            fns.append(lambda k=k: ctx[k].radiance_rays_tangent_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_v.data_ptr(), t_rv.data_ptr(),
+                                                                      out[k].data_ptr(), st))
+            fns.append(lambda k=k: radiance(k))
+            fns.append(lambda k=k: ctx[k].radiance_rays_grad_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_g.data_ptr(), table[k].data_ptr(), st))
+            fns.append(lambda k=k: twice(k))
+        t = windows(fns, calls, repeats, warm=2)
+        ctx[0].enable_stats(True)
+        fns[0]()
+        stats = ctx[0].ray_stats()
+        fns[4]()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(out[0], out[1]))
+        finite = bool(torch.isfinite(out[0]).all().item())
+        for r in ctx:
+            r.close()
+        rows[label] = {"rays": nrays, "finite": finite, "same_bits_index_off_and_on": same, "per_ray": per_ray(stats)}
+        for k, key in enumerate(("off", "on")):
+            tan, one, grad, two = t[4 * k:4 * k + 4]
+            rows[label][key] = {"tangent_ms": tan, "radiance_ms": one, "grad_ms": grad, "two_radiance_ms": two,
+                                "tangent_over_grad": round(tan["median"] / grad["median"], 3), "tangent_over_radiance": round(tan["median"] / one["median"], 2),
+                                "tangent_over_two_radiance": round(tan["median"] / two["median"], 2)}
+    return {"gaussians": len(g), "rows": rows}
+
+
+def check_tangent(z):
+    for label, r in z["rows"].items():
+        assert r["finite"] and r["same_bits_index_off_and_on"], label
+        for key in ("off", "on"):
+            assert r[key]["tangent_ms"]["median"] <= r[key]["grad_ms"]["median"], \
+                f"{label}, index {key}: the tangent bundle ({ms(r[key]['tangent_ms'])}) is slower than the gradient bundle ({ms(r[key]['grad_ms'])})"
+
+
+def markdown_tangent(z, resources=""):
+    lines = [f"""# Tangent bundles (tools/ray_bundles.py --tangent-only)
+
+`vrt_hip_radiance_rays_tangent_device` (J . v: a dense tangent table and dense ray tangents in, 4 floats per ray out) against
+`vrt_hip_radiance_rays_device` (radiance out), `vrt_hip_radiance_rays_grad_device` (J^T . u: a table, float atomic adds) and two radiance
+bundles back to back (a one-sided finite difference) of the same rays in the same run: `-g 64` (N = {z['gaussians']}), device pointers, stream
+events around back-to-back calls, the paths alternating, Morton index off / on in two contexts; ms per call, median (min .. max).
+The yardstick is the gradient bundle of the same run: the tool fails where the tangent bundle's median exceeds it.  The ratios to one
+and to two radiance bundles are written down, not judged.
+
+| bundle | rays | index | tangent | radiance | gradient (table, atomics) | two radiance | tangent / gradient | tangent / radiance | tangent / two radiance | list entries (pairs) per ray of the lane = ray kernel | long rays |
+|---|---|---|---|---|---|---|---|---|---|---|---|"""]
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            x = r[key]
+            lines.append(f"| {label} | {r['rays']} | {key} | {ms(x['tangent_ms'])} | {ms(x['radiance_ms'])} | {ms(x['grad_ms'])} | {ms(x['two_radiance_ms'])} | "
+                         f"{x['tangent_over_grad']} | {x['tangent_over_radiance']} | {x['tangent_over_two_radiance']} | "
+                         f"{r['per_ray']['list_entries']} ({r['per_ray']['pairs']}) | {r['per_ray']['long_rays']} |")
+    lines.append("""
+The tangent bundle's results with the index off and on are equal bit for bit in this run.  Not taken: a profile under rocprofv3, the
+host-pointer form, a tangent table or ray tangents alone, any scene but `-g 64`, the max-ilp scheduler on this unit.
+""")
+    if resources:
+        lines.append("Resources (`tools/kernel_resources.sh raytangent`; template arguments: Exp (0 libm, 1 vcl), Erf (0 libm, 1 A&S), INDEXED):\n\n```\n" + resources.rstrip() + "\n```\n")
+    return "\n".join(lines)
+
+
 def part_scene(g, repeats=7, warm=2):
     import torch
     from sgrt_amd import autograd
@@ -1059,6 +1171,7 @@ def main():
     ap.add_argument("--rgrad-only", action="store_true")
     ap.add_argument("--scene-update-only", action="store_true")
     ap.add_argument("--sort-only", action="store_true")
+    ap.add_argument("--tangent-only", action="store_true")
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
     if a.scene_update_only:
@@ -1071,6 +1184,17 @@ def main():
         with open(os.path.join(a.out_dir, "scene_update.md"), "w") as f:
             f.write(markdown_scene(z))
         check_scene(z)
+        return
+    if a.tangent_only:
+        z = part_tangent(g)
+        print(json.dumps({"tangent": z}))
+        os.makedirs(a.out_dir, exist_ok=True)
+        with open(os.path.join(a.out_dir, "ray_tangent.json"), "w") as f:
+            f.write(json.dumps({"what": "tangent bundles against radiance and gradient bundles of the same rays; see tools/ray_bundles.py (tn)", "tangent": z}) + "\n")
+        res = os.path.join(a.out_dir, "ray_tangent_resources.txt")
+        with open(os.path.join(a.out_dir, "ray_tangent.md"), "w") as f:
+            f.write(markdown_tangent(z, open(res).read() if os.path.exists(res) else ""))
+        check_tangent(z)
         return
     if a.sort_only:
         z = part_sort(g, a.width)
