@@ -643,6 +643,40 @@ void transmittance_bundle_grad_device(const f32 *d_origins, bool origin_per_ray,
     transmittance_bundle_grad_device<Exp, Erf>(d_origins, origin_per_ray, d_dirs, nrays, d_s, ns, s_per_ray, gaussians, d_grad_T, wrt, d_grad, d_grad_s, nullptr,
                                                hip_stream);
 }
+// Transmittance tangent bundles: forward mode, J . v of transmittance_bundle (wrt = VRT_HIP_TGRAD_T, at the samples s) or of depth_bundle
+// (VRT_HIP_TGRAD_DEPTH, s = the nrays * ns depths it returned, s_per_ray = true) along a direction: tangent (nullable; rows as
+// radiance_rays_tangent's, [4..8] read), ray_tangent (nullable; as radiance_rays_tangent's) and s_tangent (nullable; d s or d tau, nrays * ns
+// or, with s_tangent_per_ray = false, ns), not all three null.  out[r * ns + k], stored, no atomic add: bitwise reproducible
+// (vrt_hip_transmittance_bundle_tangent in include/vrt_hip.h; the pairs of radiance_rays_grad, any other throws).
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void transmittance_bundle_tangent(const vec4f_t *o, const vec4f_t *n, size_t nrays, const f32 *s, size_t ns, bool s_per_ray, const gaussians_t &gaussians,
+                                  int wrt, const f32 *tangent, const f32 *ray_tangent, const f32 *s_tangent, bool s_tangent_per_ray, f32 *out)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    std::vector<f32> oo(3 * nrays), nn(3 * nrays);
+    for (size_t r = 0; r < nrays; ++r) {
+        oo[3 * r] = o[r].x; oo[3 * r + 1] = o[r].y; oo[3 * r + 2] = o[r].z;
+        nn[3 * r] = n[r].x; nn[3 * r + 1] = n[r].y; nn[3 * r + 2] = n[r].z;
+    }
+    d.check(vrt_hip_transmittance_bundle_tangent(d.ctx, nrays, oo.data(), 1, nn.data(), s, ns, s_per_ray ? 1 : 0, wrt, tangent, ray_tangent, s_tangent,
+                                                 s_tangent_per_ray ? 1 : 0, out),
+            "vrt_hip_transmittance_bundle_tangent");
+}
+// The same on the device (d_tangent and d_ray_tangent 16-byte aligned): STORES d_out, enqueued on hip_stream, nothing waits.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void transmittance_bundle_tangent_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const f32 *d_s, size_t ns,
+                                         bool s_per_ray, const gaussians_t &gaussians, int wrt, const f32 *d_tangent, const f32 *d_ray_tangent,
+                                         const f32 *d_s_tangent, bool s_tangent_per_ray, f32 *d_out, void *hip_stream)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    d.check(vrt_hip_transmittance_bundle_tangent_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_s, ns, s_per_ray ? 1 : 0, wrt, d_tangent,
+                                                        d_ray_tangent, d_s_tangent, s_tangent_per_ray ? 1 : 0, d_out, hip_stream),
+            "vrt_hip_transmittance_bundle_tangent_device");
+}
 // Ray bundles cull through the Morton index of the scene from the next call on (vrt_hip_set_ray_index in include/vrt_hip.h: off by
 // default, the same radiance and the same pixels bit for bit either way; the index is made once per scene).
 inline void set_ray_index(bool on)

@@ -571,6 +571,53 @@ int vrt_hip_radiance_rays_tangent_device(vrt_hip_ctx *ctx, size_t nrays, const f
                                          float *d_out                /* 4 per ray, STORED */, void *hip_stream);
 int vrt_hip_radiance_rays_tangent(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
                                   const float *tangent, const float *ray_tangent, float *out);   /* host pointers, waits */
+/* -------- transmittance tangent bundles: J . v of the transmittance and of the depth of ANY rays, forward mode -----------------------
+ * The other half of the transmittance gradient bundles, as the tangent bundles are of the gradient bundles: they give J^T . u in T and
+ * in depth mode, this gives J . v -- how T(r, s_k), or the depth at which T falls to a level, moves when the Gaussians, the rays and
+ * the samples (or levels) move along a given direction.  With it every observable of the ray bundles has value, J^T u and J v: a
+ * Gauss-Newton step on a loss with mask, shadow-ray or depth terms has its J^T (J v), and a sensitivity image of a depth map is ONE call.
+ * The function, the kept list K(r) HELD FIXED, the notation (A_j, r_j, m_j, C, x_kj, D_kj, e1_j, e2_kj, E_k, T_k, S_k) and the supported
+ * pairs are those of "transmittance gradient bundles" above.  The direction, every part nullable (NULL means zero; all three NULL:
+ * VRT_HIP_ERR_INVALID):
+ *   tangent      N rows of VRT_HIP_GRAD_STRIDE floats, the gradient table's layout: [4..6] d mu xyz, [7] d sigma, [8] d magnitude;
+ *                columns 0..3 (T does not depend on the albedo) and 9..11 are never read
+ *   ray_tangent  nrays rows of VRT_HIP_RAY_GRAD_STRIDE floats, the tangent bundles' (only the part of d direction perpendicular to
+ *                dir counts; [3] and [7] never read)
+ *   s_tangent    d s[r, k] (wrt == VRT_HIP_TGRAD_T) or d tau[r, k] (VRT_HIP_TGRAD_DEPTH): nrays * ns floats [r * ns + k], or ns shared
+ *                by the rays when s_tangent_per_ray == 0 (independent of s_per_ray)
+ * From the tangent bundles' three scalars per (ray, kept Gaussian) -- dmubar_j, ds_j = dsigma_j / sigma_j and dA_j (their formulas
+ * above, with the same dc_j = dmu_j - do and c_perp_j . dn):
+ *   dE_k = sum_j [ dA_j D_kj + A_j C e2_kj (dmubar_j r_j + x_kj ds_j) ] + sum_j A_j C e1_j (m_j ds_j - dmubar_j r_j)
+ *   wrt == VRT_HIP_TGRAD_T:      out[r * ns + k] = T_k (dE_k + S_k ds_k)                        at the samples s
+ *   wrt == VRT_HIP_TGRAD_DEPTH:  out[r * ns + k] = (dtau_k / T_k - dE_k) / S_k                  at s = the depths a depth bundle returned
+ * Depth mode is the implicit function theorem on T(depth, theta) = tau, the derivative of the IDEAL crossing, as in the gradient
+ * bundles, and takes s_per_ray != 0 (s_per_ray == 0: VRT_HIP_ERR_INVALID).  There a sample whose s_k is not finite or <= 0, or whose
+ * S_k == 0 (the depth bundle's +inf, 0 and NaN results) gets exactly 0.  In T mode values that are not finite propagate as the
+ * arithmetic makes them.  This is the transpose, term for term, of vrt_hip_transmittance_bundle_grad_rays (table columns 4..8, ray rows,
+ * grad_s): sum_rk g[r, k] out[r, k] = <table, tangent> + <ray rows, ray_tangent> + <grad_s, s_tangent> to rounding.
+ * ONE walk of a ray's list per group of samples (the gradient bundles make two); every result is a STORE, no atomic add and no table:
+ * a result is a function of (ray, its samples, its part of the direction, the tangent rows of the Gaussians it keeps, scene, options)
+ * alone, bitwise reproducible from run to run, host or device form, whatever the other rays of the bundle are, with
+ * vrt_hip_set_ray_index and vrt_hip_set_ray_sort on or off (the same bits at the same ray index); vrt_hip_set_grad_ordered has no effect.
+ * A Gaussian that a ray drops contributes nothing to that ray (its row is not read for it); a ray that keeps nothing gets zeros; nothing
+ * behind out[nrays * ns - 1] is written.
+ * d_tangent and d_ray_tangent are 16-byte aligned.  Everything else is the tangent bundle's contract: origins, origin_per_ray, dirs, s,
+ * ns, s_per_ray as in the transmittance bundles; the stream rules (everything enqueued on hip_stream, no host wait, no allocation once
+ * a bundle of this size has been seen), the buffers that only grow, the shared queue / counters / scratch slots / bitmap, "counts as a
+ * frame in flight"; vrt_hip_get_ray_stats / vrt_hip_get_ray_index_stats report for the same rays every field a radiance bundle
+ * reports.  nrays == 0, ns == 0 or a scene of no Gaussians returns VRT_HIP_OK with nothing launched and nothing written; NULL origins,
+ * dirs, s or out with work to do, all three inputs NULL, wrt outside the two modes, depth mode with s_per_ray == 0, more than
+ * 2^32 - 16 rays, an nrays * ns that does not fit, or an unsupported pair: VRT_HIP_ERR_INVALID with a message, nothing enqueued.  The
+ * host form stages s, the three inputs and out in context buffers that only grow and waits once. */
+int vrt_hip_transmittance_bundle_tangent_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                                const float *d_s, size_t ns, int s_per_ray, int wrt,
+                                                const float *d_tangent      /* N rows of VRT_HIP_GRAD_STRIDE, or NULL */,
+                                                const float *d_ray_tangent  /* nrays rows of VRT_HIP_RAY_GRAD_STRIDE, or NULL */,
+                                                const float *d_s_tangent    /* nrays * ns, or ns when s_tangent_per_ray == 0, or NULL */,
+                                                int s_tangent_per_ray, float *d_out /* nrays * ns, STORED */, void *hip_stream);
+int vrt_hip_transmittance_bundle_tangent(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                                         const float *s, size_t ns, int s_per_ray, int wrt, const float *tangent, const float *ray_tangent,
+                                         const float *s_tangent, int s_tangent_per_ray, float *out);   /* host pointers, waits */
 /* -------- ordered gradient tables: reproducible bits, no float atomics --------------------------------------------------------------
  * Off by default (first value from VRT_HIP_GRAD_ORDERED=0|1 at vrt_hip_create).  With on != 0 all eight gradient entry points above
  * that are given a table (d_grad / grad_out) build it without a single float atomic add, into the table or into any staging memory,

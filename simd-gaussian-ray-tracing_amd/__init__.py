@@ -151,6 +151,10 @@ SYMBOLS = {
                                                                 _vp]),
     "vrt_hip_transmittance_bundle_grad_rays": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p, C.c_int, _f32p, _f32p,
                                                          _f32p]),
+    "vrt_hip_transmittance_bundle_tangent_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int,
+                                                              _vp, _vp]),
+    "vrt_hip_transmittance_bundle_tangent": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, C.c_int, _f32p, _f32p, _f32p,
+                                                       C.c_int, _f32p]),
     "vrt_hip_get_ray_stats": (C.c_int, [_vp, C.POINTER(RayStats)]),
     "vrt_hip_set_ray_index": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_ray_index_stats": (C.c_int, [_vp, C.POINTER(RayIndexStats)]),
@@ -740,6 +744,39 @@ class Renderer:
         RAY_GRAD_STRIDE] float32, 16-byte aligned); any of the three outputs may be 0, not all."""
         self._device("transmittance_bundle_grad_rays_device", nrays, d_origins, origin_per_ray, d_dirs, d_s or None, int(ns), int(bool(s_per_ray)),
                      d_grad_T or None, int(wrt), d_grad or None, d_grad_s or None, d_grad_rays or None, stream or None)
+
+    def transmittance_bundle_tangent(self, origins, dirs, s, tangent=None, ray_tangent=None, s_tangent=None, wrt=TGRAD_T, s_per_ray=None):
+        """vrt_hip_transmittance_bundle_tangent: forward mode, J . v -- how what transmittance_bundle returns for the same rays and samples
+        s moves along a direction (wrt = TGRAD_T), or, with wrt = TGRAD_DEPTH and s [nrays, ns] the depths depth_bundle returned, how those
+        depths move (the derivative of the ideal crossing; a depth of +inf, 0 or NaN gets exactly 0).  Each ray's kept list is held
+        fixed.  tangent and ray_tangent: as radiance_rays_tangent takes them, dicts or packed arrays ("albedo" is never read: T does not
+        depend on it); s_tangent: the direction's part in the samples (TGRAD_T) or in the levels (TGRAD_DEPTH), [ns] shared by the rays
+        or [nrays, ns].  Each may be None (zero), not all three.  Returns float32 [nrays, ns], stored without atomic adds: bitwise
+        reproducible."""
+        origins, dirs, per_ray = _rays(origins, dirs)
+        s, ns, s_per_ray = _table(s, len(dirs), s_per_ray)
+        t = None if tangent is None else _pack_tangent(tangent, self.n)
+        rt = None if ray_tangent is None else _pack_ray_tangent(ray_tangent, len(dirs))
+        st, st_per_ray = None, False
+        if s_tangent is not None:
+            st = np.ascontiguousarray(s_tangent, np.float32)
+            st_per_ray = st.ndim == 2
+            assert st.size == (len(dirs) if st_per_ray else 1) * ns, st.shape
+        out = np.zeros((len(dirs), ns), np.float32)
+        self._chk(self._L.vrt_hip_transmittance_bundle_tangent(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), _fp(s), ns, int(s_per_ray),
+                                                               int(wrt), None if t is None else _fp(t), None if rt is None else _fp(rt),
+                                                               None if st is None else _fp(st), int(st_per_ray), _fp(out)),
+                  "transmittance_bundle_tangent")
+        return out
+
+    def transmittance_bundle_tangent_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_s, ns, s_per_ray, wrt, d_tangent=0, d_ray_tangent=0,
+                                            d_s_tangent=0, s_tangent_per_ray=True, d_out=0, stream=0):
+        """vrt_hip_transmittance_bundle_tangent_device: device pointers, everything enqueued on `stream`; reads d_tangent ([N, GRAD_STRIDE]
+        float32), d_ray_tangent ([nrays, RAY_GRAD_STRIDE] float32), both 16-byte aligned, and d_s_tangent ([nrays, ns], or [ns] with
+        s_tangent_per_ray false); each may be 0, not all three; STORES d_out ([nrays, ns] float32)."""
+        self._device("transmittance_bundle_tangent_device", nrays, d_origins, origin_per_ray, d_dirs, d_s or None, int(ns), int(bool(s_per_ray)),
+                     int(wrt), d_tangent or None, d_ray_tangent or None, d_s_tangent or None, int(bool(s_tangent_per_ray)), d_out or None,
+                     stream or None)
 
     def ray_stats(self):
         """Counts of the last bundle (enable_stats first): see vrt_hip_ray_stats in include/vrt_hip.h."""

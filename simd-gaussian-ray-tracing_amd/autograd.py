@@ -26,7 +26,9 @@ Renderer.radiance_rays_tangent_device (include/vrt_hip.h, "tangent bundles"), J 
 one pass, stored without atomic adds and bitwise reproducible.  The tangent table is built from the tangents of mu, albedo, sigma and
 magnitude, the ray rows from those of origins ([3]: the same row for every ray) and dirs (only the part perpendicular to each direction
 counts); a group without any tangent is not passed, and with no tangent at all nothing is issued.  transmittance_bundle and depth_bundle
-are reverse mode only.
+work the same way: their jvp is Renderer.transmittance_bundle_tangent_device ("transmittance tangent bundles"), in T mode at the samples of
+the forward, in depth mode at the depths it returned (a depth of +inf, 0 or NaN moves by exactly 0); the tangent of s or tau is a third
+group, shaped and broadcast as s or tau is; albedo's tangent moves nothing.
 
 A Gaussian whose magnitude is exactly 0 is dropped by every ray's cull and therefore receives NO gradient, magnitude.grad included
 (although the true derivative is not 0): initialise magnitudes away from 0.
@@ -43,12 +45,6 @@ import numpy as np
 import torch
 
 from . import GRAD_STRIDE, RAY_GRAD_STRIDE, TGRAD_DEPTH, TGRAD_T, grad_columns, ray_grad_columns
-
-
-def _upload(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs):
-    """What a forward with a ctx begins with: _set_scene, then _remember.  Returns (device, origins, dirs, origin per ray)."""
-    _set_scene(renderer, mu, albedo, sigma, magnitude)
-    return _remember(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs)
 
 
 def _set_scene(renderer, mu, albedo, sigma, magnitude):
@@ -201,27 +197,89 @@ def radiance_rays(renderer, mu, albedo, sigma, magnitude, origins, dirs):
     return _RadianceRays.apply(renderer, mu, albedo, sigma, magnitude, origins, dirs)
 
 
-class _Profile(torch.autograd.Function):
-    """transmittance_bundle (wrt = TGRAD_T: values = sample distances) and depth_bundle (TGRAD_DEPTH: values = levels)."""
+class _ProfileTangentBundle(torch.autograd.Function):
+    """The library call of _Profile.jvp as a Function of its own, for the reason _TangentBundle gives.  Not differentiable itself."""
 
     @staticmethod
-    def forward(ctx, renderer, wrt, mu, albedo, sigma, magnitude, origins, dirs, values):
-        dev, o, d, per_ray = _upload(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs)
+    def forward(renderer, wrt, o, d, per_ray, s, s_per_ray, table, rows, s_tangent, s_tangent_per_ray):
+        nrays, n = d.shape[0], s.shape[-1] if s.dim() else 1
+        out = torch.zeros((nrays, n), dtype=torch.float32, device=o.device)
+        renderer.transmittance_bundle_tangent_device(nrays, o.data_ptr(), per_ray, d.data_ptr(), s.data_ptr(), n, s_per_ray, wrt,
+                                                     d_tangent=_ptr(table), d_ray_tangent=_ptr(rows), d_s_tangent=_ptr(s_tangent),
+                                                     s_tangent_per_ray=s_tangent_per_ray, d_out=out.data_ptr(),
+                                                     stream=torch.cuda.current_stream(o.device).cuda_stream)
+        return out
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+
+def _values(values):
+    """A profile's samples or levels as the library takes them, on torch's current device: (values, per ray?, values per ray)"""
+    v = values.detach().to(torch.device("cuda", torch.cuda.current_device()), torch.float32).contiguous()
+    return v, v.dim() == 2, v.shape[-1] if v.dim() else 1
+
+
+class _Profile(torch.autograd.Function):
+    """transmittance_bundle (wrt = TGRAD_T: values = sample distances) and depth_bundle (TGRAD_DEPTH: values = levels).  forward and
+    setup_context apart, as _RadianceRays and for its reason."""
+
+    @staticmethod
+    def forward(renderer, wrt, mu, albedo, sigma, magnitude, origins, dirs, values):
+        _set_scene(renderer, mu, albedo, sigma, magnitude)
+        dev, o, d, per_ray = _rays(origins, dirs)
         nrays = d.shape[0]
-        v = values.detach().to(dev, torch.float32).contiguous()
-        v_per_ray = v.dim() == 2
-        n = v.shape[-1] if v.dim() else 1
+        v, v_per_ray, n = _values(values)
         out = torch.empty((nrays, n), dtype=torch.float32, device=dev)
         if nrays and n:
             call = renderer.transmittance_bundle_device if wrt == TGRAD_T else renderer.depth_bundle_device
             call(nrays, o.data_ptr(), per_ray, d.data_ptr(), v.data_ptr(), n, v_per_ray, out.data_ptr(),
                  stream=torch.cuda.current_stream(dev).cuda_stream)
-        ctx.wrt, ctx.values, ctx.v_per_ray, ctx.v_like = wrt, v, v_per_ray, values
-        ctx.save_for_backward(out)
         return out
 
     @staticmethod
+    def setup_context(ctx, inputs, output):
+        renderer, wrt, mu, albedo, sigma, magnitude, origins, dirs, values = inputs
+        _remember(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs)
+        v, v_per_ray, _ = _values(values)
+        ctx.wrt, ctx.values, ctx.v_per_ray, ctx.v_like = wrt, v, v_per_ray, values
+        ctx.save_for_backward(output)
+        ctx.save_for_forward(output)         # depth mode differentiates at the depths the forward returned, in either mode of AD
+        ctx.set_materialize_grads(False)     # jvp sees None for an input without a tangent (_RadianceRays.setup_context)
+
+    @staticmethod
+    def jvp(ctx, _r, _w, t_mu, t_albedo, t_sigma, t_magnitude, t_origins, t_dirs, t_values):
+        """Forward mode: Renderer.transmittance_bundle_tangent_device over the scene and the rays of the forward, on torch's current
+        stream -- T mode at the samples the forward took, depth mode at the depths it returned.  The tangent table is built from the
+        tangents of mu, sigma and magnitude (albedo's moves nothing), the ray rows from those of origins and dirs as in
+        _RadianceRays.jvp, the sample tangents from that of values, which broadcasts as values does; a group without a tangent is not
+        passed, and with no tangent anywhere nothing is issued."""
+        o, d, per_ray = ctx.rays
+        (out,) = ctx.saved_tensors
+        nrays, n = d.shape[0], ctx.n
+        nv = out.shape[1]
+
+        def cols(shapes, tangents):
+            return [torch.zeros(shape, dtype=torch.float32, device=o.device) if t is None else t.detach().to(o.device, torch.float32).reshape(shape)
+                    for shape, t in zip(shapes, tangents)]
+        table = rows = st = None
+        if any(t is not None for t in (t_mu, t_sigma, t_magnitude)):                    # grad_columns' layout
+            table = torch.cat(cols(((n, 4), (n, 3), (n, 1), (n, 1), (n, GRAD_STRIDE - 9)), (None, t_mu, t_sigma, t_magnitude, None)), 1)
+        if t_origins is not None or t_dirs is not None:                                 # ray_grad_columns' layout
+            t_o = None if t_origins is None else t_origins.detach().reshape(-1, 3).expand(nrays, 3)
+            rows = torch.cat(cols(((nrays, 3), (nrays, 1), (nrays, 3), (nrays, 1)), (t_o, None, t_dirs, None)), 1)
+        if t_values is not None:
+            st = t_values.detach().to(o.device, torch.float32).reshape(ctx.values.shape).contiguous()
+        if not (nrays and n and nv) or (table is None and rows is None and st is None):
+            return torch.zeros((nrays, nv), dtype=torch.float32, device=o.device)
+        s, s_per_ray = (ctx.values, ctx.v_per_ray) if ctx.wrt == TGRAD_T else (out.detach(), True)
+        return _ProfileTangentBundle.apply(ctx.renderer, ctx.wrt, o, d, per_ray, s, s_per_ray, table, rows, st, ctx.v_per_ray)
+
+    @staticmethod
     def backward(ctx, grad_out):
+        if grad_out is None:                 # (set_materialize_grads above) nothing flows back through the profile
+            return (None,) * 9
         o, d, per_ray = ctx.rays
         (out,) = ctx.saved_tensors
         nrays, n = out.shape
@@ -244,7 +302,7 @@ class _Profile(torch.autograd.Function):
 def transmittance_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, s):
     """Transmittance [nrays, ns] (a cuda tensor on torch's current device and stream) at the sample distances s ([ns], shared by the
     rays, or [nrays, ns]) along the rays through the scene of the four parameter tensors, differentiable in mu, sigma, magnitude and
-    s; albedo gets no gradient (None).  Reverse mode only: forward-mode AD (forward_ad, torch.func.jvp) raises.  Rays, the replaced scene
+    s; albedo gets no gradient (None).  Forward mode too (forward_ad, torch.func.jvp): the module's docstring.  Rays, the replaced scene
     and the order of backward: as radiance_rays."""
     return _Profile.apply(renderer, TGRAD_T, mu, albedo, sigma, magnitude, origins, dirs, s)
 
@@ -252,6 +310,6 @@ def transmittance_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, 
 def depth_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, tau):
     """The distance [nrays, nt] along each ray at which its transmittance falls to the levels tau ([nt], shared by the rays, or
     [nrays, nt]), differentiable in mu, sigma, magnitude and tau (the derivative of the ideal crossing; a result of +inf, 0 or NaN
-    gets and gives no gradient); albedo gets no gradient (None).  Reverse mode only: forward-mode AD raises.  Rays, the replaced scene and
+    gets and gives no gradient); albedo gets no gradient (None).  Forward mode too: the module's docstring.  Rays, the replaced scene and
     the order of backward: as radiance_rays."""
     return _Profile.apply(renderer, TGRAD_DEPTH, mu, albedo, sigma, magnitude, origins, dirs, tau)

@@ -1,8 +1,8 @@
 // vrt_hip_rays.cpp -- ray bundles of libvrt_hip.so (vrt_hip_radiance_rays*, vrt_hip_transmittance_bundle*, vrt_hip_depth_bundle*,
-// vrt_hip_radiance_rays_grad*, vrt_hip_transmittance_bundle_grad*, their _rays forms, vrt_hip_radiance_rays_tangent*): radiance of caller-given rays, transmittance at sample distances along
+// vrt_hip_radiance_rays_grad*, vrt_hip_transmittance_bundle_grad*, their _rays forms, vrt_hip_radiance_rays_tangent*, vrt_hip_transmittance_bundle_tangent*): radiance of caller-given rays, transmittance at sample distances along
 // them, the distance at which their transmittance falls to given levels, or the derivative of their radiance, transmittance or depth with
-// respect to the Gaussians, or how their radiance moves along a direction (forward mode), culled per ray (vrt_ray_kernel.hip,
-// vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip, vrt_ray_grad_kernel.hip, vrt_ray_trans_grad_kernel.hip, vrt_ray_tangent_kernel.hip).  The scene tables and the
+// respect to the Gaussians, or how their radiance, transmittance or depth moves along a direction (forward mode), culled per ray (vrt_ray_kernel.hip,
+// vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip, vrt_ray_grad_kernel.hip, vrt_ray_trans_grad_kernel.hip, vrt_ray_tangent_kernel.hip, vrt_ray_trans_tangent_kernel.hip).  The scene tables and the
 // chunk spheres are the frame pipeline's; the long-ray queue, its counters and the long kernel's scratch slots belong to the context
 // and only grow.  So do the buffers of the ordered gradient tables (vrt_hip_set_grad_ordered: ordered_bundle, and the two read-outs)
 // and of the sorted bundles (vrt_hip_set_ray_sort: sort_bundle, and the two read-outs).
@@ -243,6 +243,8 @@ const BundleKind TRANS_GRADIENT = { "transmittance_bundle_grad", "NULL samples o
                                     launch_ray_trans_grad_bundle, launch_ray_trans_grad_bundle_ordered, false, 4 };
 // forward mode: a derivative (the scene of no Gaussians, the pairs), but no table: nothing for the ordered switch to order
 const BundleKind TANGENT = { "radiance_rays_tangent", "NULL output, or neither a tangent table nor ray tangents", "", true, false, launch_ray_tangent_bundle };
+const BundleKind TRANS_TANGENT = { "transmittance_bundle_tangent", "NULL samples or output, or none of a tangent table, ray tangents and sample tangents", "ns",
+                                   true, true, launch_ray_trans_tangent_bundle };
 
 // The rays of a call, device or host pointers alike
 struct Rays {
@@ -494,6 +496,54 @@ int vrt_hip_radiance_rays_tangent(vrt_hip_ctx *c, size_t nrays, const float *ori
                        { { c->rays_rad, out, nrays } }, [&](const Rays &d) {
                            return vrt_hip_radiance_rays_tangent_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, wanted(tangent, c->rays_table_in),
                                                                        wanted(ray_tangent, c->rays_rows_in), (float *)c->rays_rad.p, c->stream);
+                       });
+}
+
+// what the two forms of the transmittance tangent bundle check: every kind's, and that depth mode has a depth per ray
+static bool trans_tangent_over(vrt_hip_ctx *c, const Rays &r, size_t ns, int s_per_ray, bool io_ok, int wrt, int &rc)
+{
+    if (bundle_over(c, TRANS_TANGENT, r, ns, io_ok, wrt, rc)) return true;
+    if (wrt == VRT_HIP_TGRAD_DEPTH && !s_per_ray) {
+        rc = fail(c, VRT_HIP_ERR_INVALID, std::string(TRANS_TANGENT.name) + ": depth mode takes the depths of every ray (s_per_ray == 0)");
+        return true;
+    }
+    return false;
+}
+
+// forward mode: the direction in, J . v of the transmittance (or of the depth) out
+int vrt_hip_transmittance_bundle_tangent_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                                const float *d_s, size_t ns, int s_per_ray, int wrt, const float *d_tangent,
+                                                const float *d_ray_tangent, const float *d_s_tangent, int s_tangent_per_ray, float *d_out,
+                                                void *hip_stream)
+{
+    const Rays r = { nrays, d_origins, origin_per_ray, d_dirs };
+    const bool io_ok = d_s && d_out && (d_tangent || d_ray_tangent || d_s_tangent);
+    int rc;
+    if (trans_tangent_over(c, r, ns, s_per_ray, io_ok, wrt, rc)) return rc;
+    return device_bundle(c, TRANS_TANGENT, r, ns, io_ok, wrt, hip_stream, [&](RayArgs &a) {
+        a.s = d_s; a.ns = ns; a.s_per_ray = s_per_ray ? 1 : 0; a.wrt = wrt;
+        a.tangent = d_tangent; a.ray_tangent = d_ray_tangent;
+        a.s_tangent = d_s_tangent; a.s_tangent_per_ray = s_tangent_per_ray ? 1 : 0; a.trans_tangent_out = d_out;
+    });
+}
+
+// samples, the tangent table of the scene's size, the ray tangents and the sample tangents in, each of the three where given; a float per ray and sample out
+int vrt_hip_transmittance_bundle_tangent(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *s,
+                                         size_t ns, int s_per_ray, int wrt, const float *tangent, const float *ray_tangent, const float *s_tangent,
+                                         int s_tangent_per_ray, float *out)
+{
+    const Rays r = { nrays, origins, origin_per_ray, dirs };
+    int rc;
+    if (trans_tangent_over(c, r, ns, s_per_ray, s && out && (tangent || ray_tangent || s_tangent), wrt, rc)) return rc;
+    return host_bundle(c, r, { { c->rays_values_in, s, (s_per_ray ? nrays : 1) * ns },
+                               { c->rays_table_in, tangent, (size_t)c->n * VRT_HIP_GRAD_STRIDE },
+                               { c->rays_rows_in, ray_tangent, nrays * VRT_HIP_RAY_GRAD_STRIDE },
+                               { c->rays_each_in, s_tangent, (s_tangent_per_ray ? nrays : 1) * ns } },
+                       { { c->rays_each_out, out, nrays * ns } }, [&](const Rays &d) {
+                           return vrt_hip_transmittance_bundle_tangent_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, c->rays_values_in.p, ns,
+                                                                              s_per_ray, wrt, wanted(tangent, c->rays_table_in),
+                                                                              wanted(ray_tangent, c->rays_rows_in), wanted(s_tangent, c->rays_each_in),
+                                                                              s_tangent_per_ray, c->rays_each_out.p, c->stream);
                        });
 }
 

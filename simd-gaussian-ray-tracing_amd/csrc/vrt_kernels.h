@@ -363,6 +363,11 @@ struct RayArgs {
     const float *tangent;           // nullable, [S.n * VRT_HIP_GRAD_STRIDE], 16-byte aligned: the direction's row per Gaussian, columns 9..11 never used
     const float *ray_tangent;       // nullable, [r * VRT_HIP_RAY_GRAD_STRIDE], 16-byte aligned: d origin, -, d direction, - per ray
     float4 *tangent_out;            // [r] stored: how the radiance of ray r moves along the direction
+    // Transmittance tangent bundles (vrt_ray_trans_tangent_kernel.hip; behind everything the other kernels read).  They reuse s, ns,
+    // s_per_ray, wrt, tangent (columns 4..8 of a row) and ray_tangent.
+    const float *s_tangent;         // nullable: d s[r, k] (wrt == VRT_HIP_TGRAD_T) or d tau[r, k] (VRT_HIP_TGRAD_DEPTH), ns in all or [r * ns + k]
+    int s_tangent_per_ray;
+    float *trans_tangent_out;       // [r * ns + k] stored: how T[r, k], or the depth of level k, moves along the direction
 };
 constexpr int GRAD_ORD_COLS = 9;    // floats per record
 // the words of an ordered call, cleared on the stream ahead of its count pass: rays whose re-cull missed the counted length; records
@@ -386,6 +391,10 @@ void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool ind
 // the same cull, then J . v: how the radiance of every ray moves along the direction (a.tangent per Gaussian, a.ray_tangent per ray, either
 // nullable), stored to a.tangent_out (vrt_ray_tangent_kernel.hip).  The pairs of ray_grad_pair_supported; any other enqueues nothing.
 void launch_ray_tangent_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+// the same cull, then J . v of T at the samples a.s (a.wrt == VRT_HIP_TGRAD_T) or of the depth at the depths a.s (VRT_HIP_TGRAD_DEPTH) along
+// the direction (a.tangent, a.ray_tangent, a.s_tangent, each nullable), stored to a.trans_tangent_out (vrt_ray_trans_tangent_kernel.hip).
+// The pairs of ray_grad_pair_supported; any other enqueues nothing.
+void launch_ray_trans_tangent_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
 // Ordered gradient tables (vrt_hip_set_grad_ordered; vrt_grad_ordered_kernel.hip has the pipeline).  The same two bundles with every
 // add into a.grad replaced by a store into the records at a.ord_base[r] (the ORDERED instantiations, in translation units of their own:
 // vrt_ray_grad_ordered_kernel.hip, vrt_ray_trans_grad_ordered_kernel.hip); a.grad is not touched.

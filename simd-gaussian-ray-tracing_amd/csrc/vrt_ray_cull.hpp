@@ -1,10 +1,10 @@
 // vrt_ray_cull.hpp -- the skeleton of the ray bundles, shared by vrt_ray_kernel.hip (radiance), vrt_ray_trans_kernel.hip
 // (transmittance), vrt_ray_depth_kernel.hip (depth), vrt_ray_grad_kernel.hip (gradient), vrt_ray_trans_grad_kernel.hip (transmittance
-// gradient) and vrt_ray_tangent_kernel.hip (tangent): the sphere and member tests, the lane = ray cull into per-lane lists in LDS, the
+// gradient), vrt_ray_tangent_kernel.hip (tangent) and vrt_ray_trans_tangent_kernel.hip (transmittance tangent): the sphere and member tests, the lane = ray cull into per-lane lists in LDS, the
 // one-wave-per-ray re-cull into LDS + scratch slot, both with and without the Morton index, the queue of the long rays and the
 // statistics words; around them what every kernel pair does before its own middle -- ray_short_begin (a lane's ray, list and filing),
 // ray_long_begin / ray_long_next (a wave's claims of the queue, each with its re-cull) -- and launch_ray_kernels behind them.  One text
-// for all six translation units: the same rays keep the same Gaussians, go to the same kernel and count the same statistics.
+// for all seven translation units: the same rays keep the same Gaussians, go to the same kernel and count the same statistics.
 #pragma once
 #include "vrt_kernels_common.hpp"
 

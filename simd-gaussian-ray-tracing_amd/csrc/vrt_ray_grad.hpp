@@ -1,6 +1,7 @@
 // vrt_ray_grad.hpp -- what the derivative kernels of the ray bundles share: vrt_ray_grad_kernel.hip (d radiance / d Gaussians) and
 // vrt_ray_trans_grad_kernel.hip (d transmittance / d Gaussians and samples, d depth / d Gaussians and levels) -- and, of grad_gauss, the
-// list walk and grad_acc's layout, vrt_ray_tangent_kernel.hip (forward mode: J . v of the radiance).  One text each, for these
+// list walk and grad_acc's layout, vrt_ray_tangent_kernel.hip and vrt_ray_trans_tangent_kernel.hip (forward mode: J . v of the radiance, and
+// of the transmittance and the depth).  One text each, for these
 // translation units and for the short and the long kernel of each:
 //   grad_gauss        one Gaussian against one ray with the compensated c = mu - o and mubar = c . n that keep d / d mu accurate: the same
 //                     (ray, Gaussian) gives the same A, c_perp, d2 and Erf(-mubar r) in either kind of gradient
@@ -12,6 +13,9 @@
 //   LaneList, grad_acc, grad_walk_begin / _next, grad_flush_short   lane = ray: a lane's list, the three running sums per list position and lane in LDS, the walk of a
 //                     lane's list with the next entry's rows loaded one iteration ahead, and every position to the sink once
 //   grad_emitter_place, grad_pass1, grad_pass2    the radiance gradient's emitter set-up and the bodies of its two pair loops
+//   trans_grad_x, trans_grad_live   the transmittance derivatives' x_kj and which samples count (depth mode: finite depths > 0)
+//   TanRay, tangent_ray, TanGauss, tangent_gauss, tangent_row_load / _uload   forward mode: a direction's ray row and tangent row to three
+//                     scalars per (ray, kept Gaussian)
 #pragma once
 #include "vrt_ray_cull.hpp"
 
@@ -380,6 +384,68 @@ __device__ __forceinline__ void grad_pass2(const ErfEval<ERF> &erf, const GradGa
             y[e] = __builtin_fmaf(kf, t, y[e]);
         }
     }
+}
+
+// ---- what the transmittance derivative units share (vrt_ray_trans_grad_kernel.hip, vrt_ray_trans_tangent_kernel.hip) ----
+
+// x_kj = (s_k - mubar_j) r_j, the difference first: s r - m would round at the size of m = mubar r (20 and more for a narrow Gaussian a unit
+// away), and e2 = exp(-x^2) passes an error dx on as 2 |x| dx -- 4e-5 of a far sample's addends on the grid scene, against 5e-6 this way.
+__device__ __forceinline__ float trans_grad_x(float s, const GradGauss &q) { return (s - q.mubar) * q.r; }
+
+// is sample (s, g) live: g_k != 0, and in depth mode s_k finite and > 0 (a depth bundle's +inf, 0 and NaN results are not).  The kernels
+// carry a sample that is not as g = 0 at s = 0 (finite arithmetic, weight exactly 0).  Forward mode has no g: it asks with g = 1.
+__device__ __forceinline__ bool trans_grad_live(bool depth_mode, float s, float g)
+{
+    return g != 0.f && (!depth_mode || (s > 0.f && s < __builtin_inff()));
+}
+
+// ---- forward mode (vrt_ray_tangent_kernel.hip, vrt_ray_trans_tangent_kernel.hip): a direction's rows to scalars per (ray, kept Gaussian) ----
+
+// The ray's own tangent: d origin and d direction.  The direction tangent enters through c_perp_j . t alone (tangent_gauss), and c_perp is
+// perpendicular to n: a component of t along n -- which does not move normalise(n + eps t) -- drops out there, to rounding, exactly as the
+// gradient kernels' ray row sum_j (..) c_perp_j is perpendicular to n to rounding.  No projection of t: J . v is the transpose of that row
+// term for term, whatever the float32 direction's length is off 1 by.
+struct TanRay { float ox, oy, oz, nx, ny, nz; };
+__device__ __forceinline__ TanRay tangent_ray(const float *ray_tangent, uint64_t r)
+{
+    TanRay t = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    if (ray_tangent) { // wave-uniform
+        const float4 *row = (const float4 *)(ray_tangent + r * (uint64_t)RAY_GRAD_STRIDE);
+        const float4 a = row[0], b = row[1]; // .w of either is never used
+        t.ox = a.x; t.oy = a.y; t.oz = a.z;
+        t.nx = b.x; t.ny = b.y; t.nz = b.z;
+    }
+    return t;
+}
+
+// What the pair loop needs of one Gaussian's tangent row against one ray
+struct TanGauss { float dmubar, u, ds; };
+// q: grad_gauss of the same (ray, Gaussian); ms_t = (d mu xyz, d sigma), dm = d magnitude; `on` = false: exact zeros, whatever was loaded
+__device__ __forceinline__ TanGauss tangent_gauss(const GradGauss &q, const LaneRay &ray, const TanRay &tr, float mag, float4 ms_t, float dm, bool on)
+{
+    if (!on) { ms_t = make_float4(0.f, 0.f, 0.f, 0.f); dm = 0.f; }
+    const float cx = ms_t.x - tr.ox, cy = ms_t.y - tr.oy, cz = ms_t.z - tr.oz;
+    const float cn = dot3_ref(q.px, q.py, q.pz, tr.nx, tr.ny, tr.nz);
+    TanGauss g;
+    g.dmubar = on ? dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz) + cn : 0.f;
+    const float dd2 = 2.f * __builtin_fmaf(-q.mubar, cn, dot3_ref(q.px, q.py, q.pz, cx, cy, cz));
+    g.ds = ms_t.w * q.inv_s;
+    const float dlog = __builtin_fmaf(q.d2 * q.inv_s2, g.ds, __builtin_fmaf(-0.5f * dd2, q.inv_s2, g.ds));
+    g.u = on ? __builtin_fmaf(mag, dlog, dm) : 0.f;
+    if (!on) g.ds = 0.f;
+    return g;
+}
+// columns 4..11 of row idx of the tangent table: (d mu xyz, d sigma) and d magnitude; columns 9..11 come along and are dropped
+__device__ __forceinline__ void tangent_row_load(const float *table, uint32_t idx, float4 &ms_t, float &dm)
+{
+    const float4 *row = (const float4 *)(table + (size_t)idx * GRAD_STRIDE);
+    ms_t = row[1];
+    dm = row[2].x;
+}
+__device__ __forceinline__ void tangent_row_uload(const float *table, uint32_t idx, float4 &ms_t, float &dm)
+{
+    ms_t = uload((const float4 *)table, 3u * idx + 1u);
+    dm = uload((const float4 *)table, 3u * idx + 2u).x;
 }
 
 // ---- the launch: a bundle's run-time switches INDEXED and RAYS as the constants I.value, R.value of a generic callable f(I, R) ----

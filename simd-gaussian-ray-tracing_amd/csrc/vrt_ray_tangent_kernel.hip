@@ -28,53 +28,6 @@
 
 namespace vrtk {
 
-// The ray's own tangent: d origin and d direction.  The direction tangent enters through c_perp_j . t alone (tangent_gauss), and c_perp is
-// perpendicular to n: a component of t along n -- which does not move normalise(n + eps t) -- drops out there, to rounding, exactly as the
-// gradient kernels' ray row sum_j (..) c_perp_j is perpendicular to n to rounding.  No projection of t: J . v is the transpose of that row
-// term for term, whatever the float32 direction's length is off 1 by.
-struct TanRay { float ox, oy, oz, nx, ny, nz; };
-__device__ __forceinline__ TanRay tangent_ray(const float *ray_tangent, uint64_t r)
-{
-    TanRay t = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
-    if (ray_tangent) { // wave-uniform
-        const float4 *row = (const float4 *)(ray_tangent + r * (uint64_t)RAY_GRAD_STRIDE);
-        const float4 a = row[0], b = row[1]; // .w of either is never used
-        t.ox = a.x; t.oy = a.y; t.oz = a.z;
-        t.nx = b.x; t.ny = b.y; t.nz = b.z;
-    }
-    return t;
-}
-
-// What the pair loop needs of one Gaussian's tangent row against one ray
-struct TanGauss { float dmubar, u, ds; };
-// q: grad_gauss of the same (ray, Gaussian); ms_t = (d mu xyz, d sigma), dm = d magnitude; `on` = false: exact zeros, whatever was loaded
-__device__ __forceinline__ TanGauss tangent_gauss(const GradGauss &q, const LaneRay &ray, const TanRay &tr, float mag, float4 ms_t, float dm, bool on)
-{
-    if (!on) { ms_t = make_float4(0.f, 0.f, 0.f, 0.f); dm = 0.f; }
-    const float cx = ms_t.x - tr.ox, cy = ms_t.y - tr.oy, cz = ms_t.z - tr.oz;
-    const float cn = dot3_ref(q.px, q.py, q.pz, tr.nx, tr.ny, tr.nz);
-    TanGauss g;
-    g.dmubar = on ? dot3_ref(cx, cy, cz, ray.nx, ray.ny, ray.nz) + cn : 0.f;
-    const float dd2 = 2.f * __builtin_fmaf(-q.mubar, cn, dot3_ref(q.px, q.py, q.pz, cx, cy, cz));
-    g.ds = ms_t.w * q.inv_s;
-    const float dlog = __builtin_fmaf(q.d2 * q.inv_s2, g.ds, __builtin_fmaf(-0.5f * dd2, q.inv_s2, g.ds));
-    g.u = on ? __builtin_fmaf(mag, dlog, dm) : 0.f;
-    if (!on) g.ds = 0.f;
-    return g;
-}
-// columns 4..11 of row idx of the tangent table: (d mu xyz, d sigma) and d magnitude; columns 9..11 come along and are dropped
-__device__ __forceinline__ void tangent_row_load(const float *table, uint32_t idx, float4 &ms_t, float &dm)
-{
-    const float4 *row = (const float4 *)(table + (size_t)idx * GRAD_STRIDE);
-    ms_t = row[1];
-    dm = row[2].x;
-}
-__device__ __forceinline__ void tangent_row_uload(const float *table, uint32_t idx, float4 &ms_t, float &dm)
-{
-    ms_t = uload((const float4 *)table, 3u * idx + 1u);
-    dm = uload((const float4 *)table, 3u * idx + 2u).x;
-}
-
 // The pair loop's body: EC emitters against one absorber q with the tangent scalars g (per lane in the short kernel, wave-uniform in
 // the long): q's term of the exponents of T at the emitters' 5 EC sample points (grad_pass1's arithmetic) and of their tangents, and
 // of F, the part of the tangent that no emitter and no sample point moves.

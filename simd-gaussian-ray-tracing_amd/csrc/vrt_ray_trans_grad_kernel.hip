@@ -41,7 +41,7 @@
 // reproducible -- unless ORDERED (vrt_hip_set_grad_ordered): a template parameter of both kernels, instantiated in
 // vrt_ray_trans_grad_ordered_kernel.hip.  Where a segment goes is GradSink's (vrt_ray_grad.hpp, with the record rules).
 // Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
-// What lives where: this file has what a sample is (trans_grad_live, trans_grad_x, trans_grad_weight), the two kernels' loops over groups
+// What lives where: this file has what a sample is worth (trans_grad_weight; trans_grad_live and trans_grad_x are vrt_ray_grad.hpp's, shared with the tangent unit), the two kernels' loops over groups
 // and chunks of samples, and the launch.  The helpers named above are vrt_ray_grad.hpp's, shared with vrt_ray_grad_kernel.hip.
 #include "vrt_ray_grad.hpp"
 #include "vrt_ray_trans.hpp" // RAY_SG
@@ -67,17 +67,6 @@ __device__ __forceinline__ void trans_grad_weight(bool depth_mode, float g, floa
         gs = live ? w * Sk : 0.f;
     }
 }
-
-// is sample (s, g) live: g_k != 0, and in depth mode s_k finite and > 0.  The kernels carry a sample that is not as g = 0 at s = 0
-// (finite arithmetic, weight exactly 0).
-__device__ __forceinline__ bool trans_grad_live(bool depth_mode, float s, float g)
-{
-    return g != 0.f && (!depth_mode || (s > 0.f && s < __builtin_inff()));
-}
-
-// x_kj = (s_k - mubar_j) r_j, the difference first: s r - m would round at the size of m = mubar r (20 and more for a narrow Gaussian a unit
-// away), and e2 = exp(-x^2) passes an error dx on as 2 |x| dx -- 4e-5 of a far sample's addends on the grid scene, against 5e-6 this way.
-__device__ __forceinline__ float trans_grad_x(float s, const GradGauss &q) { return (s - q.mubar) * q.r; }
 
 // RAYS: the ray rows are asked for (P.grad_rays != nullptr); without, each kernel is the text it was before there were ray rows.
 // ORDERED: one record per list position, the lane's own, opened and stored whole at the flush.  <.., false> is the kernel as it is without.

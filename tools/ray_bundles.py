@@ -90,6 +90,18 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
       judged.  `--tangent-only` runs this part alone, prints its JSON line and writes ray_tangent.json and ray_tangent.md (and nothing
       else) to --out-dir; the .md ends with the text of <out-dir>/ray_tangent_resources.txt when that file is there (the output of
       `tools/kernel_resources.sh raytangent`).
+  (tt) transmittance tangent bundles (vrt_hip_transmittance_bundle_tangent_device, a dense tangent table, dense ray tangents and dense
+      sample tangents in, a float per ray and sample out): the 2^20 scattered shadow rays of (d) with ns = 1, the 4096 aimed rays of the
+      transmittance part with 64 samples, and the same 4096 rays in depth mode at the depths vrt_hip_depth_bundle_device returned for
+      the level 0.99 (about half of them live) -- `-g 64`, device pointers, Morton index off and on (two contexts), three paths
+      alternating in the same run: the tangent bundle, vrt_hip_transmittance_bundle_grad_rays_device with table, ray rows and grad_s
+      (J^T . u of the same rays and samples: the yardstick) and two transmittance bundles back to back (what one central difference
+      costs; samples that are not finite replaced by s = 8 for them); stream events around back-to-back calls, after warm-up.  One
+      walk of a list per group of samples instead of two and stores instead of atomic adds: the run fails where the tangent bundle's
+      median exceeds the gradient bundle's by more than the spread of the run's repeats (the larger max - min of the two paths).
+      `--ttangent-only` runs this part alone, prints its JSON line and writes ray_trans_tangent.json and ray_trans_tangent.md (and
+      nothing else) to --out-dir; the .md ends with the text of <out-dir>/ray_trans_tangent_resources.txt when that file is there (the
+      output of `tools/kernel_resources.sh rayttangent`).
 """
 import argparse
 import json
@@ -800,6 +812,116 @@ host-pointer form, a tangent table or ray tangents alone, any scene but `-g 64`,
     return "\n".join(lines)
 
 
+def part_ttangent(g, calls=3, repeats=7):
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(19)
+    t_v = torch.from_numpy(rng.uniform(-1, 1, size=(len(g), pkg.GRAD_STRIDE)).astype(f32)).cuda()
+    aimed = aimed_rays(g)
+    rows = {}
+    cases = (("shadow_2^20_ns1", scattered(g, 1 << 20), 1, pkg.TGRAD_T, np.array([8.0], f32), None),
+             ("profiles_4096_ns64", aimed, 0, pkg.TGRAD_T, np.linspace(0.5, 8.0, 64).astype(f32), None),
+             ("depth_4096_tau0.99", aimed, 0, pkg.TGRAD_DEPTH, None, 0.99))
+    for label, (o, d), per, wrt, s, level in cases:
+        nrays = len(d)
+        t_o, t_d = torch.from_numpy(np.ascontiguousarray(o, f32)).cuda(), torch.from_numpy(np.ascontiguousarray(d, f32)).cuda()
+        ctx = [pkg.Renderer(0), pkg.Renderer(0)]
+        for on, r in enumerate(ctx):
+            r.set_gaussians(g)
+            r.set_ray_index(on)
+        if wrt == pkg.TGRAD_DEPTH:      # the samples are the depths of the level, one per ray
+            tau = torch.tensor([level], dtype=torch.float32, device="cuda")
+            t_s = torch.zeros((nrays, 1), dtype=torch.float32, device="cuda")
+            ctx[0].depth_bundle_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), tau.data_ptr(), 1, 0, t_s.data_ptr(), st)
+            torch.cuda.synchronize()
+            ns, s_per_ray = 1, 1
+            live = int((torch.isfinite(t_s) & (t_s > 0)).sum().item())
+            t_sT = torch.where(torch.isfinite(t_s), t_s, torch.full_like(t_s, 8.0))      # the transmittance bundle wants finite samples
+        else:
+            t_s = torch.from_numpy(s).cuda()
+            ns, s_per_ray, live, t_sT = len(s), 0, nrays * len(s), t_s
+        t_g = torch.from_numpy(rng.uniform(-1, 1, size=(nrays, ns)).astype(f32)).cuda()
+        t_sd = torch.from_numpy(rng.uniform(-1, 1, size=(nrays, ns)).astype(f32)).cuda()
+        t_rv = torch.from_numpy(rng.uniform(-1, 1, size=(nrays, pkg.RAY_GRAD_STRIDE)).astype(f32)).cuda()
+        zeros = lambda *shape: [torch.zeros(shape, dtype=torch.float32, device="cuda") for _ in ctx]
+        out, T, gs, ray_rows = zeros(nrays, ns), zeros(nrays, ns), zeros(nrays, ns), zeros(nrays, pkg.RAY_GRAD_STRIDE)
+        # (the gradient call ADDS into its table, which is not cleared between the calls of a window: as in part_tangent, that only
+        # makes the comparison harder for the tangent bundle)
+        table = zeros(len(g), pkg.GRAD_STRIDE)
+        torch.cuda.synchronize()
+
+        def trans(k):
+            ctx[k].transmittance_bundle_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_sT.data_ptr(), ns, s_per_ray, T[k].data_ptr(), st)
+
+        def twice(k):
+            trans(k)
+            trans(k)
+        fns = []
+        for k in (0, 1):
+            fns.append(lambda k=k: ctx[k].transmittance_bundle_tangent_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_s.data_ptr(), ns, s_per_ray, wrt,
+                                                                              t_v.data_ptr(), t_rv.data_ptr(), t_sd.data_ptr(), 1, out[k].data_ptr(), st))
+            fns.append(lambda k=k: ctx[k].transmittance_bundle_grad_rays_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_s.data_ptr(), ns, s_per_ray,
+                                                                                t_g.data_ptr(), wrt, table[k].data_ptr(), gs[k].data_ptr(),
+                                                                                ray_rows[k].data_ptr(), st))
+            fns.append(lambda k=k: twice(k))
+        t = windows(fns, calls, repeats, warm=2)
+        ctx[0].enable_stats(True)
+        fns[0]()
+        stats = ctx[0].ray_stats()
+        fns[3]()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(out[0], out[1]))
+        finite = bool(torch.isfinite(out[0]).all().item())
+        for r in ctx:
+            r.close()
+        rows[label] = {"rays": nrays, "ns": ns, "live_samples": live, "finite": finite, "same_bits_index_off_and_on": same, "per_ray": per_ray(stats)}
+        for k, key in enumerate(("off", "on")):
+            tan, grad, two = t[3 * k:3 * k + 3]
+            rows[label][key] = {"tangent_ms": tan, "grad_ms": grad, "two_trans_ms": two, "spread_ms": round(max(tan["max"] - tan["min"], grad["max"] - grad["min"]), 5),
+                                "tangent_over_grad": round(tan["median"] / grad["median"], 3), "tangent_over_two_trans": round(tan["median"] / two["median"], 2)}
+    return {"gaussians": len(g), "rows": rows}
+
+
+def check_ttangent(z):
+    for label, r in z["rows"].items():
+        assert r["finite"] and r["same_bits_index_off_and_on"], label
+        for key in ("off", "on"):
+            x = r[key]
+            assert x["tangent_ms"]["median"] <= x["grad_ms"]["median"] + x["spread_ms"], \
+                f"{label}, index {key}: the tangent bundle ({ms(x['tangent_ms'])}) is slower than the gradient bundle ({ms(x['grad_ms'])}) by more than the spread"
+
+
+def markdown_ttangent(z, resources=""):
+    lines = [f"""# Transmittance tangent bundles (tools/ray_bundles.py --ttangent-only)
+
+`vrt_hip_transmittance_bundle_tangent_device` (J . v: a dense tangent table, dense ray tangents and dense sample tangents in, a float per
+ray and sample out) against `vrt_hip_transmittance_bundle_grad_rays_device` (J^T . u: table with float atomic adds, ray rows and grad_s)
+and two `vrt_hip_transmittance_bundle_device` calls back to back (one central difference) of the same rays and samples in the same run:
+`-g 64` (N = {z['gaussians']}), device pointers, stream events around back-to-back calls, the paths alternating, Morton index off / on in
+two contexts; ms per call, median (min .. max).  Depth mode runs at the depths `vrt_hip_depth_bundle_device` returned for the level; a
+ray that never reaches it has depth +inf, which both derivative calls skip (live samples: finite depths > 0) and the transmittance
+bundle is given s = 8 for.  The yardstick is the gradient bundle of the same run: the tool fails where the tangent bundle's median
+exceeds it by more than the spread of the run's repeats (the larger max - min of the two paths).  The ratio to two transmittance
+bundles is written down, not judged.
+
+| bundle | rays | ns | live samples | index | tangent | gradient (table, rows, grad_s) | two transmittance | tangent / gradient | tangent / two transmittance | list entries per ray of the lane = ray kernel | long rays |
+|---|---|---|---|---|---|---|---|---|---|---|---|"""]
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            x = r[key]
+            lines.append(f"| {label} | {r['rays']} | {r['ns']} | {r['live_samples']} | {key} | {ms(x['tangent_ms'])} | {ms(x['grad_ms'])} | {ms(x['two_trans_ms'])} | "
+                         f"{x['tangent_over_grad']} | {x['tangent_over_two_trans']} | {r['per_ray']['list_entries']} | {r['per_ray']['long_rays']} |")
+    lines.append("""
+The tangent bundle's results with the index off and on are equal bit for bit in this run.  Not taken: a profile under rocprofv3, the
+host-pointer form, one of the three inputs alone, any scene but `-g 64`, the max-ilp scheduler on this unit, `wrt` as a template
+parameter, the long kernel with its per-entry scalars kept per ray instead of formed again per group of samples, a short kernel without
+its 24 KB of scalars for ns <= 4 (shadow rays).
+""")
+    if resources:
+        lines.append("Resources (`tools/kernel_resources.sh rayttangent`; template arguments: Exp (0 libm, 1 vcl), Erf (0 libm, 1 A&S), INDEXED):\n\n```\n" + resources.rstrip() + "\n```\n")
+    return "\n".join(lines)
+
+
 def part_scene(g, repeats=7, warm=2):
     import torch
     from sgrt_amd import autograd
@@ -1172,6 +1294,7 @@ def main():
     ap.add_argument("--scene-update-only", action="store_true")
     ap.add_argument("--sort-only", action="store_true")
     ap.add_argument("--tangent-only", action="store_true")
+    ap.add_argument("--ttangent-only", action="store_true")
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
     if a.scene_update_only:
@@ -1195,6 +1318,18 @@ def main():
         with open(os.path.join(a.out_dir, "ray_tangent.md"), "w") as f:
             f.write(markdown_tangent(z, open(res).read() if os.path.exists(res) else ""))
         check_tangent(z)
+        return
+    if a.ttangent_only:
+        z = part_ttangent(g)
+        print(json.dumps({"trans_tangent": z}))
+        os.makedirs(a.out_dir, exist_ok=True)
+        with open(os.path.join(a.out_dir, "ray_trans_tangent.json"), "w") as f:
+            f.write(json.dumps({"what": "transmittance tangent bundles against transmittance gradient bundles and two transmittance bundles of the same rays; "
+                                        "see tools/ray_bundles.py (tt)", "trans_tangent": z}) + "\n")
+        res = os.path.join(a.out_dir, "ray_trans_tangent_resources.txt")
+        with open(os.path.join(a.out_dir, "ray_trans_tangent.md"), "w") as f:
+            f.write(markdown_ttangent(z, open(res).read() if os.path.exists(res) else ""))
+        check_ttangent(z)
         return
     if a.sort_only:
         z = part_sort(g, a.width)
