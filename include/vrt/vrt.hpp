@@ -716,6 +716,97 @@ inline grad_records_t grad_records()
     d.check(vrt_hip_get_grad_records(d.ctx, out.gauss.data(), out.ray.data(), out.rows.data(), n, &n), "vrt_hip_get_grad_records");
     return out;
 }
+// Ray plans: the cull of a bundle run ONCE and kept on the device ("Ray plans" in include/vrt_hip.h).  While a plan is bound
+// (vrt::set_ray_plan) every bundle call above with the plan's number of rays takes each ray's kept list from it -- the same bits, no
+// sphere test, no member test, no sort, no count pass: for loops that send the same rays through the same scene many times (a CG solve on
+// J and J^T, a forward and its backward).  Strict by default: a call after the scene or the cull options changed throws; with
+// keep_lists the lists stay in force across scene updates of the same size, which is the function the gradient and tangent bundles
+// differentiate.  An RAII handle of the process-wide context: movable, not copyable; its destructor unbinds and frees the plan.
+class ray_plan {
+  public:
+    ray_plan() = default;
+    // from host rays, one origin per ray (as the bundle calls take them); the scene and the pair as the bundle calls set them
+    template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+    static ray_plan make(const vec4f_t *o, const vec4f_t *n, size_t nrays, const gaussians_t &gaussians)
+    {
+        auto &d = detail::device_t::get();
+        d.upload_scene(gaussians.gaussians);
+        d.options(Exp, Erf);
+        std::vector<f32> oo(3 * nrays), nn(3 * nrays);
+        for (size_t r = 0; r < nrays; ++r) {
+            oo[3 * r] = o[r].x; oo[3 * r + 1] = o[r].y; oo[3 * r + 2] = o[r].z;
+            nn[3 * r] = n[r].x; nn[3 * r + 1] = n[r].y; nn[3 * r + 2] = n[r].z;
+        }
+        ray_plan p;
+        d.check(vrt_hip_ray_plan_create(d.ctx, nrays, oo.data(), 1, nn.data(), &p.plan_), "vrt_hip_ray_plan_create");
+        return p;
+    }
+    // from rays on the device: enqueued on hip_stream and waited for; the plan is complete and usable on any stream
+    template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+    static ray_plan make_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const gaussians_t &gaussians, void *hip_stream)
+    {
+        auto &d = detail::device_t::get();
+        d.upload_scene(gaussians.gaussians);
+        d.options(Exp, Erf);
+        ray_plan p;
+        d.check(vrt_hip_ray_plan_create_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, hip_stream, &p.plan_), "vrt_hip_ray_plan_create_device");
+        return p;
+    }
+    ray_plan(const ray_plan &) = delete;
+    ray_plan &operator=(const ray_plan &) = delete;
+    ray_plan(ray_plan &&o) noexcept : plan_(o.plan_) { o.plan_ = nullptr; }
+    ray_plan &operator=(ray_plan &&o) noexcept
+    {
+        if (this != &o) { reset(); plan_ = o.plan_; o.plan_ = nullptr; }
+        return *this;
+    }
+    ~ray_plan() { reset(); }
+    void reset() noexcept // waits for bundles in flight; the bound plan is unbound first
+    {
+        if (plan_) (void)vrt_hip_ray_plan_destroy(detail::device_t::get().ctx, plan_);
+        plan_ = nullptr;
+    }
+    explicit operator bool() const { return plan_ != nullptr; }
+    vrt_hip_ray_plan *get() const { return plan_; }
+    vrt_hip_ray_plan_info info() const
+    {
+        auto &d = detail::device_t::get();
+        vrt_hip_ray_plan_info i{};
+        d.check(vrt_hip_get_ray_plan_info(d.ctx, plan_, &i), "vrt_hip_get_ray_plan_info");
+        return i;
+    }
+
+  private:
+    vrt_hip_ray_plan *plan_ = nullptr;
+};
+// Binds `plan` for every later bundle call; vrt::clear_ray_plan() binds none.  Waits for bundles in flight.
+inline void set_ray_plan(const ray_plan &plan, bool keep_lists = false)
+{
+    auto &d = detail::device_t::get();
+    d.check(vrt_hip_set_ray_plan(d.ctx, plan.get(), plan.get() && keep_lists ? VRT_HIP_PLAN_KEEP_LISTS : 0), "vrt_hip_set_ray_plan");
+}
+inline void clear_ray_plan()
+{
+    auto &d = detail::device_t::get();
+    d.check(vrt_hip_set_ray_plan(d.ctx, nullptr, 0), "vrt_hip_set_ray_plan");
+}
+// The plan's lists read back: ray r (the caller's index) keeps entries[offsets[r] .. offsets[r + 1]), scene indices in ascending order.
+struct ray_plan_lists_t {
+    std::vector<u64> offsets; // nrays + 1
+    std::vector<u32> entries;
+};
+inline ray_plan_lists_t ray_plan_lists(const ray_plan &plan)
+{
+    auto &d = detail::device_t::get();
+    const vrt_hip_ray_plan_info i = plan.info();
+    ray_plan_lists_t out;
+    out.offsets.resize(i.rays + 1);
+    out.entries.resize(i.entries);
+    static_assert(sizeof(u64) == sizeof(uint64_t), "the offsets are read as they stand");
+    d.check(vrt_hip_get_ray_plan_lists(d.ctx, plan.get(), reinterpret_cast<uint64_t *>(out.offsets.data()), out.entries.empty() ? nullptr : out.entries.data()),
+            "vrt_hip_get_ray_plan_lists");
+    return out;
+}
 // The scene from DEVICE memory (vrt_hip_set_gaussians_device in include/vrt_hip.h): d_mu [n, 3], d_albedo [n, 4] with alpha in column 3,
 // d_sigma [n], d_magnitude [n], float32; everything enqueued on hip_stream, nothing waited for (but where a buffer has to grow), the same
 // scene bit for bit as the same values uploaded from the host.  It stays the scene of every later call that is given an EMPTY

@@ -737,6 +737,73 @@ int vrt_hip_get_ray_sort_stats(vrt_hip_ctx *ctx, vrt_hip_ray_sort_stats *out); /
  * *count = its rays, cap = room in each array.  Waits for the bundle.  VRT_HIP_ERR_INVALID when the switch is off or the last bundle
  * was not sorted. */
 int vrt_hip_get_ray_order(vrt_hip_ctx *ctx, uint32_t *order, uint32_t *keys, size_t cap, size_t *count);
+/* Ray plans: cull a bundle once, reuse its kept lists in every call (replaces nothing in the reference, which has no such path).
+ * Every bundle call above -- radiance, transmittance, depth, both gradients and their _rays forms, both tangents, host and device form --
+ * begins with the cull of its rays: sphere tests, member tests, the queue of the long rays and their re-cull, with vrt_hip_set_ray_sort
+ * the key kernel and the sort, with vrt_hip_set_grad_ordered a count pass that is one more cull.  A loop that sends the same rays
+ * through the same scene many times (conjugate gradients on J and J^T, a forward and a backward, a depth bundle and its gradient) pays
+ * for the same lists each time.  A plan is that cull run ONCE and kept in device memory; while it is bound, every bundle call takes
+ * every ray's list from it and returns the same bits.
+ *   Create.  vrt_hip_ray_plan_create_device runs the cull the bundles run (the same text, through the Morton index when
+ *   vrt_hip_set_ray_index is on; with vrt_hip_set_ray_sort on and more than 64 rays the key kernel and the sort first, and the plan keeps
+ *   the order) on `hip_stream`: a count pass and a scan, ONE wait for the totals, then a fill pair that copies every list out.  It waits
+ *   for its stream before it returns, so the plan is complete and may be used on any stream.  Stored per ray: the list length, where the
+ *   list begins, the list in ascending scene order (scene indices); the ids of the rays whose list is longer than 32; for a sorted plan
+ *   the order and the keys.  4 B per kept entry and per long ray plus 12 B per ray (20 B for a sorted plan); info.bytes has the size.
+ *   More than 2^32 - 1 kept entries, more than 2^32 - 16 rays, NULL rays with nrays > 0: VRT_HIP_ERR_INVALID and no plan.  nrays == 0 and
+ *   a scene of no Gaussians give legal plans of nothing.  vrt_hip_ray_plan_create is the same from host pointers (on the context's
+ *   stream).  The plan belongs to the context: vrt_hip_destroy frees those that are left, vrt_hip_copy_state carries neither plans nor
+ *   the binding, and every call below refuses (VRT_HIP_ERR_INVALID) a plan of another context.
+ *   Bind.  vrt_hip_set_ray_plan(ctx, plan, flags) binds a plan (NULL: none); it and vrt_hip_ray_plan_destroy wait for bundles in flight,
+ *   as the other switches do, and destroying the bound plan unbinds it.  While a plan is bound a bundle call runs no sphere test, no
+ *   member test, no filing into the queue, no key kernel, no sort, and uses no scratch slot and no bitmap: a ray with more than 32
+ *   entries goes to the one-wave-per-ray kernel as it would have, which takes the plan's queue, copies the first 1024 entries to LDS and
+ *   reads the rest where they stand.  The lane = ray kernels take the plan's order; the context's index and sort switches are ignored
+ *   (flipping them changes no bit and does not make a plan stale).  With vrt_hip_set_grad_ordered on, the count pass is the plan's
+ *   lengths and `mismatches` is 0 by construction.  The stream rules are unchanged -- the long kernel's work counter is still the
+ *   context's, so two bundles of one context are ordered by the stream they share -- and a planned call whose buffers need not grow
+ *   waits for nothing and allocates nothing, but for the ordered call's own wait.
+ *   Contract of a planned call.  nrays must be the plan's: otherwise VRT_HIP_ERR_INVALID with both numbers, nothing enqueued.  The
+ *   caller still passes the rays -- the plan does not own them -- and which rays those are is the caller's business: other rays than
+ *   the plan's give the sum over the plan's lists, which is defined and no error.  With flags == 0 the plan is STRICT: a call made after
+ *   the Gaussians were set again (vrt_hip_set_gaussians*, vrt_hip_set_gaussians_device, vrt_hip_copy_state into the context), or after
+ *   cull_eps or the Exp / Erf pair changed (vrt_hip_set_options), returns VRT_HIP_ERR_INVALID with a message that says which, nothing
+ *   enqueued.  With VRT_HIP_PLAN_KEEP_LISTS the lists stay in force across such updates while the scene keeps its size N (another N:
+ *   VRT_HIP_ERR_INVALID -- the entries are scene indices): the call computes the sum over the plan's lists for the CURRENT scene and the
+ *   rays given.  Nothing is dropped and nothing new is picked up: that is the function whose derivative the gradient and tangent
+ *   bundles return ("each ray's kept list is held fixed"), so a line search, a finite difference or a trial step along a tangent
+ *   evaluates the function whose J was used.
+ *   Statistics of a planned call.  rays, short_rays, long_rays, lane_entries, lane_pairs and scratch_rays of vrt_hip_ray_stats are the
+ *   unplanned call's; chunks_tested, chunks_kept and members_tested are 0; vrt_hip_get_ray_index_stats reads indexed = 0 and zeros;
+ *   vrt_hip_get_ray_sort_stats.sorted is the plan's flag (rays_without_sphere: 0, a plan does not keep it) and vrt_hip_get_ray_order
+ *   gives the plan's order and keys, whatever the sort switch says.
+ * Out of scope: the camera / frame path, the multi-GPU group, plans that follow a changing N, noticing that the rays differ from the
+ * plan's, graph capture. */
+typedef struct vrt_hip_ray_plan vrt_hip_ray_plan;
+#define VRT_HIP_PLAN_KEEP_LISTS 1
+typedef struct {
+    uint64_t rays;           /* rays of the plan                                                                     */
+    uint64_t entries;        /* kept (ray, Gaussian) pairs: the sum of the list lengths                              */
+    uint64_t short_rays;     /* rays with a list of at most 32: shaded lane = ray                                    */
+    uint64_t long_rays;      /* rays with a longer list: shaded one wave per ray                                     */
+    uint64_t longest;        /* the longest list                                                                     */
+    uint64_t scratch_rays;   /* rays with more than 1024 kept Gaussians (the list continues in the plan's memory)    */
+    uint64_t bytes;          /* device memory of the plan                                                            */
+    uint64_t sorted;         /* 1: made with vrt_hip_set_ray_sort on and more than 64 rays; the plan keeps the order  */
+    uint64_t indexed;        /* 1: made through the Morton index (the same lists either way)                         */
+    uint64_t scene_n;        /* Gaussians of the scene it was made for                                               */
+    uint64_t cull_generation; /* the context's count of scene and cull-option changes at creation                    */
+} vrt_hip_ray_plan_info;
+int vrt_hip_ray_plan_create_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                   void *hip_stream, vrt_hip_ray_plan **out);
+int vrt_hip_ray_plan_create(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                            vrt_hip_ray_plan **out);
+int vrt_hip_ray_plan_destroy(vrt_hip_ctx *ctx, vrt_hip_ray_plan *plan);
+int vrt_hip_set_ray_plan(vrt_hip_ctx *ctx, vrt_hip_ray_plan *plan, int flags);
+int vrt_hip_get_ray_plan_info(vrt_hip_ctx *ctx, vrt_hip_ray_plan *plan, vrt_hip_ray_plan_info *out);
+/* Read-out: offsets[nrays + 1] and, where entries != NULL, the info.entries kept scene indices: ray r (the caller's index) keeps
+ * entries[offsets[r] .. offsets[r + 1]), ascending. */
+int vrt_hip_get_ray_plan_lists(vrt_hip_ctx *ctx, vrt_hip_ray_plan *plan, uint64_t *offsets, uint32_t *entries);
 
 /* Numeric cross-checks of rt.cpp:8-27 (transmittance_step uses fast_exp like the reference).
  * vrt_hip_transmittance_step runs the reference's float32 loop `for (t = 0; t <= s; t += delta)` per sample point, and refuses with

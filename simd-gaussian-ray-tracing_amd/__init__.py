@@ -63,6 +63,12 @@ class GradOrderedStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("records", "gaussians", "longest", "mismatches")]
 
 
+class RayPlanInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("rays", "entries", "short_rays", "long_rays", "longest", "scratch_rays", "bytes", "sorted", "indexed",
+                                          "scene_n", "cull_generation")]
+
+
+PLAN_KEEP_LISTS = 1         # VRT_HIP_PLAN_KEEP_LISTS: a bound ray plan's lists stay in force across scene updates that keep N
 GRAD_RECORD_COLS = 9        # floats per record of an ordered gradient table: the table's columns 0..8
 
 
@@ -162,6 +168,12 @@ SYMBOLS = {
     "vrt_hip_set_ray_sort": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_ray_sort_stats": (C.c_int, [_vp, C.POINTER(RaySortStats)]),
     "vrt_hip_get_ray_order": (C.c_int, [_vp, _u32p, _u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vrt_hip_ray_plan_create_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.POINTER(_vp)]),
+    "vrt_hip_ray_plan_create": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, C.POINTER(_vp)]),
+    "vrt_hip_ray_plan_destroy": (C.c_int, [_vp, _vp]),
+    "vrt_hip_set_ray_plan": (C.c_int, [_vp, _vp, C.c_int]),
+    "vrt_hip_get_ray_plan_info": (C.c_int, [_vp, _vp, C.POINTER(RayPlanInfo)]),
+    "vrt_hip_get_ray_plan_lists": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), _u32p]),
     "vrt_hip_set_grad_ordered": (C.c_int, [_vp, C.c_int]),
     "vrt_hip_get_grad_records": (C.c_int, [_vp, _u32p, _u32p, _f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vrt_hip_get_grad_ordered_stats": (C.c_int, [_vp, C.POINTER(GradOrderedStats)]),
@@ -282,6 +294,64 @@ def _pack_ray_tangent(ray_tangent, nrays):
     return t
 
 
+class RayPlan:
+    """A ray plan (Renderer.ray_plan / ray_plan_device): the kept lists of one bundle, culled once and held in device memory.  Bind it
+    with Renderer.set_ray_plan or `with renderer.using(plan):` and every bundle call takes its lists from it: see "Ray plans" in
+    include/vrt_hip.h.  Belongs to its renderer; close() (or the renderer's) frees it."""
+
+    def __init__(self, renderer, handle):
+        self._r, self._p = renderer, handle
+
+    def info(self):
+        """rays, entries, short_rays, long_rays, longest, scratch_rays, bytes, sorted, indexed, scene_n, cull_generation: see
+        vrt_hip_ray_plan_info in include/vrt_hip.h."""
+        s = RayPlanInfo()
+        self._r._chk(self._r._L.vrt_hip_get_ray_plan_info(self._r._h, self._p, C.byref(s)), "get_ray_plan_info")
+        return {k: getattr(s, k) for k, _ in RayPlanInfo._fields_}
+
+    def lists(self):
+        """(offsets u64 [nrays + 1], entries u32 [info()["entries"]]): ray r, at the caller's index, keeps entries[offsets[r]:offsets[r + 1]],
+        scene indices in ascending order."""
+        i = self.info()
+        offsets, entries = np.zeros(i["rays"] + 1, np.uint64), np.zeros(max(i["entries"], 1), np.uint32)
+        self._r._chk(self._r._L.vrt_hip_get_ray_plan_lists(self._r._h, self._p, offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                           entries.ctypes.data_as(_u32p)), "get_ray_plan_lists")
+        return offsets, entries[:i["entries"]]
+
+    def close(self):
+        """Frees the plan; the bound plan is unbound first.  Waits for bundles in flight."""
+        if getattr(self, "_p", None) and getattr(self._r, "_h", None):
+            self._r._L.vrt_hip_ray_plan_destroy(self._r._h, self._p)
+            if self._r._plan[0] is self:
+                self._r._plan = (None, False)
+        self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _UsingPlan:
+    """`with renderer.using(plan):` -- binds the plan, and puts the binding that was there back on the way out."""
+
+    def __init__(self, renderer, plan, keep_lists):
+        self._r, self._new = renderer, (plan, keep_lists)
+
+    def __enter__(self):
+        self._old = self._r._plan
+        self._r.set_ray_plan(*self._new)
+        return self._new[0]
+
+    def __exit__(self, *exc):
+        old, keep = self._old
+        if old is not None and old._p is None:   # closed meanwhile
+            old = None
+        self._r.set_ray_plan(old, keep)
+        return False
+
+
 class Renderer:
     """One context = one GPU.  Mirrors the reference call set (main.cpp:257-296)."""
 
@@ -297,6 +367,7 @@ class Renderer:
         self._h = _handle
         self.device = device if self._owned else None   # the HIP device of a context made here (a group's members: not known)
         self._host = {}   # registered host buffers by address: kept alive while the GPU may write them
+        self._plan = (None, False)   # the bound RayPlan and its keep_lists
         self.n = 0
         self.w = self.h = 0
         self.table_step = float(os.environ.get("VRT_HIP_TABLE_STEP", TABLE_STEP_DEFAULT))
@@ -777,6 +848,39 @@ class Renderer:
         self._device("transmittance_bundle_tangent_device", nrays, d_origins, origin_per_ray, d_dirs, d_s or None, int(ns), int(bool(s_per_ray)),
                      int(wrt), d_tangent or None, d_ray_tangent or None, d_s_tangent or None, int(bool(s_tangent_per_ray)), d_out or None,
                      stream or None)
+
+    # ---- ray plans (cull once, reuse the kept lists in every bundle call) ----
+    def ray_plan(self, origins, dirs):
+        """vrt_hip_ray_plan_create: culls the bundle once, as every bundle call would (through the index and in the sorted order when
+        those switches are on), and keeps every ray's list.  origins [3] (one for the bundle) or [nrays, 3], dirs [nrays, 3].  Returns a
+        RayPlan; bind it with set_ray_plan or `with renderer.using(plan):`."""
+        origins, dirs, per_ray = _rays(origins, dirs)
+        h = _vp()
+        self._chk(self._L.vrt_hip_ray_plan_create(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), C.byref(h)), "ray_plan_create")
+        return RayPlan(self, h)
+
+    def ray_plan_device(self, nrays, d_origins, origin_per_ray, d_dirs, stream=0):
+        """vrt_hip_ray_plan_create_device: the same from device pointers, enqueued on `stream` and waited for: the plan is complete when
+        this returns and may be used on any stream."""
+        h = _vp()
+        self._chk(self._L.vrt_hip_ray_plan_create_device(self._h, int(nrays), d_origins or None, int(bool(origin_per_ray)), d_dirs or None,
+                                                         stream or None, C.byref(h)), "ray_plan_create_device")
+        return RayPlan(self, h)
+
+    def set_ray_plan(self, plan, keep_lists=False):
+        """vrt_hip_set_ray_plan: while a plan is bound (None: none) every bundle call of nrays = the plan's takes its lists from it -- the
+        same bits, no cull.  Strict by default: a call after the scene or the cull options were set again raises; with keep_lists the
+        lists stay in force across scene updates that keep N (the function the gradient and tangent bundles differentiate)."""
+        if plan is not None and (plan._p is None or plan._r is not self):
+            raise VrtHipError("set_ray_plan: the plan is closed, or belongs to another renderer")
+        self._chk(self._L.vrt_hip_set_ray_plan(self._h, plan._p if plan is not None else None, PLAN_KEEP_LISTS if (plan is not None and keep_lists) else 0),
+                  "set_ray_plan")
+        self._plan = (plan, bool(keep_lists) if plan is not None else False)
+
+    def using(self, plan, keep_lists=False):
+        """Context manager: `with renderer.using(plan, keep_lists=False):` binds the plan for the block and restores the binding that
+        was there before."""
+        return _UsingPlan(self, plan, keep_lists)
 
     def ray_stats(self):
         """Counts of the last bundle (enable_stats first): see vrt_hip_ray_stats in include/vrt_hip.h."""

@@ -40,7 +40,15 @@ nothing waited for (but where a buffer of the renderer has to grow: a larger sce
 cuda parameters never blocks the host.  With any parameter tensor elsewhere (the CPU, another device) the scene goes through the host
 as before: the four tensors are copied to the CPU and set_gaussians_soa waits for the device and rebuilds the tables.  Both ways make
 the same scene, bit for bit.
+
+Ray plans.  radiance_rays, transmittance_bundle and depth_bundle take plan=None: a RayPlan of the same rays (Renderer.ray_plan /
+ray_plan_device; include/vrt_hip.h, "Ray plans").  With one, forward, backward and the jvp bind it around their library call with
+keep_lists=True -- every forward sets the scene again, which a strict plan would refuse -- and put the renderer's previous binding back
+afterwards: no call culls, all of them sum over the plan's lists, and the values are those of the function whose derivative backward and
+jvp return.  Binding waits for bundles in flight; the default, plan=None, binds nothing and waits for nothing.
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -61,6 +69,16 @@ def _set_scene(renderer, mu, albedo, sigma, magnitude):
     else:
         host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in params]
         renderer.set_gaussians_soa(host[0], host[1][:, :3], host[2], host[3], alpha=np.ascontiguousarray(host[1][:, 3]))
+
+
+@contextlib.contextmanager
+def _planned(renderer, plan):
+    """The plan bound with its lists kept for one library call, the renderer's previous binding back behind it; nothing at all without a plan"""
+    if plan is None:
+        yield
+    else:
+        with renderer.using(plan, keep_lists=True):
+            yield
 
 
 def _rays(origins, dirs):
@@ -122,10 +140,11 @@ class _TangentBundle(torch.autograd.Function):
     and a Function's forward is where torch hands over plain ones, whose memory can be named.  Not differentiable itself."""
 
     @staticmethod
-    def forward(renderer, o, d, per_ray, table, rows):
+    def forward(renderer, o, d, per_ray, table, rows, plan):
         out = torch.zeros((d.shape[0], 4), dtype=torch.float32, device=o.device)
-        renderer.radiance_rays_tangent_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), d_tangent=_ptr(table), d_ray_tangent=_ptr(rows),
-                                              d_out=out.data_ptr(), stream=torch.cuda.current_stream(o.device).cuda_stream)
+        with _planned(renderer, plan):
+            renderer.radiance_rays_tangent_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), d_tangent=_ptr(table), d_ray_tangent=_ptr(rows),
+                                                  d_out=out.data_ptr(), stream=torch.cuda.current_stream(o.device).cuda_stream)
         return out
 
     @staticmethod
@@ -138,24 +157,26 @@ class _RadianceRays(torch.autograd.Function):
     setup_context remembers (from the inputs alone, which is all torch gives it: rays that forward had to convert are converted again)"""
 
     @staticmethod
-    def forward(renderer, mu, albedo, sigma, magnitude, origins, dirs):
+    def forward(renderer, mu, albedo, sigma, magnitude, origins, dirs, plan):
         _set_scene(renderer, mu, albedo, sigma, magnitude)
         dev, o, d, per_ray = _rays(origins, dirs)
         out = torch.empty((d.shape[0], 4), dtype=torch.float32, device=dev)
         if d.shape[0]:
-            renderer.radiance_rays_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), d_radiance=out.data_ptr(),
-                                          stream=torch.cuda.current_stream(dev).cuda_stream)
+            with _planned(renderer, plan):
+                renderer.radiance_rays_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), d_radiance=out.data_ptr(),
+                                              stream=torch.cuda.current_stream(dev).cuda_stream)
         return out
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        _remember(ctx, *inputs)
+        _remember(ctx, *inputs[:7])
+        ctx.plan = inputs[7]
         # jvp sees None for an input without a tangent, not zeros, and passes no table for them.  The switch holds for backward too: it
         # sees None where the output's gradient is undefined, and then returns no gradients instead of those of a zero grad_out.
         ctx.set_materialize_grads(False)
 
     @staticmethod
-    def jvp(ctx, _, t_mu, t_albedo, t_sigma, t_magnitude, t_origins, t_dirs):
+    def jvp(ctx, _, t_mu, t_albedo, t_sigma, t_magnitude, t_origins, t_dirs, _p):
         """Forward mode (torch.autograd.forward_ad, torch.func.jvp): Renderer.radiance_rays_tangent_device over the scene and the rays
         of the forward, on torch's current stream.  The tangent table is built from the tangents of the four parameters, the ray rows
         from those of origins (one origin for the bundle: the same row for every ray) and dirs; a group none of whose inputs has a
@@ -174,40 +195,43 @@ class _RadianceRays(torch.autograd.Function):
             rows = torch.cat(cols(((nrays, 3), (nrays, 1), (nrays, 3), (nrays, 1)), (t_o, None, t_dirs, None)), 1)
         if not (nrays and n) or (table is None and rows is None):
             return torch.zeros((nrays, 4), dtype=torch.float32, device=o.device)
-        return _TangentBundle.apply(ctx.renderer, o, d, per_ray, table, rows)
+        return _TangentBundle.apply(ctx.renderer, o, d, per_ray, table, rows, ctx.plan)
 
     @staticmethod
     def backward(ctx, grad_out):
         if grad_out is None:                 # (set_materialize_grads above) nothing flows back through the radiance
-            return (None,) * 7
+            return (None,) * 8
         o, d, per_ray = ctx.rays
         g = grad_out.to(o.device, torch.float32).contiguous()
         table, rows = _outputs(ctx, 1)
         if d.shape[0] and ctx.n and (table is not None or rows is not None):
-            ctx.renderer.radiance_rays_grad_rays_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), g.data_ptr(), d_grad=_ptr(table),
-                                                        d_grad_rays=_ptr(rows), stream=torch.cuda.current_stream(o.device).cuda_stream)
-        return (None, *_parameter_grads(ctx, table), *_ray_grads(ctx, rows))
+            with _planned(ctx.renderer, ctx.plan):
+                ctx.renderer.radiance_rays_grad_rays_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), g.data_ptr(), d_grad=_ptr(table),
+                                                            d_grad_rays=_ptr(rows), stream=torch.cuda.current_stream(o.device).cuda_stream)
+        return (None, *_parameter_grads(ctx, table), *_ray_grads(ctx, rows), None)
 
 
-def radiance_rays(renderer, mu, albedo, sigma, magnitude, origins, dirs):
+def radiance_rays(renderer, mu, albedo, sigma, magnitude, origins, dirs, plan=None):
     """Radiance [nrays, 4] (a cuda tensor on torch's current device and stream) of the rays through the scene of the four parameter
     tensors mu [N, 3], albedo [N, 4], sigma [N], magnitude [N], differentiable in those four and in the rays.  origins: [3] or
     [nrays, 3]; dirs: [nrays, 3], unit length (its gradient is the tangential one: see the module's docstring).  The scene of `renderer` is REPLACED by the parameters (see the module's docstring);
-    backward must run before the renderer's scene or options change again.  Forward mode too: the module's docstring."""
-    return _RadianceRays.apply(renderer, mu, albedo, sigma, magnitude, origins, dirs)
+    backward must run before the renderer's scene or options change again.  Forward mode too: the module's docstring.  plan: a RayPlan of
+    these rays, or None (the module's docstring, "Ray plans")."""
+    return _RadianceRays.apply(renderer, mu, albedo, sigma, magnitude, origins, dirs, plan)
 
 
 class _ProfileTangentBundle(torch.autograd.Function):
     """The library call of _Profile.jvp as a Function of its own, for the reason _TangentBundle gives.  Not differentiable itself."""
 
     @staticmethod
-    def forward(renderer, wrt, o, d, per_ray, s, s_per_ray, table, rows, s_tangent, s_tangent_per_ray):
+    def forward(renderer, wrt, o, d, per_ray, s, s_per_ray, table, rows, s_tangent, s_tangent_per_ray, plan):
         nrays, n = d.shape[0], s.shape[-1] if s.dim() else 1
         out = torch.zeros((nrays, n), dtype=torch.float32, device=o.device)
-        renderer.transmittance_bundle_tangent_device(nrays, o.data_ptr(), per_ray, d.data_ptr(), s.data_ptr(), n, s_per_ray, wrt,
-                                                     d_tangent=_ptr(table), d_ray_tangent=_ptr(rows), d_s_tangent=_ptr(s_tangent),
-                                                     s_tangent_per_ray=s_tangent_per_ray, d_out=out.data_ptr(),
-                                                     stream=torch.cuda.current_stream(o.device).cuda_stream)
+        with _planned(renderer, plan):
+            renderer.transmittance_bundle_tangent_device(nrays, o.data_ptr(), per_ray, d.data_ptr(), s.data_ptr(), n, s_per_ray, wrt,
+                                                         d_tangent=_ptr(table), d_ray_tangent=_ptr(rows), d_s_tangent=_ptr(s_tangent),
+                                                         s_tangent_per_ray=s_tangent_per_ray, d_out=out.data_ptr(),
+                                                         stream=torch.cuda.current_stream(o.device).cuda_stream)
         return out
 
     @staticmethod
@@ -226,7 +250,7 @@ class _Profile(torch.autograd.Function):
     setup_context apart, as _RadianceRays and for its reason."""
 
     @staticmethod
-    def forward(renderer, wrt, mu, albedo, sigma, magnitude, origins, dirs, values):
+    def forward(renderer, wrt, mu, albedo, sigma, magnitude, origins, dirs, values, plan):
         _set_scene(renderer, mu, albedo, sigma, magnitude)
         dev, o, d, per_ray = _rays(origins, dirs)
         nrays = d.shape[0]
@@ -234,14 +258,16 @@ class _Profile(torch.autograd.Function):
         out = torch.empty((nrays, n), dtype=torch.float32, device=dev)
         if nrays and n:
             call = renderer.transmittance_bundle_device if wrt == TGRAD_T else renderer.depth_bundle_device
-            call(nrays, o.data_ptr(), per_ray, d.data_ptr(), v.data_ptr(), n, v_per_ray, out.data_ptr(),
-                 stream=torch.cuda.current_stream(dev).cuda_stream)
+            with _planned(renderer, plan):
+                call(nrays, o.data_ptr(), per_ray, d.data_ptr(), v.data_ptr(), n, v_per_ray, out.data_ptr(),
+                     stream=torch.cuda.current_stream(dev).cuda_stream)
         return out
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        renderer, wrt, mu, albedo, sigma, magnitude, origins, dirs, values = inputs
+        renderer, wrt, mu, albedo, sigma, magnitude, origins, dirs, values, plan = inputs
         _remember(ctx, renderer, mu, albedo, sigma, magnitude, origins, dirs)
+        ctx.plan = plan
         v, v_per_ray, _ = _values(values)
         ctx.wrt, ctx.values, ctx.v_per_ray, ctx.v_like = wrt, v, v_per_ray, values
         ctx.save_for_backward(output)
@@ -249,7 +275,7 @@ class _Profile(torch.autograd.Function):
         ctx.set_materialize_grads(False)     # jvp sees None for an input without a tangent (_RadianceRays.setup_context)
 
     @staticmethod
-    def jvp(ctx, _r, _w, t_mu, t_albedo, t_sigma, t_magnitude, t_origins, t_dirs, t_values):
+    def jvp(ctx, _r, _w, t_mu, t_albedo, t_sigma, t_magnitude, t_origins, t_dirs, t_values, _p):
         """Forward mode: Renderer.transmittance_bundle_tangent_device over the scene and the rays of the forward, on torch's current
         stream -- T mode at the samples the forward took, depth mode at the depths it returned.  The tangent table is built from the
         tangents of mu, sigma and magnitude (albedo's moves nothing), the ray rows from those of origins and dirs as in
@@ -274,12 +300,12 @@ class _Profile(torch.autograd.Function):
         if not (nrays and n and nv) or (table is None and rows is None and st is None):
             return torch.zeros((nrays, nv), dtype=torch.float32, device=o.device)
         s, s_per_ray = (ctx.values, ctx.v_per_ray) if ctx.wrt == TGRAD_T else (out.detach(), True)
-        return _ProfileTangentBundle.apply(ctx.renderer, ctx.wrt, o, d, per_ray, s, s_per_ray, table, rows, st, ctx.v_per_ray)
+        return _ProfileTangentBundle.apply(ctx.renderer, ctx.wrt, o, d, per_ray, s, s_per_ray, table, rows, st, ctx.v_per_ray, ctx.plan)
 
     @staticmethod
     def backward(ctx, grad_out):
         if grad_out is None:                 # (set_materialize_grads above) nothing flows back through the profile
-            return (None,) * 9
+            return (None,) * 10
         o, d, per_ray = ctx.rays
         (out,) = ctx.saved_tensors
         nrays, n = out.shape
@@ -289,27 +315,28 @@ class _Profile(torch.autograd.Function):
         if nrays and n and ctx.n:
             # T mode: at the samples the forward took; depth mode: at the depths the forward returned, one row per ray
             s, s_per_ray = (ctx.values, ctx.v_per_ray) if ctx.wrt == TGRAD_T else (out, True)
-            ctx.renderer.transmittance_bundle_grad_rays_device(nrays, o.data_ptr(), per_ray, d.data_ptr(), s.data_ptr(), n, s_per_ray, g.data_ptr(),
-                                                               ctx.wrt, d_grad=_ptr(table), d_grad_s=gv.data_ptr(), d_grad_rays=_ptr(rows),
-                                                               stream=torch.cuda.current_stream(o.device).cuda_stream)
+            with _planned(ctx.renderer, ctx.plan):
+                ctx.renderer.transmittance_bundle_grad_rays_device(nrays, o.data_ptr(), per_ray, d.data_ptr(), s.data_ptr(), n, s_per_ray, g.data_ptr(),
+                                                                   ctx.wrt, d_grad=_ptr(table), d_grad_s=gv.data_ptr(), d_grad_rays=_ptr(rows),
+                                                                   stream=torch.cuda.current_stream(o.device).cuda_stream)
         if not ctx.v_per_ray:                       # values shared by the rays: their gradient is the sum over the rays
             gv = gv.sum(0).reshape(ctx.values.shape)
         grads = _parameter_grads(ctx, table)
         grads[1] = None                             # albedo
-        return (None, None, *grads, *_ray_grads(ctx, rows), gv.to(ctx.v_like.device, ctx.v_like.dtype))
+        return (None, None, *grads, *_ray_grads(ctx, rows), gv.to(ctx.v_like.device, ctx.v_like.dtype), None)
 
 
-def transmittance_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, s):
+def transmittance_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, s, plan=None):
     """Transmittance [nrays, ns] (a cuda tensor on torch's current device and stream) at the sample distances s ([ns], shared by the
     rays, or [nrays, ns]) along the rays through the scene of the four parameter tensors, differentiable in mu, sigma, magnitude and
     s; albedo gets no gradient (None).  Forward mode too (forward_ad, torch.func.jvp): the module's docstring.  Rays, the replaced scene
-    and the order of backward: as radiance_rays."""
-    return _Profile.apply(renderer, TGRAD_T, mu, albedo, sigma, magnitude, origins, dirs, s)
+    and the order of backward: as radiance_rays; so is plan."""
+    return _Profile.apply(renderer, TGRAD_T, mu, albedo, sigma, magnitude, origins, dirs, s, plan)
 
 
-def depth_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, tau):
+def depth_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, tau, plan=None):
     """The distance [nrays, nt] along each ray at which its transmittance falls to the levels tau ([nt], shared by the rays, or
     [nrays, nt]), differentiable in mu, sigma, magnitude and tau (the derivative of the ideal crossing; a result of +inf, 0 or NaN
     gets and gives no gradient); albedo gets no gradient (None).  Forward mode too: the module's docstring.  Rays, the replaced scene and
-    the order of backward: as radiance_rays."""
-    return _Profile.apply(renderer, TGRAD_DEPTH, mu, albedo, sigma, magnitude, origins, dirs, tau)
+    the order of backward: as radiance_rays; so is plan."""
+    return _Profile.apply(renderer, TGRAD_DEPTH, mu, albedo, sigma, magnitude, origins, dirs, tau, plan)

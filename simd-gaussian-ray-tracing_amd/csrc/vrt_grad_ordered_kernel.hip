@@ -22,7 +22,7 @@
 
 namespace vrtk {
 
-template <bool INDEXED>
+template <int SRC>
 __global__ __launch_bounds__(64) void ray_count_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -32,10 +32,14 @@ __global__ __launch_bounds__(64) void ray_count_kernel(RayArgs) // read through 
     const ShortSlot slot = ray_short_slot(&P, lane); // the waves of the record kernels behind this one: a sorted bundle is counted in its sorted order
     const uint64_t r = slot.r;
     const bool valid = slot.valid;
-    const LaneRay ray = load_ray(P, slot.rc);
-    const uint32_t N = S.n, nch = (N + 63u) / 64u;
-    RayCullCounts cnt;
-    const uint32_t nl = ray_short_cull<INDEXED>(&P, &S, N, nch, s_list, lane, valid, ray, cnt);
+    uint32_t nl;
+    if constexpr (SRC == RAY_LIST_PLAN) nl = valid ? P.pl_len[slot.rc] : 0u; // a ray plan is bound: its lengths are the count
+    else {
+        const LaneRay ray = load_ray(P, slot.rc);
+        const uint32_t N = S.n, nch = (N + 63u) / 64u;
+        RayCullCounts cnt;
+        nl = ray_short_cull<SRC>(&P, &S, N, nch, s_list, lane, valid, ray, cnt);
+    }
     if (valid) {
         P.ord_len[r] = nl;
         P.ord_count[r] = (unsigned long long)nl * (nl > (uint32_t)RAY_PL && P.ord_two ? 2ull : 1ull);
@@ -106,13 +110,14 @@ size_t grad_ordered_scan_bytes(size_t nrays)
     return bytes ? bytes : 1;
 }
 
-hipError_t launch_grad_ordered_count(const RayArgs &a, bool indexed, unsigned long long *base, void *tmp, size_t tmp_bytes, hipStream_t st)
+hipError_t launch_grad_ordered_count(const RayArgs &a, int src, unsigned long long *base, void *tmp, size_t tmp_bytes, hipStream_t st)
 {
     hipError_t e = hipMemsetAsync(a.ord_words, 0, GRAD_ORD_WORDS * sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
     const dim3 grid((uint32_t)((a.nrays + 63u) / 64u));
-    if (indexed) hipLaunchKernelGGL(ray_count_kernel<true>, grid, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(ray_count_kernel<false>, grid, dim3(64), 0, st, a);
+    if (src == RAY_LIST_PLAN) hipLaunchKernelGGL(ray_count_kernel<RAY_LIST_PLAN>, grid, dim3(64), 0, st, a);
+    else if (src == RAY_LIST_INDEX) hipLaunchKernelGGL(ray_count_kernel<RAY_LIST_INDEX>, grid, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(ray_count_kernel<RAY_LIST_CHUNKS>, grid, dim3(64), 0, st, a);
     e = rocprim::exclusive_scan(tmp, tmp_bytes, a.ord_count, base, 0ull, (size_t)a.nrays, rocprim::plus<unsigned long long>(), st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(grad_ordered_total_kernel, dim3(1), dim3(1), 0, st, a.ord_count, base, a.nrays, a.ord_words);

@@ -362,6 +362,8 @@ void vrt_hip_destroy(vrt_hip_ctx *c)
     (void)hipSetDevice(c->device);
     (void)quiesce(c); // frames still in flight on the context's stream or on the caller's last stream read its buffers
     c->host_regs.clear(); // the caller's host buffers: unregistered once nothing in flight can write them
+    for (vrt_hip_ray_plan *p : c->plans) delete p; // the ray plans that were not destroyed
+    c->plans.clear(); c->plan = nullptr;
     for (auto &e : c->batch_copied) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->tev) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -398,6 +400,7 @@ int vrt_hip_set_gaussians(vrt_hip_ctx *c, size_t n, const float *mu_x, const flo
             for (size_t i = 0; i < n; ++i) { const float v = fabsf(src[ch][i]); if (v > c->albedo_scale && v < INFINITY) c->albedo_scale = v; }
     c->n = (uint32_t)n;
     ++c->state_gen;
+    ++c->cull_gen; c->cull_gen_why = "the Gaussians were set again (vrt_hip_set_gaussians)"; // a strict ray plan is stale
     c->reset_seq = c->frame_seq;
     c->tables_dirty = true;
     c->lists_dirty = true;
@@ -458,6 +461,7 @@ int vrt_hip_set_gaussians_device(vrt_hip_ctx *c, size_t n, const float *d_mu, co
     c->n = un;
     c->scene_on_device = true;
     ++c->state_gen;
+    ++c->cull_gen; c->cull_gen_why = "the Gaussians were set again (vrt_hip_set_gaussians_device)"; // a strict ray plan is stale
     c->reset_seq = c->frame_seq;
     c->tables_dirty = false; // built eagerly; a later change of cull_eps or the Exp kind rebuilds them from soa, as after any setter
     c->ray_index_dirty = true;
@@ -507,6 +511,7 @@ int vrt_hip_copy_state(vrt_hip_ctx *dst, const vrt_hip_ctx *src)
     dst->reset_seq = dst->frame_seq;
     if (dst->tile_mode == TILES_HOST) untile(dst);
     ++dst->state_gen;
+    ++dst->cull_gen; dst->cull_gen_why = "the scene was copied in (vrt_hip_copy_state)"; // another scene: the plans and the binding of dst stay its own, and a strict one is stale
     return VRT_HIP_OK;
 }
 
@@ -519,7 +524,7 @@ int vrt_hip_set_options(vrt_hip_ctx *c, int exp_kind, int erf_kind, float cull_e
                            (exp_kind == VRT_EXP_LIBM && erf_kind == VRT_ERF_LIBM);
     if (!supported) return fail(c, VRT_HIP_ERR_INVALID, "set_options: this Exp/Erf pair is not instantiated");
     if (exp_kind != c->exp_kind || cull_eps != c->cull_eps) c->tables_dirty = true;
-    if (exp_kind != c->exp_kind || erf_kind != c->erf_kind || cull_eps != c->cull_eps) c->reset_seq = c->frame_seq;
+    if (exp_kind != c->exp_kind || erf_kind != c->erf_kind || cull_eps != c->cull_eps) { c->reset_seq = c->frame_seq; ++c->cull_gen; c->cull_gen_why = "cull_eps or the Exp / Erf pair changed (vrt_hip_set_options)"; /* a strict ray plan is stale */ }
     c->exp_kind = exp_kind; c->erf_kind = erf_kind; c->cull_eps = cull_eps;
     ++c->state_gen;
     return VRT_HIP_OK;

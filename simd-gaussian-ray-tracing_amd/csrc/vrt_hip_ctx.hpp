@@ -75,6 +75,25 @@ struct Tuning {
 
 enum TileMode { TILES_NONE = 0, TILES_HOST = 1, TILES_DEVICE = 2 };
 
+// A ray plan (vrt_hip_ray_plan_create*; vrt_hip_rays.cpp): the kept lists of one bundle in device memory of its own, CSR at the caller's
+// ray index.  12 B per ray (len, off) and 4 B per kept entry and per long ray; a sorted plan keeps the order and the packed keys as well
+// (8 B per ray).  Complete when its creation returns; read by planned bundles on any stream, written by nothing.
+struct vrt_hip_ray_plan {
+    vrt_hip_ctx *owner = nullptr;
+    size_t nrays = 0;
+    uint64_t entries = 0, long_rays = 0, scratch_rays = 0, longest = 0;
+    bool sorted = false, indexed = false;
+    uint32_t scene_n = 0;      // the scene's size, and ...
+    uint64_t cull_gen = 0;     // ... vrt_hip_ctx::cull_gen at creation
+    uint32_t spheres = 0;      // what a sorted plan's keys were packed for (ray_sort_unpack)
+    DevBuf<uint32_t> len, list, long_ids, order, keys;
+    DevBuf<unsigned long long> off;
+    size_t bytes() const
+    {
+        return nrays * 12 + (size_t)entries * 4 + (size_t)long_rays * 4 + (sorted ? nrays * 8 : 0);
+    }
+};
+
 struct vrt_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -297,6 +316,16 @@ struct vrt_hip_ctx {
     bool rs_last_sorted = false;  // it was sorted: rs_keys, rs_order and rs_none are its
     size_t rs_last_rays = 0;
     uint32_t rs_last_spheres = 0; // what its keys were packed for (ray_sort_unpack)
+    // Ray plans (vrt_hip_ray_plan_create*, vrt_hip_set_ray_plan; vrt_hip_rays.cpp).  The context owns every plan made through it; the bound
+    // one gives every bundle its lists.  cull_gen counts what makes a list stale and nothing else: the Gaussians set again (either
+    // setter, vrt_hip_copy_state into this context), cull_eps or the Exp / Erf pair changed -- not the index and sort switches, which
+    // state_gen counts too.
+    std::vector<vrt_hip_ray_plan *> plans;
+    vrt_hip_ray_plan *plan = nullptr; // bound, or nullptr
+    int plan_flags = 0;               // VRT_HIP_PLAN_KEEP_LISTS or 0
+    uint64_t cull_gen = 1;
+    const char *cull_gen_why = "";    // what bumped it last, for the message of a stale plan
+    const vrt_hip_ray_plan *rs_last_plan = nullptr; // the last bundle was planned: its order and keys are this plan's
     DevBuf<unsigned long long> d_stats, d_timeline; // d_timeline: VRT_HIP_TIMELINE diagnostics
     size_t timeline_items = 0, timeline_tiles = 0;
     DevBuf<unsigned long long> d_timeline_lists;

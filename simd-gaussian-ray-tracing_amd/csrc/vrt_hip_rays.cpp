@@ -5,12 +5,15 @@
 // vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip, vrt_ray_grad_kernel.hip, vrt_ray_trans_grad_kernel.hip, vrt_ray_tangent_kernel.hip, vrt_ray_trans_tangent_kernel.hip).  The scene tables and the
 // chunk spheres are the frame pipeline's; the long-ray queue, its counters and the long kernel's scratch slots belong to the context
 // and only grow.  So do the buffers of the ordered gradient tables (vrt_hip_set_grad_ordered: ordered_bundle, and the two read-outs)
-// and of the sorted bundles (vrt_hip_set_ray_sort: sort_bundle, and the two read-outs).
+// and of the sorted bundles (vrt_hip_set_ray_sort: sort_bundle, and the two read-outs).  Ray plans (vrt_hip_ray_plan_create*,
+// vrt_hip_set_ray_plan, at the end of this file) own their memory: a bundle enqueued while one is bound reads its lists, its queue and its
+// order from it and reserves neither queue nor scratch slots.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <initializer_list>
+#include <memory>
 #include <numeric>
 
 #include "vrt_hip_ctx.hpp"
@@ -73,7 +76,7 @@ std::vector<uint32_t> morton_order(const std::vector<float4> &ms)
 struct Bundle {
     RayArgs a{};
     uint32_t grid = 0;
-    bool indexed = false;
+    int src = RAY_LIST_CHUNKS; // where the kernels take the lists from (RayListSource)
 };
 // A bundle while vrt_hip_set_ray_sort is on (include/vrt_hip.h has the contract, vrt_ray_sort_kernel.hip the two steps): the keys by the
 // sphere tests of the cull the bundle will run, the stable sort, and a.order for the lane = ray kernels behind them -- all on the call's
@@ -105,7 +108,10 @@ int enqueue_bundle(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int ori
 {
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = rebuild_tables(c); if (rc) return rc; }
-    const bool indexed = c->ray_index;
+    // a bound ray plan (vrt_hip_set_ray_plan) gives every ray its list: no index, no sort, no queue and no scratch slot take part
+    const vrt_hip_ray_plan *plan = c->plan;
+    const int src = plan ? RAY_LIST_PLAN : c->ray_index ? RAY_LIST_INDEX : RAY_LIST_CHUNKS;
+    const bool indexed = src == RAY_LIST_INDEX;
     if (indexed && c->ray_index_dirty) { // switched on after the tables were made
         { int rc = quiesce(c); if (rc) return rc; }
         if (c->scene_on_device) { // its tables were made on the device: so is its index, on the context's stream like the host's build
@@ -117,9 +123,9 @@ int enqueue_bundle(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int ori
     c->last_stream = st;
     const uint32_t grid = long_grid(c);
     // (a buffer that grows is freed first, which waits for the device: no bundle in flight loses its memory)
-    HIPCHK(c, c->ray_queue.reserve(nrays));
+    if (!plan) HIPCHK(c, c->ray_queue.reserve(nrays));
     HIPCHK(c, c->ray_counters.reserve(2));
-    HIPCHK(c, c->ray_scratch.reserve((size_t)grid * c->n));
+    if (!plan) HIPCHK(c, c->ray_scratch.reserve((size_t)grid * c->n));
     constexpr size_t stats_words = RAY_STATS_WORDS + RAY_INDEX_STATS_WORDS;
     HIPCHK(c, c->ray_stats.reserve(stats_words));
     const uint32_t bitmap_words = (c->n + 31u) / 32u;
@@ -136,16 +142,23 @@ int enqueue_bundle(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int ori
     a.chunks = c->gChunk.p;
     a.origins = d_origins; a.dirs = d_dirs; a.origin_per_ray = origin_per_ray ? 1 : 0;
     a.nrays = nrays;
-    a.queue = c->ray_queue.p; a.queue_cap = (uint32_t)nrays;
-    a.counters = c->ray_counters.p;
-    a.scratch = c->ray_scratch.p;
+    if (!plan) { a.queue = c->ray_queue.p; a.queue_cap = (uint32_t)nrays; a.scratch = c->ray_scratch.p; }
+    a.counters = c->ray_counters.p; // [1], the long kernel's work counter, is the context's with a plan too
     a.stats = c->stats_on ? c->ray_stats.p : nullptr;
     if (indexed) {
         a.perm = c->ri_perm.p; a.mu_sig_m = c->ri_mu_sig.p; a.gB_m = c->ri_gB.p; a.leaves = c->ri_leaves.p; a.groups = c->ri_groups.p;
         a.bitmap = c->ri_bitmap.p;
         a.index_stats = c->stats_on ? c->ray_stats.p + RAY_STATS_WORDS : nullptr;
     }
-    b.grid = grid; b.indexed = indexed;
+    b.grid = grid; b.src = src;
+    c->rs_last_plan = plan;
+    if (plan) { // its lists, its queue and its order
+        a.pl_len = plan->len.p; a.pl_off = plan->off.p; a.pl_entries = plan->list.p;
+        a.pl_long = plan->long_ids.p; a.pl_nlong = (uint32_t)plan->long_rays;
+        a.order = plan->sorted ? plan->order.p : nullptr;
+        c->rs_last_valid = true; c->rs_last_sorted = plan->sorted; c->rs_last_rays = nrays; c->rs_last_spheres = plan->spheres;
+        return VRT_HIP_OK;
+    }
     return sort_bundle(c, a, indexed, st);
 }
 
@@ -227,10 +240,10 @@ struct BundleKind {
     const char *name, *io_text, *count;
     bool gradient; // a derivative: a scene of no Gaussians is a bundle of nothing, and the Exp / Erf pair must have kernels
     bool modes;    // ... of what `wrt` names
-    void (*launch)(const RayArgs &, uint32_t, bool, int, int, hipStream_t);
+    void (*launch)(const RayArgs &, uint32_t, int, int, int, hipStream_t);
     // a gradient with the ordered switch on and a table (ordered_bundle): the kernels that record, whether a long ray files two records
     // per kept Gaussian, and the first column of the table its reduction writes
-    void (*launch_ordered)(const RayArgs &, uint32_t, bool, int, int, hipStream_t) = nullptr;
+    void (*launch_ordered)(const RayArgs &, uint32_t, int, int, int, hipStream_t) = nullptr;
     bool ord_two = false;
     int ord_first_col = 0;
 };
@@ -254,6 +267,22 @@ struct Rays {
     const float *dirs;
 };
 
+// What a bound ray plan asks of a call, before anything is enqueued (include/vrt_hip.h, "Contract of a planned call")
+int plan_admits(vrt_hip_ctx *c, const std::string &name, size_t nrays)
+{
+    const vrt_hip_ray_plan *p = c->plan;
+    if (nrays != p->nrays)
+        return fail(c, VRT_HIP_ERR_INVALID, name + ": the bound ray plan was made for " + std::to_string(p->nrays) + " rays, the call has " + std::to_string(nrays));
+    if (c->plan_flags & VRT_HIP_PLAN_KEEP_LISTS) {
+        if (c->n != p->scene_n)
+            return fail(c, VRT_HIP_ERR_INVALID, name + ": the bound ray plan keeps lists of indices into a scene of " + std::to_string(p->scene_n) +
+                                                    " Gaussians, the scene now has " + std::to_string(c->n));
+    } else if (c->cull_gen != p->cull_gen)
+        return fail(c, VRT_HIP_ERR_INVALID, name + ": the bound ray plan is stale: " + c->cull_gen_why +
+                                                " after it was made (make it again, or bind it with VRT_HIP_PLAN_KEEP_LISTS to hold its lists)");
+    return VRT_HIP_OK;
+}
+
 // What every entry point checks before anything else, host and device form alike.  n: values per ray (1 for radiance and its gradient);
 // io_ok: the kind's tables and results are there; wrt: read by a kind with modes only.  True when the call is over, with rc its result:
 // an error, or VRT_HIP_OK for a bundle of nothing.
@@ -261,6 +290,7 @@ bool bundle_over(vrt_hip_ctx *c, const BundleKind &k, const Rays &r, size_t n, b
 {
     const std::string name = k.name;
     if (!c) rc = VRT_HIP_ERR_INVALID;
+    else if (c->plan && (rc = plan_admits(c, name, r.nrays)) != VRT_HIP_OK) {} // before anything else: a planned call states its plan's rays
     else if (r.nrays == 0 || n == 0 || (k.gradient && c->n == 0)) rc = VRT_HIP_OK;
     else if (!r.origins || !r.dirs) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": NULL origins or directions");
     else if (!io_ok) rc = fail(c, VRT_HIP_ERR_INVALID, name + ": " + k.io_text);
@@ -289,13 +319,13 @@ int ordered_bundle(vrt_hip_ctx *c, const BundleKind &k, Bundle &b, hipStream_t s
     a.ord_len = c->ord_len.p; a.ord_count = c->ord_count.p; a.ord_two = k.ord_two ? 1 : 0; a.ord_base = c->ord_base.p;
     a.ord_words = c->ord_words.p;
     c->ord_valid = true; c->ord_total = 0;
-    HIPCHK(c, launch_grad_ordered_count(a, b.indexed, c->ord_base.p, c->ord_scan_tmp.p, scan_bytes, st));
+    HIPCHK(c, launch_grad_ordered_count(a, b.src, c->ord_base.p, c->ord_scan_tmp.p, scan_bytes, st));
     unsigned long long total = 0;
     HIPCHK(c, hipMemcpyAsync(&total, c->ord_words.p + GRAD_ORD_TOTAL, sizeof(total), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st)); // the one wait of an ordered call: the sort takes its size on the host, and the buffers may have to grow
     if (total > 0xFFFFFFFFull) return fail(c, VRT_HIP_ERR_INVALID, std::string(k.name) + ": ordered table: more than 2^32 - 1 records in one bundle");
     if (total == 0) { // no ray keeps anything: nothing to record, sort or reduce; ray rows, grad_s and statistics by the kernels of the switch off
-        k.launch(a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
+        k.launch(a, b.grid, b.src, c->exp_kind, c->erf_kind, st);
         HIPCHK(c, hipGetLastError());
         return VRT_HIP_OK;
     }
@@ -311,7 +341,7 @@ int ordered_bundle(vrt_hip_ctx *c, const BundleKind &k, Bundle &b, hipStream_t s
         c->ord_iota_filled = rows;
     }
     a.ord_gauss = c->ord_gauss.p; a.ord_ray = c->ord_ray.p; a.ord_rows = c->ord_rows.p;
-    k.launch_ordered(a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
+    k.launch_ordered(a, b.grid, b.src, c->exp_kind, c->erf_kind, st);
     HIPCHK(c, hipGetLastError());
     GradOrderedSort o{};
     o.total = total; o.n = c->n;
@@ -335,7 +365,7 @@ int device_bundle(vrt_hip_ctx *c, const BundleKind &k, const Rays &r, size_t n, 
     if (rc) return rc;
     fill(b.a);
     if (c->grad_ordered && k.launch_ordered && b.a.grad) return ordered_bundle(c, k, b, st);
-    k.launch(b.a, b.grid, b.indexed, c->exp_kind, c->erf_kind, st);
+    k.launch(b.a, b.grid, b.src, c->exp_kind, c->erf_kind, st);
     HIPCHK(c, hipGetLastError());
     return VRT_HIP_OK;
 }
@@ -712,6 +742,7 @@ int vrt_hip_get_ray_sort_stats(vrt_hip_ctx *c, vrt_hip_ray_sort_stats *out)
     if (!c->rs_last_valid) return VRT_HIP_OK;
     out->rays = c->rs_last_rays;
     if (!c->rs_last_sorted) return VRT_HIP_OK;
+    if (c->rs_last_plan) { out->sorted = 1; return VRT_HIP_OK; } // a planned bundle in its plan's order; the plan keeps no count of the rays without sphere
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = quiesce(c); if (rc) return rc; } // waits for the bundle
     unsigned long long none = 0;
@@ -724,18 +755,157 @@ int vrt_hip_get_ray_order(vrt_hip_ctx *c, uint32_t *order, uint32_t *keys, size_
 {
     if (!c || !count) return VRT_HIP_ERR_INVALID;
     *count = 0;
-    if (!c->ray_sort || !c->rs_last_valid || !c->rs_last_sorted)
+    const vrt_hip_ray_plan *plan = c->rs_last_valid ? c->rs_last_plan : nullptr; // a planned bundle: its plan's order, whatever the switch says
+    if ((!c->ray_sort && !plan) || !c->rs_last_valid || !c->rs_last_sorted)
         return fail(c, VRT_HIP_ERR_INVALID, "get_ray_order: the sort is off, or the last bundle was not sorted");
     const size_t n = c->rs_last_rays;
     *count = n;
     if (!order || cap < n) return fail(c, VRT_HIP_ERR_INVALID, "get_ray_order: buffer too small");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = quiesce(c); if (rc) return rc; } // waits for the bundle
-    HIPCHK(c, hipMemcpy(order, c->rs_order.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(order, plan ? plan->order.p : c->rs_order.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (keys) { // filed packed: the documented key back
-        HIPCHK(c, hipMemcpy(keys, c->rs_keys.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(keys, plan ? plan->keys.p : c->rs_keys.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (size_t r = 0; r < n; ++r) keys[r] = ray_sort_unpack(keys[r], c->rs_last_spheres);
     }
+    return VRT_HIP_OK;
+}
+
+// ---- ray plans (include/vrt_hip.h has the contract, vrt_ray_plan_kernel.hip the kernels) ----
+static bool plan_of(const vrt_hip_ctx *c, const vrt_hip_ray_plan *plan)
+{
+    return plan && std::find(c->plans.begin(), c->plans.end(), plan) != c->plans.end();
+}
+
+// Count, scan, ONE wait for the totals, fill, and the wait that makes the plan complete.  The cull is the unplanned bundle's: whatever
+// plan is bound stays out of it.  The statistics words are left alone (a creation is no bundle: vrt_hip_get_ray_stats reads zeros behind it).
+int vrt_hip_ray_plan_create_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs, void *hip_stream,
+                                   vrt_hip_ray_plan **out)
+{
+    if (!c || !out) return VRT_HIP_ERR_INVALID;
+    *out = nullptr;
+    if (nrays && (!d_origins || !d_dirs)) return fail(c, VRT_HIP_ERR_INVALID, "ray_plan_create: NULL origins or directions");
+    if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "ray_plan_create: more than 2^32 - 16 rays in one plan");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::unique_ptr<vrt_hip_ray_plan> plan(new vrt_hip_ray_plan);
+    plan->owner = c; plan->nrays = nrays;
+    if (nrays) {
+        Bundle b;
+        vrt_hip_ray_plan *bound = c->plan;
+        c->plan = nullptr;
+        const int rc = enqueue_bundle(c, nrays, d_origins, origin_per_ray, d_dirs, st, b);
+        c->plan = bound;
+        if (rc) return rc;
+        RayArgs &a = b.a;
+        a.stats = nullptr; a.index_stats = nullptr;
+        c->ray_stats_valid = false;
+        plan->indexed = b.src == RAY_LIST_INDEX;
+        plan->sorted = a.order != nullptr;
+        // what only the creation needs: the scan's input and storage, the words
+        DevBuf<unsigned long long> count, words;
+        DevBuf<unsigned char> scan_tmp;
+        const size_t scan_bytes = grad_ordered_scan_bytes(nrays);
+        if (!scan_bytes) return fail(c, VRT_HIP_ERR_HIP, "ray_plan_create: the scan's storage query failed");
+        HIPCHK(c, plan->len.reserve(nrays)); HIPCHK(c, plan->off.reserve(nrays + 1));
+        HIPCHK(c, count.reserve(nrays)); HIPCHK(c, words.reserve(RAY_PLAN_WORDS)); HIPCHK(c, scan_tmp.reserve(scan_bytes));
+        a.ord_len = plan->len.p; a.ord_count = count.p; a.ord_two = 0; a.ord_words = words.p;
+        HIPCHK(c, launch_grad_ordered_count(a, b.src, plan->off.p, scan_tmp.p, scan_bytes, st));
+        HIPCHK(c, launch_ray_plan_info(plan->len.p, nrays, words.p, st));
+        unsigned long long w[RAY_PLAN_WORDS] = {};
+        HIPCHK(c, hipMemcpyAsync(w, words.p, sizeof(w), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st)); // the lists and the queue take their size on the host
+        const unsigned long long total = w[GRAD_ORD_TOTAL];
+        if (total > 0xFFFFFFFFull) return fail(c, VRT_HIP_ERR_INVALID, "ray_plan_create: more than 2^32 - 1 kept entries in one plan");
+        plan->entries = total; plan->long_rays = w[RAY_PLAN_LONG]; plan->scratch_rays = w[RAY_PLAN_SCRATCH]; plan->longest = w[RAY_PLAN_LONGEST];
+        HIPCHK(c, plan->list.reserve((size_t)total)); HIPCHK(c, plan->long_ids.reserve((size_t)plan->long_rays));
+        HIPCHK(c, hipMemcpyAsync(plan->off.p + nrays, &total, sizeof(total), hipMemcpyHostToDevice, st));
+        if (plan->sorted) { // the order the key kernel and the sort of this call made, and its keys for the read-out
+            HIPCHK(c, plan->order.reserve(nrays)); HIPCHK(c, plan->keys.reserve(nrays));
+            HIPCHK(c, hipMemcpyAsync(plan->order.p, c->rs_order.p, nrays * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(plan->keys.p, c->rs_keys.p, nrays * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+            plan->spheres = c->rs_last_spheres;
+        }
+        unsigned long long missed = 0;
+        if (total) {
+            a.pl_len = plan->len.p; a.pl_off = plan->off.p; a.pl_fill = plan->list.p; a.pl_words = words.p;
+            a.queue = plan->long_ids.p; a.queue_cap = (uint32_t)plan->long_rays; // the short kernel files the long rays into the plan's queue
+            launch_ray_plan_fill(a, b.grid, b.src, st);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(&missed, words.p + RAY_PLAN_MISMATCH, sizeof(missed), hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(c, hipStreamSynchronize(st)); // complete: usable on any stream
+        if (missed) return fail(c, VRT_HIP_ERR_HIP, "ray_plan_create: " + std::to_string(missed) + " rays missed the list length the count pass found");
+    }
+    plan->scene_n = c->n; plan->cull_gen = c->cull_gen;
+    c->plans.push_back(plan.get());
+    *out = plan.release();
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_ray_plan_create(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, vrt_hip_ray_plan **out)
+{
+    if (!c || !out) return VRT_HIP_ERR_INVALID;
+    *out = nullptr;
+    if (nrays && (!origins || !dirs)) return fail(c, VRT_HIP_ERR_INVALID, "ray_plan_create: NULL origins or directions");
+    if (nrays > 0xFFFFFFF0ull) return fail(c, VRT_HIP_ERR_INVALID, "ray_plan_create: more than 2^32 - 16 rays in one plan");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // an earlier bundle may still read the staging buffers
+    if (nrays) {
+        const size_t no = (origin_per_ray ? nrays : 1) * 3;
+        HIPCHK(c, c->rays_in[0].reserve(no)); HIPCHK(c, c->rays_in[1].reserve(nrays * 3));
+        HIPCHK(c, hipMemcpyAsync(c->rays_in[0].p, origins, no * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->rays_in[1].p, dirs, nrays * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    return vrt_hip_ray_plan_create_device(c, nrays, c->rays_in[0].p, origin_per_ray, c->rays_in[1].p, c->stream, out);
+}
+
+int vrt_hip_ray_plan_destroy(vrt_hip_ctx *c, vrt_hip_ray_plan *plan)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    if (!plan) return VRT_HIP_OK;
+    if (!plan_of(c, plan)) return fail(c, VRT_HIP_ERR_INVALID, "ray_plan_destroy: not a plan of this context");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // bundles in flight read its lists
+    if (c->plan == plan) { c->plan = nullptr; c->plan_flags = 0; }
+    if (c->rs_last_plan == plan) { c->rs_last_plan = nullptr; c->rs_last_valid = false; }
+    c->plans.erase(std::find(c->plans.begin(), c->plans.end(), plan));
+    delete plan;
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_set_ray_plan(vrt_hip_ctx *c, vrt_hip_ray_plan *plan, int flags)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    if (plan && !plan_of(c, plan)) return fail(c, VRT_HIP_ERR_INVALID, "set_ray_plan: not a plan of this context");
+    if (flags != 0 && flags != VRT_HIP_PLAN_KEEP_LISTS) return fail(c, VRT_HIP_ERR_INVALID, "set_ray_plan: flags is neither 0 nor VRT_HIP_PLAN_KEEP_LISTS");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = quiesce(c); if (rc) return rc; } // bundles in flight keep the lists they were enqueued with
+    c->plan = plan; c->plan_flags = plan ? flags : 0;
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_get_ray_plan_info(vrt_hip_ctx *c, vrt_hip_ray_plan *plan, vrt_hip_ray_plan_info *out)
+{
+    if (!c || !out) return VRT_HIP_ERR_INVALID;
+    *out = vrt_hip_ray_plan_info{};
+    if (!plan_of(c, plan)) return fail(c, VRT_HIP_ERR_INVALID, "get_ray_plan_info: not a plan of this context");
+    out->rays = plan->nrays; out->entries = plan->entries; out->short_rays = plan->nrays - plan->long_rays; out->long_rays = plan->long_rays;
+    out->longest = plan->longest; out->scratch_rays = plan->scratch_rays; out->bytes = plan->bytes();
+    out->sorted = plan->sorted; out->indexed = plan->indexed; out->scene_n = plan->scene_n; out->cull_generation = plan->cull_gen;
+    return VRT_HIP_OK;
+}
+
+int vrt_hip_get_ray_plan_lists(vrt_hip_ctx *c, vrt_hip_ray_plan *plan, uint64_t *offsets, uint32_t *entries)
+{
+    if (!c) return VRT_HIP_ERR_INVALID;
+    if (!plan_of(c, plan)) return fail(c, VRT_HIP_ERR_INVALID, "get_ray_plan_lists: not a plan of this context");
+    if (!offsets) return fail(c, VRT_HIP_ERR_INVALID, "get_ray_plan_lists: NULL offsets");
+    HIPCHK(c, hipSetDevice(c->device));
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the offsets are copied as they stand");
+    if (!plan->nrays) { offsets[0] = 0; return VRT_HIP_OK; }
+    HIPCHK(c, hipMemcpy(offsets, plan->off.p, (plan->nrays + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (entries && plan->entries) HIPCHK(c, hipMemcpy(entries, plan->list.p, (size_t)plan->entries * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return VRT_HIP_OK;
 }
 

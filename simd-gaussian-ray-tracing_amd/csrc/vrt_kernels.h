@@ -302,6 +302,9 @@ __host__ __device__ inline size_t sparse_pixel_offset(uint32_t cap) { return (SP
 constexpr int RAY_PL = VRT_RAY_PL;     // per-ray list capacity of the lane = ray kernel (u32 scene indices in LDS, [k*64 + lane]: 8 KB); a ray with a longer
                                        // list goes to the one-wave-per-ray kernel
 constexpr int RAY_LCAP = VRT_RAY_LCAP; // survivors the one-wave-per-ray kernel keeps in LDS; beyond that its list continues in its scratch slot
+// Where a bundle's kernels take every ray's list from -- a template value of all of them (SRC): the cull against the chunk spheres, the
+// same cull through the Morton index (vrt_hip_set_ray_index), or a ray plan's stored lists (vrt_hip_set_ray_plan), which culls nothing
+enum RayListSource : int { RAY_LIST_CHUNKS = 0, RAY_LIST_INDEX = 1, RAY_LIST_PLAN = 2 };
 struct RayArgs {
     SceneTables S;
     const float4 *chunks;        // bounding spheres of every 64 consecutive Gaussians (launch_build_chunks)
@@ -368,42 +371,55 @@ struct RayArgs {
     const float *s_tangent;         // nullable: d s[r, k] (wrt == VRT_HIP_TGRAD_T) or d tau[r, k] (VRT_HIP_TGRAD_DEPTH), ns in all or [r * ns + k]
     int s_tangent_per_ray;
     float *trans_tangent_out;       // [r * ns + k] stored: how T[r, k], or the depth of level k, moves along the direction
+    // Ray plans (vrt_hip_set_ray_plan; read by the RAY_LIST_PLAN instantiations and by the fill pair of vrt_ray_plan_kernel.hip only; behind
+    // everything the other kernels read).  CSR at the caller's ray index: ray r keeps pl_entries[pl_off[r] .. pl_off[r] + pl_len[r]),
+    // scene indices in ascending order.
+    const uint32_t *pl_len;             // [r] the list length of ray r, long rays too
+    const unsigned long long *pl_off;   // [r] where its list begins
+    const uint32_t *pl_entries;         // the lists
+    const uint32_t *pl_long;            // [pl_nlong] the ids of the rays with pl_len > RAY_PL: the long kernel's queue
+    uint32_t pl_nlong;
+    uint32_t *pl_fill;                  // the fill pair alone: the lists it writes, at pl_off / pl_len of the count pass
+    unsigned long long *pl_words;       // the fill pair alone: [RAY_PLAN_WORDS]
 };
 constexpr int GRAD_ORD_COLS = 9;    // floats per record
 // the words of an ordered call, cleared on the stream ahead of its count pass: rays whose re-cull missed the counted length; records
 // reduced, Gaussians with records and the longest segment (by the reduction); rows placed, sentinel rows included (by the scan)
 enum { GRAD_ORD_MISMATCH = 0, GRAD_ORD_RECORDS = 1, GRAD_ORD_TOUCHED = 2, GRAD_ORD_LONGEST = 3, GRAD_ORD_TOTAL = 4, GRAD_ORD_WORDS = 5 };
+// the words of a plan's creation: the count pass's (above; GRAD_ORD_TOTAL = the entries), then the rays with a list longer than RAY_PL,
+// those beyond RAY_LCAP, the longest list, and the rays whose fill found another length than the count pass (0, or the plan is refused)
+enum { RAY_PLAN_LONG = GRAD_ORD_WORDS, RAY_PLAN_SCRATCH, RAY_PLAN_LONGEST, RAY_PLAN_MISMATCH, RAY_PLAN_WORDS };
 constexpr int RAY_STATS_WORDS = 9, RAY_INDEX_STATS_WORDS = 5; // one device buffer: the index's words follow the nine
-void launch_ray_bundle(const RayArgs &a, uint32_t long_grid /* one-wave workgroups of the long kernel */, bool indexed, int exp_kind, int erf_kind,
+void launch_ray_bundle(const RayArgs &a, uint32_t long_grid /* one-wave workgroups of the long kernel */, int src /* RayListSource */, int exp_kind, int erf_kind,
                        hipStream_t st);
 // the same cull, then T at a.ns sample distances per ray instead of the radiance (vrt_ray_trans_kernel.hip)
-void launch_ray_trans_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+void launch_ray_trans_bundle(const RayArgs &a, uint32_t long_grid, int src /* RayListSource */, int exp_kind, int erf_kind, hipStream_t st);
 // the same cull, then the distance at which T falls to each of a.nt levels per ray (vrt_ray_depth_kernel.hip)
-void launch_ray_depth_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+void launch_ray_depth_bundle(const RayArgs &a, uint32_t long_grid, int src /* RayListSource */, int exp_kind, int erf_kind, hipStream_t st);
 // the same cull, then d(loss) / d(Gaussians) from a.grad_radiance, added into a.grad (where there), and d(loss) / d(rays) stored to
 // a.grad_rays (where there) (vrt_ray_grad_kernel.hip).  Only the pairs
 // ray_grad_pair_supported names have kernels; any other enqueues nothing.
-void launch_ray_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+void launch_ray_grad_bundle(const RayArgs &a, uint32_t long_grid, int src /* RayListSource */, int exp_kind, int erf_kind, hipStream_t st);
 bool ray_grad_pair_supported(int exp_kind, int erf_kind);
 // the same cull, then d(loss) / d(Gaussians) from a.grad_T at the samples a.s, added into columns 4..8 of a.grad, and d(loss) /
 // d(samples or levels) stored to a.grad_s, d(loss) / d(rays) to a.grad_rays (vrt_ray_trans_grad_kernel.hip).  The pairs of ray_grad_pair_supported; any other enqueues nothing.
-void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, int src /* RayListSource */, int exp_kind, int erf_kind, hipStream_t st);
 // the same cull, then J . v: how the radiance of every ray moves along the direction (a.tangent per Gaussian, a.ray_tangent per ray, either
 // nullable), stored to a.tangent_out (vrt_ray_tangent_kernel.hip).  The pairs of ray_grad_pair_supported; any other enqueues nothing.
-void launch_ray_tangent_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+void launch_ray_tangent_bundle(const RayArgs &a, uint32_t long_grid, int src /* RayListSource */, int exp_kind, int erf_kind, hipStream_t st);
 // the same cull, then J . v of T at the samples a.s (a.wrt == VRT_HIP_TGRAD_T) or of the depth at the depths a.s (VRT_HIP_TGRAD_DEPTH) along
 // the direction (a.tangent, a.ray_tangent, a.s_tangent, each nullable), stored to a.trans_tangent_out (vrt_ray_trans_tangent_kernel.hip).
 // The pairs of ray_grad_pair_supported; any other enqueues nothing.
-void launch_ray_trans_tangent_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+void launch_ray_trans_tangent_bundle(const RayArgs &a, uint32_t long_grid, int src /* RayListSource */, int exp_kind, int erf_kind, hipStream_t st);
 // Ordered gradient tables (vrt_hip_set_grad_ordered; vrt_grad_ordered_kernel.hip has the pipeline).  The same two bundles with every
 // add into a.grad replaced by a store into the records at a.ord_base[r] (the ORDERED instantiations, in translation units of their own:
 // vrt_ray_grad_ordered_kernel.hip, vrt_ray_trans_grad_ordered_kernel.hip); a.grad is not touched.
-void launch_ray_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
-void launch_ray_trans_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st);
+void launch_ray_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, int src /* RayListSource */, int exp_kind, int erf_kind, hipStream_t st);
+void launch_ray_trans_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, int src /* RayListSource */, int exp_kind, int erf_kind, hipStream_t st);
 // count and place: a.ord_words cleared, a.ord_len / a.ord_count by the cull alone, base = the exclusive scan of a.ord_count (tmp:
 // grad_ordered_scan_bytes(nrays) bytes; 0: the query failed), a.ord_words[GRAD_ORD_TOTAL] = the rows of the call.  a.nrays > 0.
 size_t grad_ordered_scan_bytes(size_t nrays);
-hipError_t launch_grad_ordered_count(const RayArgs &a, bool indexed, unsigned long long *base, void *tmp, size_t tmp_bytes, hipStream_t st);
+hipError_t launch_grad_ordered_count(const RayArgs &a, int src /* RayListSource */, unsigned long long *base, void *tmp, size_t tmp_bytes, hipStream_t st);
 // sort and reduce: `total` records (keys: Gaussian index, n for a sentinel row) into the consumed order, then table[j, first_col..8] +=
 // the ordered sum of Gaussian j's records.  sort_tmp: grad_ordered_sort_bytes(total, n) bytes; iota: 0 .. total - 1; seg: 2 n words.
 struct GradOrderedSort {
@@ -438,6 +454,14 @@ size_t ray_sort_bytes(size_t nrays, uint32_t spheres);
 uint32_t ray_sort_field_bits(uint32_t spheres);
 uint32_t ray_sort_unpack(uint32_t packed, uint32_t spheres);
 hipError_t launch_ray_sort(const RayArgs &a, bool indexed, const RaySort &o, hipStream_t st);
+// Ray plans (vrt_hip_ray_plan_create*; vrt_ray_plan_kernel.hip).  Behind launch_grad_ordered_count (a.ord_len = a.pl_len, a.ord_two = 0, base =
+// a.pl_off: lengths, offsets and the total) launch_ray_plan_info files RAY_PLAN_LONG / _SCRATCH / _LONGEST of `words` (cleared on the stream
+// here) from the lengths; launch_ray_plan_fill runs the bundle's cull once more (src: RAY_LIST_CHUNKS or RAY_LIST_INDEX; a.order as the bundle
+// would have it) and copies every list to a.pl_fill -- the short kernel its lane's list out of LDS, one wave per long ray (a.queue: the
+// plan's, a.queue_cap = the long rays the info pass counted) the LDS and scratch-slot list.  A ray whose length differs from the count pass's
+// writes nothing and counts in a.pl_words[RAY_PLAN_MISMATCH].
+hipError_t launch_ray_plan_info(const uint32_t *len, uint64_t nrays, unsigned long long *words, hipStream_t st);
+void launch_ray_plan_fill(const RayArgs &a, uint32_t long_grid, int src, hipStream_t st);
 // group spheres of the Morton index: one per 64 consecutive leaf spheres, bounding them
 void launch_build_ray_groups(uint32_t nleaves, const float4 *leaves, float4 *groups, hipStream_t st);
 

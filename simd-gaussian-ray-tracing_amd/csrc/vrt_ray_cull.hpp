@@ -5,6 +5,10 @@
 // statistics words; around them what every kernel pair does before its own middle -- ray_short_begin (a lane's ray, list and filing),
 // ray_long_begin / ray_long_next (a wave's claims of the queue, each with its re-cull) -- and launch_ray_kernels behind them.  One text
 // for all seven translation units: the same rays keep the same Gaussians, go to the same kernel and count the same statistics.
+// Where the lists come from is a template value of everything here (SRC, a RayListSource of vrt_kernels.h): the cull against the chunk
+// spheres, the same cull through the Morton index, or the lists of a ray plan (vrt_hip_set_ray_plan; vrt_ray_plan_kernel.hip makes them
+// with this very text), which are loaded and copied where the other two test -- a value and not a branch on a kernel argument, so that
+// the instantiations that cull keep the machine code they had.
 #pragma once
 #include "vrt_kernels_common.hpp"
 
@@ -73,7 +77,7 @@ struct RayCullCounts { uint32_t chunks_kept, members, groups_kept, leaf_tests; }
 // The cull of the lane = ray kernels: chunk spheres per lane, members of the chunks some lane keeps with a wave-uniform index.  Files
 // the lane's list into s_list[k*64 + lane] (RAY_PL entries per lane: consecutive lanes on consecutive banks) in ascending scene order
 // and returns its length, which runs on past RAY_PL: such a ray's list is not used.
-template <bool INDEXED>
+template <int SRC>
 __device__ __forceinline__ uint32_t ray_short_cull(const RayArgs *Pp, const SceneTables *Sp, uint32_t N, uint32_t nch /* (N + 63) / 64 */, uint32_t *s_list,
                                                    uint32_t lane, bool valid, const LaneRay &ray, RayCullCounts &cnt)
 {
@@ -81,7 +85,7 @@ __device__ __forceinline__ uint32_t ray_short_cull(const RayArgs *Pp, const Scen
     const SceneTables &S = *Sp;
     uint32_t nl = 0, chunks_kept = 0, members = 0;
     [[maybe_unused]] uint32_t groups_kept = 0, leaf_tests = 0;
-    if constexpr (INDEXED) {
+    if constexpr (SRC == RAY_LIST_INDEX) {
         // ---- the same cull through the Morton index: group spheres, the leaf spheres of the groups some lane keeps, the members of the
         // leaves some lane keeps -- all three with a wave-uniform index (scalar loads of consecutive permuted rows).  The leaf spheres
         // take the place of the chunk spheres (nch of them, 64 consecutive Morton positions each).
@@ -142,7 +146,7 @@ __device__ __forceinline__ uint32_t ray_short_cull(const RayArgs *Pp, const Scen
 }
 
 // Behind the cull: a ray whose list outgrew RAY_PL goes to the one-wave-per-ray kernel behind this one; the statistics of the lane.
-template <bool INDEXED>
+template <int SRC>
 __device__ __forceinline__ void ray_short_file(const RayArgs *Pp, uint32_t nch, uint64_t r, bool valid, bool is_long, uint32_t nl, const RayCullCounts &cnt)
 {
     const RayArgs &P = *Pp;
@@ -154,7 +158,7 @@ __device__ __forceinline__ void ray_short_file(const RayArgs *Pp, uint32_t nch, 
         atomicAdd(&P.stats[0], 1ull);
         atomicAdd(&P.stats[is_long ? 2 : 1], 1ull);
         if (!is_long) { atomicAdd(&P.stats[3], (unsigned long long)nl); atomicAdd(&P.stats[4], (unsigned long long)nl * nl); }
-        if constexpr (INDEXED) {
+        if constexpr (SRC == RAY_LIST_INDEX) {
             atomicAdd(&P.index_stats[0], (unsigned long long)((nch + 63u) / 64u));
             atomicAdd(&P.index_stats[1], (unsigned long long)cnt.groups_kept);
             atomicAdd(&P.index_stats[2], (unsigned long long)cnt.leaf_tests);
@@ -165,6 +169,17 @@ __device__ __forceinline__ void ray_short_file(const RayArgs *Pp, uint32_t nch, 
             atomicAdd(&P.stats[6], (unsigned long long)cnt.chunks_kept);
             atomicAdd(&P.stats[7], (unsigned long long)cnt.members);
         }
+    }
+}
+
+// The statistics of a lane whose list came from a ray plan: the per-ray words ray_short_file counts, and none of the tests.
+__device__ __forceinline__ void ray_plan_short_stats(const RayArgs *Pp, bool valid, bool is_long, uint32_t nl)
+{
+    const RayArgs &P = *Pp;
+    if (P.stats && valid) {
+        atomicAdd(&P.stats[0], 1ull);
+        atomicAdd(&P.stats[is_long ? 2 : 1], 1ull);
+        if (!is_long) { atomicAdd(&P.stats[3], (unsigned long long)nl); atomicAdd(&P.stats[4], (unsigned long long)nl * nl); }
     }
 }
 
@@ -191,7 +206,7 @@ __device__ __forceinline__ ShortSlot ray_short_slot(const RayArgs *Pp, uint32_t 
     s.r = s.valid ? s.rc : slot;
     return s;
 }
-template <bool INDEXED>
+template <int SRC>
 __device__ __forceinline__ ShortRay ray_short_begin(const RayArgs *Pp, const SceneTables *Sp, uint32_t *s_list /*[RAY_PL * 64]*/, uint32_t lane)
 {
     const RayArgs &P = *Pp;
@@ -199,11 +214,22 @@ __device__ __forceinline__ ShortRay ray_short_begin(const RayArgs *Pp, const Sce
     const ShortSlot s = ray_short_slot(Pp, lane);
     R.r = s.r; R.rc = s.rc; R.valid = s.valid;
     R.ray = load_ray(P, R.rc);
-    const uint32_t N = Sp->n, nch = (N + 63u) / 64u;
-    RayCullCounts cnt;
-    R.nl = ray_short_cull<INDEXED>(Pp, Sp, N, nch, s_list, lane, R.valid, R.ray, cnt);
-    R.is_long = R.nl > (uint32_t)RAY_PL;
-    ray_short_file<INDEXED>(Pp, nch, R.r, R.valid, R.is_long, R.nl, cnt); // to the one-wave-per-ray kernel behind this one; statistics
+    if constexpr (SRC == RAY_LIST_PLAN) {
+        // ---- the list of a ray plan: no sphere test, no member test, and the queue of the long rays is the plan's, made with it ----
+        R.nl = R.valid ? P.pl_len[R.rc] : 0u;
+        R.is_long = R.nl > (uint32_t)RAY_PL;
+        if (!R.is_long) {
+            const uint32_t *mine = P.pl_entries + P.pl_off[R.rc];
+            for (uint32_t k = 0; k < R.nl; ++k) s_list[k * 64u + lane] = mine[k];
+        }
+        ray_plan_short_stats(Pp, R.valid, R.is_long, R.nl);
+    } else {
+        const uint32_t N = Sp->n, nch = (N + 63u) / 64u;
+        RayCullCounts cnt;
+        R.nl = ray_short_cull<SRC>(Pp, Sp, N, nch, s_list, lane, R.valid, R.ray, cnt);
+        R.is_long = R.nl > (uint32_t)RAY_PL;
+        ray_short_file<SRC>(Pp, nch, R.r, R.valid, R.is_long, R.nl, cnt); // to the one-wave-per-ray kernel behind this one; statistics
+    }
     if (R.is_long) R.nl = 0;
     R.nmax = wave_max_u32(R.nl);
     R.writes = R.valid && !R.is_long;
@@ -230,14 +256,14 @@ __device__ __forceinline__ uint32_t ray_long_claim(const RayArgs *Pp, uint32_t l
 // the survivors in Morton order; each sets bit perm[pos] of this workgroup's bitmap (N bits of device memory, all zero between rays),
 // and the list is read off the bitmap in ascending scene order -- the list the unindexed compaction makes.
 // Returns the list length; ray_long_next's barriers stand before (the previous ray's list reads are done) and behind it.
-template <bool INDEXED>
+template <int SRC>
 __device__ __forceinline__ uint32_t ray_long_cull(const RayArgs *Pp, const SceneTables *Sp, uint32_t N, uint32_t nch /* (N + 63) / 64 */, lds_u32 *s_list,
                                                   uint32_t *slot, uint32_t lane, const LaneRay &ray)
 {
     const RayArgs &P = *Pp;
     const SceneTables &S = *Sp;
     uint32_t n = 0;
-    if constexpr (INDEXED) {
+    if constexpr (SRC == RAY_LIST_INDEX) {
         const uint32_t ngr = (nch + 63u) / 64u, nwords = (N + 31u) / 32u;
         uint32_t *bm = P.bitmap + (size_t)blockIdx.x * nwords;
         for (uint32_t g0 = 0; g0 < ngr; g0 += 64u) {
@@ -303,40 +329,53 @@ __device__ __forceinline__ uint32_t long_list_entry(const uint32_t *s_list, cons
 }
 
 // A wave's way through the long-ray queue, as every one-wave-per-ray kernel runs it:
-//     LongRay L = ray_long_begin(&P);
-//     while (ray_long_next<INDEXED>(&P, &S, s_list, lane, L)) { ... L.r, L.ray, the L.n entries long_list_entry(s_list, L.slot, p) ... }
+//     LongRay L = ray_long_begin<SRC>(&P);
+//     while (ray_long_next<SRC>(&P, &S, s_list, lane, L)) { ... L.r, L.ray, the L.n entries long_list_entry(s_list, L.slot, p) ... }
 struct LongRay {
     uint32_t n_long; // length of the queue
-    uint32_t *slot;  // this workgroup's scratch slot
+    uint32_t *slot;  // this workgroup's scratch slot; RAY_LIST_PLAN: the claimed ray's list in the plan (entry p at slot[p], as in a slot)
     uint32_t N, nch; // Gaussians and chunks of the scene
     uint64_t r;      // the ray claimed last,
     LaneRay ray;
     uint32_t n;      // and the length of its list
 };
+template <int SRC>
 __device__ __forceinline__ LongRay ray_long_begin(const RayArgs *Pp)
 {
     const RayArgs &P = *Pp;
     LongRay L;
-    L.n_long = min(P.counters[0], P.queue_cap); // final: the short kernel is done
-    L.slot = P.scratch + (size_t)blockIdx.x * P.S.n;
+    if constexpr (SRC == RAY_LIST_PLAN) {
+        L.n_long = P.pl_nlong; // the plan's queue: nothing was filed by the short kernel
+        L.slot = nullptr;
+    } else {
+        L.n_long = min(P.counters[0], P.queue_cap); // final: the short kernel is done
+        L.slot = P.scratch + (size_t)blockIdx.x * P.S.n;
+    }
     L.N = P.S.n; L.nch = (L.N + 63u) / 64u;
     return L;
 }
 // Claims the next ray of the queue and culls it again into s_list[RAY_LCAP] / L.slot; false when the queue is empty.  The whole wave
 // calls this (ray_long_claim says why the claim sits behind no branch on the lane) and comes back together.
+// RAY_LIST_PLAN: the queue and the list are the plan's -- the first RAY_LCAP entries copied to s_list, L.slot pointed at the list, so that
+// long_list_entry reads the rest where it stands.  The work counter is still the context's.
 // (ray_long_kernel of vrt_ray_kernel.hip runs a text of its own of this loop; the note at the top of that file says why.)
-template <bool INDEXED>
+template <int SRC>
 __device__ __forceinline__ bool ray_long_next(const RayArgs *Pp, const SceneTables *Sp, uint32_t *s_list /*[RAY_LCAP]*/, uint32_t lane, LongRay &L)
 {
     const RayArgs &P = *Pp;
     while (true) {
         const uint32_t k = ray_long_claim(Pp, lane);
         if (k >= L.n_long) return false;
-        L.r = P.queue[k];
+        if constexpr (SRC == RAY_LIST_PLAN) L.r = P.pl_long[k];
+        else L.r = P.queue[k];
         if (L.r >= P.nrays) continue;
         L.ray = load_ray(P, L.r);
         __syncthreads(); // the previous ray's list reads are done
-        L.n = ray_long_cull<INDEXED>(Pp, Sp, L.N, L.nch, (lds_u32 *)s_list, L.slot, lane, L.ray);
+        if constexpr (SRC == RAY_LIST_PLAN) {
+            L.slot = const_cast<uint32_t *>(P.pl_entries + P.pl_off[L.r]);
+            L.n = min(P.pl_len[L.r], L.N);
+            for (uint32_t p = lane; p < min(L.n, (uint32_t)RAY_LCAP); p += 64u) s_list[p] = L.slot[p];
+        } else L.n = ray_long_cull<SRC>(Pp, Sp, L.N, L.nch, (lds_u32 *)s_list, L.slot, lane, L.ray);
         __syncthreads(); // list and scratch writes of this wave are visible to it
         if (P.stats && lane == 0 && L.n > (uint32_t)RAY_LCAP) atomicAdd(&P.stats[8], 1ull);
         return true;

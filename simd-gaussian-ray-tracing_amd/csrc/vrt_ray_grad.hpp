@@ -448,15 +448,20 @@ __device__ __forceinline__ void tangent_row_uload(const float *table, uint32_t i
     dm = uload((const float4 *)table, 3u * idx + 2u).x;
 }
 
-// ---- the launch: a bundle's run-time switches INDEXED and RAYS as the constants I.value, R.value of a generic callable f(I, R) ----
+// ---- the launch: a bundle's run-time list source (RayListSource) and RAYS as the constants I.value, R.value of a generic callable f(I, R) ----
 template <class F>
-inline void grad_dispatch_indexed_rays(bool indexed, bool rays, F &&f)
+inline void grad_dispatch_source_rays(int src, bool rays, F &&f)
 {
+    using Chunks = std::integral_constant<int, RAY_LIST_CHUNKS>;
+    using Index = std::integral_constant<int, RAY_LIST_INDEX>;
+    using Plan = std::integral_constant<int, RAY_LIST_PLAN>;
     if (rays) {
-        if (indexed) f(std::true_type(), std::true_type());
-        else f(std::false_type(), std::true_type());
-    } else if (indexed) f(std::true_type(), std::false_type());
-    else f(std::false_type(), std::false_type());
+        if (src == RAY_LIST_PLAN) f(Plan(), std::true_type());
+        else if (src == RAY_LIST_INDEX) f(Index(), std::true_type());
+        else f(Chunks(), std::true_type());
+    } else if (src == RAY_LIST_PLAN) f(Plan(), std::false_type());
+    else if (src == RAY_LIST_INDEX) f(Index(), std::false_type());
+    else f(Chunks(), std::false_type());
 }
 
 } // namespace vrtk

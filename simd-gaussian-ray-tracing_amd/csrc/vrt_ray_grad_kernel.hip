@@ -130,7 +130,7 @@ __device__ __forceinline__ void ray_grad_chunk(const GradSink<ORDERED> &sink, co
 // RAYS: the ray rows are asked for (P.grad_rays != nullptr), and then the table may be missing; without, the table is there.
 // ORDERED: one record per list position, the lane's own -- the albedo columns at the emitter's chunk, columns 4..8 and the name at the
 // flush.  <.., false> is the kernel as it is without.
-template <int EXP, int ERF, bool INDEXED, bool RAYS, bool ORDERED = false>
+template <int EXP, int ERF, int SRC, bool RAYS, bool ORDERED = false>
 __global__ __launch_bounds__(64) void ray_short_grad_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(64) void ray_short_grad_kernel(RayArgs) // read thr
     __shared__ uint32_t s_list[RAY_PL * 64]; // [k*64 + lane]: consecutive lanes on consecutive banks
     __shared__ float s_acc[3 * RAY_PL * 64];
     const uint32_t lane = threadIdx.x & 63u;
-    const ShortRay R = ray_short_begin<INDEXED>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
+    const ShortRay R = ray_short_begin<SRC>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
     const uint32_t nl = R.nl, nmax = R.nmax;
     const LaneRay &ray = R.ray;
     const float4 g = P.grad_radiance[R.rc];
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(64) void ray_short_grad_kernel(RayArgs) // read thr
 // as an emitter, lane p mod 64, in its round and again in the last walk: it opens it with the albedo columns, stores the emitter's own
 // terms, then adds the W terms onto its own stores.  The ABSORBER record of position j (record n + j) is the wave's (GradSink::absorber),
 // its first write in the first round.
-template <int EXP, int ERF, bool INDEXED, bool RAYS, bool ORDERED = false>
+template <int EXP, int ERF, int SRC, bool RAYS, bool ORDERED = false>
 __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -181,8 +181,8 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
     GradSink<ORDERED> sink(&P, false);
     const bool table = sink.template wanted<RAYS>(); // wave-uniform
 
-    LongRay L = ray_long_begin(&P);
-    while (ray_long_next<INDEXED>(&P, &S, s_list, lane, L)) {
+    LongRay L = ray_long_begin<SRC>(&P);
+    while (ray_long_next<SRC>(&P, &S, s_list, lane, L)) {
         const LaneRay ray = L.ray;
         const uint32_t n = L.n;
         const float4 g = P.grad_radiance[L.r];
@@ -285,9 +285,9 @@ __global__ __launch_bounds__(64) void ray_long_grad_kernel(RayArgs)
 
 #ifndef VRT_GRAD_ORDERED_UNIT
 template <int EXP, int ERF>
-static void launch_ray_grad_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
+static void launch_ray_grad_bundle_t(const RayArgs &a, uint32_t long_grid, int src, hipStream_t st)
 {
-    grad_dispatch_indexed_rays(indexed, a.grad_rays != nullptr, [&](auto I, auto R) {
+    grad_dispatch_source_rays(src, a.grad_rays != nullptr, [&](auto I, auto R) {
         launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, I.value, R.value, false>, ray_long_grad_kernel<EXP, ERF, I.value, R.value, false>, a, long_grid, st);
     });
 }
@@ -296,24 +296,24 @@ bool ray_grad_pair_supported(int exp_kind, int erf_kind)
 {
     return (exp_kind == VRT_EXP_VCL || exp_kind == VRT_EXP_LIBM) && (erf_kind == VRT_ERF_AS || erf_kind == VRT_ERF_LIBM);
 }
-void launch_ray_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
+void launch_ray_grad_bundle(const RayArgs &a, uint32_t long_grid, int src, int exp_kind, int erf_kind, hipStream_t st)
 {
     if (!a.nrays || !long_grid || !ray_grad_pair_supported(exp_kind, erf_kind)) return;
-    VRT_DISPATCH_GRAD_PAIR(launch_ray_grad_bundle_t, a, long_grid, indexed, st);
+    VRT_DISPATCH_GRAD_PAIR(launch_ray_grad_bundle_t, a, long_grid, src, st);
 }
 
 #else // vrt_ray_grad_ordered_kernel.hip: the ORDERED instantiations alone, so that the build stays parallel
 template <int EXP, int ERF>
-static void launch_ray_grad_bundle_ordered_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
+static void launch_ray_grad_bundle_ordered_t(const RayArgs &a, uint32_t long_grid, int src, hipStream_t st)
 {
-    grad_dispatch_indexed_rays(indexed, a.grad_rays != nullptr, [&](auto I, auto R) {
+    grad_dispatch_source_rays(src, a.grad_rays != nullptr, [&](auto I, auto R) {
         launch_ray_kernels(ray_short_grad_kernel<EXP, ERF, I.value, R.value, true>, ray_long_grad_kernel<EXP, ERF, I.value, R.value, true>, a, long_grid, st);
     });
 }
-void launch_ray_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
+void launch_ray_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, int src, int exp_kind, int erf_kind, hipStream_t st)
 {
     if (!a.nrays || !long_grid || !a.grad || !ray_grad_pair_supported(exp_kind, erf_kind)) return;
-    VRT_DISPATCH_GRAD_PAIR(launch_ray_grad_bundle_ordered_t, a, long_grid, indexed, st);
+    VRT_DISPATCH_GRAD_PAIR(launch_ray_grad_bundle_ordered_t, a, long_grid, src, st);
 }
 #endif
 

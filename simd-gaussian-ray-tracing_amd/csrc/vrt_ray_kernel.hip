@@ -9,6 +9,7 @@
 // Both kernels come in a second, INDEXED form (vrt_hip_set_ray_index): the cull walks the scene in the Morton order of its centres --
 // group spheres (64 leaves), leaf spheres (64 consecutive Morton positions), members -- and hands the shading code the SAME list in
 // the same ascending scene order: the sphere tests only ever drop what the member test drops, so no bit of a result moves.
+// And in a third, PLANNED form (vrt_hip_set_ray_plan, SRC = RAY_LIST_PLAN): no cull at all, the lists a ray plan kept of this cull.
 // What a lane = ray kernel does before it shades (ray, cull, list, filing: ray_short_begin) and how the pair is launched
 // (launch_ray_kernels) is vrt_ray_cull.hpp's, the text the transmittance and depth bundles run.  ray_long_kernel keeps its OWN text of
 // the claim loop (ray_long_next there), of the list entry (long_list_entry there) and of the emitter set-up and emission it has in common
@@ -132,7 +133,7 @@ __device__ __forceinline__ void ray_shade_chunk(const SceneTables &S, const uint
     }
 }
 
-template <int EXP, int ERF, bool INDEXED>
+template <int EXP, int ERF, int SRC>
 __global__ __launch_bounds__(64) void ray_short_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(64) void ray_short_kernel(RayArgs) // read through 
     __shared__ uint32_t s_list[RAY_PL * 64]; // [k*64 + lane]: consecutive lanes on consecutive banks
     const uint32_t lane = threadIdx.x & 63u;
     // ---- ray, cull, list (vrt_ray_cull.hpp) ----
-    const ShortRay R = ray_short_begin<INDEXED>(&P, &S, s_list, lane);
+    const ShortRay R = ray_short_begin<SRC>(&P, &S, s_list, lane);
     const uint32_t nl = R.nl, nmax = R.nmax;
     const LaneRay &ray = R.ray;
 
@@ -164,29 +165,38 @@ __global__ __launch_bounds__(64) void ray_short_kernel(RayArgs) // read through 
 // INDEXED: the re-cull goes through the Morton index (lane = group, lane = leaf of a kept group, lane = member of a kept leaf) and finds
 // the survivors in Morton order; each sets bit perm[pos] of this workgroup's bitmap (N bits of device memory, all zero between rays),
 // and the list is read off the bitmap in ascending scene order -- the list the unindexed compaction makes.
-template <int EXP, int ERF, bool INDEXED>
+template <int EXP, int ERF, int SRC>
 __global__ __launch_bounds__(64) void ray_long_kernel(RayArgs)
 {
     const RayArgs &P = kernel_args<RayArgs>();
     const SceneTables &S = P.S;
     __shared__ uint32_t s_list[RAY_LCAP];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t n_long = min(P.counters[0], P.queue_cap); // final: the short kernel is done
-    uint32_t *slot = P.scratch + (size_t)blockIdx.x * S.n;
-    const uint32_t N = S.n, nch = (N + 63u) / 64u;
+    // RAY_LIST_PLAN (vrt_hip_set_ray_plan): the queue and every list are the plan's, as in ray_long_begin / ray_long_next
+    constexpr bool PLANNED = SRC == RAY_LIST_PLAN;
+    const uint32_t n_long = PLANNED ? P.pl_nlong : min(P.counters[0], P.queue_cap); // final: the short kernel is done
+    uint32_t *slot = PLANNED ? nullptr : P.scratch + (size_t)blockIdx.x * S.n;
+    [[maybe_unused]] const uint32_t N = S.n, nch = (N + 63u) / 64u;
     const ErfEval<ERF> erf;
     constexpr int EC = 2;
 
     while (true) {
         const uint32_t k = ray_long_claim(&P, lane); // every lane executes the atomic: see there
         if (k >= n_long) break;
-        const uint64_t r = P.queue[k];
+        uint64_t r;
+        if constexpr (PLANNED) r = P.pl_long[k];
+        else r = P.queue[k];
         if (r >= P.nrays) continue;
         const LaneRay ray = load_ray(P, r);
 
         // ---- cull: 64 chunk spheres at a time (lane = chunk), then the members of the kept ones (lane = Gaussian) ----
         __syncthreads(); // the previous ray's list reads are done
-        const uint32_t n = ray_long_cull<INDEXED>(&P, &S, N, nch, (lds_u32 *)s_list, slot, lane, ray);
+        uint32_t n;
+        if constexpr (PLANNED) { // ---- or no cull: the first RAY_LCAP entries of the plan's list to LDS, the rest read where they stand ----
+            slot = const_cast<uint32_t *>(P.pl_entries + P.pl_off[r]);
+            n = min(P.pl_len[r], N);
+            for (uint32_t p = lane; p < min(n, (uint32_t)RAY_LCAP); p += 64u) s_list[p] = slot[p];
+        } else n = ray_long_cull<SRC>(&P, &S, N, nch, (lds_u32 *)s_list, slot, lane, ray);
         __syncthreads(); // list and scratch writes of this wave are visible to it
         if (P.stats && lane == 0 && n > (uint32_t)RAY_LCAP) atomicAdd(&P.stats[8], 1ull);
         auto entry = [&](uint32_t p) -> uint32_t { return p < (uint32_t)RAY_LCAP ? s_list[p] : slot[p]; };
@@ -262,15 +272,16 @@ __global__ __launch_bounds__(64) void ray_long_kernel(RayArgs)
 }
 
 template <int EXP, int ERF>
-static void launch_ray_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
+static void launch_ray_bundle_t(const RayArgs &a, uint32_t long_grid, int src, hipStream_t st)
 {
-    if (indexed) launch_ray_kernels(ray_short_kernel<EXP, ERF, true>, ray_long_kernel<EXP, ERF, true>, a, long_grid, st);
-    else launch_ray_kernels(ray_short_kernel<EXP, ERF, false>, ray_long_kernel<EXP, ERF, false>, a, long_grid, st);
+    if (src == RAY_LIST_PLAN) launch_ray_kernels(ray_short_kernel<EXP, ERF, RAY_LIST_PLAN>, ray_long_kernel<EXP, ERF, RAY_LIST_PLAN>, a, long_grid, st);
+    else if (src == RAY_LIST_INDEX) launch_ray_kernels(ray_short_kernel<EXP, ERF, RAY_LIST_INDEX>, ray_long_kernel<EXP, ERF, RAY_LIST_INDEX>, a, long_grid, st);
+    else launch_ray_kernels(ray_short_kernel<EXP, ERF, RAY_LIST_CHUNKS>, ray_long_kernel<EXP, ERF, RAY_LIST_CHUNKS>, a, long_grid, st);
 }
-void launch_ray_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
+void launch_ray_bundle(const RayArgs &a, uint32_t long_grid, int src, int exp_kind, int erf_kind, hipStream_t st)
 {
     if (!a.nrays || !long_grid) return;
-    VRT_DISPATCH_EXP_ERF(launch_ray_bundle_t, a, long_grid, indexed, st);
+    VRT_DISPATCH_EXP_ERF(launch_ray_bundle_t, a, long_grid, src, st);
 }
 
 } // namespace vrtk

@@ -125,7 +125,7 @@ __device__ __forceinline__ void ray_tangent_chunk(const RayArgs *Pp, const Scene
     }
 }
 
-template <int EXP, int ERF, bool INDEXED>
+template <int EXP, int ERF, int SRC>
 __global__ __launch_bounds__(64) void ray_short_tangent_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(64) void ray_short_tangent_kernel(RayArgs) // read 
     __shared__ uint32_t s_list[RAY_PL * 64]; // [k*64 + lane]: consecutive lanes on consecutive banks
     __shared__ float s_tan[3 * RAY_PL * 64];
     const uint32_t lane = threadIdx.x & 63u;
-    const ShortRay R = ray_short_begin<INDEXED>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
+    const ShortRay R = ray_short_begin<SRC>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
     const uint32_t nl = R.nl, nmax = R.nmax;
     const LaneRay &ray = R.ray;
     const TanRay tr = tangent_ray(P.ray_tangent, R.rc);
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(64) void ray_short_tangent_kernel(RayArgs) // read 
 }
 
 // One wave per long ray, lane = emitter (EC rounds of 64 at a time), the absorber wave-uniform.
-template <int EXP, int ERF, bool INDEXED>
+template <int EXP, int ERF, int SRC>
 __global__ __launch_bounds__(64) void ray_long_tangent_kernel(RayArgs)
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -181,8 +181,8 @@ __global__ __launch_bounds__(64) void ray_long_tangent_kernel(RayArgs)
     constexpr int EC = 2;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
 
-    LongRay L = ray_long_begin(&P);
-    while (ray_long_next<INDEXED>(&P, &S, s_list, lane, L)) {
+    LongRay L = ray_long_begin<SRC>(&P);
+    while (ray_long_next<SRC>(&P, &S, s_list, lane, L)) {
         const LaneRay ray = L.ray;
         const uint32_t n = L.n;
         const TanRay tr = tangent_ray(P.ray_tangent, L.r);
@@ -235,15 +235,16 @@ __global__ __launch_bounds__(64) void ray_long_tangent_kernel(RayArgs)
 }
 
 template <int EXP, int ERF>
-static void launch_ray_tangent_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
+static void launch_ray_tangent_bundle_t(const RayArgs &a, uint32_t long_grid, int src, hipStream_t st)
 {
-    if (indexed) launch_ray_kernels(ray_short_tangent_kernel<EXP, ERF, true>, ray_long_tangent_kernel<EXP, ERF, true>, a, long_grid, st);
-    else launch_ray_kernels(ray_short_tangent_kernel<EXP, ERF, false>, ray_long_tangent_kernel<EXP, ERF, false>, a, long_grid, st);
+    if (src == RAY_LIST_PLAN) launch_ray_kernels(ray_short_tangent_kernel<EXP, ERF, RAY_LIST_PLAN>, ray_long_tangent_kernel<EXP, ERF, RAY_LIST_PLAN>, a, long_grid, st);
+    else if (src == RAY_LIST_INDEX) launch_ray_kernels(ray_short_tangent_kernel<EXP, ERF, RAY_LIST_INDEX>, ray_long_tangent_kernel<EXP, ERF, RAY_LIST_INDEX>, a, long_grid, st);
+    else launch_ray_kernels(ray_short_tangent_kernel<EXP, ERF, RAY_LIST_CHUNKS>, ray_long_tangent_kernel<EXP, ERF, RAY_LIST_CHUNKS>, a, long_grid, st);
 }
-void launch_ray_tangent_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
+void launch_ray_tangent_bundle(const RayArgs &a, uint32_t long_grid, int src, int exp_kind, int erf_kind, hipStream_t st)
 {
     if (!a.nrays || !long_grid || !a.tangent_out || !ray_grad_pair_supported(exp_kind, erf_kind)) return;
-    VRT_DISPATCH_GRAD_PAIR(launch_ray_tangent_bundle_t, a, long_grid, indexed, st);
+    VRT_DISPATCH_GRAD_PAIR(launch_ray_tangent_bundle_t, a, long_grid, src, st);
 }
 
 } // namespace vrtk

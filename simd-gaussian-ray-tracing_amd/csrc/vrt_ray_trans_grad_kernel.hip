@@ -70,7 +70,7 @@ __device__ __forceinline__ void trans_grad_weight(bool depth_mode, float g, floa
 
 // RAYS: the ray rows are asked for (P.grad_rays != nullptr); without, each kernel is the text it was before there were ray rows.
 // ORDERED: one record per list position, the lane's own, opened and stored whole at the flush.  <.., false> is the kernel as it is without.
-template <int EXP, int ERF, bool INDEXED, bool RAYS, bool ORDERED = false>
+template <int EXP, int ERF, int SRC, bool RAYS, bool ORDERED = false>
 __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // re
     __shared__ uint32_t s_list[RAY_PL * 64]; // [k*64 + lane]: consecutive lanes on consecutive banks
     __shared__ float s_acc[3 * RAY_PL * 64];
     const uint32_t lane = threadIdx.x & 63u;
-    const ShortRay R = ray_short_begin<INDEXED>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
+    const ShortRay R = ray_short_begin<SRC>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
     const uint32_t nl = R.nl, nmax = R.nmax;
     const LaneRay &ray = R.ray;
     const LaneList L = { s_list, lane, nl, nmax };
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(64) void ray_short_trans_grad_kernel(RayArgs) // re
 // One wave per long ray, lane l takes entries l, l + 64, ...; the samples in chunks of NSC.
 // ORDERED: one record per entry, record p owned by the lane that takes entry p: opened with the first chunk of samples, the later chunks'
 // segments added onto the lane's own stores.
-template <int EXP, int ERF, bool INDEXED, bool RAYS, bool ORDERED = false>
+template <int EXP, int ERF, int SRC, bool RAYS, bool ORDERED = false>
 __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -163,8 +163,8 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
     const bool depth_mode = P.wrt == VRT_HIP_TGRAD_DEPTH;
     const uint64_t ns = P.ns;
 
-    LongRay L = ray_long_begin(&P);
-    while (ray_long_next<INDEXED>(&P, &S, s_list, lane, L)) {
+    LongRay L = ray_long_begin<SRC>(&P);
+    while (ray_long_next<SRC>(&P, &S, s_list, lane, L)) {
         const LaneRay ray = L.ray;
         const uint32_t n = L.n;
         const float *sp = P.s + (P.s_per_ray ? L.r * ns : 0ull);
@@ -245,29 +245,29 @@ __global__ __launch_bounds__(64) void ray_long_trans_grad_kernel(RayArgs)
 
 #ifndef VRT_GRAD_ORDERED_UNIT
 template <int EXP, int ERF>
-static void launch_ray_trans_grad_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
+static void launch_ray_trans_grad_bundle_t(const RayArgs &a, uint32_t long_grid, int src, hipStream_t st)
 {
-    grad_dispatch_indexed_rays(indexed, a.grad_rays != nullptr, [&](auto I, auto R) {
+    grad_dispatch_source_rays(src, a.grad_rays != nullptr, [&](auto I, auto R) {
         launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, I.value, R.value, false>, ray_long_trans_grad_kernel<EXP, ERF, I.value, R.value, false>, a, long_grid, st);
     });
 }
-void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
+void launch_ray_trans_grad_bundle(const RayArgs &a, uint32_t long_grid, int src, int exp_kind, int erf_kind, hipStream_t st)
 {
     if (!a.nrays || !a.ns || !long_grid || !ray_grad_pair_supported(exp_kind, erf_kind)) return;
-    VRT_DISPATCH_GRAD_PAIR(launch_ray_trans_grad_bundle_t, a, long_grid, indexed, st);
+    VRT_DISPATCH_GRAD_PAIR(launch_ray_trans_grad_bundle_t, a, long_grid, src, st);
 }
 #else // vrt_ray_trans_grad_ordered_kernel.hip: the ORDERED instantiations alone, so that the build stays parallel
 template <int EXP, int ERF>
-static void launch_ray_trans_grad_bundle_ordered_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
+static void launch_ray_trans_grad_bundle_ordered_t(const RayArgs &a, uint32_t long_grid, int src, hipStream_t st)
 {
-    grad_dispatch_indexed_rays(indexed, a.grad_rays != nullptr, [&](auto I, auto R) {
+    grad_dispatch_source_rays(src, a.grad_rays != nullptr, [&](auto I, auto R) {
         launch_ray_kernels(ray_short_trans_grad_kernel<EXP, ERF, I.value, R.value, true>, ray_long_trans_grad_kernel<EXP, ERF, I.value, R.value, true>, a, long_grid, st);
     });
 }
-void launch_ray_trans_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
+void launch_ray_trans_grad_bundle_ordered(const RayArgs &a, uint32_t long_grid, int src, int exp_kind, int erf_kind, hipStream_t st)
 {
     if (!a.nrays || !a.ns || !long_grid || !a.grad || !ray_grad_pair_supported(exp_kind, erf_kind)) return;
-    VRT_DISPATCH_GRAD_PAIR(launch_ray_trans_grad_bundle_ordered_t, a, long_grid, indexed, st);
+    VRT_DISPATCH_GRAD_PAIR(launch_ray_trans_grad_bundle_ordered_t, a, long_grid, src, st);
 }
 #endif
 

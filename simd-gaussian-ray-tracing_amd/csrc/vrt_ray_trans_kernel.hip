@@ -14,14 +14,14 @@
 
 namespace vrtk {
 
-template <int EXP, int ERF, bool INDEXED>
+template <int EXP, int ERF, int SRC>
 __global__ __launch_bounds__(64) void ray_short_trans_kernel(RayArgs) // read through kernel_args<>: vrt_kernels_common.hpp
 {
     const RayArgs &P = kernel_args<RayArgs>();
     const SceneTables &S = P.S;
     __shared__ uint32_t s_list[RAY_PL * 64]; // [k*64 + lane]: consecutive lanes on consecutive banks
     const uint32_t lane = threadIdx.x & 63u;
-    const ShortRay R = ray_short_begin<INDEXED>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
+    const ShortRay R = ray_short_begin<SRC>(&P, &S, s_list, lane); // the cull: exactly the radiance kernel's
 
     // ---- samples, RAY_SG at a time: every lane walks its own list once per group ----
     const uint64_t ns = P.ns;
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(64) void ray_short_trans_kernel(RayArgs) // read th
 }
 
 // One wave per long ray.  Claim, re-cull and list are the radiance long kernel's (vrt_ray_cull.hpp); RAY_SG sums per walk of the list.
-template <int EXP, int ERF, bool INDEXED>
+template <int EXP, int ERF, int SRC>
 __global__ __launch_bounds__(64) void ray_long_trans_kernel(RayArgs)
 {
     const RayArgs &P = kernel_args<RayArgs>();
@@ -48,8 +48,8 @@ __global__ __launch_bounds__(64) void ray_long_trans_kernel(RayArgs)
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t ns = P.ns;
 
-    LongRay L = ray_long_begin(&P);
-    while (ray_long_next<INDEXED>(&P, &S, s_list, lane, L)) {
+    LongRay L = ray_long_begin<SRC>(&P);
+    while (ray_long_next<SRC>(&P, &S, s_list, lane, L)) {
         const float *sp = P.s + (P.s_per_ray ? L.r * ns : 0ull);
         float *Tp = P.T + L.r * ns;
         for (uint64_t k0 = 0; k0 < ns; k0 += RAY_SG) {
@@ -65,15 +65,16 @@ __global__ __launch_bounds__(64) void ray_long_trans_kernel(RayArgs)
 }
 
 template <int EXP, int ERF>
-static void launch_ray_trans_bundle_t(const RayArgs &a, uint32_t long_grid, bool indexed, hipStream_t st)
+static void launch_ray_trans_bundle_t(const RayArgs &a, uint32_t long_grid, int src, hipStream_t st)
 {
-    if (indexed) launch_ray_kernels(ray_short_trans_kernel<EXP, ERF, true>, ray_long_trans_kernel<EXP, ERF, true>, a, long_grid, st);
-    else launch_ray_kernels(ray_short_trans_kernel<EXP, ERF, false>, ray_long_trans_kernel<EXP, ERF, false>, a, long_grid, st);
+    if (src == RAY_LIST_PLAN) launch_ray_kernels(ray_short_trans_kernel<EXP, ERF, RAY_LIST_PLAN>, ray_long_trans_kernel<EXP, ERF, RAY_LIST_PLAN>, a, long_grid, st);
+    else if (src == RAY_LIST_INDEX) launch_ray_kernels(ray_short_trans_kernel<EXP, ERF, RAY_LIST_INDEX>, ray_long_trans_kernel<EXP, ERF, RAY_LIST_INDEX>, a, long_grid, st);
+    else launch_ray_kernels(ray_short_trans_kernel<EXP, ERF, RAY_LIST_CHUNKS>, ray_long_trans_kernel<EXP, ERF, RAY_LIST_CHUNKS>, a, long_grid, st);
 }
-void launch_ray_trans_bundle(const RayArgs &a, uint32_t long_grid, bool indexed, int exp_kind, int erf_kind, hipStream_t st)
+void launch_ray_trans_bundle(const RayArgs &a, uint32_t long_grid, int src, int exp_kind, int erf_kind, hipStream_t st)
 {
     if (!a.nrays || !a.ns || !long_grid) return;
-    VRT_DISPATCH_EXP_ERF(launch_ray_trans_bundle_t, a, long_grid, indexed, st);
+    VRT_DISPATCH_EXP_ERF(launch_ray_trans_bundle_t, a, long_grid, src, st);
 }
 
 } // namespace vrtk

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Registers, spills, LDS and occupancy of the kernels of one translation unit (compiler remarks; no GPU needed):
-#   tools/kernel_resources.sh block|table|ray|raytrans|raydepth|raygrad|raytgrad|raytangent|rayttangent|gradord|raysort|dense|assembly|query|main [name filter]     (main: vrt_kernels.hip, the frame set-up)
+#   tools/kernel_resources.sh block|table|ray|raytrans|raydepth|raygrad|raytgrad|raytangent|rayttangent|gradord|raysort|rayplan|dense|assembly|query|main [name filter]     (main: vrt_kernels.hip, the frame set-up)
 # raygrad and raytgrad list the ORDERED instantiations (units of their own) behind the others; gradord: the count pass, the sort and the reduction around them.
 cd "$(dirname "$0")/../simd-gaussian-ray-tracing_amd/csrc" || exit 1
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-pass-failed -fno-slp-vectorize --cuda-device-only -Rpass-analysis=kernel-resource-usage"
@@ -16,6 +16,7 @@ case "$1" in
   rayttangent) SRC=vrt_ray_trans_tangent_kernel.hip; EXTRA="" ;;
   gradord) SRC=vrt_grad_ordered_kernel.hip; EXTRA="" ;;
   raysort) SRC=vrt_ray_sort_kernel.hip; EXTRA="" ;;
+  rayplan) SRC=vrt_ray_plan_kernel.hip; EXTRA="" ;;
   dense|assembly|query) SRC=vrt_$1_kernel.hip; EXTRA="" ;;
   *) SRC=vrt_kernels.hip; EXTRA="" ;;
 esac

@@ -102,6 +102,16 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
       `--ttangent-only` runs this part alone, prints its JSON line and writes ray_trans_tangent.json and ray_trans_tangent.md (and
       nothing else) to --out-dir; the .md ends with the text of <out-dir>/ray_trans_tangent_resources.txt when that file is there (the
       output of `tools/kernel_resources.sh rayttangent`).
+  (pl) Ray plans (vrt_hip_ray_plan_create_device, vrt_hip_set_ray_plan): every row a bundle call with a plan bound against the same call
+      without, in the same run -- `-g 64`, device pointers, stream events around back-to-back calls, the two paths alternating, Morton
+      index off / on, each path in a context of its own (the binding is a context's).  Rows: the T bundle with ns = 1 on 2^20 scattered
+      rays; the depth-mode transmittance tangent on 4096 aimed rays; the radiance bundle on 2^20 scattered rays; one CG iteration
+      (tangent bundle plus gradient bundle with its table) on the 4096 aimed rays with the sort off and on; the ordered gradient on
+      the same rays.  Per row: unplanned ms, planned ms, the plan's build (host clock around the create call, which waits), and
+      break-even calls = build / (unplanned - planned).  The run fails where a planned call's median exceeds its unplanned twin's by
+      more than the spread (max - min) of the unplanned call's repeats, or where a stored output differs in a bit.
+      `--plan-only` runs this part alone, prints its JSON line and writes ray_plan.json and ray_plan.md (and puts
+      ray_plan_resources.md into the latter if that file is there: build times and `tools/kernel_resources.sh` tables, taken without a GPU).
 """
 import argparse
 import json
@@ -922,6 +932,113 @@ its 24 KB of scalars for ns <= 4 (shadow rays).
     return "\n".join(lines)
 
 
+def part_plan(g, calls=3, repeats=7):
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(23)
+    cuda = lambda a: torch.from_numpy(np.ascontiguousarray(a, f32)).cuda()      # noqa: E731
+    t_v = cuda(rng.uniform(-1, 1, size=(len(g), pkg.GRAD_STRIDE)))
+    scat, aimed = scattered(g, 1 << 20), aimed_rays(g)
+    rows = {}
+    cases = (("T_2^20_ns1", scat, 1, "T", False, False), ("depth_tangent_4096", aimed, 0, "depth_tangent", False, False),
+             ("radiance_2^20", scat, 1, "radiance", False, False), ("cg_iteration_4096", aimed, 0, "cg", False, False),
+             ("cg_iteration_4096_sorted", aimed, 0, "cg", True, False), ("ordered_gradient_4096", aimed, 0, "grad", False, True))
+    for label, (o, d), per, kind, sort, ordered in cases:
+        nrays = len(d)
+        t_o, t_d = cuda(o), cuda(d)
+        rows[label] = {"rays": nrays, "kind": kind, "sort": int(sort), "ordered": int(ordered)}
+        for index, key in enumerate(("off", "on")):
+            ctx = [pkg.Renderer(0), pkg.Renderer(0)]          # [unplanned, planned]
+            for r in ctx:
+                r.set_gaussians(g)
+                r.set_ray_index(index)
+                r.set_ray_sort(int(sort))
+                r.set_grad_ordered(int(ordered))
+            zeros = lambda *shape: [torch.zeros(shape, dtype=torch.float32, device="cuda") for _ in ctx]      # noqa: E731
+            out1, out4, rows8, table = zeros(nrays, 1), zeros(nrays, 4), zeros(nrays, pkg.RAY_GRAD_STRIDE), zeros(len(g), pkg.GRAD_STRIDE)
+            t_g4, t_s = cuda(rng.uniform(-1, 1, size=(nrays, 4))), cuda(np.array([8.0], f32))
+            if kind == "depth_tangent":                        # the samples are the depths of the level, one per ray
+                tau = torch.tensor([0.99], dtype=torch.float32, device="cuda")
+                t_s = torch.zeros((nrays, 1), dtype=torch.float32, device="cuda")
+                ctx[0].depth_bundle_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), tau.data_ptr(), 1, 0, t_s.data_ptr(), st)
+            torch.cuda.synchronize()
+
+            def call(k):
+                r = ctx[k]
+                if kind == "T":
+                    r.transmittance_bundle_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_s.data_ptr(), 1, 0, out1[k].data_ptr(), st)
+                elif kind == "radiance":
+                    r.radiance_rays_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), out4[k].data_ptr(), 0, PACK, st)
+                elif kind == "depth_tangent":
+                    r.transmittance_bundle_tangent_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_s.data_ptr(), 1, 1, pkg.TGRAD_DEPTH, t_v.data_ptr(), 0, 0,
+                                                          1, out1[k].data_ptr(), st)
+                else:
+                    if kind == "cg":
+                        r.radiance_rays_tangent_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_v.data_ptr(), 0, out4[k].data_ptr(), st)
+                    r.radiance_rays_grad_rays_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_g4.data_ptr(), table[k].data_ptr(), rows8[k].data_ptr(), st)
+            build = []
+            for _ in range(4):                                 # the first one warms the buffers up
+                t0 = time.perf_counter()
+                plan = ctx[1].ray_plan_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), st)
+                build.append((time.perf_counter() - t0) * 1e3)
+                info = plan.info()
+                if len(build) < 4:
+                    plan.close()
+            ctx[1].set_ray_plan(plan)
+            t = windows([lambda: call(0), lambda: call(1)], calls, repeats, warm=2)
+            for tb in table:
+                tb.zero_()
+            call(0)
+            call(1)
+            torch.cuda.synchronize()
+            same = all(bool(torch.equal(a[0], a[1])) for a in (out1, out4, rows8)) and (not ordered or bool(torch.equal(table[0], table[1])))
+            for r in ctx:
+                r.close()
+            un, pl, b = t[0], t[1], spread(build[1:])
+            gain = un["median"] - pl["median"]
+            rows[label][key] = {"unplanned_ms": un, "planned_ms": pl, "build_ms": b, "spread_ms": round(un["max"] - un["min"], 5),
+                                "planned_over_unplanned": round(pl["median"] / un["median"], 3),
+                                "break_even_calls": round(b["median"] / gain, 1) if gain > 0 else None, "same_bits": same,
+                                "entries": info["entries"], "long_rays": info["long_rays"], "plan_bytes": info["bytes"]}
+    return {"gaussians": len(g), "rows": rows}
+
+
+def check_plan(z):
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            x = r[key]
+            assert x["same_bits"], f"{label}, index {key}: a planned output differs from the unplanned one"
+            assert x["planned_ms"]["median"] <= x["unplanned_ms"]["median"] + x["spread_ms"], \
+                f"{label}, index {key}: the planned call ({ms(x['planned_ms'])}) is slower than the unplanned one ({ms(x['unplanned_ms'])}) by more than the spread"
+
+
+def markdown_plan(z, resources=""):
+    lines = [f"""# Ray plans (tools/ray_bundles.py --plan-only)
+
+Every bundle call with a plan bound (`vrt_hip_set_ray_plan`) against the same call without, in the same run: `-g 64` (N = {z['gaussians']}),
+device pointers, stream events around back-to-back calls, the two paths alternating, each in a context of its own, Morton index off / on;
+ms per call, median (min .. max).  Build: the host's clock around `vrt_hip_ray_plan_create_device`, which waits for its stream (three
+builds behind a warm one).  Break-even = build / (unplanned - planned): the calls after which the plan has paid for itself.  The tool
+fails where a planned median exceeds the unplanned one by more than the spread (max - min) of the unplanned call's repeats, or where a
+stored output (for the ordered row the table too) differs in a bit.  One CG iteration = a tangent bundle plus a gradient bundle with its
+table (float atomics).
+
+| row | rays | index | unplanned | planned | planned / unplanned | build | break-even calls | kept entries | long rays | plan bytes |
+|---|---|---|---|---|---|---|---|---|---|---|"""]
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            x = r[key]
+            lines.append(f"| {label} | {r['rays']} | {key} | {ms(x['unplanned_ms'])} | {ms(x['planned_ms'])} | {x['planned_over_unplanned']} | {ms(x['build_ms'])} | "
+                         f"{x['break_even_calls'] if x['break_even_calls'] is not None else 'never'} | {x['entries']} | {x['long_rays']} | {x['plan_bytes']} |")
+    lines.append("""
+Not taken: a profile under rocprofv3, the host-pointer forms, any scene but `-g 64`, a CSR in slot order for sorted plans, entries of 16
+bits for scenes below 65536 Gaussians, the lists staged through LDS by the wave instead of read by each lane.
+""")
+    if resources:
+        lines.append(resources.rstrip() + "\n")
+    return "\n".join(lines)
+
+
 def part_scene(g, repeats=7, warm=2):
     import torch
     from sgrt_amd import autograd
@@ -1295,6 +1412,7 @@ def main():
     ap.add_argument("--sort-only", action="store_true")
     ap.add_argument("--tangent-only", action="store_true")
     ap.add_argument("--ttangent-only", action="store_true")
+    ap.add_argument("--plan-only", action="store_true")
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
     if a.scene_update_only:
@@ -1307,6 +1425,17 @@ def main():
         with open(os.path.join(a.out_dir, "scene_update.md"), "w") as f:
             f.write(markdown_scene(z))
         check_scene(z)
+        return
+    if a.plan_only:
+        z = part_plan(g)
+        print(json.dumps({"plan": z}))
+        os.makedirs(a.out_dir, exist_ok=True)
+        with open(os.path.join(a.out_dir, "ray_plan.json"), "w") as f:
+            f.write(json.dumps({"what": "planned against unplanned bundle calls of the same rays; see tools/ray_bundles.py (pl)", "plan": z}) + "\n")
+        res = os.path.join(a.out_dir, "ray_plan_resources.md")
+        with open(os.path.join(a.out_dir, "ray_plan.md"), "w") as f:
+            f.write(markdown_plan(z, open(res).read() if os.path.exists(res) else ""))
+        check_plan(z)
         return
     if a.tangent_only:
         z = part_tangent(g)
