@@ -534,6 +534,36 @@ void radiance_rays_tangent_device(const f32 *d_origins, bool origin_per_ray, con
     d.check(vrt_hip_radiance_rays_tangent_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_tangent, d_ray_tangent, d_out, hip_stream),
             "vrt_hip_radiance_rays_tangent_device");
 }
+// Gauss-Newton diagonal bundles: diag(J^T W J) of radiance_rays for the same rays -- per parameter the sum over rays and channels of
+// weights[r] (nullable: all 1) times the squared derivative of that channel of that ray, each ray's kept list held fixed
+// (vrt_hip_radiance_rays_gn_diag in include/vrt_hip.h; the pairs of radiance_rays_grad, any other throws).  diag_out: gaussians.size() rows
+// of VRT_HIP_GRAD_STRIDE floats in radiance_rays_grad's layout, OVERWRITTEN, [9..11] 0.  Float atomics on the device: not bitwise
+// reproducible unless vrt_hip_set_grad_ordered is on.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void radiance_rays_gn_diag(const vec4f_t *o, const vec4f_t *n, size_t nrays, const gaussians_t &gaussians, const vec4f_t *weights, f32 *diag_out)
+{
+    static_assert(sizeof(vec4f_t) == 4 * sizeof(f32), "weights are handed to the library as 4 floats per ray");
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    std::vector<f32> oo(3 * nrays), nn(3 * nrays);
+    for (size_t r = 0; r < nrays; ++r) {
+        oo[3 * r] = o[r].x; oo[3 * r + 1] = o[r].y; oo[3 * r + 2] = o[r].z;
+        nn[3 * r] = n[r].x; nn[3 * r + 1] = n[r].y; nn[3 * r + 2] = n[r].z;
+    }
+    d.check(vrt_hip_radiance_rays_gn_diag(d.ctx, nrays, oo.data(), 1, nn.data(), weights ? &weights[0].x : nullptr, diag_out), "vrt_hip_radiance_rays_gn_diag");
+}
+// The same on the device (d_weights 16-byte aligned, nullable): ADDS into d_diag (the caller clears it), enqueued on hip_stream, nothing waits.
+template <exp_kind Exp = exp_kind::vcl, erf_kind Erf = erf_kind::abramowitz_stegun>
+void radiance_rays_gn_diag_device(const f32 *d_origins, bool origin_per_ray, const f32 *d_dirs, size_t nrays, const gaussians_t &gaussians,
+                                  const f32 *d_weights, f32 *d_diag, void *hip_stream)
+{
+    auto &d = detail::device_t::get();
+    d.upload_scene(gaussians.gaussians);
+    d.options(Exp, Erf);
+    d.check(vrt_hip_radiance_rays_gn_diag_device(d.ctx, nrays, d_origins, origin_per_ray ? 1 : 0, d_dirs, d_weights, d_diag, hip_stream),
+            "vrt_hip_radiance_rays_gn_diag_device");
+}
 // Transmittance bundles: broadcast_transmittance for ANY number of rays at ns depths each in ONE call, under the same per-ray cull
 // (vrt_hip_transmittance_bundle in include/vrt_hip.h: the exponent moves by less than 0.8 * cull_eps * min(N, 4096) = 3.3e-6 at the
 // defaults).  s: ns sample distances shared by all rays (s_per_ray = false) or nrays * ns, [r * ns + k]; T_out[r * ns + k].  Shadow

@@ -24,7 +24,10 @@
  *     (set_gaussians*, set_plane, set_tiles, tile_gaussians with another tile size, a frame
  *     on another stream) first waits for the frames in flight, so no synchronisation by the
  *     caller is needed before changing state.  A stream passed to a *_device call has to
- *     stay valid until the context's next state change, vrt_hip_sync() or destroy.
+ *     stay valid until the context's next state change, vrt_hip_sync() or destroy.  The null
+ *     stream (hip_stream == NULL: torch's default stream) is a stream like any other here:
+ *     what was enqueued on it is waited for too, by the host-pointer forms as well, which
+ *     run on the context's own non-blocking stream and share its buffers with the bundles.
  *
  * All paths are relative to /root/reference/src.
  */
@@ -571,6 +574,38 @@ int vrt_hip_radiance_rays_tangent_device(vrt_hip_ctx *ctx, size_t nrays, const f
                                          float *d_out                /* 4 per ray, STORED */, void *hip_stream);
 int vrt_hip_radiance_rays_tangent(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
                                   const float *tangent, const float *ray_tangent, float *out);   /* host pointers, waits */
+/* -------- Gauss-Newton diagonal bundles: diag(J^T W J) of the radiance of ANY rays ---------------------------------------------------
+ * The third part of a Gauss-Newton or Levenberg-Marquardt fit next to J^T u (the gradient bundles) and J . v (the tangent bundles): for
+ * every parameter theta of every Gaussian (albedo rgba, mu xyz, sigma, magnitude)
+ *   D[theta] = sum_r sum_{c=0..3} w[r, c] (d L_c(r) / d theta)^2
+ * -- the Jacobi preconditioner of a CG solve on J^T W J, Marquardt's damping J^T W J + lambda diag(J^T W J), and the per-parameter
+ * sensitivity of the rays.  L, the kept list K held fixed, the cull, the analytic derivatives and the supported pairs are exactly those
+ * stated for vrt_hip_radiance_rays_grad above: the row of channel c is that bundle's row for grad_radiance = e_c, and the rows are
+ * squared PER RAY AND CHANNEL before anything is summed.  Row j of the table has the gradient table's layout:
+ *   [0..3] D of albedo rgba of j   [4..6] D of mu xyz   [7] D of sigma   [8] D of magnitude   [9..11] never touched
+ * and the albedo columns are sum_r w[r, c] (m_j V_j)^2, since d L_c / d a_jc' = delta_cc' m_j V_j.  weights: 4 floats per ray, 16-byte
+ * aligned in the device form, or NULL for all 1; they are not required to be non-negative (the sum is linear in them); under
+ * non-negative weights every entry is >= 0.
+ * The _device form ADDS into d_diag (N rows of VRT_HIP_GRAD_STRIDE floats) with float atomics: the caller clears the table, and may let
+ * several bundles add into it.  A row of a Gaussian that no ray keeps is not written at all; a Gaussian of magnitude 0, which every ray
+ * drops, gets nothing.  Not bitwise reproducible from run to run -- unless vrt_hip_set_grad_ordered is on: then every (ray, kept
+ * Gaussian) files ONE record (long rays too), the ray's own share of D, the table gets the ordered sums with the bits that contract
+ * states (segment depth ceil(n_j / 64) + 6 for n_j rays that keep j), and vrt_hip_get_grad_records returns the shares.  The host form
+ * overwrites diag_out (columns 9..11 with 0).
+ * Everything else is the gradient bundle's contract: origins, origin_per_ray, dirs, the stream rules, the buffers that only grow, the
+ * shared queue / counters / scratch slots / bitmap, the Morton index, vrt_hip_set_ray_sort and a bound ray plan (the same kept lists
+ * either way), "counts as a frame in flight"; vrt_hip_get_ray_stats / vrt_hip_get_ray_index_stats report for the same rays every field a
+ * radiance bundle reports, and the same rays go to the same kind of kernel.  One buffer more belongs to the context and only grows: a
+ * ray whose list is longer than 1024 keeps 48 bytes per further list position in a workspace of (N - 1024) * 48 bytes per workgroup of
+ * the one-wave-per-ray kernel, 256 MB in all at the most where more than one workgroup runs (fewer workgroups for larger scenes); the
+ * kernel never runs on fewer than one workgroup, whose single slot passes 256 MB from N = 5.6 M on and is reserved in full.
+ * nrays == 0 or a scene of no Gaussians returns VRT_HIP_OK with nothing launched and the table untouched; NULL origins, dirs or table
+ * with work to do, more than 2^32 - 16 rays, or an unsupported pair: VRT_HIP_ERR_INVALID with a message, nothing enqueued. */
+int vrt_hip_radiance_rays_gn_diag_device(vrt_hip_ctx *ctx, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                         const float *d_weights /* 4 per ray, or NULL = all 1 */,
+                                         float *d_diag /* N rows of VRT_HIP_GRAD_STRIDE, ADDED into */, void *hip_stream);
+int vrt_hip_radiance_rays_gn_diag(vrt_hip_ctx *ctx, size_t nrays, const float *origins, int origin_per_ray, const float *dirs,
+                                  const float *weights, float *diag_out /* N rows, OVERWRITTEN; columns 9..11 written as 0 */);
 /* -------- transmittance tangent bundles: J . v of the transmittance and of the depth of ANY rays, forward mode -----------------------
  * The other half of the transmittance gradient bundles, as the tangent bundles are of the gradient bundles: they give J^T . u in T and
  * in depth mode, this gives J . v -- how T(r, s_k), or the depth at which T falls to a level, moves when the Gaussians, the rays and

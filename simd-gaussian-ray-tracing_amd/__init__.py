@@ -151,6 +151,8 @@ SYMBOLS = {
     "vrt_hip_transmittance_bundle_grad": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, C.c_size_t, C.c_int, _f32p, C.c_int, _f32p, _f32p]),
     "vrt_hip_radiance_rays_grad_rays_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "vrt_hip_radiance_rays_grad_rays": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p]),
+    "vrt_hip_radiance_rays_gn_diag_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "vrt_hip_radiance_rays_gn_diag": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _f32p]),
     "vrt_hip_radiance_rays_tangent_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "vrt_hip_radiance_rays_tangent": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p]),
     "vrt_hip_transmittance_bundle_grad_rays_device": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int, _vp, _vp, _vp,
@@ -778,6 +780,24 @@ class Renderer:
         all three 16-byte aligned."""
         self._device("radiance_rays_tangent_device", nrays, d_origins, origin_per_ray, d_dirs, d_tangent or None, d_ray_tangent or None,
                      d_out or None, stream or None)
+
+    def radiance_rays_gn_diag(self, origins, dirs, weights=None):
+        """vrt_hip_radiance_rays_gn_diag: the diagonal of the Gauss-Newton matrix J^T W J of what radiance_rays returns for the same
+        rays (each ray's kept list is held fixed): per parameter the sum over rays and channels of weights[r, c] times the squared
+        derivative of channel c of ray r.  weights [nrays, 4] or None (all 1).  Returns float32 [N, GRAD_STRIDE] in the gradient table's
+        layout (grad_columns splits it); float atomics on the device, bitwise reproducible with set_grad_ordered on."""
+        origins, dirs, per_ray = _rays(origins, dirs)
+        w = None if weights is None else np.ascontiguousarray(weights, np.float32).reshape(-1, 4)
+        assert w is None or len(w) == len(dirs)
+        out = np.zeros((self.n, GRAD_STRIDE), np.float32)
+        self._chk(self._L.vrt_hip_radiance_rays_gn_diag(self._h, len(dirs), _fp(origins), int(per_ray), _fp(dirs), None if w is None else _fp(w),
+                                                        _fp(out)), "radiance_rays_gn_diag")
+        return out
+
+    def radiance_rays_gn_diag_device(self, nrays, d_origins, origin_per_ray, d_dirs, d_weights=0, d_diag=0, stream=0):
+        """vrt_hip_radiance_rays_gn_diag_device: device pointers, everything enqueued on `stream`; reads d_weights ([nrays, 4] float32,
+        16-byte aligned, or 0: all 1) and ADDS into d_diag ([N, GRAD_STRIDE] float32: grad_columns names its columns)."""
+        self._device("radiance_rays_gn_diag_device", nrays, d_origins, origin_per_ray, d_dirs, d_weights or None, d_diag or None, stream or None)
 
     def transmittance_bundle_grad(self, origins, dirs, s, grad_T, wrt=TGRAD_T, s_per_ray=None, want_table=True, want_grad_s=True, want_rays=False):
         """vrt_hip_transmittance_bundle_grad_rays: the derivative of a loss with respect to the Gaussians and the samples, given its

@@ -340,3 +340,24 @@ def depth_bundle(renderer, mu, albedo, sigma, magnitude, origins, dirs, tau, pla
     gets and gives no gradient); albedo gets no gradient (None).  Forward mode too: the module's docstring.  Rays, the replaced scene and
     the order of backward: as radiance_rays; so is plan."""
     return _Profile.apply(renderer, TGRAD_DEPTH, mu, albedo, sigma, magnitude, origins, dirs, tau, plan)
+
+
+def radiance_rays_gn_diag(renderer, mu, albedo, sigma, magnitude, origins, dirs, weights=None, plan=None):
+    """The diagonal of the Gauss-Newton matrix J^T W J of radiance_rays for the same arguments (Renderer.radiance_rays_gn_diag_device;
+    include/vrt_hip.h, "Gauss-Newton diagonal bundles"): per parameter the sum over rays and channels of weights[r, c] ([nrays, 4], or
+    None: all 1) times the squared derivative of channel c of ray r -- the Jacobi preconditioner of a CG solve on J and J^T, Marquardt's
+    damping.  The scene of `renderer` is REPLACED by the parameters as radiance_rays does it; a plan is bound with keep_lists=True.
+    Returns four tensors (mu, albedo, sigma, magnitude) shaped, placed and typed like the parameters, without graph."""
+    with torch.no_grad():
+        _set_scene(renderer, mu, albedo, sigma, magnitude)
+        dev, o, d, per_ray = _rays(origins, dirs)
+        n = sigma.numel()
+        table = torch.zeros((n, GRAD_STRIDE), dtype=torch.float32, device=dev)
+        w = None if weights is None else weights.detach().to(dev, torch.float32).contiguous().reshape(-1, 4)
+        assert w is None or w.shape[0] == d.shape[0]
+        if d.shape[0] and n:
+            with _planned(renderer, plan):
+                renderer.radiance_rays_gn_diag_device(d.shape[0], o.data_ptr(), per_ray, d.data_ptr(), d_weights=_ptr(w), d_diag=table.data_ptr(),
+                                                      stream=torch.cuda.current_stream(dev).cuda_stream)
+        cols = grad_columns(table)
+        return tuple(cols[k].reshape(t.shape).to(t.device, t.dtype) for k, t in zip(("mu", "albedo", "sigma", "magnitude"), (mu, albedo, sigma, magnitude)))

@@ -24,7 +24,7 @@ int fail(vrt_hip_ctx *c, int code, const std::string &msg)
 // An error from it (it may have been destroyed, which completes its work) is not this call's error.
 void wait_for_last_stream(vrt_hip_ctx *c, hipStream_t st)
 {
-    if (!c->last_stream || c->last_stream == st) return;
+    if (c->last_stream == VRT_NO_STREAM || c->last_stream == st) return;
     if (hipStreamSynchronize(c->last_stream) != hipSuccess) (void)hipGetLastError();
     c->last_stream = st;
 }
@@ -37,7 +37,7 @@ int quiesce(vrt_hip_ctx *c)
 {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     wait_for_last_stream(c, c->stream);
-    c->last_stream = nullptr;
+    c->last_stream = VRT_NO_STREAM;
     return VRT_HIP_OK;
 }
 

@@ -94,12 +94,15 @@ struct vrt_hip_ray_plan {
     }
 };
 
+// vrt_hip_ctx::last_stream when nothing is in flight on a caller's stream.  Not nullptr: that is the null stream, which callers do pass
+// (torch's default stream), which does not order with the context's non-blocking stream and has to be waited for like any other.
+#define VRT_NO_STREAM ((hipStream_t)(intptr_t)-1)
 struct vrt_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     // the caller's stream the last *_device call enqueued on (may differ from `stream`): state-changing calls wait for
     // it before they touch buffers its kernels may still be reading (quiesce)
-    hipStream_t last_stream = nullptr;
+    hipStream_t last_stream = VRT_NO_STREAM;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::string err;
     Tuning tune;
@@ -265,6 +268,7 @@ struct vrt_hip_ctx {
     // ray bundles (vrt_hip_rays.cpp): the long-ray queue, its two counters, the long kernel's scratch slots and the
     // statistics words grow only; the rays_* buffers stage the host-pointer forms and grow only, each named by what passes through it
     DevBuf<uint32_t> ray_queue, ray_counters, ray_scratch;
+    DevBuf<float> gn_work;        // the Gauss-Newton diagonal's long kernel: the running sums of list positions from RAY_LCAP on, a slot per workgroup
     DevBuf<unsigned long long> ray_stats;
     DevBuf<float> rays_in[2];     // origins (one or one per ray), directions
     DevBuf<float> rays_values_in; // a table of values, one for the bundle or one per ray: sample distances, levels

@@ -1,5 +1,5 @@
 // vrt_hip_rays.cpp -- ray bundles of libvrt_hip.so (vrt_hip_radiance_rays*, vrt_hip_transmittance_bundle*, vrt_hip_depth_bundle*,
-// vrt_hip_radiance_rays_grad*, vrt_hip_transmittance_bundle_grad*, their _rays forms, vrt_hip_radiance_rays_tangent*, vrt_hip_transmittance_bundle_tangent*): radiance of caller-given rays, transmittance at sample distances along
+// vrt_hip_radiance_rays_grad*, vrt_hip_transmittance_bundle_grad*, their _rays forms, vrt_hip_radiance_rays_gn_diag*, vrt_hip_radiance_rays_tangent*, vrt_hip_transmittance_bundle_tangent*): radiance of caller-given rays, transmittance at sample distances along
 // them, the distance at which their transmittance falls to given levels, or the derivative of their radiance, transmittance or depth with
 // respect to the Gaussians, or how their radiance, transmittance or depth moves along a direction (forward mode), culled per ray (vrt_ray_kernel.hip,
 // vrt_ray_trans_kernel.hip, vrt_ray_depth_kernel.hip, vrt_ray_grad_kernel.hip, vrt_ray_trans_grad_kernel.hip, vrt_ray_tangent_kernel.hip, vrt_ray_trans_tangent_kernel.hip).  The scene tables and the
@@ -254,6 +254,9 @@ const BundleKind GRADIENT = { "radiance_rays_grad", "NULL grad_radiance or gradi
                               launch_ray_grad_bundle_ordered, true, 0 };
 const BundleKind TRANS_GRADIENT = { "transmittance_bundle_grad", "NULL samples or grad_T, or neither a gradient table nor grad_s", "ns", true, true,
                                     launch_ray_trans_grad_bundle, launch_ray_trans_grad_bundle_ordered, false, 4 };
+// the diagonal of J^T W J: a derivative; ordered, one record per (ray, kept Gaussian) in either kernel
+const BundleKind GN_DIAG = { "radiance_rays_gn_diag", "NULL diagonal table", "", true, false, launch_ray_gn_diag_bundle, launch_ray_gn_diag_bundle_ordered,
+                             false, 0 };
 // forward mode: a derivative (the scene of no Gaussians, the pairs), but no table: nothing for the ordered switch to order
 const BundleKind TANGENT = { "radiance_rays_tangent", "NULL output, or neither a tangent table nor ray tangents", "", true, false, launch_ray_tangent_bundle };
 const BundleKind TRANS_TANGENT = { "transmittance_bundle_tangent", "NULL samples or output, or none of a tangent table, ray tangents and sample tangents", "ns",
@@ -353,12 +356,14 @@ int ordered_bundle(vrt_hip_ctx *c, const BundleKind &k, Bundle &b, hipStream_t s
     return VRT_HIP_OK;
 }
 
-// The device form of every kind: the check, what every bundle enqueues, the kind's own fields of RayArgs (fill), its two kernels
-template <class Fill>
-int device_bundle(vrt_hip_ctx *c, const BundleKind &k, const Rays &r, size_t n, bool io_ok, int wrt, void *hip_stream, Fill &&fill)
+// The device form of every kind: the check, what the kind reserves of its own behind it (reserve: an error ends the call), what every
+// bundle enqueues, the kind's own fields of RayArgs (fill), its two kernels
+template <class Fill, class Reserve>
+int device_bundle(vrt_hip_ctx *c, const BundleKind &k, const Rays &r, size_t n, bool io_ok, int wrt, void *hip_stream, Fill &&fill, Reserve &&reserve)
 {
     int rc;
     if (bundle_over(c, k, r, n, io_ok, wrt, rc)) return rc;
+    if ((rc = reserve()) != VRT_HIP_OK) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     Bundle b;
     rc = enqueue_bundle(c, r.nrays, r.origins, r.origin_per_ray, r.dirs, st, b);
@@ -368,6 +373,12 @@ int device_bundle(vrt_hip_ctx *c, const BundleKind &k, const Rays &r, size_t n, 
     k.launch(b.a, b.grid, b.src, c->exp_kind, c->erf_kind, st);
     HIPCHK(c, hipGetLastError());
     return VRT_HIP_OK;
+}
+
+template <class Fill>
+int device_bundle(vrt_hip_ctx *c, const BundleKind &k, const Rays &r, size_t n, bool io_ok, int wrt, void *hip_stream, Fill &&fill)
+{
+    return device_bundle(c, k, r, n, io_ok, wrt, hip_stream, fill, [] { return (int)VRT_HIP_OK; });
 }
 
 // A staging buffer of any element type, as the host path sees it: the path moves bytes
@@ -502,6 +513,48 @@ int vrt_hip_radiance_rays_grad(vrt_hip_ctx *c, size_t nrays, const float *origin
                                const float *grad_radiance, float *grad_out)
 {
     return vrt_hip_radiance_rays_grad_rays(c, nrays, origins, origin_per_ray, dirs, grad_radiance, grad_out, nullptr);
+}
+
+// The workspace of the diagonal's long kernel: a list position from RAY_LCAP on keeps its GN_SUMS running sums in device memory, in the
+// slot of its workgroup -- GN_SUMS * 4 bytes per Gaussian beyond RAY_LCAP.  The slots stay within 256 MB, which caps the long kernel's
+// grid -- never below one workgroup, whose single slot is reserved in full even where it alone passes 256 MB (N above 5.6 M); a
+// scene of at most RAY_LCAP Gaussians has no workspace.  Grows only, like the scratch slots.
+static int gn_diag_workspace(vrt_hip_ctx *c, uint64_t &slot, uint32_t &grid)
+{
+    grid = long_grid(c);
+    slot = c->n > (uint32_t)RAY_LCAP ? (uint64_t)(c->n - (uint32_t)RAY_LCAP) * GN_SUMS : 0;
+    if (!slot) return VRT_HIP_OK;
+    const uint64_t by_memory = ((uint64_t)256 << 20) / (slot * sizeof(float));
+    grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, by_memory));
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->gn_work.reserve((size_t)slot * grid)); // (a buffer that grows is freed first, which waits for the device)
+    return VRT_HIP_OK;
+}
+
+// weights in (or none); the diagonal ADDED into the caller's table
+int vrt_hip_radiance_rays_gn_diag_device(vrt_hip_ctx *c, size_t nrays, const float *d_origins, int origin_per_ray, const float *d_dirs,
+                                         const float *d_weights, float *d_diag, void *hip_stream)
+{
+    uint64_t slot = 0;
+    uint32_t grid = 0;
+    return device_bundle(c, GN_DIAG, { nrays, d_origins, origin_per_ray, d_dirs }, 1, d_diag != nullptr, 0, hip_stream, [&](RayArgs &a) {
+        a.gn_weights = (const float4 *)d_weights; a.grad = d_diag;
+        a.gn_work = c->gn_work.p; a.gn_work_slot = slot; a.gn_grid = grid;
+    }, [&] { return gn_diag_workspace(c, slot, grid); });
+}
+
+// a cleared table of the scene's size out
+int vrt_hip_radiance_rays_gn_diag(vrt_hip_ctx *c, size_t nrays, const float *origins, int origin_per_ray, const float *dirs, const float *weights,
+                                  float *diag_out)
+{
+    const Rays r = { nrays, origins, origin_per_ray, dirs };
+    int rc;
+    if (bundle_over(c, GN_DIAG, r, 1, diag_out != nullptr, 0, rc)) return rc;
+    return host_bundle(c, r, { { c->rays_each_in, weights, nrays * 4 } }, { { c->rays_table_out, diag_out, (size_t)c->n * VRT_HIP_GRAD_STRIDE, true } },
+                       [&](const Rays &d) {
+                           return vrt_hip_radiance_rays_gn_diag_device(c, d.nrays, d.origins, d.origin_per_ray, d.dirs, wanted(weights, c->rays_each_in),
+                                                                       c->rays_table_out.p, c->stream);
+                       });
 }
 
 // forward mode: the direction in, J . v of the radiance out

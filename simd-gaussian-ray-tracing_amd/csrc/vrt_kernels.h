@@ -381,8 +381,16 @@ struct RayArgs {
     uint32_t pl_nlong;
     uint32_t *pl_fill;                  // the fill pair alone: the lists it writes, at pl_off / pl_len of the count pass
     unsigned long long *pl_words;       // the fill pair alone: [RAY_PLAN_WORDS]
+    // Gauss-Newton diagonal bundles (vrt_ray_gn_diag_kernel.hip; behind everything the other kernels read).  They reuse grad (the table D
+    // is added into; never nullptr here) and the ord_* fields.
+    const float4 *gn_weights;           // nullable, [r] the four channel weights of ray r; nullptr: all 1
+    float *gn_work;                     // the long kernel's workspace: gn_work_slot floats per workgroup, the running sums of the list
+                                        // positions from RAY_LCAP on, [(p - RAY_LCAP) * GN_SUMS + c]; nullptr where S.n <= RAY_LCAP
+    uint64_t gn_work_slot;
+    uint32_t gn_grid;                   // workgroups of the long kernel: the bundle's long grid, capped by the workspace
 };
 constexpr int GRAD_ORD_COLS = 9;    // floats per record
+constexpr int GN_SUMS = 12;         // the diagonal's running sums per (ray, list position): channel c has 3 c + 0 M (d magnitude), + 1 the coefficient of n, + 2 the sigma sum
 // the words of an ordered call, cleared on the stream ahead of its count pass: rays whose re-cull missed the counted length; records
 // reduced, Gaussians with records and the longest segment (by the reduction); rows placed, sentinel rows included (by the scan)
 enum { GRAD_ORD_MISMATCH = 0, GRAD_ORD_RECORDS = 1, GRAD_ORD_TOUCHED = 2, GRAD_ORD_LONGEST = 3, GRAD_ORD_TOTAL = 4, GRAD_ORD_WORDS = 5 };
@@ -411,6 +419,12 @@ void launch_ray_tangent_bundle(const RayArgs &a, uint32_t long_grid, int src /* 
 // the direction (a.tangent, a.ray_tangent, a.s_tangent, each nullable), stored to a.trans_tangent_out (vrt_ray_trans_tangent_kernel.hip).
 // The pairs of ray_grad_pair_supported; any other enqueues nothing.
 void launch_ray_trans_tangent_bundle(const RayArgs &a, uint32_t long_grid, int src /* RayListSource */, int exp_kind, int erf_kind, hipStream_t st);
+// the same cull, then the diagonal of the Gauss-Newton matrix: sum over rays and channels of a.gn_weights times the squared derivative of
+// the radiance, added into a.grad (vrt_ray_gn_diag_kernel.hip); _ordered: stored as one record per (ray, kept Gaussian), long rays too
+// (vrt_ray_gn_diag_ordered_kernel.hip).  The pairs of ray_grad_pair_supported; any other enqueues nothing.  The long kernel runs on
+// min(long_grid, a.gn_grid) workgroups.
+void launch_ray_gn_diag_bundle(const RayArgs &a, uint32_t long_grid, int src /* RayListSource */, int exp_kind, int erf_kind, hipStream_t st);
+void launch_ray_gn_diag_bundle_ordered(const RayArgs &a, uint32_t long_grid, int src /* RayListSource */, int exp_kind, int erf_kind, hipStream_t st);
 // Ordered gradient tables (vrt_hip_set_grad_ordered; vrt_grad_ordered_kernel.hip has the pipeline).  The same two bundles with every
 // add into a.grad replaced by a store into the records at a.ord_base[r] (the ORDERED instantiations, in translation units of their own:
 // vrt_ray_grad_ordered_kernel.hip, vrt_ray_trans_grad_ordered_kernel.hip); a.grad is not touched.

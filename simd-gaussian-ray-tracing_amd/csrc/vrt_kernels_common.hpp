@@ -6,6 +6,7 @@
 //   vrt_ray_depth_kernel.hip  depth bundles: the distance at which T falls to a level
 //   vrt_ray_grad_kernel.hip   gradient bundles: d(radiance) / d(Gaussians) along such rays
 //   vrt_ray_trans_grad_kernel.hip  transmittance gradient bundles: d(T) / d(Gaussians, samples) and d(depth) / d(Gaussians, levels)
+//   vrt_ray_gn_diag_kernel.hip  Gauss-Newton diagonal bundles: diag(J^T W J) of the radiance along such rays (over vrt_ray_cull.hpp and vrt_ray_grad.hpp too)
 //   vrt_ray_tangent_kernel.hip  tangent bundles: J . v of the radiance along such rays, forward mode
 //   vrt_ray_trans_tangent_kernel.hip  transmittance tangent bundles: J . v of T and of the depth, forward mode (all seven over vrt_ray_cull.hpp)
 //   vrt_kernels.hip        the frame's set-up: scene tables, tile cones, list kernels

@@ -1,5 +1,6 @@
 // vrt_ray_grad.hpp -- what the derivative kernels of the ray bundles share: vrt_ray_grad_kernel.hip (d radiance / d Gaussians) and
-// vrt_ray_trans_grad_kernel.hip (d transmittance / d Gaussians and samples, d depth / d Gaussians and levels) -- and, of grad_gauss, the
+// vrt_ray_trans_grad_kernel.hip (d transmittance / d Gaussians and samples, d depth / d Gaussians and levels), vrt_ray_gn_diag_kernel.hip
+// (the diagonal of J^T W J of the radiance) -- and, of grad_gauss, the
 // list walk and grad_acc's layout, vrt_ray_tangent_kernel.hip and vrt_ray_trans_tangent_kernel.hip (forward mode: J . v of the radiance, and
 // of the transmittance and the depth).  One text each, for these
 // translation units and for the short and the long kernel of each:
@@ -12,7 +13,9 @@
 //   grad_ray_add, _w, grad_ray_store   the same segment's share of the RAY's row (d origin, d direction), and the row's two stores
 //   LaneList, grad_acc, grad_walk_begin / _next, grad_flush_short   lane = ray: a lane's list, the three running sums per list position and lane in LDS, the walk of a
 //                     lane's list with the next entry's rows loaded one iteration ahead, and every position to the sink once
-//   grad_emitter_place, grad_pass1, grad_pass2    the radiance gradient's emitter set-up and the bodies of its two pair loops
+//   grad_emitter_place, grad_emitter, grad_pass1, grad_pass2    the radiance gradient's emitter set-up, an emitter's weights and the bodies of its two pair loops
+//   grad_spread, gn_pass2, gn_rows_squared   the Gauss-Newton diagonal (vrt_ray_gn_diag_kernel.hip): grad_deal's sums spread over the four channels by the
+//                     emitter's albedo, pass 2 for the four rows at once, and a complete position's rows squared, weighted and summed
 //   trans_grad_x, trans_grad_live   the transmittance derivatives' x_kj and which samples count (depth mode: finite depths > 0)
 //   TanRay, tangent_ray, TanGauss, tangent_gauss, tangent_row_load / _uload   forward mode: a direction's ray row and tangent row to three
 //                     scalars per (ray, kept Gaussian)
@@ -351,6 +354,34 @@ __device__ __forceinline__ void grad_emitter_place(bool on, float4 ms, const Lan
     sigma = on ? ms.w : 1.f;
 }
 
+// What an emitter contributes once the exponents of its five samples are known: t_k = sigma exp(acc_k - d2 / (2 sigma^2) - k^2 / 2)
+// (the ik term of L without m_i), V = sum_k t_k, w_k = G m t_k.
+template <int EXP>
+__device__ __forceinline__ float grad_emitter(bool on, float sigma, float d2, float inv2s2, float Gm, const float (&acc)[5], float (&w)[5])
+{
+    float V = 0.f;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const float kf = (float)(k - 4);
+        const float t = sigma * vexp<EXP>(acc[k] - d2 * inv2s2 - 0.5f * kf * kf);
+        V += t;
+        w[k] = on ? Gm * t : 0.f;
+    }
+    return on ? V : 0.f; // a lane without this emitter: exact zeros, whatever its exponents came to
+}
+
+// One emitter's scalar sums p, q, r (what grad_deal makes of w = m t, the weights without their albedo) spread over the four channels by
+// the emitter's albedo: the sums of channel c are a_c times the scalar ones (the Gauss-Newton diagonal, vrt_ray_gn_diag_kernel.hip)
+__device__ __forceinline__ void grad_spread(const float (&alb)[4], float p, float q, float r, float (&Pc)[4], float (&Qc)[4], float (&Rc)[4])
+{
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        Pc[c] = __builtin_fmaf(alb[c], p, Pc[c]);
+        Qc[c] = __builtin_fmaf(alb[c], q, Qc[c]);
+        Rc[c] = __builtin_fmaf(alb[c], r, Rc[c]);
+    }
+}
+
 // pass 1: q's term of the exponents of T at the emitters' 5 EC sample points (the radiance kernel's pair loop)
 template <int ERF, int EC>
 __device__ __forceinline__ void grad_pass1(const ErfEval<ERF> &erf, const GradGauss &q, const float (&e_mubar)[EC], const float (&e_sigma)[EC], float (&acc)[EC][5])
@@ -383,6 +414,47 @@ __device__ __forceinline__ void grad_pass2(const ErfEval<ERF> &erf, const GradGa
             z[e] += t;
             y[e] = __builtin_fmaf(kf, t, y[e]);
         }
+    }
+}
+
+// ---- the Gauss-Newton diagonal (vrt_ray_gn_diag_kernel.hip): the four Jacobian rows of a (ray, kept Gaussian), squared per ray ----
+// (GN_SUMS of vrt_kernels.h: the running sums per (ray, list position))
+
+// pass 2 for all four channels at once: w = m t (no albedo, no g); per emitter the scalar sums of grad_deal are formed once and spread by
+// its albedo (grad_spread), z and y stay scalar (the channel's are a_c z, a_c y).  D, e2, the Erf and both Exps are paid once.
+template <int EXP, int ERF, int EC>
+__device__ __forceinline__ void gn_pass2(const ErfEval<ERF> &erf, const GradGauss &q, const float (&e_mubar)[EC], const float (&e_sigma)[EC], const float (&w)[EC][5],
+                                         const float (&alb)[EC][4], float (&z)[EC], float (&y)[EC], float (&Pc)[4], float (&Qc)[4], float (&Rc)[4])
+{
+#pragma unroll
+    for (int e = 0; e < EC; ++e) {
+        const float base = __builtin_fmaf(e_mubar[e], q.r, -q.m);
+        const float step = e_sigma[e] * q.r;
+        float p = 0.f, qq = 0.f, r = 0.f;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const float kf = (float)(k - 4);
+            const float t = q.Ar * grad_deal<EXP>(erf, w[e][k], __builtin_fmaf(kf, step, base), q.E, p, qq, r);
+            z[e] += t;
+            y[e] = __builtin_fmaf(kf, t, y[e]);
+        }
+        grad_spread(alb[e], p, qq, r, Pc, Qc, Rc);
+    }
+}
+
+// A complete position: grad_row_w per channel as it stands, each row squared and weighted, d[i] = sum_c wt_c row_c[i]^2 (columns 4..8)
+template <int EXP>
+__device__ __forceinline__ void gn_rows_squared(const GradGauss &q, const LaneRay &ray, float mag, const float (&sums)[GN_SUMS], const float (&W)[4], const float (&wt)[4],
+                                                float (&d)[5])
+{
+#pragma unroll
+    for (int i = 0; i < 5; ++i) d[i] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float row[5];
+        grad_row_w<EXP>(q, ray, mag, sums[3 * c], sums[3 * c + 1], sums[3 * c + 2], W[c], row);
+#pragma unroll
+        for (int i = 0; i < 5; ++i) d[i] = __builtin_fmaf(wt[c] * row[i], row[i], d[i]);
     }
 }
 
@@ -448,20 +520,22 @@ __device__ __forceinline__ void tangent_row_uload(const float *table, uint32_t i
     dm = uload((const float4 *)table, 3u * idx + 2u).x;
 }
 
-// ---- the launch: a bundle's run-time list source (RayListSource) and RAYS as the constants I.value, R.value of a generic callable f(I, R) ----
+// ---- the launch: a bundle's run-time list source (RayListSource) as the constant I.value of a generic callable f(I), and with RAYS as
+// the constants I.value, R.value of f(I, R) ----
+template <class F>
+inline void grad_dispatch_source(int src, F &&f)
+{
+    if (src == RAY_LIST_PLAN) f(std::integral_constant<int, RAY_LIST_PLAN>());
+    else if (src == RAY_LIST_INDEX) f(std::integral_constant<int, RAY_LIST_INDEX>());
+    else f(std::integral_constant<int, RAY_LIST_CHUNKS>());
+}
 template <class F>
 inline void grad_dispatch_source_rays(int src, bool rays, F &&f)
 {
-    using Chunks = std::integral_constant<int, RAY_LIST_CHUNKS>;
-    using Index = std::integral_constant<int, RAY_LIST_INDEX>;
-    using Plan = std::integral_constant<int, RAY_LIST_PLAN>;
-    if (rays) {
-        if (src == RAY_LIST_PLAN) f(Plan(), std::true_type());
-        else if (src == RAY_LIST_INDEX) f(Index(), std::true_type());
-        else f(Chunks(), std::true_type());
-    } else if (src == RAY_LIST_PLAN) f(Plan(), std::false_type());
-    else if (src == RAY_LIST_INDEX) f(Index(), std::false_type());
-    else f(Chunks(), std::false_type());
+    grad_dispatch_source(src, [&](auto I) {
+        if (rays) f(I, std::true_type());
+        else f(I, std::false_type());
+    });
 }
 
 } // namespace vrtk

@@ -37,28 +37,12 @@
 // over the wave in its fixed order (long), no atomic add, bitwise reproducible.  With RAYS the table may be missing (P.grad == nullptr): no
 // table add is issued.  RAYS is a template parameter: <.., false> is the kernel from before there were ray rows, register for register.
 // Compiled with the default scheduler: nobody has measured -amdgpu-sched-strategy=max-ilp on these loops.
-// What lives where: this file has the emitter's weights (grad_emitter), the chunk of the short kernel, the two kernels' own loops -- how
+// What lives where: this file has the chunk of the short kernel, the two kernels' own loops -- how
 // the absorber is loaded (per lane; readfirstlane + uload) and where a sum goes (LDS; the sink) -- and the launch.  Every formula named
 // above is vrt_ray_grad.hpp's, shared with vrt_ray_trans_grad_kernel.hip.
 #include "vrt_ray_grad.hpp"
 
 namespace vrtk {
-
-// What an emitter contributes once the exponents of its five samples are known: t_k = sigma exp(acc_k - d2 / (2 sigma^2) - k^2 / 2)
-// (the ik term of L without m_i), V = sum_k t_k, w_k = G m t_k.
-template <int EXP>
-__device__ __forceinline__ float grad_emitter(bool on, float sigma, float d2, float inv2s2, float Gm, const float (&acc)[5], float (&w)[5])
-{
-    float V = 0.f;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const float kf = (float)(k - 4);
-        const float t = sigma * vexp<EXP>(acc[k] - d2 * inv2s2 - 0.5f * kf * kf);
-        V += t;
-        w[k] = on ? Gm * t : 0.f;
-    }
-    return on ? V : 0.f; // a lane without this emitter: exact zeros, whatever its exponents came to
-}
 
 // One chunk of EC emitters (list positions i0 .. i0+EC-1 of every lane) against the lane's whole list, both passes.  The albedo
 // columns of position p leave here, for record p of the lane's ray: its first write to them (the flush opens the record).

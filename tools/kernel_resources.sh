@@ -1,7 +1,7 @@
 #!/bin/bash
 # Registers, spills, LDS and occupancy of the kernels of one translation unit (compiler remarks; no GPU needed):
-#   tools/kernel_resources.sh block|table|ray|raytrans|raydepth|raygrad|raytgrad|raytangent|rayttangent|gradord|raysort|rayplan|dense|assembly|query|main [name filter]     (main: vrt_kernels.hip, the frame set-up)
-# raygrad and raytgrad list the ORDERED instantiations (units of their own) behind the others; gradord: the count pass, the sort and the reduction around them.
+#   tools/kernel_resources.sh block|table|ray|raytrans|raydepth|raygrad|raytgrad|raygndiag|raytangent|rayttangent|gradord|raysort|rayplan|dense|assembly|query|main [name filter]     (main: vrt_kernels.hip, the frame set-up)
+# raygrad, raytgrad and raygndiag list the ORDERED instantiations (units of their own) behind the others; gradord: the count pass, the sort and the reduction around them.
 cd "$(dirname "$0")/../simd-gaussian-ray-tracing_amd/csrc" || exit 1
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-pass-failed -fno-slp-vectorize --cuda-device-only -Rpass-analysis=kernel-resource-usage"
 case "$1" in
@@ -12,6 +12,7 @@ case "$1" in
   raydepth) SRC=vrt_ray_depth_kernel.hip; EXTRA="" ;;
   raygrad) SRC="vrt_ray_grad_kernel.hip vrt_ray_grad_ordered_kernel.hip"; EXTRA="" ;;
   raytgrad) SRC="vrt_ray_trans_grad_kernel.hip vrt_ray_trans_grad_ordered_kernel.hip"; EXTRA="" ;;
+  raygndiag) SRC="vrt_ray_gn_diag_kernel.hip vrt_ray_gn_diag_ordered_kernel.hip"; EXTRA="" ;;
   raytangent) SRC=vrt_ray_tangent_kernel.hip; EXTRA="" ;;
   rayttangent) SRC=vrt_ray_trans_tangent_kernel.hip; EXTRA="" ;;
   gradord) SRC=vrt_grad_ordered_kernel.hip; EXTRA="" ;;

@@ -110,6 +110,12 @@ and the camera path of vrt_hip_frame_device.  Needs the GPU.
       the same rays.  Per row: unplanned ms, planned ms, the plan's build (host clock around the create call, which waits), and
       break-even calls = build / (unplanned - planned).  The run fails where a planned call's median exceeds its unplanned twin's by
       more than the spread (max - min) of the unplanned call's repeats, or where a stored output differs in a bit.
+      `--diag-only` runs (gn) alone -- the Gauss-Newton diagonal bundle against the gradient bundle and against the four ordered gradient
+      calls, record read-backs and host-side squares it replaces, unplanned and planned -- prints its JSON line and writes ray_gn_diag.json
+      and ray_gn_diag.md (and nothing else) to --out-dir; it fails where the diagonal call is slower than what it replaces by more than that
+      run's spread.  It also records, without any condition, how many CG iterations one damped Gauss-Newton step on `-g 16` takes to a fixed
+      relative residual without a preconditioner and with D as the Jacobi preconditioner (part_cg; `--diag-cg-only` runs that alone and
+      writes nothing).
       `--plan-only` runs this part alone, prints its JSON line and writes ray_plan.json and ray_plan.md (and puts
       ray_plan_resources.md into the latter if that file is there: build times and `tools/kernel_resources.sh` tables, taken without a GPU).
 """
@@ -1039,6 +1045,193 @@ bits for scenes below 65536 Gaussians, the lists staged through LDS by the wave 
     return "\n".join(lines)
 
 
+def part_diag(g, calls=3, repeats=5, repeats_b=2):
+    """(gn) the Gauss-Newton diagonal bundle against (a) the gradient bundle with table of the same rays and (b) what it replaces: four
+    ordered gradient calls with g = e_c, the record read-back and the host-side squaring -- unplanned and with a bound plan"""
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    cuda = lambda a: torch.from_numpy(np.ascontiguousarray(a, f32)).cuda()      # noqa: E731
+    rows = {}
+    for label, (o, d), per in (("scattered_2^20", scattered(g, 1 << 20), 1), ("aimed_4096", aimed_rays(g), 0)):
+        nrays = len(d)
+        t_o, t_d = cuda(o), cuda(d)
+        t_g = cuda(np.random.default_rng(3).uniform(-1, 1, size=(nrays, 4)))
+        t_w = cuda(np.random.default_rng(4).uniform(0.25, 4.0, size=(nrays, 4)))
+        t_e = [cuda(np.tile(np.eye(4, dtype=f32)[c], (nrays, 1))) for c in range(4)]
+        rows[label] = {"rays": nrays}
+        for index, key in enumerate(("off", "on")):
+            ctx = {}
+            for name in ("diag", "grad", "diag_planned", "grad_planned", "records", "records_planned"):
+                r = pkg.Renderer(0)
+                r.set_gaussians(g)
+                r.set_ray_index(index)
+                r.set_grad_ordered(int(name.startswith("records")))
+                ctx[name] = r
+            table = {k: torch.zeros((len(g), pkg.GRAD_STRIDE), dtype=torch.float32, device="cuda") for k in ctx}
+            plans = {k: ctx[k].ray_plan_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), st) for k in ctx if k.endswith("planned")}
+            for k, plan in plans.items():
+                ctx[k].set_ray_plan(plan)
+            torch.cuda.synchronize()
+
+            def diag(k):
+                ctx[k].radiance_rays_gn_diag_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_w.data_ptr(), table[k].data_ptr(), st)
+
+            def grad(k):
+                ctx[k].radiance_rays_grad_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_g.data_ptr(), table[k].data_ptr(), st)
+
+            def replaced(k):
+                """what the diagonal call replaces, to the finished [N, 9] on the host (unit weights)"""
+                out = np.zeros((len(g), 9))
+                for c in range(4):
+                    ctx[k].radiance_rays_grad_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), t_e[c].data_ptr(), table[k].data_ptr(), st)
+                    gauss, ray, rec = ctx[k].grad_records()
+                    pair = ray.astype(np.int64) * len(g) + gauss             # a long ray files two records per kept Gaussian: summed before the square
+                    order = np.argsort(pair, kind="stable")
+                    first = np.concatenate([[True], np.diff(pair[order]) != 0])
+                    sums = np.add.reduceat(rec[order].astype(np.float64), np.nonzero(first)[0], axis=0)
+                    np.add.at(out, gauss[order][first], sums * sums)
+                return out
+            print(f"(gn) {label}, index {key}: the diagonal and the gradient calls", file=sys.stderr, flush=True)
+            t = windows([lambda: diag("diag"), lambda: grad("grad"), lambda: diag("diag_planned"), lambda: grad("grad_planned")], calls, repeats, warm=2)
+            tb = {"records": [], "records_planned": []}
+            for rep in range(repeats_b + 1):                                  # the first one warms the buffers up
+                for k in tb:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    want = replaced(k)
+                    tb[k].append((time.perf_counter() - t0) * 1e3)
+                    print(f"(gn) {label}, index {key}: {k} {tb[k][-1]:.0f} ms", file=sys.stderr, flush=True)
+            table["diag"].zero_()
+            ones = torch.ones_like(t_w)
+            ctx["diag"].radiance_rays_gn_diag_device(nrays, t_o.data_ptr(), per, t_d.data_ptr(), ones.data_ptr(), table["diag"].data_ptr(), st)
+            torch.cuda.synchronize()
+            got = table["diag"].cpu().numpy()[:, :9].astype(np.float64)
+            scale = np.maximum(np.abs(want).max(0, keepdims=True), 1e-300)
+            for plan in plans.values():
+                plan.close()
+            for r in ctx.values():
+                r.close()
+            b, bp = spread(tb["records"][1:]), spread(tb["records_planned"][1:])
+            rows[label][key] = {"diag_ms": t[0], "grad_ms": t[1], "diag_planned_ms": t[2], "grad_planned_ms": t[3], "replaced_ms": b, "replaced_planned_ms": bp,
+                                "diag_over_grad": round(t[0]["median"] / t[1]["median"], 2), "diag_over_grad_planned": round(t[2]["median"] / t[3]["median"], 2),
+                                "replaced_over_diag": round(b["median"] / t[0]["median"], 1), "replaced_over_diag_planned": round(bp["median"] / t[2]["median"], 1),
+                                "replaced_spread_ms": round(b["max"] - b["min"], 5), "replaced_planned_spread_ms": round(bp["max"] - bp["min"], 5),
+                                "max_abs_diag_minus_replaced_over_column_max": float((np.abs(got - want) / scale).max()), "finite": bool(np.isfinite(got).all())}
+    return {"gaussians": len(g), "rows": rows}
+
+
+def part_cg(grid=16, lam=1e-2, tol=1e-4, cap=400):
+    """(gn) one damped Gauss-Newton step on `-g <grid>`: (J^T J + lam D) x = -J^T res by conjugate gradients, every product a planned tangent
+    bundle plus a planned gradient bundle (host/ray_plan_example.cpp's round), D = diag(J^T J) by the diagonal bundle; iterations to
+    |residual| <= tol |right-hand side| without a preconditioner and with D as the Jacobi preconditioner.  res = the radiance of the
+    scene minus that of the same scene disturbed (seeded: centres by 0.1 sigma, albedo, sigma and magnitude by 5 %)."""
+    g = scene.grid_scene(grid)
+    o, d = aimed_rays(g)
+    rng = np.random.default_rng(31)
+    g2 = g.copy()
+    g2["mu"][:, :3] += (0.1 * g["sigma"][:, None] * rng.normal(size=(len(g), 3))).astype(f32)
+    for k in ("albedo", "sigma", "magnitude"):
+        g2[k] = (g[k] * (1.0 + 0.05 * rng.normal(size=g[k].shape))).astype(f32)
+    r = pkg.Renderer(0)
+    r.set_gaussians(g2)
+    target = r.radiance_rays(o, d).astype(np.float64)
+    r.set_gaussians(g)
+    res = r.radiance_rays(o, d).astype(np.float64) - target
+    plan = r.ray_plan(o, d)
+    r.set_ray_plan(plan)
+
+    def table(cols):
+        return np.concatenate([cols["albedo"], cols["mu"], cols["sigma"][:, None], cols["magnitude"][:, None]], 1).astype(np.float64)
+
+    def packed(x):
+        t = np.zeros((len(g), pkg.GRAD_STRIDE), f32)
+        t[:, :9] = x
+        return t
+    D = r.radiance_rays_gn_diag(o, d)[:, :9].astype(np.float64)
+    on = D > 0                                                     # a parameter no ray moves has no equation
+    b = -table(r.radiance_rays_grad(o, d, res.astype(f32))) * on
+
+    def A(x):
+        Jx = r.radiance_rays_tangent(o, d, tangent=packed(x * on))
+        return (table(r.radiance_rays_grad(o, d, Jx)) + lam * D * x) * on
+
+    def cg(M):
+        x, rr = np.zeros_like(b), b.copy()
+        z = rr / M if M is not None else rr
+        p, rz, b2 = z.copy(), float((rr * z).sum()), float((b * b).sum()) ** 0.5
+        for it in range(1, cap + 1):
+            Ap = A(p)
+            alpha = rz / float((p * Ap).sum())
+            x += alpha * p
+            rr -= alpha * Ap
+            rel = float((rr * rr).sum()) ** 0.5 / b2
+            if rel <= tol:
+                return {"iterations": it, "reached": True, "relative_residual": rel}
+            z = rr / M if M is not None else rr
+            rz_new = float((rr * z).sum())
+            p = z + (rz_new / rz) * p
+            rz = rz_new
+        return {"iterations": cap, "reached": False, "relative_residual": rel}
+    M = np.where(on, (1.0 + lam) * D, 1.0)
+    out = {"grid": grid, "gaussians": len(g), "rays": len(d), "unknowns": int(on.sum()), "lambda": lam, "tolerance": tol, "cap": cap,
+           "diag_min_over_max": float(D[on].min() / D[on].max()), "plain": cg(None), "jacobi": cg(M)}
+    plan.close()
+    r.close()
+    return out
+
+
+def check_diag(z):
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            x = r[key]
+            assert x["finite"], f"{label}, index {key}: the diagonal is not finite"
+            for d, b, sp in (("diag_ms", "replaced_ms", "replaced_spread_ms"), ("diag_planned_ms", "replaced_planned_ms", "replaced_planned_spread_ms")):
+                assert x[d]["median"] <= x[b]["median"] + x[sp], \
+                    f"{label}, index {key}: the diagonal call ({ms(x[d])}) is slower than what it replaces ({ms(x[b])}) by more than the spread"
+
+
+def markdown_diag(z, resources=""):
+    lines = [f"""# Gauss-Newton diagonal bundles (tools/ray_bundles.py --diag-only)
+
+`vrt_hip_radiance_rays_gn_diag_device` (seeded weights in, the table added into) in the same run against (a) `vrt_hip_radiance_rays_grad_device`
+with table of the same rays and (b) what it replaces: four ordered gradient calls with g = e_c, `vrt_hip_get_grad_records` after each and
+the squaring on the host (numpy), timed on the host clock from the first call to the finished [N, 9].  `-g 64` (N = {z['gaussians']}), device
+pointers, stream events around back-to-back calls for the diagonal and (a), the calls alternating; unplanned and with a bound ray plan; ms per
+call, median (min .. max).  The tool fails where the diagonal call is slower than (b) by more than the spread of (b); the ratio to (a) is
+recorded, not judged.
+
+| bundle | rays | index | plan | diagonal | (a) gradient | diagonal / (a) | (b) replaced | (b) / diagonal | max abs diagonal - (b), of the column's largest |
+|---|---|---|---|---|---|---|---|---|---|"""]
+    for label, r in z["rows"].items():
+        for key in ("off", "on"):
+            x = r[key]
+            lines.append(f"| {label} | {r['rays']} | {key} | no | {ms(x['diag_ms'])} | {ms(x['grad_ms'])} | {x['diag_over_grad']} | {ms(x['replaced_ms'])} | "
+                         f"{x['replaced_over_diag']} | {x['max_abs_diag_minus_replaced_over_column_max']:.2e} |")
+            lines.append(f"| {label} | {r['rays']} | {key} | bound | {ms(x['diag_planned_ms'])} | {ms(x['grad_planned_ms'])} | {x['diag_over_grad_planned']} | "
+                         f"{ms(x['replaced_planned_ms'])} | {x['replaced_over_diag_planned']} | |")
+    c = z.get("cg")
+    if c:
+        lines.append(f"""
+One damped Gauss-Newton step on `-g {c['grid']}` (N = {c['gaussians']}, {c['rays']} aimed rays, {c['unknowns']} parameters that some ray moves; the
+smallest entry of D is {c['diag_min_over_max']:.1e} of the largest): `(JᵀJ + λ D) x = -Jᵀ res` with λ = {c['lambda']} by conjugate gradients, every product
+a planned tangent bundle plus a planned gradient bundle, to a relative residual of {c['tolerance']} (at most {c['cap']} iterations).  Recorded,
+not judged.
+
+| preconditioner | iterations | reached | relative residual at the end |
+|---|---|---|---|
+| none | {c['plain']['iterations']} | {c['plain']['reached']} | {c['plain']['relative_residual']:.2e} |
+| Jacobi, (1 + λ) D | {c['jacobi']['iterations']} | {c['jacobi']['reached']} | {c['jacobi']['relative_residual']:.2e} |
+""")
+    lines.append("""
+Not taken: the arrangement of the lane = ray kernel that keeps 7 floats per list position in two passes (not built), a profile under
+rocprofv3, any scene but `-g 64` for the timings.
+""")
+    if resources:
+        lines.append("Resources (`tools/kernel_resources.sh raygndiag`; template arguments: Exp (0 libm, 1 vcl), Erf (0 libm, 1 A&S), list source, ORDERED):\n\n```\n"
+                     + resources.rstrip() + "\n```\n")
+    return "\n".join(lines)
+
+
 def part_scene(g, repeats=7, warm=2):
     import torch
     from sgrt_amd import autograd
@@ -1413,6 +1606,8 @@ def main():
     ap.add_argument("--tangent-only", action="store_true")
     ap.add_argument("--ttangent-only", action="store_true")
     ap.add_argument("--plan-only", action="store_true")
+    ap.add_argument("--diag-only", action="store_true")
+    ap.add_argument("--diag-cg-only", action="store_true")
     a = ap.parse_args()
     g = scene.grid_scene(a.grid)
     if a.scene_update_only:
@@ -1425,6 +1620,22 @@ def main():
         with open(os.path.join(a.out_dir, "scene_update.md"), "w") as f:
             f.write(markdown_scene(z))
         check_scene(z)
+        return
+    if a.diag_cg_only:                                              # the CG study of (gn) alone: prints its JSON line, writes nothing
+        print(json.dumps({"gn_diag_cg": part_cg()}))
+        return
+    if a.diag_only:
+        z = part_diag(g)
+        z["cg"] = part_cg()
+        print(json.dumps({"gn_diag": z}))
+        os.makedirs(a.out_dir, exist_ok=True)
+        with open(os.path.join(a.out_dir, "ray_gn_diag.json"), "w") as f:
+            f.write(json.dumps({"what": "the Gauss-Newton diagonal bundle against the gradient bundle and against four ordered gradient calls with their "
+                                        "records squared on the host; see tools/ray_bundles.py (gn)", "gn_diag": z}) + "\n")
+        res = os.path.join(a.out_dir, "ray_gn_diag_resources.txt")
+        with open(os.path.join(a.out_dir, "ray_gn_diag.md"), "w") as f:
+            f.write(markdown_diag(z, open(res).read() if os.path.exists(res) else ""))
+        check_diag(z)
         return
     if a.plan_only:
         z = part_plan(g)
