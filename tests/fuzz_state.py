@@ -1,6 +1,9 @@
-"""State-machine fuzz, run by hand on an MI355X (not collected by pytest):
+"""State-machine fuzz of the frame path, run by hand on an MI355X:
 
     python tests/fuzz_state.py [seed] [steps]
+
+(a script, not a test module; tests/test_gpu_fuzz.py runs a short seeded run of it as part of the GPU suite, and
+tests/bundle_state_scenes.py is its counterpart for the ray bundles)
 
 One long-lived context receives a random sequence of state changes (scene, image size, rays by plane arrays / view
 matrix, tiling on the device / by the caller / none, Exp/Erf variant, cull_eps, table mode, shard) and renders after each
